@@ -415,13 +415,53 @@ def single_chain_leg(system, device, t_step, r_step, steps=4000, k=4):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SAMPLE_CHAINS = 64            # chains whose sites and A(k) --dump-outputs writes ...
+DUMP_BYTES = 60 << 20              # ... fewer where all its files together would pass this (64 MB allowed)
+
+
+def dump_outputs(out_dir, farm, system, host, totals):
+    """--dump-outputs: what the timed region left, as float64 .npy files under out_dir.
+      energy             (R, 5) running energy components of every chain (K; the numpy driver keeps the first 3)
+      molecule_counts    (R, n_active) molecule counts of every chain (Fortran driver)
+      timed_totals       accepted moves, trials, Delta-E evaluations of the timed region
+      sample_chains      the sampled chains: a fixed seeded choice, the same for the same arguments
+      sites_type<t>      (sample, n_max, n1, 3) sites of active residue type t, zero beyond a chain's molecule count
+      structure_factor   (sample, Nk, 2) A(k) of the sampled chains, in the reference's k order (re, im)"""
+    os.makedirs(out_dir, exist_ok=True)
+    eng, R, topo = farm.eng, farm.R, system.topo
+    active = [t for t in range(topo.n_res) if topo.is_active[t]]
+    if host == "fortran":
+        energy = np.array([farm.energy(r) for r in range(R)])
+        counts = farm.counts()
+    else:
+        energy = np.asarray(farm.energy)
+        counts = np.tile(np.array([system.n_mol[t] for t in active]), (R, 1))
+    n_max = [int(counts[:, k].max()) for k in range(len(active))]
+    chain_bytes = 8 * (sum(n * int(topo.atoms_in_res[t]) * 3 for n, t in zip(n_max, active)) + 2 * eng.nk)
+    n_sample = max(1, min(R, DUMP_SAMPLE_CHAINS, (DUMP_BYTES - 8 * (energy.size + counts.size)) // chain_bytes))
+    sample = np.sort(np.random.default_rng(2024).choice(R, n_sample, replace=False))
+    arrays = {"energy": energy, "timed_totals": np.array(totals), "sample_chains": sample}
+    if host == "fortran":
+        arrays["molecule_counts"] = counts
+    for k, t in enumerate(active):
+        sites = np.zeros((n_sample, n_max[k], int(topo.atoms_in_res[t]), 3))
+        for i, r in enumerate(sample):
+            s = eng.get_molecules(int(r), t)
+            sites[i, :s.shape[0]] = s
+        arrays[f"sites_type{t}"] = sites
+    arrays["structure_factor"] = np.stack([np.stack([a.real, a.imag], axis=-1)
+                                           for a in (eng.structure_factor(int(r)) for r in sample)])
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def config_legs(args, device):
     """BASELINE.json configs[2]-[4] as short self-timed legs: child processes of this one, one after the other (this
     process has closed its farm; a child is an ordinary `bench.py --workload ...` run and prints its own JSON line)."""
     import subprocess
     out = {}
     for wl in ("co2_gcmc", "framework_water", "co2_isotherm", "spce_triclinic", "adsorbate24"):
-        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", str(args.config_steps), "--warmup", "20",
+        cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--full", "--steps", str(args.config_steps), "--warmup", "20",
                "--sustained-steps", "0", "--configs", "0", "--replicas-sweep", "", "--cpu-budget", "1.0", "--cpu-all-cores-budget", "0",
                "--device", str(device)]
         if args.no_cpu_baseline:
@@ -531,17 +571,26 @@ def main():
                          "torch.distributed (the default otherwise).  If the C-ABI communicator cannot be created on every rank "
                          "within 90 s the ranks agree to fall back to torch.distributed and the line's `exchange` block says so.")
     ap.add_argument("--device", type=int, default=None, help="HIP device ordinal (default: LOCAL_RANK)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region, also run what the headline figure does not need: the `sustained` window, the "
+                         "kernels' isolated launches (roofline `isolated`), `replicas_sweep` + `single_chain`, `configs` and the CPU "
+                         "baselines.  Without it the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write what it computed (rank 0's chains) as DIR/<name>.npy, float64: every "
+                         "chain's running energy components and molecule counts, the region's accepted / trial / evaluation "
+                         "totals, and the sites and A(k) of a fixed seeded sample of chains (< 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--kernel-timing", type=int, default=1, choices=[0, 1],
                     help="0 (diagnostic): no HIP events on the launches of the timed region -- the per-launch figures of the roofline "
                          "block are then empty; shows what the event bookkeeping costs a host-bound workload")
-    ap.add_argument("--cpu-budget", type=float, default=4.0, help="seconds of the 1-core reference leg")
+    ap.add_argument("--cpu-budget", type=float, default=4.0, help="--full: seconds of the 1-core reference leg")
     ap.add_argument("--cpu-all-cores-budget", type=float, default=2.0,
-                    help="seconds of the labelled all-core OpenMP leg of the C restatement (0: skip; SPC/E workload only)")
-    ap.add_argument("--settle-s", type=float, default=0.5,
-                    help="untimed settle phase after the warm-up steps, seconds of the same step (0: none)")
+                    help="--full: seconds of the labelled all-core OpenMP leg of the C restatement (0: skip; SPC/E workload only)")
+    ap.add_argument("--settle-steps", type=int, default=400,
+                    help="untimed settle steps after the warm-up steps (0: none); a step count, not a time, so that the state the "
+                         "timed region starts from is the same from run to run")
     ap.add_argument("--sustained-steps", type=int, default=1000,
-                    help="a second, self-timed window of this many steps after the timed region when --steps is smaller "
+                    help="--full: a second, self-timed window of this many steps after the timed region when --steps is smaller "
                          "(reported as `sustained`; 0: none)")
     ap.add_argument("--fugacity-n", type=float, default=None,
                     help="grand-canonical workloads: fugacity as the ideal-gas molecule count f V (default 100 for co2_gcmc, "
@@ -555,17 +604,19 @@ def main():
                          "rank 0 prints the rank-ordered table gathered over the process group")
     ap.add_argument("--dump-counts", default=None, help="directory: every rank writes its chains' final molecule counts (tests)")
     ap.add_argument("--configs", type=int, default=None, choices=[0, 1],
-                    help="1: after the headline workload, time the other BASELINE.json configs (co2_gcmc, framework_water, "
+                    help="--full, 1: after the headline workload, time the other BASELINE.json configs (co2_gcmc, framework_water, "
                          "co2_isotherm) as short self-timed legs (child processes of this one, one after the other) and put them "
                          "into the same JSON line as `configs` (default: 1 for the default single-GPU SPC/E run)")
-    ap.add_argument("--config-steps", type=int, default=300, help="steps of each `configs` leg")
+    ap.add_argument("--config-steps", type=int, default=300, help="--full: steps of each `configs` leg")
     ap.add_argument("--replicas-sweep", default=None,
-                    help="comma-separated chain counts: after the headline region, the same SPC/E step with that many chains per "
-                         "GPU (`replicas_sweep` in the JSON line: throughput against chain count), plus the single-chain driver "
-                         "(mc_chain.f90, one launch per window); default 1,8,64,512,4096 for the default single-GPU SPC/E run, "
+                    help="--full, comma-separated chain counts: after the headline region, the same SPC/E step with that many chains "
+                         "per GPU (`replicas_sweep` in the JSON line: throughput against chain count), plus the single-chain driver "
+                         "(mc_chain.f90, one launch per window); default 1,8,64,512,1024,4096 for the default single-GPU SPC/E run, "
                          "'' for none")
-    ap.add_argument("--sweep-seconds", type=float, default=0.4, help="timed seconds per point of --replicas-sweep")
+    ap.add_argument("--sweep-seconds", type=float, default=0.4, help="--full: timed seconds per point of --replicas-sweep")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0 or args.settle_steps < 0:
+        ap.error("--steps must be at least 1, --warmup and --settle-steps at least 0")
 
     wl = args.workload
     default_run = wl == "spce" and args.replicas is None and args.gpus <= 1 and args.host == "fortran" and not args.dry_run
@@ -715,12 +766,10 @@ def main():
     farm.run(args.warmup)
     # Declared, untimed settle phase: the timed region may be as short as 20 steps (~5 ms), far below the time
     # the GPU clocks, the OpenMP team and the host caches need to reach their steady state; run the same step
-    # until --settle-s seconds have passed (reported as settle_steps; `steps` and `warmup` stay as given).
-    settle_steps = 0
-    t_settle = time.perf_counter()
-    while args.settle_s > 0 and time.perf_counter() - t_settle < args.settle_s:
-        farm.run(100)
-        settle_steps += 100
+    # --settle-steps more times (400: ~0.6 s of the SPC/E step; reported as settle_steps; `steps` and `warmup` stay as given).
+    settle_steps = args.settle_steps
+    if settle_steps:
+        farm.run(settle_steps)
     eng.profile_reset()
     timers0 = farm.timers() if hasattr(farm, "timers") else None
 
@@ -793,11 +842,13 @@ def main():
     n_rec, ms_rec = eng.profile_get(_lib.KERNEL_RECIP)
     n_com, ms_com = eng.profile_get(_lib.KERNEL_COMMIT)
     timers1 = farm.timers() if hasattr(farm, "timers") else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, farm, system, args.host, [float(accepted), trials_now, evals_now])
 
     # A second, self-timed window when the timed region is a short sample (the driver's --steps 20 is ~17 ms):
     # the same step for --sustained-steps more steps, same fences, reported beside the headline figure.
     sustained = None
-    if args.sustained_steps > args.steps:
+    if args.full and args.sustained_steps > args.steps:
         fence()
         ts0 = time.perf_counter()
         acc_s = farm.run(args.sustained_steps)
@@ -807,7 +858,7 @@ def main():
         sustained = {"steps": args.sustained_steps, "value": acc_s / el_s, "unit": "accepted MC moves/s",
                      "ms_per_step": el_s / args.sustained_steps * 1e3, "timed_region_s": el_s,
                      "note": "second self-timed window after the headline region (same step, same fences)"}
-    elif args.sustained_steps > 0:
+    elif args.full and args.sustained_steps > 0:
         sustained = {"steps": args.steps, "value": tot_acc / elapsed, "unit": "accepted MC moves/s",
                      "ms_per_step": elapsed / args.steps * 1e3, "timed_region_s": elapsed, "note": "the timed region itself"}
 
@@ -815,9 +866,9 @@ def main():
     # the kernels of different lanes share the CUs, which raises throughput but stretches every kernel's own
     # duration; this gives the kernel's un-shared time for comparison.
     iso_us = None
-    if not args.kernel_timing:
+    if args.full and not args.kernel_timing:
         eng.profile_enable(True)           # the isolated legs below are timed either way
-    if rank == 0 and args.host == "fortran" and wl in NVT_WORKLOADS:
+    if args.full and rank == 0 and args.host == "fortran" and wl in NVT_WORKLOADS:
         rng = np.random.default_rng(5)
         n_l = max(1, R // farm.n_lanes)
         m_iso = rng.integers(0, int(system.n_mol[0]), n_l).astype(np.int32)
@@ -828,7 +879,7 @@ def main():
         n_iso, ms_iso = eng.profile_get(_lib.KERNEL_PAIR)
         iso_us = ms_iso / max(1, n_iso) * 1e3
     iso_gc = None
-    if rank == 0 and wl not in NVT_WORKLOADS and args.device_build:
+    if args.full and rank == 0 and wl not in NVT_WORKLOADS and args.device_build:
         # grand-canonical workloads: one lane's batch of device-built trials (the farm's move mix on the chains' current
         # states) launched alone, evaluation only
         rng = np.random.default_rng(5)
@@ -1022,7 +1073,7 @@ def main():
     farm.close()
     if comm is not None:
         comm.close()
-    if rank == 0:
+    if rank == 0 and args.full:
         # GPU legs first, CPU baselines last (short), so that whoever samples the GPU from outside sees it busy
         if world == 1 and args.replicas_sweep and wl in ("spce", "co2_gcmc") and args.host == "fortran":
             pts = [int(x) for x in args.replicas_sweep.split(",") if x.strip()]
@@ -1048,6 +1099,7 @@ def main():
             else:
                 f_cpu = fug_one if fug_one is not None else float(fug_grid[ISOTHERM_POINTS // 2])
                 out["cpu_baseline"] = cpu_baseline_gcmc(system, t_act, p_move, t_step, r_step, f_cpu, budget_s=args.cpu_budget)
+    if rank == 0:
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -38,14 +38,6 @@ def refcpu_mod():
     return refcpu
 
 
-@pytest.fixture(scope="session")
-def reflib_mod():
-    from oracle import reflib
-    if not reflib.available():
-        pytest.skip("oracle/_ref/libmaniac_ref.so not built (needs /root/reference + amdflang)")
-    return reflib
-
-
 @pytest.fixture(autouse=True)
 def _close_leftover_farm():
     """A test that fails before farm.close() must not leave the process-wide Fortran farm occupied."""

@@ -58,7 +58,7 @@ def test_isotherm_two_gloo_ranks_on_one_gpu_histogram_matches_rank_counts(tmp_pa
     points; the gathered per-point histogram must equal the histogram of the ranks' own final molecule counts."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     out = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dist-backend", "gloo", "--workload", "co2_isotherm",
-                          "--replicas", "64", "--steps", "120", "--warmup", "10", "--settle-s", "0", "--device", "0",
+                          "--replicas", "64", "--steps", "120", "--warmup", "10", "--settle-steps", "0", "--device", "0",
                           "--no-pin", "--host-threads", "2", "--sustained-steps", "0", "--dump-counts", str(tmp_path)],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -86,11 +86,11 @@ def test_isotherm_two_gloo_ranks_on_one_gpu_histogram_matches_rank_counts(tmp_pa
 
 @pytest.mark.gpu
 def test_default_line_carries_the_other_configs_the_chain_count_curve_and_both_baselines():
-    """The driver's command shape (`bench.py --gpus 1 --steps K --warmup W`, nothing else): ONE JSON line with the headline
-    metric, `roofline`, `cpu_baseline`, and -- round 4 -- `configs` (BASELINE.json configs[2]-[4] as short legs with their own
-    roofline and CPU baseline), `replicas_sweep` and `single_chain`.  Short legs here; the structure is what is checked."""
+    """`bench.py --gpus 1 --full`: ONE JSON line with the headline metric, `roofline`, `cpu_baseline`, and -- round 4 --
+    `configs` (BASELINE.json configs[2]-[4] as short legs with their own roofline and CPU baseline), `replicas_sweep` and
+    `single_chain`.  Short legs here; the structure is what is checked."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
-    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "5", "--warmup", "2", "--settle-s", "0", "--sustained-steps", "0",
+    out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--full", "--steps", "5", "--warmup", "2", "--settle-steps", "0", "--sustained-steps", "0",
                           "--config-steps", "40", "--sweep-seconds", "0.05", "--replicas-sweep", "1,64", "--cpu-budget", "0.5",
                           "--cpu-all-cores-budget", "0", "--configs", "1"],
                          env=env, capture_output=True, text=True, timeout=900)
@@ -111,3 +111,35 @@ def test_default_line_carries_the_other_configs_the_chain_count_curve_and_both_b
     assert all(r["path"].startswith("window") for r in d["replicas_sweep"])                 # round 5: one launch per lane step
     assert d["exchange"]["ranks_seen"] == 1 and d["exchange"]["per_rank_device"] == [0]
     assert d["single_chain"]["value"] > 0 and d["single_chain"]["windows"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_alone_and_its_dumped_outputs_repeat(tmp_path):
+    """The driver's command shape (`bench.py --gpus 1 --steps K --warmup W`): the headline region alone -- everything else is
+    behind --full -- and --dump-outputs writes the same float arrays for the same arguments, twice."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
+    lines = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "6", "--warmup", "2", "--settle-steps", "30",
+                              "--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines.append(_last_json(out.stdout))
+    d = lines[0]
+    assert d["metric"] == "MC moves/sec" and d["steps"] == 6 and d["warmup"] == 2 and d["settle_steps"] == 30
+    assert d["value"] > 0 and d["ms_per_step"] == pytest.approx(d["timed_region_s"] / 6 * 1e3)
+    assert not {"configs", "replicas_sweep", "single_chain", "cpu_baseline", "sustained"} & set(d)
+    assert "isolated" not in d["roofline"]
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    assert {"energy.npy", "molecule_counts.npy", "timed_totals.npy", "sample_chains.npy", "sites_type0.npy",
+            "structure_factor.npy"} <= set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and np.array_equal(a, b), n
+    R = d["config"]["replicas_per_gpu"]
+    assert np.load(tmp_path / "a" / "energy.npy").shape == (R, 5)
+    assert np.load(tmp_path / "a" / "sites_type0.npy").shape[1:] == (3375, 3, 3)
+    totals = np.load(tmp_path / "a" / "timed_totals.npy")
+    assert totals[0] == pytest.approx(d["value"] * d["timed_region_s"], rel=1e-9)
+    assert totals[1] == pytest.approx(d["trial_moves_per_s"] * d["timed_region_s"], rel=1e-9) and 0 < totals[1] <= R * 6

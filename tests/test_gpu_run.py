@@ -17,7 +17,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.util import GOLDEN, TOL_K
+from tests.util import GOLDEN, TOL_K, blank_output_path
 
 RUNS = os.path.join(GOLDEN, "runs")
 SUMMARY = json.load(open(os.path.join(RUNS, "summary.json")))
@@ -62,7 +62,7 @@ def test_run_writes_the_reference_files(case, mode, tmp_path):
         want = open(os.path.join(expected, f)).read().split("\n")
         got = open(os.path.join(out, f)).read().split("\n")
         if f == "log.maniac":
-            got = ["<output path>" if out.rstrip("/") in ln else ln for ln in got]
+            got = blank_output_path(got, out)
         assert len(got) == len(want), f
         bad = [i for i, (a, b) in enumerate(zip(got, want)) if a != b]
         assert not bad, f"{f}: first differing line {bad[0] + 1}: {got[bad[0]]!r} vs {want[bad[0]]!r} ({len(bad)} lines differ)"

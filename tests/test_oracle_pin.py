@@ -2,11 +2,14 @@
 
   (1) the golden vectors in tests/golden/ (generated from the reference itself by
       tests/golden/make_golden.py), and
-  (2) the compiled reference (oracle/_ref/libmaniac_ref.so) called live on extra seeded inputs,
+  (2) the compiled reference (oracle/_ref/libmaniac_ref.so) on extra seeded inputs: its answers to every call
+      of the two pins below are stored in tests/golden/reference_pins.npz (tests/golden/make_reference_pins.py),
 
 bit for bit where the arithmetic is the same libm on the same host, and the setup values quoted
 in SURVEY.md section 8 (alpha, kmax, Nk) that the reference logs for these boxes.
 """
+import hashlib
+
 import numpy as np
 import pytest
 
@@ -53,82 +56,131 @@ def test_refcpu_reproduces_golden(name, refcpu_mod):
         assert np.array_equal(P.amplitude(), A0)
 
 
-@pytest.mark.parametrize("maker", [lambda: synth.spce_box(5, seed=2), lambda: synth.mixture_box(seed=8),
-                                   lambda: synth.co2_box(12, seed=5), lambda: synth.mixture_box(n_a=7, n_b=5, box=(15, 15, 15), seed=1),
-                                   lambda: synth.framework_water_box(n_water=6, n_frame=200, L=22.0, seed=4),
-                                   lambda: synth.mixture_box(seed=6, tilt=(1.5, -0.8, 0.6))])
-def test_refcpu_matches_compiled_reference_bitwise(maker, refcpu_mod, reflib_mod):
-    s = maker()
-    R = reflib_mod.Reference(s)
-    P = refcpu_mod.RefCPU(s)
-    assert (R.alpha, R.rc, R.tol, R.nk) == (P.alpha, P.rc, P.tol, P.nk)
-    er, ep = R.system_energy(), P.system_energy()
-    for k in E_KEYS:
-        assert er[k] == ep[k], k
-    R.init_amplitude(True); P.init_amplitude(True)
-    assert np.array_equal(R.amplitude(), P.amplitude())
+# the systems of the live pins; the compiled reference's answers to their calls are stored in
+# tests/golden/reference_pins.npz (tests/golden/make_reference_pins.py)
+PIN_MAKERS = [lambda: synth.spce_box(5, seed=2), lambda: synth.mixture_box(seed=8),
+              lambda: synth.co2_box(12, seed=5), lambda: synth.mixture_box(n_a=7, n_b=5, box=(15, 15, 15), seed=1),
+              lambda: synth.framework_water_box(n_water=6, n_frame=200, L=22.0, seed=4),
+              lambda: synth.mixture_box(seed=6, tilt=(1.5, -0.8, 0.6))]
+PIN_SMALL = lambda: synth.mixture_box(seed=12)          # noqa: E731
+
+
+class Trace:
+    """Every value one oracle returns along a pin's call sequence, in call order, as float64 arrays."""
+
+    def __init__(self):
+        self.items = []
+
+    def __call__(self, label, v):
+        v = np.asarray(v)
+        if np.iscomplexobj(v):
+            v = np.stack([v.real, v.imag], axis=-1)
+        self.items.append((label, np.asarray(v, dtype=np.float64)))
+        return v
+
+    def digest(self, label, v):
+        """A(k) is compared bit for bit through the sha256 of its float64 bytes (32 bytes stored instead of 16 Nk)."""
+        v = np.ascontiguousarray(self(label, v))
+        self.items[-1] = (self.items[-1][0], np.frombuffer(hashlib.sha256(v.tobytes()).digest(), dtype=np.uint8).astype(np.float64))
+
+    def arrays(self, prefix):
+        """The trace as three arrays: call labels, value sizes and all values in one float64 vector."""
+        return {f"{prefix}_labels": np.array([k for k, _ in self.items]),
+                f"{prefix}_sizes": np.array([v.size for _, v in self.items], dtype=np.int64),
+                f"{prefix}_values": np.concatenate([v.ravel() for _, v in self.items])}
+
+
+def moves_trace(X, s):
+    """Set-up, system energy, A(k), then old / new energies, A(k), intra / self terms and both reciprocal updates of a
+    translated and rotated molecule, for up to three molecules of every active type."""
+    rec = Trace()
+    rec("setup", [X.alpha, X.rc, X.tol, X.nk])
+    e = X.system_energy()
+    rec("system_energy", [e[k] for k in E_KEYS])
+    X.init_amplitude(True)
+    rec.digest("amplitude", X.amplitude())
     rng = np.random.default_rng(0)
     for t in range(s.topo.n_res):
         if not s.topo.is_active[t]:
             continue
         for m in rng.choice(int(s.n_mol[t]), size=min(3, int(s.n_mol[t])), replace=False):
             m = int(m)
-            for X in (R, P):
-                X.save_fourier(t, m)
-            assert np.array_equal(R.old_energy(t, m, 0), P.old_energy(t, m, 0))
-            com, off = R.get_molecule(t, m)
+            X.save_fourier(t, m)
+            rec("old_energy", X.old_energy(t, m, 0))
+            com, off = X.get_molecule(t, m)
+            rec("com", com)
+            rec("off", off)
             trial = com + rng.uniform(-0.3, 0.3, 3)
-            ncom = R.apply_pbc(trial)
-            assert np.array_equal(ncom, P.apply_pbc(trial))
-            rot = R.rotation_matrix(int(rng.integers(1, 4)), float(rng.uniform(-0.3, 0.3)))
-            noff = off @ rot.T
-            for X in (R, P):
-                X.set_molecule(t, m, ncom, noff)
-            assert np.array_equal(R.new_energy(t, m, 0), P.new_energy(t, m, 0))
-            assert np.array_equal(R.amplitude(), P.amplitude())
-            assert R.intra_singlemol(t, m) == P.intra_singlemol(t, m)
-            assert R.self_singlemol(t) == P.self_singlemol(t)
+            ncom = rec("apply_pbc", X.apply_pbc(trial))
+            rot = rec("rotation_matrix", X.rotation_matrix(int(rng.integers(1, 4)), float(rng.uniform(-0.3, 0.3))))
+            X.set_molecule(t, m, ncom, off @ rot.T)
+            rec("new_energy", X.new_energy(t, m, 0))
+            rec.digest("amplitude", X.amplitude())
+            rec("intra_singlemol", X.intra_singlemol(t, m))
+            rec("self_singlemol", X.self_singlemol(t))
             # deletion-mode and creation-mode reciprocal updates
             for mode in (2, 1):
-                assert R.recip_singlemol(t, m, mode) == P.recip_singlemol(t, m, mode)
-            assert np.array_equal(R.amplitude(), P.amplitude())
+                rec(f"recip_singlemol_{mode}", X.recip_singlemol(t, m, mode))
+            rec.digest("amplitude", X.amplitude())
+    return rec
 
 
-def test_small_functions_bitwise(refcpu_mod, reflib_mod):
-    s = synth.mixture_box(seed=12)
-    R = reflib_mod.Reference(s)
-    P = refcpu_mod.RefCPU(s)
+def small_functions_trace(X, s):
+    """Distance, LJ, Coulomb, PBC, rotation, acceptance, fugacity conversion, tabulated potentials and the swap rule."""
+    rec = Trace()
     rng = np.random.default_rng(3)
     for _ in range(200):
         t1, t2 = rng.integers(0, 2, 2)
         m1, m2 = rng.integers(0, s.n_mol[t1]), rng.integers(0, s.n_mol[t2])
         a1, a2 = rng.integers(0, s.topo.atoms_in_res[t1]), rng.integers(0, s.topo.atoms_in_res[t2])
-        assert R.distance(t1, m1, a1, t2, m2, a2) == P.distance(t1, m1, a1, t2, m2, a2)
+        rec("distance", X.distance(t1, m1, a1, t2, m2, a2))
         r, sg, ep = rng.uniform(0.5, 12), rng.uniform(2, 4), rng.uniform(10, 200)
-        assert R.lj(r, sg, ep) == P.lj(r, sg, ep)
+        rec("lj", X.lj(r, sg, ep))
         q1, q2 = rng.uniform(-1, 1, 2)
-        assert R.coulomb(r, q1, q2) == P.coulomb(r, q1, q2)
-        p = rng.uniform(-60, 60, 3)
-        assert np.array_equal(R.apply_pbc(p), P.apply_pbc(p))
+        rec("coulomb", X.coulomb(r, q1, q2))
+        rec("apply_pbc", X.apply_pbc(rng.uniform(-60, 60, 3)))
         th = rng.uniform(-3, 3)
-        ax = int(rng.integers(1, 4))
-        assert np.array_equal(R.rotation_matrix(ax, th), P.rotation_matrix(ax, th))
-    assert R.coulomb(1e-11, 0.5, 0.5) == 0.0 == P.coulomb(1e-11, 0.5, 0.5)
-    assert R.coulomb(2.0, 1e-11, 0.5) == 0.0 == P.coulomb(2.0, 1e-11, 0.5)
-    assert R.lj(s.real_space_cutoff, 3.0, 100.0) == 0.0 == P.lj(s.real_space_cutoff, 3.0, 100.0)
+        rec("rotation_matrix", X.rotation_matrix(int(rng.integers(1, 4)), th))
+    rec("coulomb_short", X.coulomb(1e-11, 0.5, 0.5))
+    rec("coulomb_small_charge", X.coulomb(2.0, 1e-11, 0.5))
+    rec("lj_at_cutoff", X.lj(s.real_space_cutoff, 3.0, 100.0))
     for mt in (1, 2, 3, 4):
         for de in (-50.0, 0.0, 37.5, 900.0):
-            assert R.acceptance(100.0, 100.0 + de, 0, mt, 1e-4) == P.acceptance(100.0, 100.0 + de, 0, mt, 1e-4)
-    assert R.convert_fugacity(0.7, 310.0) == P.convert_fugacity(0.7, 310.0)
+            rec("acceptance", X.acceptance(100.0, 100.0 + de, 0, mt, 1e-4))
+    rec("convert_fugacity", X.convert_fugacity(0.7, 310.0))
     # the reference's tabulated potentials (dead code there, parameters.f90:42): table build + linear lookup
     for which in (1, 2, 3):
         for r in list(rng.uniform(0.0, 1.05 * s.real_space_cutoff, 40)) + [0.0, -1.0, s.real_space_cutoff, 1e-12]:
-            assert R.table_lookup(which, float(r)) == P.table_lookup(which, float(r)), (which, r)
+            rec(f"table_lookup_{which}", X.table_lookup(which, float(r)))
     # the swap acceptance rule (all the reference has of a swap move, monte_carlo_utils.f90:228-268)
     if s.topo.n_res >= 2:
         for de in (-50.0, 0.0, 37.5, 900.0):
             for (a, b) in ((0, 1), (1, 0)):
-                assert R.acceptance_swap(100.0, 100.0 + de, a, b, 2e-4, 5e-5) == P.acceptance_swap(100.0, 100.0 + de, a, b, 2e-4, 5e-5)
+                rec("acceptance_swap", X.acceptance_swap(100.0, 100.0 + de, a, b, 2e-4, 5e-5))
+    return rec
+
+
+def assert_trace_is_the_references(rec, prefix):
+    ref = load_golden("reference_pins")
+    labels, sizes = list(ref[f"{prefix}_labels"]), ref[f"{prefix}_sizes"]
+    assert [k for k, _ in rec.items] == labels, f"{prefix}: the call sequence differs from the one the reference answered"
+    for i, (want, (label, got)) in enumerate(zip(np.split(ref[f"{prefix}_values"], np.cumsum(sizes)[:-1]), rec.items)):
+        assert got.size == sizes[i] and np.array_equal(got.ravel(), want), (prefix, i, label)
+
+
+@pytest.mark.parametrize("maker", PIN_MAKERS)
+def test_refcpu_matches_compiled_reference_bitwise(maker, refcpu_mod):
+    s = maker()
+    assert_trace_is_the_references(moves_trace(refcpu_mod.RefCPU(s), s), f"case{PIN_MAKERS.index(maker)}")
+
+
+def test_small_functions_bitwise(refcpu_mod):
+    s = PIN_SMALL()
+    P = refcpu_mod.RefCPU(s)
+    assert_trace_is_the_references(small_functions_trace(P, s), "small")
+    # the cut-offs themselves
+    assert P.coulomb(1e-11, 0.5, 0.5) == 0.0 and P.coulomb(2.0, 1e-11, 0.5) == 0.0
+    assert P.lj(s.real_space_cutoff, 3.0, 100.0) == 0.0
 
 
 def test_survey_logged_values():

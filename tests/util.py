@@ -59,3 +59,14 @@ def split_sites(system, t, sites_padded):
     s = np.asarray(sites_padded)[:n1]
     com = s[0].copy()
     return com, s - com[None, :]
+
+
+def blank_output_path(log_lines, out):
+    """log.maniac's closing box names the output directory `out`, cut to the box's width when it is longer
+    (log_box_line): that line, whole or cut, becomes "<output path>" as in the stored logs."""
+    def names_out(ln):
+        if not (ln.startswith(" | ") and ln.endswith(" |")):
+            return False
+        body = ln[3:-2]
+        return body.rstrip() in (out, out.rstrip("/")) or (body == body.rstrip() and out.startswith(body))
+    return ["<output path>" if names_out(ln) else ln for ln in log_lines]

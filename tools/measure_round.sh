@@ -7,6 +7,7 @@ set -e -o pipefail
 part=${1:-1}
 out=gpurun_out/r5final
 mkdir -p $out
+root=$(pwd)
 export TMPDIR=/tmp
 sha256sum maniac_mc_amd/libmaniac_hip.so > $out/lib_sha256.txt
 if [ "$part" = 1 ]; then
@@ -24,14 +25,14 @@ if [ "$part" = 1 ]; then
   MGPU_PAIR_NSPLIT=1 python tools/bench_kernels.py --replicas 4096 --reps 5 --workload spce > $out/k_spce_R4096_nsplit1.json   # the default bench's launch shape
   for wl in spce framework_water; do python tools/bench_kernels.py --replicas 2048 --reps 5 --workload $wl --decide > $out/k_${wl}_R2048_decide.json; done
   python tools/bench_kernels.py --replicas 4096 --reps 5 --workload co2_gcmc --decide > $out/k_co2_gcmc_R4096_decide.json
-  t0=$(date +%s); python bench.py --steps 20 --warmup 5 > $out/bench_driver_format.json 2> $out/bench_driver_format.err; echo "bench.py --steps 20 --warmup 5: $(( $(date +%s) - t0 )) s wall" > $out/bench_driver_format_wall.txt
-  python bench.py --configs 0 --replicas-sweep "" > $out/bench_spce.json 2> $out/bench_spce.err
-  python bench.py --workload co2_gcmc --replicas-sweep 1,8,64,512,1024,4096 > $out/bench_co2_gcmc.json 2> $out/bench_co2_gcmc.err
-  python bench.py --workload framework_water > $out/bench_framework_water.json 2> $out/bench_framework_water.err
-  python bench.py --workload co2_isotherm > $out/bench_co2_isotherm.json 2> $out/bench_co2_isotherm.err
-  python bench.py --workload co2_isotherm --exchange torch --no-cpu-baseline > $out/bench_co2_isotherm_exchange_torch.json 2> $out/bench_co2_isotherm_exchange_torch.err
-  python bench.py --workload spce_triclinic > $out/bench_spce_triclinic.json 2> $out/bench_spce_triclinic.err
-  python bench.py --workload adsorbate24 > $out/bench_adsorbate24.json 2> $out/bench_adsorbate24.err
+  t0=$(date +%s); python bench.py --full --steps 20 --warmup 5 > $out/bench_driver_format.json 2> $out/bench_driver_format.err; echo "bench.py --full --steps 20 --warmup 5: $(( $(date +%s) - t0 )) s wall" > $out/bench_driver_format_wall.txt
+  python bench.py --full --configs 0 --replicas-sweep "" > $out/bench_spce.json 2> $out/bench_spce.err
+  python bench.py --full --workload co2_gcmc --replicas-sweep 1,8,64,512,1024,4096 > $out/bench_co2_gcmc.json 2> $out/bench_co2_gcmc.err
+  python bench.py --full --workload framework_water > $out/bench_framework_water.json 2> $out/bench_framework_water.err
+  python bench.py --full --workload co2_isotherm > $out/bench_co2_isotherm.json 2> $out/bench_co2_isotherm.err
+  python bench.py --full --workload co2_isotherm --exchange torch --no-cpu-baseline > $out/bench_co2_isotherm_exchange_torch.json 2> $out/bench_co2_isotherm_exchange_torch.err
+  python bench.py --full --workload spce_triclinic > $out/bench_spce_triclinic.json 2> $out/bench_spce_triclinic.err
+  python bench.py --full --workload adsorbate24 > $out/bench_adsorbate24.json 2> $out/bench_adsorbate24.err
   # round 5: the few-chain regime (one launch per lane step) against the batched path, and the many-site reciprocal kernels
   python tools/farm_window_speed.py --replicas 1,8,64,512,1024 --modes batched,w1,w2,w3 --lanes 1,2 --seconds 0.5 --json $out/farm_window_speed.json > $out/farm_window_speed.txt 2>&1
   python tools/farm_window_speed.py --workload co2_gcmc --replicas 1,8,64,512,1024,4096 --modes batched,w1,w3 --lanes 1,2 --drivers 1,2 --threads 6 --seconds 0.4 > $out/farm_window_speed_co2.txt 2>&1
@@ -49,11 +50,11 @@ else
   mkdir -p profiles/r05
   for wl in spce co2_gcmc framework_water; do cp $out/pmc/pmc_${wl}_r05.json profiles/r05/pmc_${wl}.json; done
   for wl in spce co2_gcmc framework_water; do
-    (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /root/repo/$out/prof_$wl -o p -- python3 /root/repo/bench.py --workload $wl --no-cpu-baseline --steps 200 --settle-s 0 --sustained-steps 0 --configs 0 --replicas-sweep "" > /root/repo/$out/bench_${wl}_under_rocprof.json 2> /root/repo/$out/bench_${wl}_under_rocprof.err)
+    (cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d "$root/$out/prof_$wl" -o p -- python3 "$root/bench.py" --workload $wl --full --no-cpu-baseline --steps 200 --settle-steps 0 --sustained-steps 0 --configs 0 --replicas-sweep "" > "$root/$out/bench_${wl}_under_rocprof.json" 2> "$root/$out/bench_${wl}_under_rocprof.err")
     rm -f $out/prof_$wl/*kernel_trace.csv
   done
   # the headline line again, now that profiles/r05/pmc_*.json are of this build (roofline.traffic / valu_issue filled in)
-  python bench.py --steps 20 --warmup 5 > $out/bench_driver_format_with_pmc.json 2> $out/bench_driver_format_with_pmc.err
+  python bench.py --full --steps 20 --warmup 5 > $out/bench_driver_format_with_pmc.json 2> $out/bench_driver_format_with_pmc.err
 fi
 find $out -name '*kernel_trace.csv' -path '*pmc*' -delete
 find $out -name '*counter_collection.csv' -size +2M -delete
