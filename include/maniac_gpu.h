@@ -437,6 +437,15 @@ int mgpu_chain_get_timing(mgpu_engine *e, double us[15]);
  *               driver replays the same arithmetic with its own counts when it collects the window (a by-count record of
  *               a replica that waits for the driver's decision comes back 4 whatever its count says: the step it waits
  *               for may change the count)
+ *   insertion into an empty type: an insertion copies the offsets of molecule 1 of its type whatever the count, as
+ *               InsertAndOrientMolecule does without a reservoir (src/create_molecule.f90:196-200): slot 0's frame, which a
+ *               deletion of the type's last molecule leaves in place.  So a type deleted down to zero on a replica takes
+ *               insertions again (caller-picked or by count), built from the last molecule it held in slot 0.  A type that
+ *               has never held a molecule on the replica -- mgpu_replica_set_frames gave it none, and no copy or insertion
+ *               has given it one since -- has no such geometry: a window with an insertion of it is refused with
+ *               MGPU_ERR_STATE, as are mgpu_move_trial_submit / mgpu_move_trial_decide_submit with one
+ *   reloads     a replica whose state is rewritten (mgpu_replica_set_molecules, _set_frames, _set_num_molecules, the
+ *               destination of mgpu_replica_copy) no longer waits for the driver's decision of an earlier step
  * mgpu_farm_window_wait collects the lane's OLDEST window: old_energy / new_energy [n][5] as mgpu_gcmc_trial_wait fills
  * them, verdict[c] = 0 rejected, 1 accepted and committed, 2 UNDECIDED, 4 nothing done (the replica waits for the driver's
  * decision of an earlier step), 5 idle record.  Undecided: the draw lies within the engine's relative margin (16 ulp;

@@ -231,6 +231,9 @@ struct mgpu_engine {
     std::vector<char> frames_ok;     // [R][n_res]: the frames of (replica, type) mirror its sites
     std::vector<char> frames_tight;  // [R][n_res]: every molecule's centre lies in the cell and its offsets within 0.24 L:
                                      // any device-built candidate then lies within the fast fold's range
+    std::vector<char> frames_held;   // [R][n_res]: slot 0's frame holds a molecule's offsets (set_frames gave one; a deletion
+                                     // leaves them): a device-built insertion copies them whatever the count
+                                     // (create_molecule.f90:196-200), and is refused where this is 0
     // Register-site sweeps of this engine go through pair_flat_kernel (one software-pipelined loop over all units of
     // a work unit) instead of the plane-by-plane pair_sweep_kernel: chosen at creation for topologies with short planes
     // (every plane-major residue type has at most kFlatMaxCap molecule slots) or a frozen residue; MGPU_PAIR_FLAT=0 / 1
@@ -299,6 +302,7 @@ int upload_sites(Lane &ln, const double *sites, int n_rows, int site_stride);
 int upload_sites(mgpu_engine *e, const double *sites, int n_rows, int site_stride, const int *t);
 double self_energy_host(const mgpu_engine *e, int t);
 int farm_window_normalize(mgpu_engine *e);      // mgpu_windows.hip
+int farm_clear_stall(mgpu_engine *e, int replica);   // the replica's state was rewritten: it waits for no decision (mgpu_windows.hip)
 int chain_topo(mgpu_engine *e, const Topo **d_topo);   // the engine's Topo in device memory (mgpu_windows.hip)
 // mgpu_launch.hip
 int launch_pair(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, int common_n1, int site_stride,

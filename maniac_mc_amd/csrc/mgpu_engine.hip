@@ -348,6 +348,7 @@ int mgpu_engine_create(mgpu_engine **out, int device, int n_replicas, int n_res,
     e->frozen_diff.assign(n_res, n_replicas);
     e->frozen_batch = std::getenv("MGPU_NO_FROZEN_BATCH") == nullptr;
     e->frames_tight.assign((size_t)n_replicas * n_res, 0);
+    e->frames_held.assign((size_t)n_replicas * n_res, 0);
     // Layout of the big inactive residues and the register-site pair kernel go together: "frozen" (sites sorted by
     // atom type, one group per type present) + pair_flat_kernel, or site-major + pair_sweep_kernel.  Default: flat
     // wherever a framework (inactive, >= 64 atoms) is present -- measured round 3, 2208-atom framework + 4-site water,
@@ -679,6 +680,7 @@ int mgpu_replica_set_molecules(mgpu_engine *e, int replica, int t, int n_mol, co
             for (int d = 0; d < 3; ++d) st[d * seg + j] = sites[((size_t)m * n1 + a) * 3 + d];
         }
     if ((rc = sync_all_lanes(e))) return rc;
+    if ((rc = farm_clear_stall(e, replica))) return rc;      // a rewritten replica waits for no earlier decision
     for (int d = 0; d < 3; ++d)
         HIP_TRY(hipMemcpy(e->d_pos + ((size_t)replica * 3 + d) * tp.n_cap_atoms + tp.seg_off[t], st + d * seg,
                           seg * sizeof(double), hipMemcpyHostToDevice));
@@ -791,6 +793,7 @@ int mgpu_replica_set_frames(mgpu_engine *e, int replica, int t, int n_mol, const
     }
     e->frames_ok[(size_t)replica * tp.n_res + t] = 1;
     e->frames_tight[(size_t)replica * tp.n_res + t] = tight ? 1 : 0;
+    e->frames_held[(size_t)replica * tp.n_res + t] = n_mol > 0 ? 1 : 0;      // (the slots past n_mol were zeroed above)
     return MGPU_OK;
 }
 
@@ -846,6 +849,7 @@ int mgpu_replica_set_num_molecules(mgpu_engine *e, int replica, int t, int n_mol
     }
     // a larger count exposes slots the range flag was never computed for (zero-filled, or stale coordinates)
     if (n_mol > e->h_nmol[replica * e->tp.n_res + t]) e->in_range[(size_t)replica * e->tp.n_res + t] = 0;
+    if ((rc = farm_clear_stall(e, replica))) return rc;
     e->h_nmol[replica * e->tp.n_res + t] = n_mol;
     HIP_TRY(hipMemcpy(e->d_nmol + replica * e->tp.n_res + t, &n_mol, sizeof(int), hipMemcpyHostToDevice));
     return MGPU_OK;
@@ -858,6 +862,7 @@ int mgpu_replica_copy(mgpu_engine *e, int dst, int src) {
     if (dst == src) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
+    if ((rc = farm_clear_stall(e, dst))) return rc;
     const Topo &tp = e->tp;
     HIP_TRY(hipMemcpyAsync(e->d_pos + (size_t)dst * 3 * tp.n_cap_atoms, e->d_pos + (size_t)src * 3 * tp.n_cap_atoms,
                            (size_t)3 * tp.n_cap_atoms * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
@@ -889,6 +894,7 @@ int mgpu_replica_copy(mgpu_engine *e, int dst, int src) {
                 }
         }
         e->frames_tight[(size_t)dst * tp.n_res + t] = e->frames_tight[(size_t)src * tp.n_res + t];
+        e->frames_held[(size_t)dst * tp.n_res + t] = e->frames_held[(size_t)src * tp.n_res + t];
     }
     return sync_stream(e);
 }

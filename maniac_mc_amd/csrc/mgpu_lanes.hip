@@ -346,6 +346,12 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
                     errs[q].set(c, MGPU_ERR_INVALID_ARG, "move_trial_submit: move code does not match the candidate kind");
                     return;
                 }
+                // the insertion copies slot 0's frame whatever the count (create_molecule.f90:196-200): there must be one
+                if (k == MGPU_CREATION && !e->frames_held[idx]) {
+                    errs[q].set(c, MGPU_ERR_STATE, "move_trial_submit: an insertion copies the geometry of molecule 1 of its type, "
+                                                   "and this type has never held one on this replica");
+                    return;
+                }
                 // a built candidate's centre lies in the cell (ApplyPBC / uniform insertion); with tight frames its sites are
                 // within the fast fold's range
                 if (k != MGPU_DELETION) { ln.cand_ok[c] = e->frames_tight[idx]; P.fast = P.fast && ln.cand_ok[c]; }

@@ -35,6 +35,13 @@ int farm_window_normalize(mgpu_engine *e) {
     return MGPU_OK;
 }
 
+// A replica whose state is rewritten (set_molecules / set_frames / set_num_molecules, the destination of replica_copy)
+// waits for no decision of an earlier step: its stall flag goes.  The callers have drained every lane.
+int farm_clear_stall(mgpu_engine *e, int replica) {
+    if (e->farm.d_stalled) HIP_TRY(hipMemset(e->farm.d_stalled + replica, 0, sizeof(int)));
+    return MGPU_OK;
+}
+
 }  // namespace mgpu
 
 extern "C" {
@@ -363,8 +370,9 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         FarmRec &r = recs[c];
         r = FarmRec{};
         const int mv = move[c];
-        if (mv < 0 || mv > 4) return set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: unknown move code");
-        if (replica[c] < 0 || replica[c] >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: replica out of range");
+        // (every refusal breaks out of the loop: the replicas marked so far are unmarked below)
+        if (mv < 0 || mv > 4) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: unknown move code"); break; }
+        if (replica[c] < 0 || replica[c] >= e->n_replicas) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: replica out of range"); break; }
         twice = twice || ln.mark[replica[c]] == -3;
         ln.mark[replica[c]] = -3;
         r.replica = replica[c];
@@ -380,7 +388,6 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
             // the caller picked the molecule: against the engine's counts, which must then be current
             if ((rc = check_candidate(e, c, replica[c], t[c], mc, k != MGPU_CREATION))) break;
             if (k == MGPU_CREATION && e->h_nmol[idx] >= e->tp.cap[t[c]]) { rc = set_error(MGPU_ERR_CAPACITY, "farm_window_submit: residue type is at mol_capacity"); break; }
-            if (k == MGPU_CREATION && e->h_nmol[idx] < 1) { rc = set_error(MGPU_ERR_STATE, "farm_window_submit: an insertion copies the geometry of molecule 1 of its type"); break; }
             if (k != MGPU_MOVE) pd.counts_change = true;
         } else {
             // the device picks it from the replica's count when the launch runs (FarmRec::by_count)
@@ -388,11 +395,17 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
             r.by_count = 1;
             r.sel_u = slot_u[c];
         }
+        // an insertion copies the offsets of molecule 1 of its type, whatever the count (create_molecule.f90:196-200): slot
+        // 0's frame, which a deletion leaves in place -- a type that never held a molecule on this replica has none
+        if (k == MGPU_CREATION && !e->frames_held[idx]) { rc = set_error(MGPU_ERR_STATE, "farm_window_submit: an insertion copies the geometry of molecule 1 of its type, and this type has never held one on this replica"); break; }
         n1_max = std::max(n1_max, n1);
         pd.kind[c] = k;
         // a built candidate's centre lies in the cell; with tight frames its sites are within the fast fold's range
         fast = fast && replica_in_range(e, replica[c]);
         if (k != MGPU_DELETION) { pd.ok[c] = e->frames_tight[idx]; fast = fast && pd.ok[c]; }
+        // windows still in flight behind this one must not take the fast fold if this step is accepted: the range flag is
+        // lowered now, not when the window is collected (a rejected step costs the replica the fast fold and nothing else)
+        if (k != MGPU_DELETION && !pd.ok[c]) e->in_range[idx] = 0;
         r.t = t[c]; r.m = (k == MGPU_CREATION || slot_u) ? 0 : m[c]; r.move = mv;
         r.forced = forced ? forced[c] : 0;
         if (r.forced < 0 || r.forced > 2) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: forced is 0, 1 (accept) or 2 (reject)"); break; }
@@ -463,8 +476,9 @@ int mgpu_farm_window_wait(mgpu_engine *e, int lane, double *old_energy, double *
             if (++spins >= 200000 && (spins % 65536) == 0) {
                 // long past any window's run time: make sure the stream is still alive
                 const hipError_t q = hipStreamQuery(ln.stream);
-                if (q == hipSuccess && tag[c] != pd.seq) return set_error(MGPU_ERR_HIP, "farm_window_wait: the kernel finished without publishing its results");
-                if (q != hipSuccess && q != hipErrorNotReady) return set_error(MGPU_ERR_HIP, std::string("farm_window_wait: ") + hipGetErrorString(q));
+                // (either way the window is lost: it leaves the queue, so that the lane is not left waiting for it)
+                if (q == hipSuccess && tag[c] != pd.seq) { fw.pending.pop_front(); return set_error(MGPU_ERR_HIP, "farm_window_wait: the kernel finished without publishing its results"); }
+                if (q != hipSuccess && q != hipErrorNotReady) { fw.pending.pop_front(); return set_error(MGPU_ERR_HIP, std::string("farm_window_wait: ") + hipGetErrorString(q)); }
             }
         }
     }
@@ -481,7 +495,7 @@ int mgpu_farm_window_wait(mgpu_engine *e, int lane, double *old_energy, double *
         const size_t idx = (size_t)pd.rep[c] * e->tp.n_res + pd.t[c];
         if (pd.kind[c] == MGPU_CREATION) e->h_nmol[idx] += 1;
         if (pd.kind[c] == MGPU_DELETION) e->h_nmol[idx] -= 1;
-        if (pd.kind[c] != MGPU_DELETION && !pd.ok[c]) e->in_range[idx] = 0;
+        // (the range flag was lowered at submit)
     }
     fw.pending.pop_front();
     return MGPU_OK;
