@@ -428,7 +428,10 @@ int mgpu_engine_create(mgpu_engine **out, int device, int n_replicas, int n_res,
     // lower-triangular box%matrix (the reader's triclinic cells): the exact eight-evaluation image search applies
     bx.tri_lower = (bx.triclinic && box_matrix[1] == 0.0 && box_matrix[2] == 0.0 && box_matrix[5] == 0.0 &&
                     box_matrix[0] > 0.0 && box_matrix[4] > 0.0 && box_matrix[8] > 0.0 && std::getenv("MGPU_TRI_FULL_SEARCH") == nullptr) ? 1 : 0;
+    // the least double whose sqrt reaches rc: `r2 < rc2` is then the reference's sqrt(r2) < rc (energy_utils.f90:417)
     bx.rc2 = e->rc * e->rc;
+    while (std::sqrt(std::nextafter(bx.rc2, 0.0)) >= e->rc) bx.rc2 = std::nextafter(bx.rc2, 0.0);
+    while (std::sqrt(bx.rc2) < e->rc) bx.rc2 = std::nextafter(bx.rc2, HUGE_VAL);
     bx.alpha = e->alpha;
     bx.volume = e->volume;
     bx.nk = e->nk;
