@@ -239,6 +239,21 @@ int mgpu_recip_energy_candidates(mgpu_engine *e, int n_candidates, const int *re
                                  const int *m, const int *kind, const double *sites,
                                  int site_stride, double *u_recip);
 
+/* The form of the reciprocal update for molecules of up to n1_max sites (host only, no device work): what the engine's
+ * launch chooses for a trial (kind = MGPU_RECIP_TRIAL: old + new or new only) and for a commit (MGPU_RECIP_COMMIT).
+ * out[0] = MGPU_RECIP_FORM_*; out[1] = site-states (two per site: old and new) per LDS tile; out[2] = rows of k per
+ * XY-table tile (0: the form keeps no XY table); out[3] = site tiles a molecule of n1_max sites passes through.
+ * The items of one launch are grouped by the form of each one's own residue type, so a molecule's update takes the form
+ * its type reports here whatever shares the launch.  MGPU_ERR_CAPACITY where no form fits (kmax too large). */
+#define MGPU_RECIP_TRIAL 0
+#define MGPU_RECIP_COMMIT 1
+#define MGPU_RECIP_FORM_ROWS 0              /* recip_rows_kernel: the XY table of every row in LDS */
+#define MGPU_RECIP_FORM_WIDE_VECTOR 1       /* recip_rows_wide_kernel, vector form: the XY table a tile of rows at a time */
+#define MGPU_RECIP_FORM_WIDE_MFMA 2         /* recip_rows_wide_kernel, matrix-unit form, one tile of site-states */
+#define MGPU_RECIP_FORM_WIDE_MFMA_TILED 3   /* ... several tiles of site-states, the sums carried from tile to tile */
+#define MGPU_RECIP_FORM_PER_K 4             /* recip_kernel: one k per thread, the sites a tile at a time */
+int mgpu_recip_form(const mgpu_engine *e, int n1_max, int kind, int out[4]);
+
 /* ComputeEwaldSelfInteractionSingleMol (ewald_energy.f90:308-336); configuration independent. */
 int mgpu_self_energy(const mgpu_engine *e, int t, double *e_self);
 

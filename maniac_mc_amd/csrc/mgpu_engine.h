@@ -73,6 +73,9 @@ struct ProfileSlot {
 
 // One submission lane: a HIP stream with its own scratch, so that work queued on one lane (for
 // one group of replicas) overlaps the host's processing of the other lane's results.
+// a run of items of one launch that share a reciprocal-update form (recip_groups, mgpu_launch.hip)
+struct RecipGroup { int first, n, n1_max; };
+
 struct Lane {
     hipStream_t stream = nullptr;
     DevBuf d_items, d_items2, d_sites, d_partials, d_out;
@@ -102,6 +105,13 @@ struct Lane {
     const RecipItem *d_trial_items = nullptr;   // RecipItems of the last trial, resident while last_trial_n != 0
     const RecipItem *h_trial_items = nullptr;   // their host image in h_in (valid until the next trial_submit)
     int trial_n1_max = 1;
+    // the k sweep of a trial or commit whose candidates' types take different forms (recip_groups): one launch per form,
+    // the items in group order (recip_order[slot] = candidate) in their own staging blocks; recip_slot[c] = candidate c's
+    // result slot in the trial in flight (empty: one group, slot = c)
+    std::vector<RecipGroup> recip_groups;
+    std::vector<int> recip_order, recip_slot;
+    HostBuf h_recip_items;
+    DevBuf d_recip_items;
     std::vector<int> pair_old, pair_new, intra_idx, kinds;   // per-candidate rows of the trial in flight
     std::vector<double> self_of;                              // per-candidate Ewald self term (host constant)
     std::vector<char> cand_ok;                                // per candidate: its sites are within the fast fold's range
@@ -318,6 +328,15 @@ bool recip_by_rows(const mgpu_engine *e, int n1_max);
 int recip_wide_rows_per_tile(const mgpu_engine *e, int n1_max);   // 0: the wide row form does not apply
 bool recip_wide_mfma(const mgpu_engine *e, int n1_max);
 int recip_wide_mfma_tile(const mgpu_engine *e, int n1_max);       // site-states per LDS tile (0: the matrix-unit form does not apply)
+struct RecipPlan {
+    int form = MGPU_RECIP_FORM_ROWS;   // MGPU_RECIP_FORM_*
+    bool by_rows = true;
+    int tile = 1;                      // row form: n1_max; per-k form: sites per LDS tile
+    int mfma_tile = 0;                 // matrix-unit wide form: site-states per LDS tile (else 0)
+    int wide_rpt = 0;                  // vector wide form: rows per XY tile (else 0)
+};
+RecipPlan recip_plan(const mgpu_engine *e, int n1_max, bool wide_ok);
+void recip_groups(const mgpu_engine *e, const RecipItem *items, int n, std::vector<RecipGroup> &groups, std::vector<int> &order);
 int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items, int n1_max, int site_stride,
                  bool commit, double2 *A_base, double *d_u, double *d_u_old = nullptr, const AcceptBits *accept = nullptr,
                  const double *sites_override = nullptr, const DecideArgs *decide = nullptr);

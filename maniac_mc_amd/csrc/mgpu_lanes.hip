@@ -59,7 +59,6 @@ int mgpu_recip_energy_candidates(mgpu_engine *e, int n, const int *replica, cons
     if ((rc = sync_all_lanes(e))) return rc;
     std::vector<RecipItem> items(n);
     bool any_sites = false;
-    int n1_max = 1;
     for (int c = 0; c < n; ++c) {
         if (kind[c] < MGPU_MOVE || kind[c] > MGPU_NONE) return set_error(MGPU_ERR_INVALID_ARG, "unknown candidate kind");
         const bool need_old = (kind[c] == MGPU_MOVE || kind[c] == MGPU_DELETION);
@@ -69,20 +68,51 @@ int mgpu_recip_energy_candidates(mgpu_engine *e, int n, const int *replica, cons
             any_sites = true;
             if (e->tp.n1[t[c]] > site_stride) return set_error(MGPU_ERR_INVALID_ARG, "site_stride smaller than atoms_in_res");
         }
-        n1_max = std::max(n1_max, e->tp.n1[t[c]]);
         items[c] = RecipItem{replica[c], t[c], m[c], kind[c], need_new ? c : -1, 0};
     }
     if (any_sites && !sites) return set_error(MGPU_ERR_INVALID_ARG, "recip_energy_candidates: sites is null");
+    // one launch per form of the candidates' own types (recip_groups): results in group order, order[slot] = candidate
+    std::vector<RecipGroup> groups;
+    std::vector<int> order;
+    recip_groups(e, items.data(), n, groups, order);
+    if (!order.empty()) {
+        std::vector<RecipItem> by_form(n);
+        for (int s = 0; s < n; ++s) by_form[s] = items[order[s]];
+        items.swap(by_form);
+    }
     if ((rc = e->d_items2.reserve(n * sizeof(RecipItem)))) return rc;
     if ((rc = e->d_out.reserve((size_t)n * sizeof(double)))) return rc;
     if ((rc = e->h_out.reserve((size_t)n * sizeof(double)))) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_items2.p, items.data(), n * sizeof(RecipItem), hipMemcpyHostToDevice, e->stream));
     if (any_sites && (rc = upload_sites(e, sites, n, site_stride, t))) return rc;
-    if ((rc = launch_recip(e, e->lanes[0], (const RecipItem *)e->d_items2.p, n, n1_max, site_stride, false, e->d_A, (double *)e->d_out.p)))
-        return rc;
+    for (const RecipGroup &g : groups)
+        if ((rc = launch_recip(e, e->lanes[0], (const RecipItem *)e->d_items2.p + g.first, g.n, g.n1_max, site_stride, false, e->d_A,
+                               (double *)e->d_out.p + g.first)))
+            return rc;
     HIP_TRY(hipMemcpyAsync(e->h_out.p, e->d_out.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
     if ((rc = sync_stream(e))) return rc;
-    std::memcpy(u, e->h_out.p, n * sizeof(double));
+    if (order.empty()) std::memcpy(u, e->h_out.p, n * sizeof(double));
+    else for (int s = 0; s < n; ++s) u[order[s]] = ((const double *)e->h_out.p)[s];
+    return MGPU_OK;
+}
+
+int mgpu_recip_form(const mgpu_engine *e, int n1_max, int kind, int out[4]) {
+    if (!e || !out) return set_error(MGPU_ERR_INVALID_ARG, "mgpu_recip_form: null argument");
+    if (n1_max < 1) return set_error(MGPU_ERR_INVALID_ARG, "mgpu_recip_form: n1_max must be positive");
+    if (kind != MGPU_RECIP_TRIAL && kind != MGPU_RECIP_COMMIT) return set_error(MGPU_ERR_INVALID_ARG, "mgpu_recip_form: unknown kind");
+    // (a trial and a commit take the same form: launch_recip decides by n1_max alone, so that they share the sum order)
+    const RecipPlan p = recip_plan(e, n1_max, true);
+    const size_t lds = p.by_rows ? recip_rows_lds_bytes(e, n1_max) : recip_lds_bytes(e, p.tile);
+    if (lds > 64 * 1024) return set_error(MGPU_ERR_CAPACITY, "mgpu_recip_form: kmax too large for the LDS phase tables");
+    out[0] = p.form;
+    out[2] = 0;
+    out[3] = 1;
+    switch (p.form) {
+        case MGPU_RECIP_FORM_ROWS: out[1] = 2 * n1_max; out[2] = e->n_rrows; break;
+        case MGPU_RECIP_FORM_WIDE_VECTOR: out[1] = 2 * n1_max; out[2] = p.wide_rpt; break;
+        case MGPU_RECIP_FORM_PER_K: out[1] = 2 * p.tile; out[3] = (n1_max + p.tile - 1) / p.tile; break;
+        default: out[1] = p.mfma_tile; out[3] = (((2 * n1_max + 3) & ~3) + p.mfma_tile - 1) / p.mfma_tile; break;
+    }
     return MGPU_OK;
 }
 
@@ -490,8 +520,24 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
             scratch_at += (size_t)sg.n_items * (sg.fused ? 2 : 1) * n_chunks_f;
         }
     }
-    if (!decide && (rc = launch_recip(e, ln, d_rit, n, n1_max, site_stride, false, e->d_A, d_un, d_uo)))
-        return rc;
+    ln.recip_slot.clear();
+    if (!decide) {
+        // one k sweep per form of the candidates' own types (recip_groups; a trial of one type, or of row-form types only,
+        // is one launch over d_rit as it stands): a candidate's energies do not depend on what shares its trial
+        recip_groups(e, rit, n, ln.recip_groups, ln.recip_order);
+        const RecipItem *d_rit_k = d_rit;
+        if (!ln.recip_order.empty()) {
+            if ((rc = ln.h_recip_items.reserve(rit_bytes)) || (rc = ln.d_recip_items.reserve(rit_bytes))) return rc;
+            RecipItem *h = (RecipItem *)ln.h_recip_items.p;
+            ln.recip_slot.resize(n);
+            for (int s = 0; s < n; ++s) { h[s] = rit[ln.recip_order[s]]; ln.recip_slot[ln.recip_order[s]] = s; }
+            HIP_TRY(hipMemcpyAsync(ln.d_recip_items.p, h, rit_bytes, hipMemcpyHostToDevice, ln.stream));
+            d_rit_k = (const RecipItem *)ln.d_recip_items.p;
+        }
+        for (const RecipGroup &g : ln.recip_groups)
+            if ((rc = launch_recip(e, ln, d_rit_k + g.first, g.n, g.n1_max, site_stride, false, e->d_A, d_un + g.first, d_uo + g.first)))
+                return rc;
+    }
     if (n_intra && (rc = launch_intra(e, ln, d_iit, n_intra, (const double *)ln.d_sites.p, site_stride, d_in))) return rc;
     if (decide) {
         // the k sweep comes last: its workgroups decide and commit (everything else of the trial has read the old state)
@@ -556,8 +602,9 @@ static int trial_wait_impl(mgpu_engine *e, Lane &ln, double *old_energy, double 
         for (int k = 0; k < ncomp; ++k) { o[k] = 0.0; w[k] = 0.0; }
         if (ln.pair_old[c] >= 0) { o[0] = lj[ln.pair_old[c]]; o[1] = cc[ln.pair_old[c]]; }
         if (ln.pair_new[c] >= 0) { w[0] = lj[ln.pair_new[c]]; w[1] = cc[ln.pair_new[c]]; }
-        o[2] = uo[c];
-        w[2] = un[c];
+        const int slot = ln.recip_slot.empty() ? c : ln.recip_slot[c];
+        o[2] = uo[slot];
+        w[2] = un[slot];
         if (ncomp == 5) {
             // ewald_self / intra_coulomb enter on the side where the molecule exists
             // (monte_carlo_utils.f90:298-299 creation new, :378-379 deletion old)
@@ -597,11 +644,10 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
     if (++ln.commit_stamp == 0x7fffffff) { std::fill(ln.commit_mark.begin(), ln.commit_mark.end(), -1); ln.commit_stamp = 1; }
     const int stamp = ln.commit_stamp;
     bool any_sites = false;
-    int n1_max = 1;
     // two passes in ranges, as in trial_submit_impl: count the accepted candidates of every range, then validate them and
     // write their items at the range's place -- the items keep candidate order
     struct Part {
-        int n_acc = 0, at = 0, n1_max = 1;
+        int n_acc = 0, at = 0;
         bool any_sites = false;
         std::vector<int> new_counts;  // (index into h_nmol, value) pairs applied after validation
         std::vector<int> range_lost;  // (replica, type) entries whose atoms leave the fast fold's range with this commit
@@ -662,7 +708,6 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
                 if (!ok) P.range_lost.push_back(idx);
                 if (e->tp.n1[t[c]] > site_stride) { errs[q].set(c, MGPU_ERR_INVALID_ARG, "site_stride smaller than atoms_in_res"); return; }
             }
-            P.n1_max = std::max(P.n1_max, e->tp.n1[t[c]]);
             if (kind[c] != MGPU_MOVE) { P.new_counts.push_back(idx); P.new_counts.push_back(it.aux); }
             items[at++] = it;
         }
@@ -692,7 +737,7 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         }
         return rc;
     }
-    for (int q = 0; q < parts; ++q) { any_sites = any_sites || part_of[q].any_sites; n1_max = std::max(n1_max, part_of[q].n1_max); }
+    for (int q = 0; q < parts; ++q) any_sites = any_sites || part_of[q].any_sites;
     if (n_items == 0) return MGPU_OK;
     if (any_sites && !sites && !reuse_sites) return set_error(MGPU_ERR_INVALID_ARG, "commit_candidates: sites is null");
     // Committing the lane's last trial from its resident rows: the trial's items are still on the device too,
@@ -724,6 +769,11 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         ln.d_trial_items = nullptr;
         ln.h_trial_items = nullptr;
     } else {
+        recip_groups(e, items, n_items, ln.recip_groups, ln.recip_order);
+        if (!ln.recip_order.empty()) {
+            const std::vector<RecipItem> as_accepted(items, items + n_items);
+            for (int s = 0; s < n_items; ++s) items[s] = as_accepted[ln.recip_order[s]];
+        }
         if ((rc = ln.d_items2.reserve((size_t)n_items * sizeof(RecipItem)))) return rc;
         HIP_TRY(hipMemcpyAsync(ln.d_items2.p, items, (size_t)n_items * sizeof(RecipItem), hipMemcpyHostToDevice, ln.stream));
         if (any_sites && sites) {
@@ -736,8 +786,10 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         if (!ln.commit_staged_ev) HIP_TRY(hipEventCreateWithFlags(&ln.commit_staged_ev, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(ln.commit_staged_ev, ln.stream));
         ln.commit_staged = true;
-        if ((rc = launch_recip(e, ln, (const RecipItem *)ln.d_items2.p, n_items, n1_max, site_stride, true, e->d_A, nullptr)))
-            return rc;
+        // each accepted candidate in the form of its own type, as in its trial (the items touch one replica each: any order)
+        for (const RecipGroup &g : ln.recip_groups)
+            if ((rc = launch_recip(e, ln, (const RecipItem *)ln.d_items2.p + g.first, g.n, g.n1_max, site_stride, true, e->d_A, nullptr)))
+                return rc;
     }
     for (int q = 0; q < parts; ++q) {
         const std::vector<int> &new_counts = part_of[q].new_counts;

@@ -244,12 +244,77 @@ int recip_wide_mfma_tile(const mgpu_engine *e, int n1_max) {
 }
 bool recip_wide_mfma(const mgpu_engine *e, int n1_max) { return recip_wide_mfma_tile(e, n1_max) > 0; }
 
+// The kernel launch_recip takes for molecules of up to n1_max sites.  wide_ok = false: a commit by accept mask or the deciding
+// sweep, which have the row form only.
+RecipPlan recip_plan(const mgpu_engine *e, int n1_max, bool wide_ok) {
+    RecipPlan p;
+    p.by_rows = recip_by_rows(e, n1_max);
+    p.tile = p.by_rows ? n1_max : recip_tile_sites(e, n1_max);
+    const bool wide = wide_ok && !p.by_rows;
+    p.mfma_tile = wide ? recip_wide_mfma_tile(e, n1_max) : 0;
+    p.wide_rpt = (wide && !p.mfma_tile) ? recip_wide_rows_per_tile(e, n1_max) : 0;
+    const int nss = ((2 * n1_max + 3) & ~3);
+    if (p.by_rows) p.form = MGPU_RECIP_FORM_ROWS;
+    else if (p.mfma_tile) p.form = p.mfma_tile < nss ? MGPU_RECIP_FORM_WIDE_MFMA_TILED : MGPU_RECIP_FORM_WIDE_MFMA;
+    else if (p.wide_rpt) p.form = MGPU_RECIP_FORM_WIDE_VECTOR;
+    else p.form = MGPU_RECIP_FORM_PER_K;
+    return p;
+}
+
+// Two molecules whose updates run in one launch of the form their types take alone: the same kernel with the same tile
+// shape.  Any two row-form types qualify: recip_rows_kernel's sums do not depend on the launch's largest molecule.
+static bool same_recip_form(const RecipPlan &a, const RecipPlan &b) {
+    if (a.form != b.form) return false;
+    switch (a.form) {
+        case MGPU_RECIP_FORM_ROWS: return true;
+        case MGPU_RECIP_FORM_PER_K: return a.tile == b.tile;
+        case MGPU_RECIP_FORM_WIDE_VECTOR: return a.tile == b.tile && a.wide_rpt == b.wide_rpt;
+        default: return a.mfma_tile == b.mfma_tile;
+    }
+}
+
+// The items of a launch by the form of each one's own residue type: groups of one form, items in their
+// order within a group.  order[slot] = item; empty when there is one group (every launch of one residue type, every mix of
+// row-form types), whose items stay as they are.
+void recip_groups(const mgpu_engine *e, const RecipItem *items, int n, std::vector<RecipGroup> &groups, std::vector<int> &order) {
+    groups.clear();
+    order.clear();
+    RecipPlan plan_of[kMaxRes];
+    int group_of[kMaxRes];
+    bool seen[kMaxRes] = {false};
+    std::vector<RecipPlan> group_plan;
+    int n1_all = 1;
+    for (int c = 0; c < n; ++c) {
+        const int t = items[c].t;
+        n1_all = std::max(n1_all, e->tp.n1[t]);
+        if (seen[t]) continue;
+        seen[t] = true;
+        plan_of[t] = recip_plan(e, e->tp.n1[t], true);
+        int g = 0;
+        while (g < (int)groups.size() && !same_recip_form(group_plan[g], plan_of[t])) ++g;
+        if (g == (int)groups.size()) { groups.push_back(RecipGroup{0, 0, 1}); group_plan.push_back(plan_of[t]); }
+        group_of[t] = g;
+        groups[g].n1_max = std::max(groups[g].n1_max, e->tp.n1[t]);
+    }
+    if (groups.size() <= 1) {
+        groups.assign(1, RecipGroup{0, n, n1_all});
+        return;
+    }
+    for (int c = 0; c < n; ++c) groups[group_of[items[c].t]].n += 1;
+    for (size_t g = 1; g < groups.size(); ++g) groups[g].first = groups[g - 1].first + groups[g - 1].n;
+    order.resize(n);
+    std::vector<int> at(groups.size());
+    for (size_t g = 0; g < groups.size(); ++g) at[g] = groups[g].first;
+    for (int c = 0; c < n; ++c) order[at[group_of[items[c].t]]++] = c;
+}
+
 // accept != nullptr (commit, row form only): d_items are the candidates of the lane's last trial and only
 // those whose bit is set are applied
 int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items, int n1_max, int site_stride,
                  bool commit, double2 *A_base, double *d_u, double *d_u_old, const AcceptBits *accept, const double *sites_override,
                  const DecideArgs *decide) {
-    const bool by_rows = recip_by_rows(e, n1_max);
+    const RecipPlan plan = recip_plan(e, n1_max, !accept && !decide);
+    const bool by_rows = plan.by_rows;
     const double *d_cand = sites_override ? sites_override : (const double *)ln.d_sites.p;
     static const AcceptBits no_bits{};
     const AcceptBits &bits = accept ? *accept : no_bits;
@@ -259,7 +324,7 @@ int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items
     const DecideArgs no_decide{};
     // per-k form: the molecule's sites pass through LDS a tile at a time (recip_kernel), so no molecule is too large;
     // the tile is the most sites whose two table sets fit kRecipTileBytes (a few-site molecule: one tile, as before)
-    const int tile = by_rows ? n1_max : recip_tile_sites(e, n1_max);
+    const int tile = plan.tile;
     const size_t lds = by_rows ? recip_rows_lds_bytes(e, n1_max) : recip_lds_bytes(e, tile);
     if (lds > 64 * 1024)
         return set_error(MGPU_ERR_CAPACITY, "reciprocal update: kmax too large for the LDS phase tables (" +
@@ -280,12 +345,11 @@ int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items
                                   e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_kpack, e->d_kslot, e->d_kw, A_base, d_items,  \
                                d_cand, site_stride, tile, d_u, d_u_old);                         \
     } while (0)
-    const bool wide_ok = !by_rows && !accept && !decide;
-    const bool wide_mfma = wide_ok && recip_wide_mfma(e, n1_max);
-    const int wide_rpt = wide_mfma ? 0 : (wide_ok ? recip_wide_rows_per_tile(e, n1_max) : 0);
+    const bool wide_mfma = plan.mfma_tile > 0;
+    const int wide_rpt = plan.wide_rpt;
     if (wide_mfma || wide_rpt > 0) {
         // (matrix-unit form: nss_max = the site-states of one LDS tile, a multiple of four)
-        const int ktot = e->kmax[0] + e->kmax[1] + e->kmax[2] + 3, nss_max = wide_mfma ? recip_wide_mfma_tile(e, n1_max) : 2 * n1_max;
+        const int ktot = e->kmax[0] + e->kmax[1] + e->kmax[2] + 3, nss_max = wide_mfma ? plan.mfma_tile : 2 * n1_max;
         const size_t lds_w = (size_t)nss_max * ktot * sizeof(double2) + (size_t)wide_rpt * nss_max * sizeof(double2) + (size_t)nss_max * sizeof(double) +
                              (wide_mfma ? (size_t)e->n_rrows * sizeof(int4) : 0);
         // more than one tile of site-states: the tasks' four sums travel through a per-lane block [item][task][4]

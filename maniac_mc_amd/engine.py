@@ -322,6 +322,14 @@ class Engine:
                                                   _d(sites), C.c_int(stride), _d(u)))
         return u
 
+    def recip_form(self, n1_max, commit=False):
+        """mgpu_recip_form: the form of the reciprocal update for molecules of up to n1_max sites, as a trial
+        (commit=False) or a commit takes it -- dict(form= one of _lib.RECIP_FORMS, site_states= per LDS tile,
+        rows_per_tile= of the XY table (0: none), site_tiles=)."""
+        out = np.zeros(4, np.int32)
+        check(self.L.mgpu_recip_form(self.h, C.c_int(int(n1_max)), C.c_int(_lib.RECIP_COMMIT if commit else _lib.RECIP_TRIAL), _i(out)))
+        return dict(form=_lib.RECIP_FORMS[int(out[0])], site_states=int(out[1]), rows_per_tile=int(out[2]), site_tiles=int(out[3]))
+
     def self_energy(self, t):
         e = C.c_double()
         check(self.L.mgpu_self_energy(self.h, C.c_int(t), C.byref(e)))
