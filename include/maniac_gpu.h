@@ -471,8 +471,11 @@ int mgpu_chain_get_timing(mgpu_engine *e, double us[15]);
  * One record per replica and launch; a window with an insertion / deletion must be collected before the lane's next
  * submit (the engine validates slots against its molecule counts).  A(k): a farm window leaves a replica's current A(k) in
  * one of two buffers; every other entry point that touches A(k) copies it back first (mgpu_farm_window_flush does only
- * that).  mgpu_farm_window_capacity: chains per launch (0: the path does not apply -- triclinic box, per-k reciprocal
- * form, an active molecule of more than 5 sites; otherwise min(4096, replicas)) and windows per lane in flight.  Lanes may be
+ * that).  mgpu_farm_window_capacity: chains per launch and windows per lane in flight.  Chains: min(4096, replicas) where
+ * every active residue type is a molecule of <= 5 sites whose type takes the row form, or a plane-major molecule of <= 63
+ * sites whose type takes (mgpu_recip_form, for the type alone) the row form, the vector wide form or the untiled
+ * matrix-unit wide form.  0 where the path does not apply: a triclinic box, a site-major type (64 sites or more), the per-k
+ * form, the tiled matrix-unit form, a Coulomb table over 64 KiB, or the windows' LDS beyond its budget.  Lanes may be
  * driven by different host threads (one thread per lane at a time), as the other per-lane entry points. */
 int mgpu_farm_window_capacity(const mgpu_engine *e, int *max_chains, int *max_in_flight);
 int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica, const int *t, const int *m, const int *move,

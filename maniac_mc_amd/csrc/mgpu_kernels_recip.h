@@ -740,17 +740,20 @@ __global__ __launch_bounds__(kBlock, COMMIT ? MGPU_COMMIT_MINWAVES : MGPU_RECIP_
 // formed in registers from the 1-D tables (no XY table, no row tiles, no barrier after phase 1).  Needs every row's tasks
 // to be a run of consecutive kz (the engine checks: rows_contiguous).  A sum over site-states in the matrix unit's order:
 // the trial and the commit pass share it, so A + delta is the same in both.
-template <bool COMMIT, bool BOTH, bool MFMA = false, bool TILED = false>
-__global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
-    Topo tp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
-    const int *__restrict__ trj, const double2 *__restrict__ tw, const RecipRow *__restrict__ rows, const int *__restrict__ row_first,
-    int n_rows, int rows_per_tile, int nss_max, double2 *__restrict__ A_base, const RecipItem *__restrict__ items,
-    const double *__restrict__ cand_sites, int site_stride, double *__restrict__ u_new, double *__restrict__ u_old,
-    double *__restrict__ site_tile_sums, int n_tasks) {
-    extern __shared__ double2 s_tab[];
-    __shared__ double s_red[2 * kWavesPerBlock];
-    const RecipItem it = items[blockIdx.x];
-    const int tid = threadIdx.x;
+// The sweep of ONE item in the wide row form, shared by recip_rows_wide_kernel and farm_window_kernel: phase 1 and the tiles,
+// the sums of the first kBlock threads of the workgroup (`active`) into acc / acc0 (energy sweeps) or A <- A + delta (COMMIT).
+// Every thread of the workgroup must reach the barriers inside; the others run `spare()` once, right after the barrier that
+// ends phase 1 (farm_window_kernel's intra-molecular term).  s_tab: the dynamic LDS of the form (see below); sums: the item's
+// block [task][4] of carried sums (TILED only).  ALT = 1 (energy sweeps only): A + delta is ALSO stored into A_alt, with the
+// commit's arithmetic (recip_rows_pass's ALT).
+template <bool COMMIT, bool BOTH, bool MFMA, bool TILED, int ALT = 0, class Spare>
+__device__ __forceinline__ void recip_wide_sweep(
+    const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q,
+    const int *trj, const double2 *tw, const RecipRow *rows, const int *row_first,
+    int n_rows, int rows_per_tile, int nss_max, double2 *A, const RecipItem &it, const double *cand_row,
+    double *sums_item, int n_tasks, double2 *s_tab, int tid, bool active, double &acc, double &acc0,
+    double2 *A_alt, Spare &&spare) {
+    static_assert(ALT == 0 || !COMMIT, "A + delta into another buffer: energy sweeps only");
     const int n1 = tp.n1[it.t];
     const bool use_new = (it.kind == 0 /*MOVE*/ || it.kind == 1 /*CREATION*/ || it.kind == 4 /*FOURIER_ADD*/);
     const bool use_old = (it.kind == 0 /*MOVE*/ || it.kind == 2 /*DELETION*/);
@@ -759,9 +762,8 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
     const int kofs1 = bx.kmax[0] + 1, kofs2 = bx.kmax[0] + bx.kmax[1] + 2, ktot = bx.kmax[0] + bx.kmax[1] + bx.kmax[2] + 3;
     double2 *tab = s_tab, *xyt = s_tab + (size_t)nss_max * ktot;
     double *sq = reinterpret_cast<double *>(xyt + (size_t)rows_per_tile * nss_max);
-    double *px = pos + (size_t)it.replica * 3 * tp.n_cap_atoms;
-    double *py = px + tp.n_cap_atoms, *pz = py + tp.n_cap_atoms;
-    const double *cand_row = cand_sites + (size_t)(it.src < 0 ? 0 : it.src) * site_stride * 3;
+    const double *px = pos + (size_t)it.replica * 3 * tp.n_cap_atoms;
+    const double *py = px + tp.n_cap_atoms, *pz = py + tp.n_cap_atoms;
     // ---- phase 1, once: entry (s, axis, k >= 0) at tab[s * ktot + kofs[axis] + k]; s = set * n1 + a with both sets (set 0 =
     //      the new sites, 1 = the old ones), s = a with one
     // (matrix-unit form: the site-states padded to a multiple of four with entries of 0 and charge 0 -- its steps of four
@@ -774,12 +776,11 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
     // (TILED is a template flag so that the one-tile kernel keeps its 118 registers: with the carried sums compiled in it took 156)
     const int tile_ss = MFMA ? nss_max : nss_fill, n_st = (MFMA && TILED) ? (nss_fill + tile_ss - 1) / tile_ss : 1;
     [[maybe_unused]] int4 *rowmeta = reinterpret_cast<int4 *>(sq + nss_max);
-    double2 *A = A_base + (size_t)it.replica * bx.n_slots;
     const double2 *zt = tab + kofs2;
-    double acc = 0.0, acc0 = 0.0;
     for (int st = 0; st < n_st; ++st) {
     const int ss0 = (MFMA && TILED) ? st * tile_ss : 0, ssn = (MFMA && TILED) ? min(tile_ss, nss_fill - ss0) : nss_fill;
     if (st > 0) __syncthreads();                        // every wave has left the tables of the tile before
+    if (active)
     for (int e = tid; e < ssn * ktot; e += kBlock) {
         const int sl = e / ktot, kk = e - sl * ktot, s = ss0 + sl;
         if (MFMA && s >= nss) { tab[e] = make_double2(0.0, 0.0); continue; }
@@ -793,6 +794,7 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
         const int k0 = axis == 2 ? kofs2 : (axis == 1 ? kofs1 : 0);
         tab[e] = used ? phase_entry(atom_phase(bx, axis, x, y, z), kk - k0) : make_double2(0.0, 0.0);
     }
+    if (active)
     for (int sl = tid; sl < ssn; sl += kBlock) {
         const int s = ss0 + sl;
         if (MFMA && s >= nss) { sq[sl] = 0.0; continue; }
@@ -803,7 +805,7 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
     // matrix-unit form: every row's {kx, ky, first task, first kz | tasks << 8} beside the tables, so that a tile's
     // addresses cost one LDS read instead of a chain of three global loads per tile
     if constexpr (MFMA) {
-        if (st == 0)
+        if (st == 0 && active)
             for (int rr = tid; rr < n_rows; rr += kBlock) {
                 const RecipRow r = rows[rr];
                 const int t0 = row_first[rr], t1 = row_first[rr + 1];
@@ -812,7 +814,8 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
             }
     }
     __syncthreads();
-    if constexpr (MFMA) {
+    if (!active && st == 0) spare();
+    if constexpr (MFMA) if (active) {
         typedef double double4v __attribute__((ext_vector_type(4)));
         const int lane = tid & 63, wave = tid >> 6;
         const int li = lane & 15, lk = lane >> 4;          // operand A: (kz li, site-state lk); B: (site-state lk, row li); D: (kz lk + 4 i, row li)
@@ -839,7 +842,7 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
             const int t0 = rm.z, t1 = rv ? rm.z + (rm.w >> 8) : rm.z;
             const int j0 = rm.w & 0xff;
             const bool last_st = !TILED || st == n_st - 1;
-            [[maybe_unused]] double *sums = site_tile_sums + (size_t)blockIdx.x * n_tasks * 4;
+            [[maybe_unused]] double *sums = sums_item;
             int tt[4], rjv[4];
             double2 Apv[4], Amv[4], wv[4];
 #pragma unroll
@@ -904,6 +907,10 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
                     A[2 * t + 1] = (rjv[i] & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0);
                 } else {
                     acc += fma(w.x, fma(npx, npx, npy * npy), w.y * fma(nmx, nmx, nmy * nmy));   // ewald_energy.f90:259-266
+                    if constexpr (ALT != 0) {   // the commit's stores above, to the other buffer
+                        A_alt[2 * t] = (rjv[i] & kTaskHasP) ? make_double2(npx, npy) : make_double2(0.0, 0.0);
+                        A_alt[2 * t + 1] = (rjv[i] & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0);
+                    }
                 }
             }
             }
@@ -914,6 +921,7 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
     for (int r0 = 0; r0 < n_rows; r0 += rows_per_tile) {
         const int r1 = min(n_rows, r0 + rows_per_tile);
         // ---- phase 2 for the rows of this tile: XY[row][s] = +-q X[kx] Y[ky]  (recip_rows_phase2's expression)
+        if (active)
         for (int idx = tid; idx < (r1 - r0) * nss; idx += kBlock) {
             const int rr = idx / nss, s = idx - rr * nss;
             const RecipRow r = rows[r0 + rr];
@@ -930,6 +938,7 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
         }
         __syncthreads();
         // ---- phase 3 for the tasks of those rows (recip_rows_pass's arithmetic per task)
+        if (active)
         for (int t = row_first[r0] + tid; t < row_first[r1]; t += kBlock) {
             const int rj = trj[t];
             const double2 Ap = A[2 * t], Am = A[2 * t + 1];
@@ -958,10 +967,36 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
                 A[2 * t + 1] = (rj & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0);
             } else {
                 acc += fma(w.x, fma(npx, npx, npy * npy), w.y * fma(nmx, nmx, nmy * nmy));   // ewald_energy.f90:259-266
+                if constexpr (ALT != 0) {   // the commit's stores above, to the other buffer
+                    A_alt[2 * t] = (rj & kTaskHasP) ? make_double2(npx, npy) : make_double2(0.0, 0.0);
+                    A_alt[2 * t + 1] = (rj & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0);
+                }
             }
         }
         __syncthreads();                                 // the next tile overwrites XY
     }
+}
+
+template <bool COMMIT, bool BOTH, bool MFMA = false, bool TILED = false>
+__global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
+    Topo tp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
+    const int *__restrict__ trj, const double2 *__restrict__ tw, const RecipRow *__restrict__ rows, const int *__restrict__ row_first,
+    int n_rows, int rows_per_tile, int nss_max, double2 *__restrict__ A_base, const RecipItem *__restrict__ items,
+    const double *__restrict__ cand_sites, int site_stride, double *__restrict__ u_new, double *__restrict__ u_old,
+    double *__restrict__ site_tile_sums, int n_tasks) {
+    extern __shared__ double2 s_tab[];
+    __shared__ double s_red[2 * kWavesPerBlock];
+    const RecipItem it = items[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int n1 = tp.n1[it.t];
+    double *px = pos + (size_t)it.replica * 3 * tp.n_cap_atoms;
+    double *py = px + tp.n_cap_atoms, *pz = py + tp.n_cap_atoms;
+    const double *cand_row = cand_sites + (size_t)(it.src < 0 ? 0 : it.src) * site_stride * 3;
+    double2 *A = A_base + (size_t)it.replica * bx.n_slots;
+    double acc = 0.0, acc0 = 0.0;
+    recip_wide_sweep<COMMIT, BOTH, MFMA, TILED>(tp, bx, pos, res_q, trj, tw, rows, row_first, n_rows, rows_per_tile, nss_max, A, it, cand_row,
+                                                site_tile_sums + (size_t)blockIdx.x * n_tasks * 4, n_tasks, s_tab, tid, true, acc, acc0,
+                                                nullptr, [] {});
     if (!COMMIT) {
         acc = wave_sum(acc);
         if (BOTH) acc0 = wave_sum(acc0);
@@ -1225,16 +1260,15 @@ static __global__ void intra_kernel(Topo tp, BoxDev bx, const double *__restrict
 // every lane adds its terms in that (a1, a2) order and the lanes are added by the wave butterfly: a fixed order, the same
 // bits run to run (the one-thread loop's order it is not: the two differ by rounding, ~1e-13 relative).
 constexpr int kIntraTile = 512;                  // sites per LDS tile (16 KB)
-static __global__ __launch_bounds__(64) void intra_wave_kernel(Topo tp, BoxDev bx, const double *__restrict__ pos, const double *__restrict__ res_q,
-                                                        const PairItem *__restrict__ items, int n_items, const double *__restrict__ cand_sites,
-                                                        int site_stride, double *__restrict__ u_out) {
-    __shared__ double4 s_a[kIntraTile], s_b[kIntraTile];
-    const int i = blockIdx.x;
-    if (i >= n_items) return;
-    const PairItem it = items[i];
+// The sum of one item by ONE WAVE (shared by intra_wave_kernel and farm_window_kernel): s_a / s_b hold TILE sites each,
+// `sync()` orders the wave's LDS stores before its loads.  With n1 <= TILE the tiling has one tile, so the lanes' terms
+// and their order do not depend on TILE.
+template <int TILE, class Sync>
+__device__ __forceinline__ double intra_energy_wave(const Topo &tp, const BoxDev &bx, const double *pos,
+                                                   const double *res_q, const PairItem &it,
+                                                   const double *cand_sites, int site_stride, int lane, double4 *s_a,
+                                                   double4 *s_b, Sync &&sync) {
     const int n1 = tp.n1[it.t];
-    if (n1 <= kIntraThreadMax) return;                        // intra_kernel's
-    const int lane = threadIdx.x;
     const double *px = pos + (size_t)it.replica * 3 * tp.n_cap_atoms;
     const double *py = px + tp.n_cap_atoms, *pz = py + tp.n_cap_atoms;
     auto site = [&](int a) {
@@ -1250,15 +1284,15 @@ static __global__ __launch_bounds__(64) void intra_wave_kernel(Topo tp, BoxDev b
     };
     double u = 0.0;
     // tiles (A, B) with B >= A: a1 runs over tile A, a2 over tile B
-    for (int a0 = 0; a0 < n1; a0 += kIntraTile) {
-        const int na = min(kIntraTile, n1 - a0);
-        __syncthreads();
+    for (int a0 = 0; a0 < n1; a0 += TILE) {
+        const int na = min(TILE, n1 - a0);
+        sync();
         for (int a = lane; a < na; a += 64) s_a[a] = site(a0 + a);
-        for (int b0 = a0; b0 < n1; b0 += kIntraTile) {
-            const int nb = min(kIntraTile, n1 - b0);
-            __syncthreads();
+        for (int b0 = a0; b0 < n1; b0 += TILE) {
+            const int nb = min(TILE, n1 - b0);
+            sync();
             for (int b = lane; b < nb; b += 64) s_b[b] = site(b0 + b);
-            __syncthreads();
+            sync();
             for (int a = 0; a < na; ++a) {
                 const double4 p1 = s_a[a];
                 const int first = (b0 == a0) ? a + 1 : 0;
@@ -1272,7 +1306,19 @@ static __global__ __launch_bounds__(64) void intra_wave_kernel(Topo tp, BoxDev b
         }
     }
     u = wave_sum(u);
-    if (lane == 0) u_out[i] = u * kEps0InvEvA / kKbEvK;
+    return u * kEps0InvEvA / kKbEvK;
+}
+static __global__ __launch_bounds__(64) void intra_wave_kernel(Topo tp, BoxDev bx, const double *__restrict__ pos, const double *__restrict__ res_q,
+                                                        const PairItem *__restrict__ items, int n_items, const double *__restrict__ cand_sites,
+                                                        int site_stride, double *__restrict__ u_out) {
+    __shared__ double4 s_a[kIntraTile], s_b[kIntraTile];
+    const int i = blockIdx.x;
+    if (i >= n_items) return;
+    const PairItem it = items[i];
+    if (tp.n1[it.t] <= kIntraThreadMax) return;               // intra_kernel's
+    const int lane = threadIdx.x;
+    const double u = intra_energy_wave<kIntraTile>(tp, bx, pos, res_q, it, cand_sites, site_stride, lane, s_a, s_b, [] { __syncthreads(); });
+    if (lane == 0) u_out[i] = u;
 }
 
 }  // namespace mgpu

@@ -38,6 +38,9 @@ namespace mgpu {
 // (link = -2).  Orthorhombic boxes, row-form k sweep, molecules of <= kMaxFusedSitesWide sites.
 // ------------------------------------------------------------------------------------------
 constexpr int kChainMaxCand = 16;
+#ifndef MGPU_FARM_WIDE_MINWAVES
+#define MGPU_FARM_WIDE_MINWAVES 2   // farm_window_kernel<..., WIDE>: 140 VGPRs, no spills (at 4: 128 and 32 bytes of spills); DESIGN 4.4
+#endif
 constexpr int kChainBlock = kPairBlock;          // 512 threads: 8 pair waves; the k role uses the first kBlock of them
 constexpr int kChainStamps = 8;                  // stage time stamps per role (k role of candidate 0, first pair workgroup, resolver)
 struct ChainResult {                             // what the k role of candidate c leaves for the resolving workgroup
@@ -344,8 +347,23 @@ struct FarmArgs {
     double t_step, r_step, temperature, margin;
     double self_of_type[kMaxRes];
     FarmRec inline_recs[kFarmInline];
+    // the WIDE instances only (behind everything the narrow ones read): per residue type the k role's form and its tile,
+    // the rows' first tasks, and where the pair role's slabs start in dynamic LDS
+    const int *row_first;
+    int wide_at;                                 // bytes: the Coulomb table's, rounded up to 16
+    signed char kform[kMaxRes];                  // kFarmForm*
+    int wide_rpt[kMaxRes];                       // vector form: rows per tile
+    int wide_nss[kMaxRes];                       // site-states per tile (the layout of the form's tables)
 };
 static_assert(sizeof(BoxDev) + sizeof(FarmArgs) + 160 <= 4096, "a farm window must fit the kernel-argument segment");
+// WIDE instances (launches with a molecule of more than kMaxFusedSitesWide sites, at most kFarmWideSites - 1): the k role's
+// form per residue type, as recip_plan picks it for the type alone
+constexpr int kFarmFormRows = 0, kFarmFormWideVector = 1, kFarmFormWideMfma = 2;
+constexpr int kFarmWideSites = 64;               // candidate row stride of a wide chain (plane-major types: n1 <= 63)
+// dynamic LDS of a wide chain's k role: candidate row | the intra wave's two site tiles | the form's tables
+constexpr size_t kFarmKFront = (size_t)kFarmWideSites * 3 * sizeof(double) + 2 * (size_t)kFarmWideSites * sizeof(double4);
+// dynamic LDS of the pair role behind the Coulomb table: per wave a candidate row, a site slab and a type slab (NS = 0 sweep)
+constexpr size_t kFarmWidePairBytes = (size_t)kPairWaves * ((kFarmWideSites * 3 + kSiteChunk * 4) * sizeof(double) + kSiteChunk * sizeof(int));
 
 // Diagnostic builds only (-DMGPU_FARM_STAMPS, tools/farm_stages.py; the shipped library has none of this): wall-clock stamps of
 // chain 0's k role (row 0), the launch's first pair workgroup (row 1) and chain 0's resolver (row 2).
@@ -475,11 +493,116 @@ __device__ __forceinline__ void farm_resolve(const Topo &tp, const BoxDev &bx, d
     publish_tag();
 }
 
+// ---- the WIDE instances' pieces for a chain of more than kMaxFusedSitesWide sites
+// One pair work unit (entry, split) by ONE WAVE: the candidate row rebuilt into the wave's row in dynamic LDS, then
+// pair_sweep_item<0, ...> with the wave's slabs, exactly the batched path's NS = 0 sweep of the unit.
+__device__ __forceinline__ void farm_wide_pair_unit(const Topo &tp, const BoxDev &bx, const double *pos, const int *nmol, const double *res_q,
+                                                    const int *res_atype, const double2 *pair_tab, const FarmArgs &g, const FarmRec &rec,
+                                                    int kind, int ent, int split, int ns, char *s_dyn, const double2 *s_pair, int wave, int lane,
+                                                    int wg) {
+    double *slab = reinterpret_cast<double *>(s_dyn + g.wide_at);
+    double *cand = slab + (size_t)wave * kFarmWideSites * 3;
+    double *w_site = slab + (size_t)kPairWaves * kFarmWideSites * 3 + (size_t)wave * kSiteChunk * 4;
+    int *w_sty = reinterpret_cast<int *>(slab + (size_t)kPairWaves * (kFarmWideSites * 3 + kSiteChunk * 4)) + wave * kSiteChunk;
+    if (ent == 1) {
+        const TrialFrame f = trial_frame(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+        if (lane < tp.n1[rec.t]) {
+            double off[3];
+            trial_offset(tp, f, rec.replica, rec.t, lane, off);
+            for (int d = 0; d < 3; ++d) cand[lane * 3 + d] = f.com[d] + off[d];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    // old state: the resident molecule; new state: the candidate row; an insertion excludes nothing
+    const PairItem it{rec.replica, rec.t, kind == 1 ? -1 : rec.m, ent == 1 ? 0 : -1, 0};
+    pair_sweep_item<0, false, false, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, w_site, w_sty, it, cand,
+                                                         kFarmWideSites, split, ns, lane, g.partials, wg);
+}
+
+// The k role of chain c (every thread of the workgroup; s_skip is clear): candidate row, the sweep of the type's form with A +
+// delta into the replica's other A(k) buffer, the intra term of an insertion / deletion on the spare waves meanwhile, and the
+// energies into g.res[c].  Dynamic LDS: kFarmKFront bytes of row and intra tiles, the form's tables behind them.
+__device__ __forceinline__ void farm_wide_k_role(const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q, const int *trj,
+                                                 const double2 *tw, int n_tasks, const RecipRow *rows, int n_rows, double2 *A_base,
+                                                 const FarmArgs &g, const FarmRec &rec, int c, int acur, char *s_dyn, double *s_red, int tid) {
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
+    const int n1 = tp.n1[rec.t];
+    double *cand = reinterpret_cast<double *>(s_dyn);
+    double4 *intra_a = reinterpret_cast<double4 *>(s_dyn + (size_t)kFarmWideSites * 3 * sizeof(double)), *intra_b = intra_a + kFarmWideSites;
+    double2 *tabs = reinterpret_cast<double2 *>(s_dyn + kFarmKFront);
+    if (kind != 2 && tid < n1) {
+        const TrialFrame f = trial_frame(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+        double off[3];
+        trial_offset(tp, f, rec.replica, rec.t, tid, off);
+        for (int d = 0; d < 3; ++d) cand[tid * 3 + d] = f.com[d] + off[d];
+    }
+    __syncthreads();
+    double2 *A = (acur ? g.A_alt : A_base) + (size_t)rec.replica * bx.n_slots;
+    double2 *A_other = (acur ? A_base : g.A_alt) + (size_t)rec.replica * bx.n_slots;
+    const RecipItem it{rec.replica, rec.t, kind == 1 ? -1 : rec.m, kind, 0, 0, 0};
+    const bool active = tid < kBlock;
+    // ComputeIntraResidueRealCoulombEnergySingleMol of the inserted (candidate row) / deleted (resident) molecule, in the form
+    // launch_intra gives its size: one thread up to kIntraThreadMax sites, one wave above
+    auto spare = [&] {
+        if (kind == 0) return;
+        const PairItem pit{rec.replica, rec.t, rec.m, kind == 1 ? 0 : -1, 0};
+        if (n1 <= kIntraThreadMax) {
+            if (tid == kBlock)
+                __hip_atomic_store(&g.res[c].intra, intra_energy(tp, bx, pos, res_q, pit, cand, kFarmWideSites), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        } else if (wave == kWavesPerBlock) {
+            const double u = intra_energy_wave<kFarmWideSites>(tp, bx, pos, res_q, pit, cand, kFarmWideSites, lane, intra_a, intra_b, [] {
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            });
+            if (lane == 0) __hip_atomic_store(&g.res[c].intra, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    double acc = 0.0, acc0 = 0.0;
+    const int form = g.kform[rec.t];
+    if (form == kFarmFormRows) {
+        const RecipLds v = recip_lds_view(tp, bx, it, n_rows, tabs);
+        RecipInFlight<kRecipTaskChunk> inflight;
+        recip_rows_tables(tp, bx, pos, res_q, rows, n_rows, it, cand, v, tid, active,
+                          [&] { recip_rows_prefetch<false>(inflight, trj, tw, n_tasks, A, tid); });
+        if (active) recip_rows_pass<false, true, kRecipTaskChunk, 1>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0, A_other);
+        else spare();
+    } else if (form == kFarmFormWideMfma) {
+        recip_wide_sweep<false, true, true, false, 1>(tp, bx, pos, res_q, trj, tw, rows, g.row_first, n_rows, 0, g.wide_nss[rec.t], A, it, cand,
+                                                      nullptr, n_tasks, tabs, tid, active, acc, acc0, A_other, spare);
+    } else {
+        recip_wide_sweep<false, true, false, false, 1>(tp, bx, pos, res_q, trj, tw, rows, g.row_first, n_rows, g.wide_rpt[rec.t],
+                                                       g.wide_nss[rec.t], A, it, cand, nullptr, n_tasks, tabs, tid, active, acc, acc0, A_other,
+                                                       spare);
+    }
+    if (active) {
+        acc = wave_sum(acc);
+        acc0 = wave_sum(acc0);
+        if (lane == 0) { s_red[2 * wave] = acc; s_red[2 * wave + 1] = acc0; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double u = 0.0, u0 = 0.0;
+        for (int wv = 0; wv < kWavesPerBlock; ++wv) { u += s_red[2 * wv]; u0 += s_red[2 * wv + 1]; }
+        __hip_atomic_store(&g.res[c].u_new, u * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ewald_energy.f90:272
+        __hip_atomic_store(&g.res[c].u_old, u0 * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // (launch bounds: four waves per SIMD = two of these 8-wave workgroups per CU, i.e. at most 128 VGPRs.  Left to itself
 //  the compiler took 130-132 -- ONE workgroup per CU -- and every farm of more than ~28 chains paid a second round of
 //  workgroups: 64 chains 22 -> 32 us per step, 512 chains 57 -> 82 us.)
-template <bool FLAT, bool FASTW>
-__global__ __launch_bounds__(kChainBlock, 4) void farm_window_kernel(
+// WIDE: a launch with a chain of a molecule of 6..63 sites.  Such a chain's pair units run the LDS-staged
+// NS = 0 sweep (the batched path's kernel for the size: pair_sweep_kernel<0, ...>, the engine's nsplit) with its candidate row
+// and slabs in dynamic LDS; its k role takes the form of its own type -- the row form, or the wide row form (vector or
+// matrix unit, one tile of site-states: recip_wide_sweep) -- storing A + delta into the other A(k) buffer; its intra term is
+// the thread form up to kIntraThreadMax sites and the wave form above, on the k workgroup's spare waves.  Chains of
+// <= kMaxFusedSitesWide sites take the narrow instance's code.
+template <bool FLAT, bool FASTW, bool WIDE = false>
+__global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) void farm_window_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
@@ -552,7 +675,9 @@ __global__ __launch_bounds__(kChainBlock, 4) void farm_window_kernel(
         // ---------------- k role: chain c_lo
         const int c = c_lo;
         const FarmRec &rec = s_rec[0];
-        if (!s_skip[0]) {
+        if (WIDE && !s_skip[0] && tp.n1[rec.t] > kMaxFusedSitesWide) {
+            farm_wide_k_role(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, A_base, g, rec, c, s_acur, s_dyn, s_red, tid);
+        } else if (!s_skip[0]) {
             const int kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
             const int n1 = tp.n1[rec.t];
             if (kind != 2 && tid < n1) {
@@ -604,7 +729,9 @@ __global__ __launch_bounds__(kChainBlock, 4) void farm_window_kernel(
             const int kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
             const int ent = j / ns, split = j - ent * ns;
             const int n1 = tp.n1[rec.t];
-            if (ent == 0 ? kind != 1 : kind != 2) {
+            if (WIDE && n1 > kMaxFusedSitesWide && (ent == 0 ? kind != 1 : kind != 2)) {
+                farm_wide_pair_unit(tp, bx, pos, nmol, res_q, res_atype, pair_tab, g, rec, kind, ent, split, ns, s_dyn, s_pair, wave, lane, wg);
+            } else if (ent == 0 ? kind != 1 : kind != 2) {
                 double *cand = &s_cand[wave][0];
                 if (ent == 1) {
                     const TrialFrame f = trial_frame(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);

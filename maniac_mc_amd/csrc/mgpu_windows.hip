@@ -256,19 +256,71 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
 // kFarmDepth windows per lane may be in flight (a farm whose move selection does not depend on earlier outcomes -- NVT --
 // queues the next step before it has seen the last).
 
-// chains per launch the engine accepts, 0 where the path does not apply (triclinic box, an active molecule of more than
-// kMaxFusedSitesWide sites, per-k reciprocal form, a Coulomb table beyond 64 KiB)
+// The k role a farm window gives a chain of residue type t -- the form recip_plan picks for the type alone, as the batched
+// path's per-type launches do (recip_groups) -- and the dynamic LDS that role needs.  false: windows do not take the type
+// (site-major types, i.e. molecules of kFarmWideSites sites or more; a molecule of <= kMaxFusedSitesWide sites whose type
+// does not take the row form; a larger one in a triclinic box, or whose type takes the per-k or the tiled matrix-unit form).
+struct FarmTypeForm {
+    int form = kFarmFormRows, rpt = 0, nss = 0;
+    size_t lds = 0;
+};
+static bool farm_type_form(const mgpu_engine *e, int t, FarmTypeForm &f) {
+    const int n1 = e->tp.n1[t];
+    if (e->tp.site_major[t] || n1 >= kFarmWideSites) return false;
+    const RecipPlan p = recip_plan(e, n1, true);
+    f = FarmTypeForm{};
+    if (n1 <= kMaxFusedSitesWide) {                                 // the narrow instance's chains
+        if (p.form != MGPU_RECIP_FORM_ROWS) return false;
+        f.lds = recip_rows_lds_bytes(e, n1);
+        return true;
+    }
+    if (e->bx.triclinic) return false;
+    const size_t ktot = (size_t)e->kmax[0] + e->kmax[1] + e->kmax[2] + 3;
+    switch (p.form) {
+        case MGPU_RECIP_FORM_ROWS:
+            f.lds = kFarmKFront + recip_rows_lds_bytes(e, n1);
+            return true;
+        case MGPU_RECIP_FORM_WIDE_VECTOR:                           // launch_recip's tables with nss_max = 2 n1
+            f.form = kFarmFormWideVector; f.rpt = p.wide_rpt; f.nss = 2 * n1;
+            f.lds = kFarmKFront + (size_t)f.nss * ktot * sizeof(double2) + (size_t)f.rpt * f.nss * sizeof(double2) + (size_t)f.nss * sizeof(double);
+            return true;
+        case MGPU_RECIP_FORM_WIDE_MFMA:                             // one tile of site-states
+            f.form = kFarmFormWideMfma; f.nss = p.mfma_tile;
+            f.lds = kFarmKFront + (size_t)f.nss * ktot * sizeof(double2) + (size_t)f.nss * sizeof(double) + (size_t)e->n_rrows * sizeof(int4);
+            return true;
+        default:                                                    // the tiled matrix-unit form, the per-k form
+            return false;
+    }
+}
+
+// Dynamic LDS of the WIDE instances for this engine: the larger of the pair role's (Coulomb table, then the waves' candidate
+// rows and slabs), the k role's over the active types, and the resolving waves' scratch.  gfx950 gives a workgroup up to
+// 160 KiB; the instances' static LDS takes up to kFarmWideStaticMax of it.
+constexpr size_t kFarmWideStaticMax = 16 * 1024, kFarmWideLdsMax = 160 * 1024 - kFarmWideStaticMax;
+static size_t farm_wide_lds(const mgpu_engine *e) {
+    size_t lds = ((e->coul_bytes + 15) & ~(size_t)15) + kFarmWidePairBytes;
+    lds = std::max(lds, (size_t)kPairWaves * (4 * e->pair_nsplit + 4) * sizeof(double));
+    for (int t = 0; t < e->tp.n_res; ++t) {
+        FarmTypeForm f;
+        if (!e->frozen[t] && farm_type_form(e, t, f)) lds = std::max(lds, f.lds);      // (every type a chain may carry)
+    }
+    return lds;
+}
+
+// chains per launch the engine accepts, 0 where the path does not apply: a triclinic box, an active type windows do not take
+// (farm_type_form), a Coulomb table beyond 64 KiB, LDS beyond the budget
 static int farm_max_chains(const mgpu_engine *e) {
     if (e->bx.triclinic) return 0;
-    int n1_max = 1;
+    bool wide = false;
     for (int t = 0; t < e->tp.n_res; ++t) {
         if (!e->is_active[t]) continue;
-        if (e->tp.n1[t] > kMaxFusedSitesWide || e->tp.site_major[t]) return 0;
-        n1_max = std::max(n1_max, e->tp.n1[t]);
+        FarmTypeForm f;
+        if (!farm_type_form(e, t, f)) return 0;
+        wide = wide || e->tp.n1[t] > kMaxFusedSitesWide;
     }
-    if (!recip_by_rows(e, n1_max)) return 0;
     if (e->coul_bytes > 64 * 1024) return 0;
     if ((size_t)kPairWaves * (4 * e->pair_nsplit + 4) * sizeof(double) > 64 * 1024) return 0;      // the resolving waves' scratch
+    if (wide && farm_wide_lds(e) > kFarmWideLdsMax) return 0;
     return std::min(kFarmMaxChains, e->n_replicas);
 }
 
@@ -379,7 +431,8 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         if (mv == 0) continue;                                   // the chain does nothing this step
         if (t[c] < 0 || t[c] >= e->tp.n_res) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: residue type out of range"); break; }
         const int n1 = e->tp.n1[t[c]];
-        if (n1 > kMaxFusedSitesWide || e->tp.site_major[t[c]] || e->frozen[t[c]]) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: molecule too large for the one-launch path"); break; }
+        FarmTypeForm tf;
+        if (!farm_type_form(e, t[c], tf) || e->frozen[t[c]]) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: molecule too large for the one-launch path"); break; }
         const size_t idx = (size_t)replica[c] * e->tp.n_res + t[c];
         if (!e->d_com || !e->frames_ok[idx]) { rc = set_error(MGPU_ERR_STATE, "farm_window_submit: no molecule frames for chain " + std::to_string(c) + " (mgpu_replica_set_frames)"); break; }
         const int k = mv <= 2 ? MGPU_MOVE : (mv == 3 ? MGPU_CREATION : MGPU_DELETION);
@@ -421,8 +474,17 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         return set_error(MGPU_ERR_STATE, "farm_window_submit: a window with an insertion / deletion needs the lane's earlier windows collected "
                                          "(its molecule counts must be current)");
     const int nsplit = e->pair_nsplit;
-    const size_t lds = std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), (size_t)kPairWaves * (4 * nsplit + 4) * sizeof(double));
-    if (lds > 64 * 1024) return set_error(MGPU_ERR_CAPACITY, "farm_window_submit: the window does not fit the LDS budget");
+    // a chain of more than kMaxFusedSitesWide sites: the WIDE instance (its own LDS rule), else the narrow one
+    const bool wide = n1_max > kMaxFusedSitesWide;
+    const size_t lds = wide ? farm_wide_lds(e)
+                            : std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), (size_t)kPairWaves * (4 * nsplit + 4) * sizeof(double));
+    if (lds > (wide ? kFarmWideLdsMax : 64 * 1024)) return set_error(MGPU_ERR_CAPACITY, "farm_window_submit: the window does not fit the LDS budget");
+    if (lds > 64 * 1024) {
+        // beyond 64 KiB of dynamic LDS a kernel opts in (gfx950: up to 160 KiB per workgroup); only the WIDE instances get here
+        const void *wide_kernels[4] = {(const void *)farm_window_kernel<false, false, true>, (const void *)farm_window_kernel<false, true, true>,
+                                       (const void *)farm_window_kernel<true, false, true>, (const void *)farm_window_kernel<true, true, true>};
+        for (const void *k : wide_kernels) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
     fw.seq += 1;
     for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
     g.recs = fw.h_recs + (size_t)slot * fw.cap;
@@ -433,6 +495,15 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     g.seq = pd.seq;
     g.n = n; g.nsplit = nsplit;
     g.t_step = t_step; g.r_step = r_step; g.temperature = temperature; g.margin = e->chain.margin;
+    if (wide) {
+        g.row_first = e->d_row_first;
+        g.wide_at = (int)((e->coul_bytes + 15) & ~(size_t)15);
+        for (int tt = 0; tt < e->tp.n_res; ++tt) {
+            FarmTypeForm f;
+            if (!farm_type_form(e, tt, f)) continue;              // (no chain of such a type passed the checks above)
+            g.kform[tt] = (signed char)f.form; g.wide_rpt[tt] = f.rpt; g.wide_nss[tt] = f.nss;
+        }
+    }
     const int wpc = 2 * nsplit;
     const int grid = (n * wpc + kPairWaves - 1) / kPairWaves + n;
     const bool ff = fast && e->pair_fast_fold;
@@ -441,12 +512,19 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     ln.d_trial_items = nullptr;
     ln.h_trial_items = nullptr;
     e->farm.dirty = true;
-#define MGPU_LAUNCH_FARM(FL, FW)                                                                                           \
-    hipLaunchKernelGGL((farm_window_kernel<FL, FW>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, \
-                       e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, \
-                       e->d_A, g)
-    if (e->pair_flat) { if (ff) MGPU_LAUNCH_FARM(true, true); else MGPU_LAUNCH_FARM(true, false); }
-    else { if (ff) MGPU_LAUNCH_FARM(false, true); else MGPU_LAUNCH_FARM(false, false); }
+#define MGPU_LAUNCH_FARM(FL, FW, WI)                                                                                       \
+    do {                                                                                                                   \
+        hipLaunchKernelGGL((farm_window_kernel<FL, FW, WI>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, \
+                           e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, \
+                           e->d_A, g);                                                                                     \
+    } while (0)
+    if (wide) {
+        if (e->pair_flat) { if (ff) MGPU_LAUNCH_FARM(true, true, true); else MGPU_LAUNCH_FARM(true, false, true); }
+        else { if (ff) MGPU_LAUNCH_FARM(false, true, true); else MGPU_LAUNCH_FARM(false, false, true); }
+    } else {
+        if (e->pair_flat) { if (ff) MGPU_LAUNCH_FARM(true, true, false); else MGPU_LAUNCH_FARM(true, false, false); }
+        else { if (ff) MGPU_LAUNCH_FARM(false, true, false); else MGPU_LAUNCH_FARM(false, false, false); }
+    }
 #undef MGPU_LAUNCH_FARM
     HIP_TRY(hipGetLastError());
     fw.pending.push_back(std::move(pd));

@@ -23,14 +23,18 @@ def main():
     ap.add_argument("--threads", type=int, default=2)
     ap.add_argument("--drivers", default="1", help="driver threads (each runs its own lanes' windows)")
     ap.add_argument("--side", type=int, default=15)
-    ap.add_argument("--workload", default="spce", choices=("spce", "co2_gcmc"),
-                    help="spce: the 10 125-atom box, translation / rotation; co2_gcmc: bench.py's 50 A CO2 box, insertion / deletion only")
+    ap.add_argument("--workload", default="spce", choices=("spce", "co2_gcmc", "adsorbate24"),
+                    help="spce: the 10 125-atom box, translation / rotation; co2_gcmc: bench.py's 50 A CO2 box, insertion / deletion only; "
+                         "adsorbate24: bench.py's 64 rigid 24-site adsorbates in a 60 A box, translation / rotation")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     from maniac_mc_amd import synth
     from maniac_mc_amd.fortran_host import FortranFarm
     if args.workload == "spce":
         s = synth.spce_box(args.side, seed=12345)
+        kw = dict(translation_step=0.3, rotation_step=0.3, p_translation=0.5)
+    elif args.workload == "adsorbate24":
+        s = synth.rigid_adsorbate_box(n_mol=64, L=60.0, seed=17)
         kw = dict(translation_step=0.3, rotation_step=0.3, p_translation=0.5)
     else:
         s = synth.co2_box(64, seed=13)
