@@ -105,6 +105,13 @@ struct Lane {
     const RecipItem *d_trial_items = nullptr;   // RecipItems of the last trial, resident while last_trial_n != 0
     const RecipItem *h_trial_items = nullptr;   // their host image in h_in (valid until the next trial_submit)
     int trial_n1_max = 1;
+    // the k sweep of the trial in flight stored every candidate's A + delta into its replica's other A(k) buffer (one
+    // row-form launch, one candidate per replica), under alt_owner stamp trial_stamp: a commit of it may switch buffers
+    bool trial_alt = false;
+    unsigned long long trial_stamp = 0;
+    // accepted share of the lane's last commit from its resident rows: the stores pay for every candidate, the switch saves
+    // the commit pass of the accepted ones only (measured alone, 4096 candidates: k sweep 38 -> 69 us, commit 40 -> 6 us)
+    double accept_share = 1.0;
     // the k sweep of a trial or commit whose candidates' types take different forms (recip_groups): one launch per form,
     // the items in group order (recip_order[slot] = candidate) in their own staging blocks; recip_slot[c] = candidate c's
     // result slot in the trial in flight (empty: one group, slot = c)
@@ -276,13 +283,24 @@ struct mgpu_engine {
         long long windows = 0, undecided = 0;
         bool timing = false;                         // stage stamps wanted (mgpu_chain_set_timing)
     } chain;
-    // farm windows (mgpu_farm_window_*): the other A(k) buffer of every replica, which of the two is current, and the
-    // per-replica stall flag, all allocated on first use; `dirty` = some replica's current A(k) may live in d_A_alt (every
-    // entry point that reads or writes A(k) outside a farm window first copies it back: farm_window_normalize)
+    // The A(k) double buffer: the other buffer of every replica and which of the two is its current one (d_acur[r] = 1:
+    // d_A_alt), allocated on first use (alt_reserve).  Farm windows and the batched trials store every candidate's A + delta into
+    // the other buffer, and an accepted candidate is committed by making that buffer current.  `a_switched` = some replica's
+    // current A(k) may live in d_A_alt: the synchronous entry points copy it back into d_A first (normalize_A); the kernels of
+    // the lanes pick each replica's current buffer themselves (RecipA).
+    double2 *d_A_alt = nullptr;
+    int *d_acur = nullptr;
+    std::atomic<bool> a_switched{false};
+    // alt_owner[r]: the stamp of the batched trial whose A + delta replica r's other buffer holds (0: none -- anything else
+    // that rewrote the replica's state since clears it); trial_stamps hands the stamps out.  Entries are written by the lanes'
+    // driver threads (each for its own replicas): relaxed atomic accesses.
+    std::vector<unsigned long long> alt_owner;
+    std::atomic<unsigned long long> trial_stamps{0};
+    bool commit_pass = false;        // MGPU_COMMIT_PASS=1: every commit recomputes A + delta (no commit by switching; tests, A/B)
+    std::mutex alt_mu;               // the double buffer's first allocation
+    // farm windows (mgpu_farm_window_*): the per-replica stall flag, allocated on first use, and the window counters
     struct Farm {
-        double2 *d_A_alt = nullptr;
-        int *d_acur = nullptr, *d_stalled = nullptr;
-        std::atomic<bool> dirty{false};
+        int *d_stalled = nullptr;
         std::atomic<long long> windows{0}, undecided{0};   // (the lanes may be driven by different host threads)
         std::mutex mu;                                     // the engine-wide blocks' first allocation
     } farm;
@@ -311,7 +329,9 @@ bool any_frozen(const mgpu_engine *e, int n, const int *t);
 int upload_sites(Lane &ln, const double *sites, int n_rows, int site_stride);
 int upload_sites(mgpu_engine *e, const double *sites, int n_rows, int site_stride, const int *t);
 double self_energy_host(const mgpu_engine *e, int t);
-int farm_window_normalize(mgpu_engine *e);      // mgpu_windows.hip
+int normalize_A(mgpu_engine *e);                // every replica's current A(k) back into d_A (mgpu_windows.hip)
+int alt_reserve(mgpu_engine *e);                // the A(k) double buffer (mgpu_windows.hip)
+void alt_forget(mgpu_engine *e, int replica);   // replica's other buffer holds nothing a commit may switch to (-1: every replica)
 int farm_clear_stall(mgpu_engine *e, int replica);   // the replica's state was rewritten: it waits for no decision (mgpu_windows.hip)
 int chain_topo(mgpu_engine *e, const Topo **d_topo);   // the engine's Topo in device memory (mgpu_windows.hip)
 // mgpu_launch.hip
@@ -339,7 +359,8 @@ RecipPlan recip_plan(const mgpu_engine *e, int n1_max, bool wide_ok);
 void recip_groups(const mgpu_engine *e, const RecipItem *items, int n, std::vector<RecipGroup> &groups, std::vector<int> &order);
 int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items, int n1_max, int site_stride,
                  bool commit, double2 *A_base, double *d_u, double *d_u_old = nullptr, const AcceptBits *accept = nullptr,
-                 const double *sites_override = nullptr, const DecideArgs *decide = nullptr);
+                 const double *sites_override = nullptr, const DecideArgs *decide = nullptr, bool store_alt = false);
+int launch_commit_switch(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items, int site_stride, const AcceptBits &accept);
 int launch_sfactor(mgpu_engine *e, int replica, double2 *dst);
 int launch_intra(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, const double *d_sites, int site_stride, double *d_out);
 

@@ -67,8 +67,10 @@ int sync_all_lanes(mgpu_engine *e) {
     for (auto &ln : e->lanes)
         if (&ln == &e->lanes[0] || ln.dirty || !ln.pending.empty())
             if (int rc = sync_lane(e, ln)) return rc;
-    // farm windows leave a replica's current A(k) in either of its two buffers: back into the primary one
-    if (e->farm.dirty) return farm_window_normalize(e);
+    // farm windows and commits by switching leave a replica's current A(k) in either of its two buffers: back into the primary
+    // one.  Either way the caller may rewrite any replica's state next: no trial's A + delta may be switched to after this.
+    if (e->a_switched) return normalize_A(e);
+    alt_forget(e, -1);
     return MGPU_OK;
 }
 
@@ -415,6 +417,8 @@ int mgpu_engine_create(mgpu_engine **out, int device, int n_replicas, int n_res,
     e->pair_fast_fold = std::getenv("MGPU_PAIR_EXACT_FOLD") == nullptr;
     e->recip_no_mfma = std::getenv("MGPU_RECIP_NO_MFMA") != nullptr;
     e->recip_force_per_k = std::getenv("MGPU_RECIP_PER_K") != nullptr;
+    e->commit_pass = std::getenv("MGPU_COMMIT_PASS") != nullptr;
+    e->alt_owner.assign(n_replicas, 0);
 
     BoxDev &bx = e->bx;
     for (int d = 0; d < 3; ++d) {
@@ -617,7 +621,7 @@ int mgpu_engine_destroy(mgpu_engine *e) {
     for (void *p : {(void *)e->chain.h_out, (void *)e->chain.h_tag})
         if (p) (void)hipHostFree(p);
     for (void *p : {(void *)e->chain.d_res, (void *)e->chain.d_part, (void *)e->chain.d_ticket, (void *)e->chain.d_topo, (void *)e->chain.d_alt,
-                    (void *)e->farm.d_A_alt, (void *)e->farm.d_acur, (void *)e->farm.d_stalled})
+                    (void *)e->d_A_alt, (void *)e->d_acur, (void *)e->farm.d_stalled})
         if (p) (void)hipFree(p);
     for (auto &ln : e->lanes) {
         ln.release();

@@ -72,6 +72,17 @@ static __global__ void phase_factors_kernel(int n, const double *__restrict__ th
     if (i < n) out[i] = phase_entry(theta[i], k[i]);
 }
 
+// A(k) of the replicas as the reciprocal kernels see it: the primary block, the other buffer, and which of the two is each
+// replica's current one (cur[r] = 1: alt).  cur == nullptr: the primary block only (no double buffer yet, or a scratch A(k)
+// such as the static energy's S(k)).  One scalar load per workgroup: a workgroup holds one item.
+struct RecipA {
+    double2 *base, *alt;
+    const int *cur;
+    __device__ __forceinline__ bool on_alt(int r) const { return cur && cur[r]; }
+    __device__ __forceinline__ double2 *current(int r, int n_slots) const { return (on_alt(r) ? alt : base) + (size_t)r * n_slots; }
+    __device__ __forceinline__ double2 *other(int r, int n_slots) const { return (on_alt(r) ? base : alt) + (size_t)r * n_slots; }
+};
+
 // SingleMolFourierTerms + ComputeRecipEnergySingleMol (ewald_phase.f90:383-420,
 // ewald_energy.f90:191-274) for one item per workgroup.
 // COMMIT = false: u_new[item] = prefactor * sum_k ff W |A + delta|^2, A untouched; with BOTH also
@@ -90,7 +101,7 @@ template <bool COMMIT, bool BOTH>
 __global__ __launch_bounds__(kBlock) void recip_kernel(
     Topo tp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ kpack, const int *__restrict__ kslot, const double *__restrict__ kw,
-    double2 *__restrict__ A_base, const RecipItem *__restrict__ items, const double *__restrict__ cand_sites,
+    RecipA Ab, const RecipItem *__restrict__ items, const double *__restrict__ cand_sites,
     int site_stride, int tile, double *__restrict__ u_new, double *__restrict__ u_old) {
     extern __shared__ double2 s_tab[];
     __shared__ double s_red[2 * kWavesPerBlock];
@@ -127,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void recip_kernel(
         for (int a = threadIdx.x; a < na; a += kBlock) s_q[a] = res_q[it.t * tp.max_atom + a0 + a];
     };
 
-    double2 *A = A_base + (size_t)it.replica * bx.n_slots;
+    double2 *A = Ab.current(it.replica, bx.n_slots);
     double acc = 0.0, acc0 = 0.0;
     // (the trip count is uniform over the workgroup: the tile barriers sit inside)
     for (int kb = 0; kb < bx.nk; kb += kBlock * kRecipChunk) {
@@ -653,14 +664,34 @@ __device__ __forceinline__ void recip_commit_target(const Topo &tp, const int *_
     else it.aux = nm - 1;                                 // swap-with-last target
 }
 
-template <bool COMMIT, bool BOTH, bool DECIDE = false>
+// Commit by switching: the lane's last trial stored every candidate's A + delta into its replica's other buffer
+// (recip_rows_kernel<false, true, false, 1>, the commit's arithmetic), so an accepted candidate's commit is its coordinates,
+// frames and count (recip_commit_tail) and the flip of the replica's current buffer -- no phase tables, no pass over A(k).
+// One wave per candidate of the trial, kBlock / 64 candidates per workgroup; molecules of at most 64 sites.
+static __global__ __launch_bounds__(kBlock) void commit_switch_kernel(Topo tp, double *__restrict__ pos, int *__restrict__ nmol,
+                                                                      const RecipItem *__restrict__ items, int n_items,
+                                                                      const double *__restrict__ cand_sites, int site_stride,
+                                                                      AcceptBits accept, int *__restrict__ acur) {
+    const int c = blockIdx.x * kWavesPerBlock + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= n_items || !((accept.w[c >> 5] >> (c & 31)) & 1u)) return;     // uniform per wave
+    RecipItem it = items[c];
+    recip_commit_target(tp, nmol, it);
+    __builtin_amdgcn_wave_barrier();      // (every lane has read the live count before lane 0 rewrites it)
+    recip_commit_tail(tp, pos, nmol, it, cand_sites + (size_t)(it.src < 0 ? 0 : it.src) * site_stride * 3, lane);
+    if (lane == 0) acur[it.replica] ^= 1;
+}
+
+// ALT = 1 (the trial's old + new sweep): every candidate's A + delta is also stored into its replica's other buffer
+// (recip_rows_pass's ALT), for a commit by switching (commit_switch_kernel)
+template <bool COMMIT, bool BOTH, bool DECIDE = false, int ALT = 0>
 __global__ __launch_bounds__(kBlock, COMMIT ? MGPU_COMMIT_MINWAVES : MGPU_RECIP_MINWAVES) void recip_rows_kernel(
     Topo tp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
-    double2 *__restrict__ A_base, const RecipItem *__restrict__ items,
+    RecipA Ab, const RecipItem *__restrict__ items,
     const double *__restrict__ cand_sites, int site_stride, double *__restrict__ u_new, double *__restrict__ u_old,
     AcceptBits accept, int use_accept, DecideArgs dec) {
     static_assert(!DECIDE || (!COMMIT && BOTH), "the deciding form is the old + new k sweep");
+    static_assert(ALT == 0 || (!COMMIT && !DECIDE), "A + delta into the other buffer: the trial's sweep only");
     extern __shared__ double2 s_tab[];
     __shared__ double s_red[2 * kWavesPerBlock];
     __shared__ int s_flag;
@@ -672,7 +703,7 @@ __global__ __launch_bounds__(kBlock, COMMIT ? MGPU_COMMIT_MINWAVES : MGPU_RECIP_
     }
     const double *cand_row = cand_sites + (size_t)(it.src < 0 ? 0 : it.src) * site_stride * 3;
     const RecipLds v = recip_lds_view(tp, bx, it, n_rows, s_tab);
-    double2 *A = A_base + (size_t)it.replica * bx.n_slots;
+    double2 *A = Ab.current(it.replica, bx.n_slots);
     const int tid = threadIdx.x;
 
     // the energy sweeps request their first chunks of A(k) under the table phases; the commit, whose registers buy it a
@@ -688,7 +719,8 @@ __global__ __launch_bounds__(kBlock, COMMIT ? MGPU_COMMIT_MINWAVES : MGPU_RECIP_
     if (COMMIT) recip_rows_prefetch<COMMIT>(inflight, trj, tw, n_tasks, A, tid);
     double acc = 0.0, acc0 = 0.0;
     if (!COMMIT) __builtin_amdgcn_s_setprio(0);
-    recip_rows_pass<COMMIT, BOTH>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0);
+    recip_rows_pass<COMMIT, BOTH, recip_chunk_tasks<COMMIT>(), ALT>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0,
+                                                                    ALT ? Ab.other(it.replica, bx.n_slots) : nullptr);
 
     if (!COMMIT) {
         acc = wave_sum(acc);
@@ -981,7 +1013,7 @@ template <bool COMMIT, bool BOTH, bool MFMA = false, bool TILED = false>
 __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
     Topo tp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ trj, const double2 *__restrict__ tw, const RecipRow *__restrict__ rows, const int *__restrict__ row_first,
-    int n_rows, int rows_per_tile, int nss_max, double2 *__restrict__ A_base, const RecipItem *__restrict__ items,
+    int n_rows, int rows_per_tile, int nss_max, RecipA Ab, const RecipItem *__restrict__ items,
     const double *__restrict__ cand_sites, int site_stride, double *__restrict__ u_new, double *__restrict__ u_old,
     double *__restrict__ site_tile_sums, int n_tasks) {
     extern __shared__ double2 s_tab[];
@@ -992,7 +1024,7 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
     double *px = pos + (size_t)it.replica * 3 * tp.n_cap_atoms;
     double *py = px + tp.n_cap_atoms, *pz = py + tp.n_cap_atoms;
     const double *cand_row = cand_sites + (size_t)(it.src < 0 ? 0 : it.src) * site_stride * 3;
-    double2 *A = A_base + (size_t)it.replica * bx.n_slots;
+    double2 *A = Ab.current(it.replica, bx.n_slots);
     double acc = 0.0, acc0 = 0.0;
     recip_wide_sweep<COMMIT, BOTH, MFMA, TILED>(tp, bx, pos, res_q, trj, tw, rows, row_first, n_rows, rows_per_tile, nss_max, A, it, cand_row,
                                                 site_tile_sums + (size_t)blockIdx.x * n_tasks * 4, n_tasks, s_tab, tid, true, acc, acc0,

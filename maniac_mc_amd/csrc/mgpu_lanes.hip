@@ -179,12 +179,14 @@ struct TrialDecide {
     const double *u, *pref;
     double temperature;
 };
+// the accepted share of a lane's commits above which its trials store A + delta for a commit by switching (Lane::accept_share)
+constexpr double kSwitchMinShare = 0.5;
+
 static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica, const int *t, const int *m,
                              const int *kind, const double *sites, int site_stride, const TrialBuild *build = nullptr,
                              const TrialDecide *decide = nullptr) {
     if (ln.n_submitted != 0) return set_error(MGPU_ERR_STATE, "trial_submit: the lane still holds an un-waited trial");
     int rc;
-    if (e->farm.dirty && (rc = farm_window_normalize(e))) return rc;       // (farm windows ran before: A(k) back into its primary buffer)
     if (decide) {
         if (!(decide->temperature > 0.0)) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: temperature must be positive");
         // one candidate per replica: the workgroups commit independently
@@ -216,6 +218,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
     ln.last_trial_n = 0;
     ln.d_trial_items = nullptr;
     ln.h_trial_items = nullptr;
+    ln.trial_alt = false;
     const size_t site_bytes = (size_t)n * site_stride * 3 * sizeof(double);
     const size_t pit_cap = 2 * (size_t)n * sizeof(PairItem), rit_bytes = (size_t)n * sizeof(RecipItem);
     const size_t iit_cap = (size_t)n * sizeof(PairItem);       // intra items
@@ -534,9 +537,29 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
             HIP_TRY(hipMemcpyAsync(ln.d_recip_items.p, h, rit_bytes, hipMemcpyHostToDevice, ln.stream));
             d_rit_k = (const RecipItem *)ln.d_recip_items.p;
         }
+        // A trial whose commit can switch A(k) buffers (commit_submit_impl): its k sweep also stores every candidate's A + delta
+        // into the replica's other buffer.  One row-form launch (the commit by accept mask's form, whose sums it shares), one
+        // candidate per replica (their stores would collide), molecules of at most 64 sites (commit_switch_kernel), and a
+        // lane whose last commit accepted at least kSwitchMinShare of its candidates.
+        bool alt = !e->commit_pass && ln.accept_share >= kSwitchMinShare && ln.recip_groups.size() == 1 && recip_by_rows(e, n1_max) && n1_max <= 64 && n <= 32 * kAcceptWords;
+        if (alt) {
+            if ((int)ln.mark.size() != e->n_replicas) ln.mark.assign(e->n_replicas, -1);
+            for (int c = 0; c < n; ++c) {
+                alt = alt && ln.mark[replica[c]] != -3;
+                ln.mark[replica[c]] = -3;
+            }
+            for (int c = 0; c < n; ++c) ln.mark[replica[c]] = -1;
+        }
+        if (alt && (rc = alt_reserve(e))) return rc;
+        if (alt) {
+            ln.trial_stamp = ++e->trial_stamps;
+            for (int c = 0; c < n; ++c) __atomic_store_n(&e->alt_owner[replica[c]], ln.trial_stamp, __ATOMIC_RELAXED);
+        }
         for (const RecipGroup &g : ln.recip_groups)
-            if ((rc = launch_recip(e, ln, d_rit_k + g.first, g.n, g.n1_max, site_stride, false, e->d_A, d_un + g.first, d_uo + g.first)))
+            if ((rc = launch_recip(e, ln, d_rit_k + g.first, g.n, g.n1_max, site_stride, false, e->d_A, d_un + g.first, d_uo + g.first,
+                                   nullptr, nullptr, nullptr, alt)))
                 return rc;
+        ln.trial_alt = alt;
     }
     if (n_intra && (rc = launch_intra(e, ln, d_iit, n_intra, (const double *)ln.d_sites.p, site_stride, d_in))) return rc;
     if (decide) {
@@ -544,6 +567,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
         const DecideArgs da{(const DecideItem *)((const char *)ln.d_sites.p + dec_at), (const double *)ln.d_out.p, d_in,
                             (int *)((double *)ln.d_out.p + acc_at), decide->temperature};
         if ((rc = launch_recip(e, ln, d_rit, n, n1_max, site_stride, false, e->d_A, d_un, d_uo, nullptr, nullptr, &da))) return rc;
+        for (int c = 0; c < n; ++c) alt_forget(e, replica[c]);      // (its accepted candidates are committed in place)
         ln.decided_n = n;
         ln.decided_wait_n = n;
         ln.decided_at = acc_at * sizeof(double);
@@ -625,7 +649,6 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
     int rc;
     const size_t site_bytes = sites ? (size_t)n * site_stride * 3 * sizeof(double) : 0;
     if (ln.n_submitted != 0) return set_error(MGPU_ERR_STATE, "commit_submit: wait for the lane's trial first");
-    if (e->farm.dirty && (rc = farm_window_normalize(e))) return rc;
     ln.dirty = true;
     // committing a device-built trial from its resident rows: the rows carry the candidates' frames
     const bool built = !sites && reuse_sites && ln.last_trial_built && n == ln.last_trial_n;
@@ -738,7 +761,10 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         return rc;
     }
     for (int q = 0; q < parts; ++q) any_sites = any_sites || part_of[q].any_sites;
-    if (n_items == 0) return MGPU_OK;
+    if (n_items == 0) {
+        if (!sites && reuse_sites) ln.accept_share = 0.0;
+        return MGPU_OK;
+    }
     if (any_sites && !sites && !reuse_sites) return set_error(MGPU_ERR_INVALID_ARG, "commit_candidates: sites is null");
     // Committing the lane's last trial from its resident rows: the trial's items are still on the device too,
     // so the accept flags travel as a kernel argument and nothing is uploaded.
@@ -762,7 +788,16 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         bool same = true;
         for (int q = 0; q < parts; ++q) same = same && same_of[q];
         if (!same) return set_error(MGPU_ERR_INVALID_ARG, "commit_submit: candidates differ from the lane's last trial");
-        if ((rc = launch_recip(e, ln, ln.d_trial_items, n, ln.trial_n1_max, site_stride, true, e->d_A, nullptr, nullptr, &bits)))
+        // The trial stored the A + delta of its candidates into their replicas' other buffers, and nothing has touched those
+        // since (alt_owner still holds the trial's stamp for every accepted one): switch buffers.  Otherwise A + delta again.
+        bool switch_ok = ln.trial_alt && !e->commit_pass;
+        for (int c = 0; c < n && switch_ok; ++c)
+            switch_ok = !accept[c] || __atomic_load_n(&e->alt_owner[replica[c]], __ATOMIC_RELAXED) == ln.trial_stamp;
+        ln.accept_share = (double)n_items / n;
+        if (switch_ok) {
+            if ((rc = launch_commit_switch(e, ln, ln.d_trial_items, n, site_stride, bits))) return rc;
+            e->a_switched = true;
+        } else if ((rc = launch_recip(e, ln, ln.d_trial_items, n, ln.trial_n1_max, site_stride, true, e->d_A, nullptr, nullptr, &bits)))
             return rc;
         // applied once: a second commit_submit(sites = NULL) must not find these rows "resident" again
         ln.last_trial_n = 0;
@@ -791,6 +826,10 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
             if ((rc = launch_recip(e, ln, (const RecipItem *)ln.d_items2.p + g.first, g.n, g.n1_max, site_stride, true, e->d_A, nullptr)))
                 return rc;
     }
+    // the committed replicas' other buffers hold no trial's A + delta for their new state
+    for (int c = 0; c < n; ++c)
+        if (accept[c]) alt_forget(e, replica[c]);
+    ln.trial_alt = false;
     for (int q = 0; q < parts; ++q) {
         const std::vector<int> &new_counts = part_of[q].new_counts;
         for (size_t i = 0; i < new_counts.size(); i += 2) e->h_nmol[new_counts[i]] = new_counts[i + 1];

@@ -312,8 +312,12 @@ void recip_groups(const mgpu_engine *e, const RecipItem *items, int n, std::vect
 // those whose bit is set are applied
 int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items, int n1_max, int site_stride,
                  bool commit, double2 *A_base, double *d_u, double *d_u_old, const AcceptBits *accept, const double *sites_override,
-                 const DecideArgs *decide) {
+                 const DecideArgs *decide, bool store_alt) {
     const RecipPlan plan = recip_plan(e, n1_max, !accept && !decide);
+    // the replicas' A(k): each one's current buffer where the engine keeps two (a scratch A(k) such as S(k): as it is)
+    const RecipA Ab = (A_base == e->d_A && e->d_acur) ? RecipA{e->d_A, e->d_A_alt, e->d_acur} : RecipA{A_base, nullptr, nullptr};
+    if (store_alt && (!plan.by_rows || commit || decide || !d_u_old || !Ab.cur))
+        return set_error(MGPU_ERR_STATE, "A + delta into the other buffer needs the row-form old + new k sweep and the double buffer");
     const bool by_rows = plan.by_rows;
     const double *d_cand = sites_override ? sites_override : (const double *)ln.d_sites.p;
     static const AcceptBits no_bits{};
@@ -338,11 +342,11 @@ int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items
         if (by_rows)                                                                                                 \
             hipExtLaunchKernelGGL((recip_rows_kernel<COMMIT, BOTH>), dim3(n_items), dim3(kBlock), lds, ln.stream, a, b, \
                                   0, e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, \
-                               A_base, d_items, d_cand, site_stride, d_u, d_u_old,      \
+                               Ab, d_items, d_cand, site_stride, d_u, d_u_old,      \
                                   bits, use_accept, no_decide);                                                     \
         else                                                                                                         \
             hipExtLaunchKernelGGL((recip_kernel<COMMIT, BOTH>), dim3(n_items), dim3(kBlock), lds, ln.stream, a, b, 0,   \
-                                  e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_kpack, e->d_kslot, e->d_kw, A_base, d_items,  \
+                                  e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_kpack, e->d_kslot, e->d_kw, Ab, d_items,  \
                                d_cand, site_stride, tile, d_u, d_u_old);                         \
     } while (0)
     const bool wide_mfma = plan.mfma_tile > 0;
@@ -362,7 +366,7 @@ int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items
         do {                                                                                                         \
             hipExtLaunchKernelGGL((recip_rows_wide_kernel<COMMIT, BOTH, MF, TI>), dim3(n_items), dim3(kBlock), lds_w, ln.stream, a, b, 0, e->tp, \
                                   e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->d_rrows, e->d_row_first, e->n_rrows, wide_rpt, \
-                                  nss_max, A_base, d_items, d_cand, site_stride, d_u, d_u_old, tile_sums, e->n_rtasks);     \
+                                  nss_max, Ab, d_items, d_cand, site_stride, d_u, d_u_old, tile_sums, e->n_rtasks);     \
         } while (0)
 #define MGPU_LAUNCH_WIDE(COMMIT, BOTH, MF)                                                                           \
         do { if (MF && tile_sums) MGPU_LAUNCH_WIDE_1(COMMIT, BOTH, MF, true); else MGPU_LAUNCH_WIDE_1(COMMIT, BOTH, MF, false); } while (0)
@@ -379,13 +383,31 @@ int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items
 #undef MGPU_LAUNCH_WIDE_1
     } else if (decide)
         hipExtLaunchKernelGGL((recip_rows_kernel<false, true, true>), dim3(n_items), dim3(kBlock), lds, ln.stream, a, b, 0, e->tp,
-                              e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, A_base,
+                              e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, Ab,
                               d_items, d_cand, site_stride, d_u, d_u_old, bits, 0, *decide);
+    else if (store_alt)
+        hipExtLaunchKernelGGL((recip_rows_kernel<false, true, false, 1>), dim3(n_items), dim3(kBlock), lds, ln.stream, a, b, 0, e->tp,
+                              e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, Ab,
+                              d_items, d_cand, site_stride, d_u, d_u_old, bits, 0, no_decide);
     else if (commit) MGPU_LAUNCH_RECIP(true, false);
     else if (d_u_old) MGPU_LAUNCH_RECIP(false, true);
     else MGPU_LAUNCH_RECIP(false, false);
 #undef MGPU_LAUNCH_RECIP
     rc = prof_end(e, ln, slot, a, b);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return MGPU_OK;
+}
+
+// The commit of the lane's last trial by switching A(k) buffers (commit_switch_kernel): d_items are the trial's candidates,
+// `accept` marks the committed ones; the trial stored their A + delta (launch_recip's store_alt).  Timed as the commit.
+int launch_commit_switch(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items, int site_stride, const AcceptBits &accept) {
+    hipEvent_t a = nullptr, b = nullptr;
+    int rc = prof_begin(e, ln, MGPU_KERNEL_COMMIT, &a, &b);
+    if (rc) return rc;
+    hipExtLaunchKernelGGL(commit_switch_kernel, dim3((n_items + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, ln.stream, a, b, 0,
+                          e->tp, e->d_pos, e->d_nmol, d_items, n_items, (const double *)ln.d_sites.p, site_stride, accept, e->d_acur);
+    rc = prof_end(e, ln, MGPU_KERNEL_COMMIT, a, b);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return MGPU_OK;

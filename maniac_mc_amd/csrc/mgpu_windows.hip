@@ -22,17 +22,40 @@ int chain_topo(mgpu_engine *e, const Topo **d_topo) {
     return MGPU_OK;
 }
 
-// Every replica's current A(k) back into the primary buffer d_A (farm windows switch a replica between d_A and d_A_alt):
-// drains the lanes, one small launch, a synchronise.  Windows still un-waited keep their results in host memory.
-int farm_window_normalize(mgpu_engine *e) {
-    e->farm.dirty = false;
-    if (!e->farm.d_A_alt) return MGPU_OK;
+// Every replica's current A(k) back into the primary buffer d_A (farm windows and commits by switching move a replica between
+// d_A and d_A_alt): drains the lanes, one small launch, a synchronise.  Windows still un-waited keep their results in host memory.
+// Afterwards no replica's other buffer holds anything a commit may switch to.
+int normalize_A(mgpu_engine *e) {
+    e->a_switched = false;
+    if (!e->d_A_alt) return MGPU_OK;
     for (auto &ln : e->lanes) HIP_TRY(hipStreamSynchronize(ln.stream));
-    hipLaunchKernelGGL(farm_normalize_kernel, dim3(e->n_replicas), dim3(kBlock), 0, e->lanes[0].stream, e->farm.d_acur, e->d_A,
-                       (const double2 *)e->farm.d_A_alt, e->n_slots);
+    hipLaunchKernelGGL(farm_normalize_kernel, dim3(e->n_replicas), dim3(kBlock), 0, e->lanes[0].stream, e->d_acur, e->d_A,
+                       (const double2 *)e->d_A_alt, e->n_slots);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(e->lanes[0].stream));
+    alt_forget(e, -1);
     return MGPU_OK;
+}
+
+// The A(k) double buffer, on first use: R x n_slots complex entries more, every replica current in d_A
+int alt_reserve(mgpu_engine *e) {
+    std::lock_guard<std::mutex> lock(e->alt_mu);
+    if (e->d_A_alt) return MGPU_OK;
+    double2 *alt = nullptr;
+    int *cur = nullptr;
+    HIP_TRY(hipMalloc((void **)&alt, (size_t)e->n_replicas * e->n_slots * sizeof(double2)));
+    HIP_TRY(hipMalloc((void **)&cur, (size_t)e->n_replicas * sizeof(int)));
+    HIP_TRY(hipMemset(cur, 0, (size_t)e->n_replicas * sizeof(int)));
+    HIP_TRY(hipDeviceSynchronize());
+    e->d_acur = cur;
+    e->d_A_alt = alt;
+    return MGPU_OK;
+}
+
+void alt_forget(mgpu_engine *e, int replica) {
+    if (e->alt_owner.empty()) return;
+    if (replica >= 0) { __atomic_store_n(&e->alt_owner[replica], 0ull, __ATOMIC_RELAXED); return; }
+    for (auto &o : e->alt_owner) __atomic_store_n(&o, 0ull, __ATOMIC_RELAXED);
 }
 
 // A replica whose state is rewritten (set_molecules / set_frames / set_num_molecules, the destination of replica_copy)
@@ -141,7 +164,8 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     }
     const Topo *d_topo = nullptr;
     if ((rc = chain_topo(e, &d_topo))) return rc;
-    if (e->farm.dirty && (rc = farm_window_normalize(e))) return rc;
+    if (e->a_switched && (rc = normalize_A(e))) return rc;      // (the window reads and writes d_A)
+    alt_forget(e, replica);
     // ---- the window travels in the kernel arguments
     ChainArgs g{};
     bool fast = replica_in_range(e, replica);
@@ -348,12 +372,9 @@ static int farm_lane(mgpu_engine *e, int lane, Lane **ln) {
 // the lane's blocks for windows of up to `cap` chains; the engine's second A(k) buffer and flags
 static int farm_reserve(mgpu_engine *e, Lane &ln, int cap) {
     Lane::FarmWindow &fw = ln.farm;
-    if (!e->farm.d_A_alt) {
-        const size_t bytes = (size_t)e->n_replicas * e->n_slots * sizeof(double2);
-        HIP_TRY(hipMalloc((void **)&e->farm.d_A_alt, bytes));
-        HIP_TRY(hipMalloc((void **)&e->farm.d_acur, (size_t)e->n_replicas * sizeof(int)));
+    if (int rc = alt_reserve(e)) return rc;
+    if (!e->farm.d_stalled) {
         HIP_TRY(hipMalloc((void **)&e->farm.d_stalled, (size_t)e->n_replicas * sizeof(int)));
-        HIP_TRY(hipMemset(e->farm.d_acur, 0, (size_t)e->n_replicas * sizeof(int)));
         HIP_TRY(hipMemset(e->farm.d_stalled, 0, (size_t)e->n_replicas * sizeof(int)));
         HIP_TRY(hipDeviceSynchronize());
     }
@@ -489,7 +510,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
     g.recs = fw.h_recs + (size_t)slot * fw.cap;
     g.partials = fw.d_part; g.res = fw.d_res; g.tickets = fw.d_tickets;
-    g.stalled = e->farm.d_stalled; g.acur = e->farm.d_acur; g.A_alt = e->farm.d_A_alt;
+    g.stalled = e->farm.d_stalled; g.acur = e->d_acur; g.A_alt = e->d_A_alt;
     g.host_out = fw.h_out + (size_t)slot * fw.cap * kFarmOut;
     g.host_tag = fw.h_tag + (size_t)slot * fw.cap;
     g.seq = pd.seq;
@@ -511,7 +532,9 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     ln.last_trial_n = 0;
     ln.d_trial_items = nullptr;
     ln.h_trial_items = nullptr;
-    e->farm.dirty = true;
+    ln.trial_alt = false;
+    for (int c = 0; c < n; ++c) alt_forget(e, replica[c]);     // (the window's k role overwrites their other buffers)
+    e->a_switched = true;
 #define MGPU_LAUNCH_FARM(FL, FW, WI)                                                                                       \
     do {                                                                                                                   \
         hipLaunchKernelGGL((farm_window_kernel<FL, FW, WI>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, \
