@@ -312,6 +312,30 @@ int mgpu_replica_get_frames(mgpu_engine *e, int replica, int t, int *n_mol, doub
  * candidates from the rows the device built, sites and frames. */
 int mgpu_move_trial_submit(mgpu_engine *e, int lane, int n_candidates, const int *replica, const int *t, const int *m,
                            const int *move, const double *u, double translation_step, double rotation_step);
+/* Reservoirs (MANIAC's `-r reservoir.data`; src/create_molecule.f90:117-128, :185-193, src/delete_molecule.f90:146-166): one
+ * replica's molecules of one residue type held outside the box, offsets only (off[n][n1][3]; the reservoir's centres are
+ * read by nothing but reservoir.lammpstrj).  Where (replica, t) has a reservoir, every DEVICE-BUILT step of the type
+ * (mgpu_move_trial_submit + mgpu_commit_submit from the resident rows, mgpu_move_trial_decide_submit, farm windows) follows it:
+ *   insertion   pick = min(int(u[3] n_r), n_r - 1) of the reservoir's count n_r as the launch sees it (u[3] is the
+ *               rotation angle's uniform number without a reservoir); the candidate's offsets are reservoir[pick], bit for
+ *               bit and unrotated, its centre placed as before.  Accepted: reservoir[pick] <- reservoir[n_r - 1], n_r -= 1.
+ *   deletion    accepted: the reservoir gains the offsets stored in the box's LAST slot of the type -- not necessarily the
+ *               deleted molecule's geometry: the reference's own choice (delete_molecule.f90:159-161), kept.
+ *   rejected    the reservoir is unchanged.
+ * Box count + reservoir count is conserved per (replica, type), so a capacity of n + the type's mol_capacity never
+ * overflows.  An EMPTY reservoir (the reference reads an undefined slot there and takes the count to -1): an insertion of
+ * the type does nothing -- verdict 5 in a farm window (4 while the replica waits for the driver's decision of an earlier
+ * step, which may refill it), rejected by mgpu_move_trial_decide_submit; a driver of the
+ * host-decided batched path tells it from its own counts (box count == the conserved total) and must not accept one.
+ * Device-built insertions of a type with a reservoir need no molecule in slot 0 (mgpu_replica_set_frames' frames_held rule
+ * does not apply).  Host-built paths (candidate rows from the caller) do not touch a reservoir.
+ * mgpu_replica_set_reservoir: cap = 0 -> the conservation bound; n = 0 and cap = 0 removes the reservoir; a capacity below
+ * the bound (n + mol_capacity) is refused, as is a call while farm windows of the replica are in flight.  Like the other reloads, it clears the replica's
+ * stall mark; the first reservoir of an engine makes the lanes' resident rows uncommittable.  mgpu_replica_copy copies
+ * reservoirs with the rest of the replica.  mgpu_replica_get_reservoir: the count, and the offsets [n][n1][3] where off is
+ * not NULL (n = 0 where there is no reservoir). */
+int mgpu_replica_set_reservoir(mgpu_engine *e, int replica, int t, int n, int cap, const double *off);
+int mgpu_replica_get_reservoir(mgpu_engine *e, int replica, int t, int *n, double *off);
 /* The same trials with the ACCEPTANCE TEST ON THE DEVICE.  The k sweep is the last kernel of a trial, one workgroup per
  * candidate; once it has summed the candidate's reciprocal energies its first thread holds everything
  * mc_acceptance_probability (src/monte_carlo_utils.f90:184-226) needs, so it applies the rule itself,

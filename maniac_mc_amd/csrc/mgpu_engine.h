@@ -251,6 +251,16 @@ struct mgpu_engine {
     std::vector<char> frames_held;   // [R][n_res]: slot 0's frame holds a molecule's offsets (set_frames gave one; a deletion
                                      // leaves them): a device-built insertion copies them whatever the count
                                      // (create_molecule.f90:196-200), and is refused where this is 0
+    // reservoirs (mgpu_replica_set_reservoir), allocated on first use: rsv_ptr[r * n_res + t] = the device block
+    // [rsv_cap][n1][3] (null: none) whose table d_rsv the kernels read (Topo::rsv), d_rsv_nc = {count, capacity} per entry
+    // (the count lives on the device only: the device-built paths change it); rsv_tight = every offset the reservoir was
+    // given lies within frames_tight's bound (frames_tight of the type includes it)
+    std::vector<double *> rsv_ptr;
+    std::vector<int> rsv_cap;
+    std::vector<char> rsv_tight;
+    double **d_rsv = nullptr;
+    int *d_rsv_nc = nullptr;
+    bool rsv_any = false;            // some reservoir was set: device-built rows carry the pick (reservoir_row_pick)
     // Register-site sweeps of this engine go through pair_flat_kernel (one software-pipelined loop over all units of
     // a work unit) instead of the plane-by-plane pair_sweep_kernel: chosen at creation for topologies with short planes
     // (every plane-major residue type has at most kFlatMaxCap molecule slots) or a frozen residue; MGPU_PAIR_FLAT=0 / 1
@@ -323,6 +333,8 @@ int sync_all_lanes(mgpu_engine *e);
 int check_candidate(const mgpu_engine *e, int c, int replica, int t, int m, bool need_resident);
 bool sites_in_range(const mgpu_engine *e, const double *sites, int n_sites);
 bool replica_in_range(const mgpu_engine *e, int replica);
+// (replica, t) has a reservoir (mgpu_replica_set_reservoir): its insertions copy reservoir molecules, not slot 0's frame
+inline bool has_reservoir(const mgpu_engine *e, size_t idx) { return !e->rsv_ptr.empty() && e->rsv_ptr[idx] != nullptr; }
 int engine_nsplit(const mgpu_engine *e);
 void permute_frozen_rows(const mgpu_engine *e, double *rows, int n_rows, int site_stride, const int *t);
 bool any_frozen(const mgpu_engine *e, int n, const int *t);

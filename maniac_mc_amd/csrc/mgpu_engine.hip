@@ -617,6 +617,10 @@ int mgpu_engine_destroy(mgpu_engine *e) {
                     (void *)e->d_atom_mol, (void *)e->d_atom_q, (void *)e->d_atom_q_on, (void *)e->d_phase_tab, (void *)e->d_S, (void *)e->d_trj,
                     (void *)e->d_tw, (void *)e->d_kslot, (void *)e->d_rrows, (void *)e->d_row_first, (void *)e->d_atom_ty, (void *)e->d_com, (void *)e->d_off})
         if (p) (void)hipFree(p);
+    for (double *p : e->rsv_ptr)
+        if (p) (void)hipFree(p);
+    for (void *p : {(void *)e->d_rsv, (void *)e->d_rsv_nc})
+        if (p) (void)hipFree(p);
     e->h_stage.release();
     for (void *p : {(void *)e->chain.h_out, (void *)e->chain.h_tag})
         if (p) (void)hipHostFree(p);
@@ -799,6 +803,12 @@ int mgpu_replica_set_frames(mgpu_engine *e, int replica, int t, int n_mol, const
                           hipMemcpyHostToDevice));
     }
     e->frames_ok[(size_t)replica * tp.n_res + t] = 1;
+    if (has_reservoir(e, (size_t)replica * tp.n_res + t)) {
+        // the reservoir may hold offsets that deletions took from the frames being replaced: tight only if those were
+        char &rt = e->rsv_tight[(size_t)replica * tp.n_res + t];
+        rt = rt && e->frames_tight[(size_t)replica * tp.n_res + t];
+        tight = tight && rt;
+    }
     e->frames_tight[(size_t)replica * tp.n_res + t] = tight ? 1 : 0;
     e->frames_held[(size_t)replica * tp.n_res + t] = n_mol > 0 ? 1 : 0;      // (the slots past n_mol were zeroed above)
     return MGPU_OK;
@@ -862,6 +872,107 @@ int mgpu_replica_set_num_molecules(mgpu_engine *e, int replica, int t, int n_mol
     return MGPU_OK;
 }
 
+// ---- reservoirs ---------------------------------------------------------------------------------
+
+// the table the kernels read (Topo::rsv / rsv_nc), allocated on first use
+static int reservoir_tables(mgpu_engine *e) {
+    if (e->d_rsv) return MGPU_OK;
+    const size_t nent = (size_t)e->n_replicas * e->tp.n_res;
+    HIP_TRY(hipMalloc(&e->d_rsv, nent * sizeof(double *)));
+    HIP_TRY(hipMemset(e->d_rsv, 0, nent * sizeof(double *)));
+    HIP_TRY(hipMalloc(&e->d_rsv_nc, 2 * nent * sizeof(int)));
+    HIP_TRY(hipMemset(e->d_rsv_nc, 0, 2 * nent * sizeof(int)));
+    e->rsv_ptr.assign(nent, nullptr);
+    e->rsv_cap.assign(nent, 0);
+    e->rsv_tight.assign(nent, 1);
+    e->tp.rsv = e->d_rsv;
+    e->tp.rsv_nc = e->d_rsv_nc;
+    e->rsv_any = true;
+    e->chain.topo_stale = true;
+    // device-built rows carry the reservoir pick from now on: rows built before cannot be committed
+    for (Lane &ln : e->lanes) {
+        ln.last_trial_n = 0;
+        ln.d_trial_items = nullptr;
+        ln.h_trial_items = nullptr;
+        ln.trial_alt = false;
+    }
+    return MGPU_OK;
+}
+
+// entry idx gets a block of `cap` molecules (cap = 0: none); its count is set to 0
+static int reservoir_block(mgpu_engine *e, size_t idx, int cap) {
+    const int n1 = e->tp.n1[idx % e->tp.n_res];
+    if (e->rsv_ptr[idx] && e->rsv_cap[idx] != cap) {
+        HIP_TRY(hipFree(e->rsv_ptr[idx]));
+        e->rsv_ptr[idx] = nullptr;
+        e->rsv_cap[idx] = 0;
+    }
+    if (cap > 0 && !e->rsv_ptr[idx]) {
+        const size_t bytes = (size_t)cap * n1 * 3 * sizeof(double);
+        HIP_TRY(hipMalloc(&e->rsv_ptr[idx], bytes));
+        HIP_TRY(hipMemset(e->rsv_ptr[idx], 0, bytes));       // (an empty reservoir's stand-in molecule: in bounds, never committed)
+        e->rsv_cap[idx] = cap;
+    }
+    const int nc[2] = {0, cap};
+    HIP_TRY(hipMemcpy(e->d_rsv + idx, &e->rsv_ptr[idx], sizeof(double *), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_rsv_nc + 2 * idx, nc, sizeof(nc), hipMemcpyHostToDevice));
+    return MGPU_OK;
+}
+
+int mgpu_replica_set_reservoir(mgpu_engine *e, int replica, int t, int n, int cap, const double *off) {
+    int rc = check_replica_t(e, replica, t);
+    if (rc) return rc;
+    const Topo &tp = e->tp;
+    if (n < 0 || cap < 0) return set_error(MGPU_ERR_INVALID_ARG, "set_reservoir: negative count or capacity");
+    if (n > 0 && !off) return set_error(MGPU_ERR_INVALID_ARG, "set_reservoir: null offsets");
+    // box count + reservoir count is conserved: a capacity of n + the type's mol_capacity never overflows, and a smaller one
+    // could (an accepted deletion would have nowhere to put the geometry): refused
+    if (cap == 0 && n > 0) cap = n + tp.cap[t];
+    if (n > cap) return set_error(MGPU_ERR_CAPACITY, "set_reservoir: more molecules than the capacity");
+    if (cap > 0 && cap < n + tp.cap[t])
+        return set_error(MGPU_ERR_CAPACITY, "set_reservoir: capacity below n + the type's mol_capacity (the conservation bound)");
+    if ((rc = use_device(e))) return rc;
+    for (const Lane &ln : e->lanes)
+        for (const auto &pd : ln.farm.pending)
+            for (int r : pd.rep)
+                if (r == replica) return set_error(MGPU_ERR_STATE, "set_reservoir: farm windows of this replica are in flight (wait for them first)");
+    if ((rc = sync_all_lanes(e))) return rc;
+    if (cap == 0 && !e->d_rsv) return MGPU_OK;                // nothing to remove
+    if ((rc = reservoir_tables(e))) return rc;
+    const size_t idx = (size_t)replica * tp.n_res + t;
+    if ((rc = reservoir_block(e, idx, cap))) return rc;
+    const int n1 = tp.n1[t];
+    bool tight = true;
+    const double r_max = 0.24 * std::min(e->bx.L[0], std::min(e->bx.L[1], e->bx.L[2]));   // (mgpu_replica_set_frames' bound)
+    for (size_t i = 0; i < (size_t)n * n1; ++i) {
+        double o2 = 0.0;
+        for (int d = 0; d < 3; ++d) o2 += off[i * 3 + d] * off[i * 3 + d];
+        tight = tight && o2 <= r_max * r_max;
+    }
+    if (n > 0) {
+        HIP_TRY(hipMemcpy(e->rsv_ptr[idx], off, (size_t)n * n1 * 3 * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(e->d_rsv_nc + 2 * idx, &n, sizeof(int), hipMemcpyHostToDevice));
+    }
+    e->rsv_tight[idx] = tight ? 1 : 0;
+    if (cap > 0 && !tight) e->frames_tight[idx] = 0;         // an inserted reservoir molecule may leave the fast fold's range
+    return farm_clear_stall(e, replica);
+}
+
+int mgpu_replica_get_reservoir(mgpu_engine *e, int replica, int t, int *n, double *off) {
+    int rc = check_replica_t(e, replica, t);
+    if (rc) return rc;
+    if (!n) return set_error(MGPU_ERR_INVALID_ARG, "get_reservoir: null count");
+    *n = 0;
+    const size_t idx = (size_t)replica * e->tp.n_res + t;
+    if (!has_reservoir(e, idx)) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    HIP_TRY(hipMemcpy(n, e->d_rsv_nc + 2 * idx, sizeof(int), hipMemcpyDeviceToHost));
+    if (off && *n > 0)
+        HIP_TRY(hipMemcpy(off, e->rsv_ptr[idx], (size_t)*n * e->tp.n1[t] * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return MGPU_OK;
+}
+
 int mgpu_replica_copy(mgpu_engine *e, int dst, int src) {
     int rc = check_replica_t(e, dst, 0);
     if (rc) return rc;
@@ -902,6 +1013,18 @@ int mgpu_replica_copy(mgpu_engine *e, int dst, int src) {
         }
         e->frames_tight[(size_t)dst * tp.n_res + t] = e->frames_tight[(size_t)src * tp.n_res + t];
         e->frames_held[(size_t)dst * tp.n_res + t] = e->frames_held[(size_t)src * tp.n_res + t];
+    }
+    // reservoirs: dst's become src's (count, capacity and molecules; none where src has none)
+    if (e->d_rsv) {
+        if ((rc = sync_stream(e))) return rc;
+        for (int t = 0; t < tp.n_res; ++t) {
+            const size_t is = (size_t)src * tp.n_res + t, id = (size_t)dst * tp.n_res + t;
+            if ((rc = reservoir_block(e, id, e->rsv_cap[is]))) return rc;
+            if (!e->rsv_ptr[is]) continue;
+            HIP_TRY(hipMemcpy(e->rsv_ptr[id], e->rsv_ptr[is], (size_t)e->rsv_cap[is] * tp.n1[t] * 3 * sizeof(double), hipMemcpyDeviceToDevice));
+            HIP_TRY(hipMemcpy(e->d_rsv_nc + 2 * id, e->d_rsv_nc + 2 * is, 2 * sizeof(int), hipMemcpyDeviceToDevice));
+            e->rsv_tight[id] = e->rsv_tight[is];
+        }
     }
     return sync_stream(e);
 }

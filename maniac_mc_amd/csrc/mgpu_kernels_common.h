@@ -80,6 +80,12 @@ struct Topo {
     double *off;
     int mol_off[kMaxRes];
     int n_mol_slots;
+    // Reservoirs (only once mgpu_replica_set_reservoir has been used, else null): rsv[r * n_res + t] = the offsets
+    // [cap][n1][3] of the molecules of replica r's reservoir of type t (null: none), rsv_nc[2 (r * n_res + t)] = its
+    // count and capacity.  A device-built insertion of such a type copies reservoir[pick] unrotated, and its commit
+    // takes that molecule out of the reservoir; a deletion puts the box's last molecule of the type into it.
+    double *const *rsv;
+    int *rsv_nc;
 };
 
 struct BoxDev {
@@ -118,6 +124,53 @@ struct RecipItem {
 
 __device__ __forceinline__ int atom_slot(const Topo &tp, int t, int m, int a) {
     return tp.site_major[t] ? tp.seg_off[t] + m * tp.n1[t] + a : tp.seg_off[t] + a * tp.cap[t] + m;
+}
+
+// ---- reservoirs (Topo::rsv): one replica's molecules of one type held outside the box, offsets only (create_molecule.f90:
+// 185-193, :117-128; delete_molecule.f90:146-166)
+// the reservoir of (replica, t), or null
+__device__ __forceinline__ const double *reservoir_of(const Topo &tp, int replica, int t) {
+    return tp.rsv ? tp.rsv[replica * tp.n_res + t] : nullptr;
+}
+// the molecule an insertion copies: min(int(u n_r), n_r - 1) of the count n_r; -1 for an empty reservoir
+__device__ __forceinline__ int reservoir_pick(const Topo &tp, int replica, int t, double u) {
+    const int nr = tp.rsv_nc[2 * (replica * tp.n_res + t)];
+    return nr > 0 ? min((int)(u * nr), nr - 1) : -1;
+}
+// the reservoir molecule a device-built insertion's row was built from: trial_build_kernel stores it behind the offsets
+// (site index 2 frame + 1) where the engine holds a reservoir; -1 for an empty reservoir
+__device__ __forceinline__ int reservoir_row_pick(const double *row, int frame) { return (int)row[(size_t)(2 * frame + 1) * 3]; }
+
+// The reservoir's side of an accepted device-built step, by the lanes of ONE wave (lane < 64; the other threads return):
+//   kind 1 (insertion of reservoir molecule `pick`)   reservoir[pick] <- reservoir[n_r - 1], n_r -= 1
+//   kind 2 (deletion; `last` = the box's last slot of the type, read before the swap-with-last overwrites anything)
+//          reservoir[n_r] <- the offsets in slot `last`, n_r += 1 -- the LAST molecule's geometry, not necessarily the
+//          deleted one's, as the reference does (delete_molecule.f90:159-161)
+// The callers' candidate was built from reservoir[pick] before this runs (the same lane reads site a before it writes it);
+// every lane reads the count before lane 0 rewrites it (one load instruction; lane 0's store depends on it).
+__device__ __forceinline__ void reservoir_commit(const Topo &tp, int replica, int t, int kind, int pick, int last, int lane) {
+    if (lane >= 64 || !tp.rsv || (kind != 1 && kind != 2)) return;
+    const int idx = replica * tp.n_res + t;
+    double *R = tp.rsv[idx];
+    if (!R) return;
+    const int n1 = tp.n1[t], nr = tp.rsv_nc[2 * idx], cap = tp.rsv_nc[2 * idx + 1];
+    if (kind == 1) {
+        if (nr <= 0 || pick < 0 || pick >= nr) return;
+        if (pick != nr - 1)
+            for (int a = lane; a < n1; a += 64)
+                for (int d = 0; d < 3; ++d) R[((size_t)pick * n1 + a) * 3 + d] = R[((size_t)(nr - 1) * n1 + a) * 3 + d];
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) tp.rsv_nc[2 * idx] = nr - 1;
+    } else {
+        if (nr >= cap) return;                        // (never, with the conservation bound as capacity)
+        const size_t rep3 = (size_t)replica * 3;
+        for (int a = lane; a < n1; a += 64) {
+            const int jl = atom_slot(tp, t, last, a);
+            for (int d = 0; d < 3; ++d) R[((size_t)nr * n1 + a) * 3 + d] = tp.off[(rep3 + d) * tp.n_cap_atoms + jl];
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane == 0) tp.rsv_nc[2 * idx] = nr + 1;
+    }
 }
 
 // a pair-sweep partial {e_lj, e_coul}; SC1: agent-scope write-through stores (see pair_sweep_item)

@@ -252,6 +252,9 @@ __global__ __launch_bounds__(kBlock) void recip_kernel(
                 }
             }
         }
+        if (tp.rsv && it.frame > 0)
+            reservoir_commit(tp, it.replica, it.t, it.kind, it.kind == 1 ? reservoir_row_pick(cand_sites + (size_t)it.src * site_stride * 3, it.frame) : -1,
+                             it.aux, threadIdx.x);
         if (threadIdx.x == 0 && (it.kind == 1 || it.kind == 2)) nmol[it.replica * tp.n_res + it.t] = it.aux;
     }
 }
@@ -654,6 +657,9 @@ __device__ __forceinline__ void recip_commit_tail(const Topo &tp, double *__rest
             }
         }
     }
+    // a device-built step of a type with a reservoir (row `frame` > 0; deletions carry the flag too)
+    if (tp.rsv && it.frame > 0)
+        reservoir_commit(tp, it.replica, it.t, it.kind, it.kind == 1 ? reservoir_row_pick(cand_row, it.frame) : -1, it.aux, tid);
     if (tid == 0 && (it.kind == 1 || it.kind == 2 || it.kind == 5)) nmol[it.replica * tp.n_res + it.t] = it.aux;
 }
 // a trial's item carries no target slot / new count: take them from the replica's live count
@@ -735,7 +741,10 @@ __global__ __launch_bounds__(kBlock, COMMIT ? MGPU_COMMIT_MINWAVES : MGPU_RECIP_
             u_new[blockIdx.x] = e_new;
             if (BOTH) u_old[blockIdx.x] = e_old;
             if constexpr (DECIDE) {
-                const bool yes = decide_candidate(dec.items[blockIdx.x], dec, e_old, e_new);
+                // (an insertion from an empty reservoir has nothing to insert: it is rejected, whatever its energies)
+                const bool empty = tp.rsv && it.kind == 1 && it.frame > 0 && reservoir_of(tp, it.replica, it.t) &&
+                                   reservoir_pick(tp, it.replica, it.t, 0.0) < 0;
+                const bool yes = !empty && decide_candidate(dec.items[blockIdx.x], dec, e_old, e_new);
                 dec.accepted[blockIdx.x] = yes ? 1 : 0;
                 s_flag = yes ? 1 : 0;
             }
@@ -1077,6 +1086,8 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
                 }
             }
         }
+        if (tp.rsv && it.frame > 0)
+            reservoir_commit(tp, it.replica, it.t, it.kind, it.kind == 1 ? reservoir_row_pick(cand_row, it.frame) : -1, it.aux, tid);
         if (tid == 0 && (it.kind == 1 || it.kind == 2)) nmol[it.replica * tp.n_res + it.t] = it.aux;
     }
 }
@@ -1108,10 +1119,16 @@ struct TrialFrame {
     int src_m;                    // the molecule whose frame the candidate starts from (creation: molecule 1 of the type)
     bool rot;
 };
-template <class TopoT>
-__device__ __forceinline__ TrialFrame trial_frame(const TopoT &tp, const BoxDev &bx, int replica, int t, int m, int mv, const double *u,
+// ... with the reservoir an insertion copies (RSV: the engine holds reservoirs); without, the frame the code had before them
+template <bool RSV> struct TrialFrameR : TrialFrame {
+    const double *rsv;            // a reservoir insertion: the offsets [n1][3] it copies, unrotated (else null)
+};
+template <> struct TrialFrameR<false> : TrialFrame {};
+// RSV = false: the code of an engine that holds no reservoir (the farm windows' instances without one)
+template <bool RSV = true, class TopoT>
+__device__ __forceinline__ TrialFrameR<RSV> trial_frame(const TopoT &tp, const BoxDev &bx, int replica, int t, int m, int mv, const double *u,
                                                   double t_step, double r_step) {
-    TrialFrame f;
+    TrialFrameR<RSV> f;
     const int n1 = tp.n1[t];
     const size_t rep3 = (size_t)replica * 3;
     f.src_m = mv == 3 ? 0 : m;                     // creation: the geometry of molecule 1 (create_molecule.f90:197-199)
@@ -1139,11 +1156,29 @@ __device__ __forceinline__ TrialFrame trial_frame(const TopoT &tp, const BoxDev 
     }
     if (mv == 3)
         for (int d = 0; d < 3; ++d) f.com[d] = bx.lo[d] + bx.L[d] * u[d];     // create_molecule.f90:180-184
+    if constexpr (RSV) {
+    f.rsv = nullptr;
+    if (mv == 3 && tp.rsv) {
+        // a type with a reservoir copies reservoir[min(int(u[3] n_r), n_r - 1)] and rotates nothing (create_molecule.f90:
+        // 185-193); an empty reservoir's insertion is never committed (molecule 0 of its block stands in: in bounds, zero-
+        // filled or stale)
+        if (const double *R = reservoir_of(tp, replica, t)) {
+            f.rsv = R + (size_t)max(reservoir_pick(tp, replica, t, u[3]), 0) * n1 * 3;
+            f.rot = false;
+        }
+    }
+    }
     return f;
 }
-template <class TopoT>
-__device__ __forceinline__ void trial_offset(const TopoT &tp, const TrialFrame &f, int replica, int t, int a, double o[3]) {
+template <bool RSV = true, class TopoT>
+__device__ __forceinline__ void trial_offset(const TopoT &tp, const TrialFrameR<RSV> &f, int replica, int t, int a, double o[3]) {
     const size_t rep3 = (size_t)replica * 3;
+    if constexpr (RSV) {
+        if (f.rsv) {
+            for (int d = 0; d < 3; ++d) o[d] = f.rsv[(size_t)a * 3 + d];
+            return;
+        }
+    }
     const int j = atom_slot(tp, t, f.src_m, a);
     for (int d = 0; d < 3; ++d) o[d] = tp.off[(rep3 + d) * tp.n_cap_atoms + j];
     if (f.rot) {                                                             // (p, q) = (1, 2), (2, 0) or (0, 1)
@@ -1159,16 +1194,18 @@ __device__ __forceinline__ void trial_offset(const TopoT &tp, const TrialFrame &
 
 static __global__ void trial_build_kernel(Topo tp, BoxDev bx, const RecipItem *__restrict__ items, const int *__restrict__ move,
                                    const double *__restrict__ uu, double t_step, double r_step, double *__restrict__ rows,
-                                   int row_stride, int frame_at, int n) {
+                                   int row_stride, int frame_at, int n, int pick_at) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n) return;
     const RecipItem it = items[c];
     const int mv = move[c];
     if (mv == 4) return;
     const int n1 = tp.n1[it.t];
-    const TrialFrame f = trial_frame(tp, bx, it.replica, it.t, it.m, mv, uu + 5 * (size_t)c, t_step, r_step);
+    const auto f = trial_frame(tp, bx, it.replica, it.t, it.m, mv, uu + 5 * (size_t)c, t_step, r_step);
     double *row = rows + (size_t)c * row_stride * 3;
     for (int d = 0; d < 3; ++d) row[(size_t)frame_at * 3 + d] = f.com[d];
+    // (pick_at > 0: the engine holds reservoirs, and the row has room for the commit's reservoir_row_pick)
+    if (pick_at > 0 && f.rsv) row[(size_t)pick_at * 3] = (double)reservoir_pick(tp, it.replica, it.t, uu[5 * (size_t)c + 3]);
     for (int a = 0; a < n1; ++a) {
         double o[3];
         trial_offset(tp, f, it.replica, it.t, a, o);

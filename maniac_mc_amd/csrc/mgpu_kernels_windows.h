@@ -375,6 +375,7 @@ static __device__ long long g_farm_stamps[3][8];
 #endif
 
 // One chain resolved by ONE WAVE (all 64 lanes arrive): `scratch` = 4 nsplit + 4 doubles of LDS of its own.
+template <bool RSV>
 __device__ __forceinline__ void farm_resolve(const Topo &tp, const BoxDev &bx, double *__restrict__ pos, int *__restrict__ nmol,
                                              const FarmArgs &g, const FarmRec &rec, int c, int lane, double *scratch) {
     double *ho = g.host_out + (size_t)kFarmOut * c;
@@ -465,16 +466,17 @@ __device__ __forceinline__ void farm_resolve(const Topo &tp, const BoxDev &bx, d
     const int nm = nmol[rec.replica * tp.n_res + rec.t];
     if (kind != 2) {
         const int m = kind == 1 ? nm : rec.m;                 // appended at the first free slot (monte_carlo.f90:63, create_molecule.f90:64)
-        const TrialFrame f = trial_frame(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+        const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
         if (lane < n1) {
             double off[3];
-            trial_offset(tp, f, rec.replica, rec.t, lane, off);
+            trial_offset<RSV>(tp, f, rec.replica, rec.t, lane, off);
             const int j = atom_slot(tp, rec.t, m, lane);
             px[j] = f.com[0] + off[0]; py[j] = f.com[1] + off[1]; pz[j] = f.com[2] + off[2];
             for (int d = 0; d < 3; ++d) foff[(size_t)d * tp.n_cap_atoms + j] = off[d];
         }
         if (lane < 3) fcom[(size_t)lane * tp.n_mol_slots + m] = f.com[lane];
         if (lane == 0 && kind == 1) nmol[rec.replica * tp.n_res + rec.t] = nm + 1;
+        if constexpr (RSV) if (kind == 1 && f.rsv) reservoir_commit(tp, rec.replica, rec.t, 1, reservoir_pick(tp, rec.replica, rec.t, rec.u[3]), 0, lane);
     } else {
         const int last = nm - 1;                                 // swap-with-last, delete_molecule.f90:107-114
         if (last != rec.m) {
@@ -486,6 +488,7 @@ __device__ __forceinline__ void farm_resolve(const Topo &tp, const BoxDev &bx, d
             if (lane < 3) fcom[(size_t)lane * tp.n_mol_slots + rec.m] = fcom[(size_t)lane * tp.n_mol_slots + last];
         }
         if (lane == 0) nmol[rec.replica * tp.n_res + rec.t] = last;
+        if (RSV) reservoir_commit(tp, rec.replica, rec.t, 2, -1, last, lane);   // (slot `last` is read, never written, above)
     }
     // A(k): the buffer the k role filled with A + delta becomes the replica's current one
     if (lane == 0) g.acur[rec.replica] ^= 1;
@@ -496,6 +499,7 @@ __device__ __forceinline__ void farm_resolve(const Topo &tp, const BoxDev &bx, d
 // ---- the WIDE instances' pieces for a chain of more than kMaxFusedSitesWide sites
 // One pair work unit (entry, split) by ONE WAVE: the candidate row rebuilt into the wave's row in dynamic LDS, then
 // pair_sweep_item<0, ...> with the wave's slabs, exactly the batched path's NS = 0 sweep of the unit.
+template <bool RSV>
 __device__ __forceinline__ void farm_wide_pair_unit(const Topo &tp, const BoxDev &bx, const double *pos, const int *nmol, const double *res_q,
                                                     const int *res_atype, const double2 *pair_tab, const FarmArgs &g, const FarmRec &rec,
                                                     int kind, int ent, int split, int ns, char *s_dyn, const double2 *s_pair, int wave, int lane,
@@ -505,10 +509,10 @@ __device__ __forceinline__ void farm_wide_pair_unit(const Topo &tp, const BoxDev
     double *w_site = slab + (size_t)kPairWaves * kFarmWideSites * 3 + (size_t)wave * kSiteChunk * 4;
     int *w_sty = reinterpret_cast<int *>(slab + (size_t)kPairWaves * (kFarmWideSites * 3 + kSiteChunk * 4)) + wave * kSiteChunk;
     if (ent == 1) {
-        const TrialFrame f = trial_frame(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+        const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
         if (lane < tp.n1[rec.t]) {
             double off[3];
-            trial_offset(tp, f, rec.replica, rec.t, lane, off);
+            trial_offset<RSV>(tp, f, rec.replica, rec.t, lane, off);
             for (int d = 0; d < 3; ++d) cand[lane * 3 + d] = f.com[d] + off[d];
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -523,6 +527,7 @@ __device__ __forceinline__ void farm_wide_pair_unit(const Topo &tp, const BoxDev
 // The k role of chain c (every thread of the workgroup; s_skip is clear): candidate row, the sweep of the type's form with A +
 // delta into the replica's other A(k) buffer, the intra term of an insertion / deletion on the spare waves meanwhile, and the
 // energies into g.res[c].  Dynamic LDS: kFarmKFront bytes of row and intra tiles, the form's tables behind them.
+template <bool RSV>
 __device__ __forceinline__ void farm_wide_k_role(const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q, const int *trj,
                                                  const double2 *tw, int n_tasks, const RecipRow *rows, int n_rows, double2 *A_base,
                                                  const FarmArgs &g, const FarmRec &rec, int c, int acur, char *s_dyn, double *s_red, int tid) {
@@ -534,9 +539,9 @@ __device__ __forceinline__ void farm_wide_k_role(const Topo &tp, const BoxDev &b
     double4 *intra_a = reinterpret_cast<double4 *>(s_dyn + (size_t)kFarmWideSites * 3 * sizeof(double)), *intra_b = intra_a + kFarmWideSites;
     double2 *tabs = reinterpret_cast<double2 *>(s_dyn + kFarmKFront);
     if (kind != 2 && tid < n1) {
-        const TrialFrame f = trial_frame(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+        const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
         double off[3];
-        trial_offset(tp, f, rec.replica, rec.t, tid, off);
+        trial_offset<RSV>(tp, f, rec.replica, rec.t, tid, off);
         for (int d = 0; d < 3; ++d) cand[tid * 3 + d] = f.com[d] + off[d];
     }
     __syncthreads();
@@ -601,7 +606,8 @@ __device__ __forceinline__ void farm_wide_k_role(const Topo &tp, const BoxDev &b
 // matrix unit, one tile of site-states: recip_wide_sweep) -- storing A + delta into the other A(k) buffer; its intra term is
 // the thread form up to kIntraThreadMax sites and the wave form above, on the k workgroup's spare waves.  Chains of
 // <= kMaxFusedSitesWide sites take the narrow instance's code.
-template <bool FLAT, bool FASTW, bool WIDE = false>
+// RSV: the engine holds reservoirs (mgpu_replica_set_reservoir); without them the instances are the code they were before.
+template <bool FLAT, bool FASTW, bool WIDE = false, bool RSV = false>
 __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) void farm_window_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
@@ -665,6 +671,11 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) vo
             if (r.move == 4) r.pref = ((double)(nm - 1) + 1.0) / r.pref;   // (N' + 1) / (phi V), N' = the count after it
         }
     }
+    // an insertion from an empty reservoir: nothing to do (verdict 5) -- unless the replica waits for the driver's decision of
+    // an earlier step (which may refill it): the record then stays as it is, and the resolver returns 4
+    if (RSV && tid < n_c && s_rec[tid].move == 3 && reservoir_of(tp, s_rec[tid].replica, s_rec[tid].t) &&
+        reservoir_pick(tp, s_rec[tid].replica, s_rec[tid].t, 0.0) < 0 && !(s_rec[tid].forced == 0 && g.stalled[s_rec[tid].replica] != 0))
+        s_rec[tid].move = 0;
     if (tid < n_c) s_skip[tid] = s_rec[tid].move == 0 ? 1 : 0;          // (a stalled replica is the resolver's business)
     if (k_role && tid == 0) s_acur = s_rec[0].move != 0 ? g.acur[s_rec[0].replica] : 0;
     __syncthreads();
@@ -676,14 +687,14 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) vo
         const int c = c_lo;
         const FarmRec &rec = s_rec[0];
         if (WIDE && !s_skip[0] && tp.n1[rec.t] > kMaxFusedSitesWide) {
-            farm_wide_k_role(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, A_base, g, rec, c, s_acur, s_dyn, s_red, tid);
+            farm_wide_k_role<RSV>(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, A_base, g, rec, c, s_acur, s_dyn, s_red, tid);
         } else if (!s_skip[0]) {
             const int kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
             const int n1 = tp.n1[rec.t];
             if (kind != 2 && tid < n1) {
-                const TrialFrame f = trial_frame(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                 double off[3];
-                trial_offset(tp, f, rec.replica, rec.t, tid, off);
+                trial_offset<RSV>(tp, f, rec.replica, rec.t, tid, off);
                 for (int d = 0; d < 3; ++d) s_cand[0][tid * 3 + d] = f.com[d] + off[d];
             }
             __syncthreads();                                           // (uniform: s_skip is the workgroup's)
@@ -730,14 +741,14 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) vo
             const int ent = j / ns, split = j - ent * ns;
             const int n1 = tp.n1[rec.t];
             if (WIDE && n1 > kMaxFusedSitesWide && (ent == 0 ? kind != 1 : kind != 2)) {
-                farm_wide_pair_unit(tp, bx, pos, nmol, res_q, res_atype, pair_tab, g, rec, kind, ent, split, ns, s_dyn, s_pair, wave, lane, wg);
+                farm_wide_pair_unit<RSV>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, g, rec, kind, ent, split, ns, s_dyn, s_pair, wave, lane, wg);
             } else if (ent == 0 ? kind != 1 : kind != 2) {
                 double *cand = &s_cand[wave][0];
                 if (ent == 1) {
-                    const TrialFrame f = trial_frame(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                    const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                     if (lane < n1) {
                         double off[3];
-                        trial_offset(tp, f, rec.replica, rec.t, lane, off);
+                        trial_offset<RSV>(tp, f, rec.replica, rec.t, lane, off);
                         for (int d = 0; d < 3; ++d) cand[lane * 3 + d] = f.com[d] + off[d];
                     }
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -787,7 +798,7 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) vo
     MGPU_FSTAMP(tid == 0 && k_role && c_lo == 0, 0, 7);
     if (wave < n_c && s_resolve[wave]) {
         double *scratch = reinterpret_cast<double *>(s_dyn) + (size_t)wave * (4 * ns + 4);
-        farm_resolve(tp, bx, pos, nmol, g, s_rec[wave], c_lo + wave, lane, scratch);
+        farm_resolve<RSV>(tp, bx, pos, nmol, g, s_rec[wave], c_lo + wave, lane, scratch);
     }
 }
 

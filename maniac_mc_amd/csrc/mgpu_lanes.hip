@@ -211,7 +211,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
             n1_all = std::max(n1_all, e->tp.n1[t[c]]);
         }
         frame_at = n1_all;
-        site_stride = 2 * n1_all + 1;
+        site_stride = 2 * n1_all + 1 + (e->rsv_any ? 1 : 0);     // (+ the reservoir pick, reservoir_row_pick)
     }
     // from here on the rows of the lane's previous trial are gone (the staging block below may be regrown and is
     // overwritten): a failed submit must not leave them committable "from the lane's resident rows"
@@ -380,7 +380,8 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
                     return;
                 }
                 // the insertion copies slot 0's frame whatever the count (create_molecule.f90:196-200): there must be one
-                if (k == MGPU_CREATION && !e->frames_held[idx]) {
+                // (a type with a reservoir copies a reservoir molecule instead)
+                if (k == MGPU_CREATION && !e->frames_held[idx] && !has_reservoir(e, idx)) {
                     errs[q].set(c, MGPU_ERR_STATE, "move_trial_submit: an insertion copies the geometry of molecule 1 of its type, "
                                                    "and this type has never held one on this replica");
                     return;
@@ -496,7 +497,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
         hipLaunchKernelGGL(trial_build_kernel, dim3((n + 127) / 128), dim3(128), 0, ln.stream, e->tp, e->bx,
                            (const RecipItem *)((char *)ln.d_sites.p + site_bytes + pit_cap), (const int *)((char *)ln.d_sites.p + build_at),
                            (const double *)((char *)ln.d_sites.p + build_at + build_mv), build->t_step, build->r_step,
-                           (double *)ln.d_sites.p, site_stride, frame_at, n);
+                           (double *)ln.d_sites.p, site_stride, frame_at, n, e->rsv_any ? 2 * frame_at + 1 : 0);
         HIP_TRY(hipGetLastError());
     } else {
         HIP_TRY(hipMemcpyAsync(ln.d_sites.p, ln.h_in.p, in_bytes, hipMemcpyHostToDevice, ln.stream));
@@ -731,6 +732,7 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
                 if (!ok) P.range_lost.push_back(idx);
                 if (e->tp.n1[t[c]] > site_stride) { errs[q].set(c, MGPU_ERR_INVALID_ARG, "site_stride smaller than atoms_in_res"); return; }
             }
+            if (kind[c] == MGPU_DELETION && built) it.frame = ln.last_trial_frame;   // (device-built: a reservoir receives the last slot)
             if (kind[c] != MGPU_MOVE) { P.new_counts.push_back(idx); P.new_counts.push_back(it.aux); }
             items[at++] = it;
         }
@@ -865,7 +867,7 @@ int mgpu_lane_site_buffer(mgpu_engine *e, int lane, int n_max, int site_stride, 
     ln.h_trial_items = nullptr;
     // sized for the largest trial shape the lane accepts for n_max candidates: host rows of site_stride sites, or
     // device-built rows [sites | com | offsets] with their move codes and uniform numbers, acceptance records included
-    const size_t built = trial_staging_bytes(n_max, 2 * site_stride + 1) + ((size_t)n_max * sizeof(int) + 8) + (size_t)5 * n_max * sizeof(double) + 16;
+    const size_t built = trial_staging_bytes(n_max, 2 * site_stride + 2) + ((size_t)n_max * sizeof(int) + 8) + (size_t)5 * n_max * sizeof(double) + 16;
     if ((rc = ln.h_in.reserve(std::max(trial_staging_bytes(n_max, site_stride), built)))) return rc;
     ln.h_in_lent = true;
     *sites = (double *)ln.h_in.p;

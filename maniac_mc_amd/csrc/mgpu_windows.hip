@@ -471,7 +471,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         }
         // an insertion copies the offsets of molecule 1 of its type, whatever the count (create_molecule.f90:196-200): slot
         // 0's frame, which a deletion leaves in place -- a type that never held a molecule on this replica has none
-        if (k == MGPU_CREATION && !e->frames_held[idx]) { rc = set_error(MGPU_ERR_STATE, "farm_window_submit: an insertion copies the geometry of molecule 1 of its type, and this type has never held one on this replica"); break; }
+        if (k == MGPU_CREATION && !e->frames_held[idx] && !has_reservoir(e, idx)) { rc = set_error(MGPU_ERR_STATE, "farm_window_submit: an insertion copies the geometry of molecule 1 of its type, and this type has never held one on this replica"); break; }
         n1_max = std::max(n1_max, n1);
         pd.kind[c] = k;
         // a built candidate's centre lies in the cell; with tight frames its sites are within the fast fold's range
@@ -502,8 +502,10 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     if (lds > (wide ? kFarmWideLdsMax : 64 * 1024)) return set_error(MGPU_ERR_CAPACITY, "farm_window_submit: the window does not fit the LDS budget");
     if (lds > 64 * 1024) {
         // beyond 64 KiB of dynamic LDS a kernel opts in (gfx950: up to 160 KiB per workgroup); only the WIDE instances get here
-        const void *wide_kernels[4] = {(const void *)farm_window_kernel<false, false, true>, (const void *)farm_window_kernel<false, true, true>,
-                                       (const void *)farm_window_kernel<true, false, true>, (const void *)farm_window_kernel<true, true, true>};
+        const void *wide_kernels[8] = {(const void *)farm_window_kernel<false, false, true>, (const void *)farm_window_kernel<false, true, true>,
+                                       (const void *)farm_window_kernel<true, false, true>, (const void *)farm_window_kernel<true, true, true>,
+                                       (const void *)farm_window_kernel<false, false, true, true>, (const void *)farm_window_kernel<false, true, true, true>,
+                                       (const void *)farm_window_kernel<true, false, true, true>, (const void *)farm_window_kernel<true, true, true, true>};
         for (const void *k : wide_kernels) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     fw.seq += 1;
@@ -535,11 +537,16 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     ln.trial_alt = false;
     for (int c = 0; c < n; ++c) alt_forget(e, replica[c]);     // (the window's k role overwrites their other buffers)
     e->a_switched = true;
-#define MGPU_LAUNCH_FARM(FL, FW, WI)                                                                                       \
+#define MGPU_LAUNCH_FARM_RS(FL, FW, WI, RS)                                                                                \
     do {                                                                                                                   \
-        hipLaunchKernelGGL((farm_window_kernel<FL, FW, WI>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, \
+        hipLaunchKernelGGL((farm_window_kernel<FL, FW, WI, RS>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, \
                            e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, \
                            e->d_A, g);                                                                                     \
+    } while (0)
+    // (an engine without reservoirs runs the instances without their code)
+#define MGPU_LAUNCH_FARM(FL, FW, WI)                                                                                       \
+    do {                                                                                                                   \
+        if (e->rsv_any) MGPU_LAUNCH_FARM_RS(FL, FW, WI, true); else MGPU_LAUNCH_FARM_RS(FL, FW, WI, false);               \
     } while (0)
     if (wide) {
         if (e->pair_flat) { if (ff) MGPU_LAUNCH_FARM(true, true, true); else MGPU_LAUNCH_FARM(true, false, true); }
@@ -549,6 +556,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         else { if (ff) MGPU_LAUNCH_FARM(false, true, false); else MGPU_LAUNCH_FARM(false, false, false); }
     }
 #undef MGPU_LAUNCH_FARM
+#undef MGPU_LAUNCH_FARM_RS
     HIP_TRY(hipGetLastError());
     fw.pending.push_back(std::move(pd));
     e->farm.windows += 1;

@@ -156,6 +156,23 @@ class Engine:
         check(self.L.mgpu_replica_get_frames(self.h, C.c_int(replica), C.c_int(t), C.byref(nm), _d(com), _d(off)))
         return com, off
 
+    def set_reservoir(self, replica, t, off, cap=0):
+        """mgpu_replica_set_reservoir: the reservoir of (replica, t) holds the molecule offsets off (n, n1, 3); cap = 0 sizes it
+        by the conservation bound (n + the type's capacity).  off of no molecules with cap = 0 removes it."""
+        n1 = int(self.topo.atoms_in_res[t]) if 0 <= t < len(self.topo.atoms_in_res) else 1   # (a bad type: the engine refuses it)
+        off = np.ascontiguousarray(np.asarray(off, dtype=np.float64).reshape(-1, n1, 3))
+        check(self.L.mgpu_replica_set_reservoir(self.h, C.c_int(replica), C.c_int(t), C.c_int(off.shape[0]), C.c_int(cap), _d(off)))
+
+    def get_reservoir(self, replica, t):
+        """mgpu_replica_get_reservoir: the reservoir's molecule offsets (n, n1, 3) as the device holds them now."""
+        n1 = int(self.topo.atoms_in_res[t])
+        nr = C.c_int()
+        check(self.L.mgpu_replica_get_reservoir(self.h, C.c_int(replica), C.c_int(t), C.byref(nr), None))
+        off = np.zeros((nr.value, n1, 3))
+        if nr.value:
+            check(self.L.mgpu_replica_get_reservoir(self.h, C.c_int(replica), C.c_int(t), C.byref(nr), _d(off)))
+        return off
+
     def move_trial(self, replica, t, m, move, u, translation_step, rotation_step, lane=0):
         """Device-built trials (mgpu_move_trial_submit + wait): (old[n,5], new[n,5])."""
         m = _ints(m); n = m.shape[0]

@@ -225,6 +225,22 @@ module maniac_gpu
             real(c_double), intent(out) :: com(*), off(*)
             integer(c_int) :: rc
         end function
+        ! reservoirs of the device-built steps: offsets only, off(3, n1, n)
+        function mgpu_replica_set_reservoir(e, replica, t, n, cap, off) bind(C, name="mgpu_replica_set_reservoir") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: replica, t, n, cap
+            real(c_double), intent(in) :: off(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_replica_get_reservoir(e, replica, t, n, off) bind(C, name="mgpu_replica_get_reservoir") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: replica, t
+            integer(c_int), intent(out) :: n
+            real(c_double), intent(out) :: off(*)
+            integer(c_int) :: rc
+        end function
         function mgpu_move_trial_submit(e, lane, n, replica, t, m, move, u, translation_step, rotation_step) &
                 bind(C, name="mgpu_move_trial_submit") result(rc)
             import :: c_ptr, c_int, c_double

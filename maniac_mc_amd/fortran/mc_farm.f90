@@ -48,7 +48,7 @@ module mc_farm
     public :: mfarm_create, mfarm_run, mfarm_destroy, mfarm_get_energy, mfarm_get_molecule, mfarm_recalibrate
     public :: mfarm_get_timers, mfarm_set_gcmc, mfarm_get_counts, mfarm_get_counters, mfarm_set_triclinic
     public :: mfarm_rng_sample, mfarm_set_drivers, mfarm_configure, mfarm_select, mfarm_exchange_block
-    public :: mfarm_window_mode, mfarm_set_window_depth
+    public :: mfarm_window_mode, mfarm_set_window_depth, mfarm_set_reservoir, mfarm_get_reservoir
 
     real(real64), parameter :: PI = 3.14159265358979323846_real64
     real(real64), parameter :: TWOPI = 2.0_real64 * PI
@@ -136,6 +136,16 @@ module mc_farm
         integer :: depth = 2
         integer(int64) :: undecided = 0
         integer(int64), allocatable :: cxs(:, :)           ! (4, R) xoshiro256+ state of every chain
+        ! Reservoirs (mfarm_set_reservoir; create_molecule.f90:117-128, :185-193, delete_molecule.f90:146-166): an insertion of a
+        ! type with one copies reservoir[min(int(u7 n_r), n_r - 1) + 1] unrotated, and the commits keep the reservoir (swap with
+        ! the last / the box's last molecule appended).  Box count + reservoir count is conserved: rsv_total(ia, r) -- so an
+        ! EMPTY reservoir is cnt == rsv_total, and its insertion is skipped (the reference reads an undefined slot there).
+        ! Host-built farms keep the reservoir here (rsv, rsv_n); device-built ones leave it to the engine.
+        logical :: has_rsv = .false.
+        logical, allocatable :: rsv_on(:)                  ! (n_active)
+        integer, allocatable :: rsv_total(:, :)            ! (n_active, R)
+        integer, allocatable :: rsv_n(:, :)                ! (n_active, R) host-built: reservoir counts
+        real(real64), allocatable :: rsv(:, :, :, :)       ! (3 * max_n1, rsv_cap, n_active, R) host-built: offsets
     end type farm_state
 
     ! Several farms may exist in one process (one per engine: different boxes, force fields or GPUs); the entry points act
@@ -457,6 +467,10 @@ contains
         end if
         if (allocated(F%energy)) deallocate(F%energy)
         if (allocated(F%cxs)) deallocate(F%cxs)
+        if (allocated(F%rsv_on)) deallocate(F%rsv_on, F%rsv_total)
+        if (allocated(F%rsv_n)) deallocate(F%rsv_n)
+        if (allocated(F%rsv)) deallocate(F%rsv)
+        F%has_rsv = .false.
         do g = 0, MGPU_LANES - 1
             if (allocated(F%lane(g)%rep)) then
                 deallocate(F%lane(g)%rep, F%lane(g)%t, F%lane(g)%m, F%lane(g)%kind, F%lane(g)%accept, &
@@ -569,7 +583,7 @@ contains
                     if (n > 0) slot = min(int(L%u(2, i) * n) + 1, n)
                 end if                                                  ! GCMC: rotation.f90:45 returns
             else if (mv == MV_CREATION) then
-                if (n < F%cap(ia)) slot = n + 1                         ! monte_carlo.f90:63; full: the reference aborts
+                if (n < F%cap(ia) .and. .not. rsv_empty(ia, r, n)) slot = n + 1   ! monte_carlo.f90:63; full: the reference aborts
             else
                 if (n > 0) slot = min(int(L%u(2, i) * n) + 1, n)        ! PickRandomMoleculeIndex; 0: the drivers return
             end if
@@ -696,7 +710,15 @@ contains
                                                      F%matrix(d, 3) * L%u(6, i))
                     end do
                 end if
-                if (n1 > 1) then
+                if (rsv_host(ia)) then
+                    ! create_molecule.f90:185-193: the offsets of a reservoir molecule, unrotated
+                    k = rsv_pick(ia, r, L%u(7, i))
+                    do a = 1, n1
+                        do d = 1, 3
+                            L%new_off(d, a, j) = F%rsv(3 * (a - 1) + d, k, ia, r)
+                        end do
+                    end do
+                else if (n1 > 1) then
                     axis = int(L%u(8, i) * 3.0_real64) + 1
                     call rotate_offsets(L%new_off(:, :, j), n1, axis, L%u(7, i) * TWOPI)
                 end if
@@ -820,10 +842,21 @@ contains
                 select case (L%move(j))
                 case (MV_CREATION)
                     if (.not. F%device_build) call store_molecule(F%mol(:, base + slot, r), L%new_com(:, j), L%new_off(:, :, j), n1)
+                    if (rsv_host(ia)) then
+                        ! create_molecule.f90:121-127: the copied molecule leaves the reservoir, the last one takes its place
+                        k = rsv_pick(ia, r, L%u(7, i))
+                        F%rsv(:, k, ia, r) = F%rsv(:, F%rsv_n(ia, r), ia, r)
+                        F%rsv_n(ia, r) = F%rsv_n(ia, r) - 1
+                    end if
                     F%cnt(ia, r) = F%cnt(ia, r) + 1
                     k_c = k_c + 1
                 case (MV_DELETION)
                     last = F%cnt(ia, r)                                    ! RemoveMolecule, delete_molecule.f90:107-114
+                    if (rsv_host(ia)) then
+                        ! delete_molecule.f90:159-161: the reservoir gains the offsets of the box's LAST molecule of the type
+                        F%rsv_n(ia, r) = F%rsv_n(ia, r) + 1
+                        F%rsv(1:3 * n1, F%rsv_n(ia, r), ia, r) = F%mol(4:3 + 3 * n1, base + last, r)
+                    end if
                     if (.not. F%device_build) then
                         do k = 1, 3 + 3 * n1
                             F%mol(k, base + slot, r) = F%mol(k, base + last, r)
@@ -893,11 +926,38 @@ contains
                 if (n > 0) slot = min(int(u(2) * n) + 1, n)
             end if                                                      ! GCMC: rotation.f90:45 returns
         else if (mv == MV_CREATION) then
-            if (n < F%cap(ia)) slot = n + 1                             ! monte_carlo.f90:63; full: the reference aborts
+            if (n < F%cap(ia) .and. .not. rsv_empty(ia, r, n)) slot = n + 1   ! monte_carlo.f90:63; full: the reference aborts
         else
             if (n > 0) slot = min(int(u(2) * n) + 1, n)                 ! PickRandomMoleculeIndex; 0: the drivers return
         end if
     end subroutine select_move
+
+    ! an insertion of type ia on chain r (count n) would copy from an empty reservoir: the step is skipped (the device paths
+    ! find the same: verdict 5)
+    pure function rsv_empty(ia, r, n) result(yes)
+        integer, intent(in) :: ia, r, n
+        logical :: yes
+        yes = .false.
+        if (.not. F%has_rsv) return
+        if (F%rsv_on(ia)) yes = n >= F%rsv_total(ia, r)
+    end function rsv_empty
+
+    ! the host-built farm's reservoir molecule an insertion copies (u7: the rotation angle's number without a reservoir)
+    pure function rsv_pick(ia, r, u7) result(pick)
+        integer, intent(in) :: ia, r
+        real(real64), intent(in) :: u7
+        integer :: pick, nr
+        nr = F%rsv_n(ia, r)
+        pick = min(int(u7 * real(nr, real64)), nr - 1) + 1
+    end function rsv_pick
+
+    pure function rsv_host(ia) result(yes)
+        integer, intent(in) :: ia
+        logical :: yes
+        yes = .false.
+        if (.not. F%has_rsv .or. F%device_build) return
+        yes = F%rsv_on(ia)
+    end function rsv_host
 
     ! what mc_acceptance_probability multiplies exp(-dE / T) by (monte_carlo_utils.f90:184-226), as resolve_and_commit forms it
     pure function acceptance_prefactor(mv, ia, r) result(pref)
@@ -1461,5 +1521,92 @@ contains
         com = F%mol(1:3, F%first(ia + 1) + slot + 1, replica + 1)
         off = reshape(F%mol(4:, F%first(ia + 1) + slot + 1, replica + 1), [3, F%max_n1])
     end subroutine mfarm_get_molecule
+
+    ! The reservoir of the active type of engine residue type t (0-based), the same for every chain: off(3, n1, n) offsets.
+    ! Host-built farms keep it in their mirror; device-built ones hand it to the engine (mgpu_replica_set_reservoir, the
+    ! conservation bound as capacity).  Call after mfarm_create (and mfarm_set_gcmc), before the first mfarm_run.
+    function mfarm_set_reservoir(t, n, off) bind(C, name="mfarm_set_reservoir") result(rc)
+        integer(c_int), value :: t, n
+        real(c_double), intent(in) :: off(*)
+        integer(c_int) :: rc
+        integer :: ia, r, k, n1, cap_need
+        real(real64), allocatable :: grown(:, :, :, :)
+        rc = MGPU_OK
+        ia = 0
+        if (F%ready .and. allocated(F%res_type)) then
+            do k = 1, F%n_active
+                if (F%res_type(k) == t) ia = k
+            end do
+        end if
+        if (ia == 0 .or. n < 0) then
+            rc = 3
+            return
+        end if
+        n1 = F%n1(ia)
+        if (.not. allocated(F%rsv_on)) then
+            allocate(F%rsv_on(F%n_active), F%rsv_total(F%n_active, F%n_replicas))
+            F%rsv_on = .false.
+            F%rsv_total = 0
+        end if
+        if (F%device_build) then
+            do r = 1, F%n_replicas
+                rc = mgpu_replica_set_reservoir(F%engine, int(r - 1, c_int), t, n, 0_c_int, off)
+                if (rc /= MGPU_OK) return
+            end do
+        else
+            cap_need = n + F%cap(ia)
+            if (.not. allocated(F%rsv_n)) then
+                allocate(F%rsv_n(F%n_active, F%n_replicas))
+                F%rsv_n = 0
+            end if
+            if (.not. allocated(F%rsv)) then
+                allocate(F%rsv(3 * F%max_n1, max(1, cap_need), F%n_active, F%n_replicas))
+                F%rsv = 0.0_real64
+            else if (size(F%rsv, 2) < cap_need) then
+                allocate(grown(3 * F%max_n1, cap_need, F%n_active, F%n_replicas))
+                grown = 0.0_real64
+                grown(:, 1:size(F%rsv, 2), :, :) = F%rsv
+                call move_alloc(grown, F%rsv)
+            end if
+            do r = 1, F%n_replicas
+                do k = 1, n
+                    F%rsv(1:3 * n1, k, ia, r) = off(3 * n1 * (k - 1) + 1:3 * n1 * k)
+                end do
+                F%rsv_n(ia, r) = n
+            end do
+        end if
+        do r = 1, F%n_replicas
+            F%rsv_total(ia, r) = F%cnt(ia, r) + n
+        end do
+        F%rsv_on(ia) = .true.
+        F%has_rsv = .true.
+    end function mfarm_set_reservoir
+
+    ! chain `replica` (0-based)'s reservoir of active type ia (0-based): its count, and off(3, n1, n) where room allows (cap)
+    function mfarm_get_reservoir(replica, ia, cap, n, off) bind(C, name="mfarm_get_reservoir") result(rc)
+        integer(c_int), value :: replica, ia, cap
+        integer(c_int), intent(out) :: n
+        real(c_double), intent(out) :: off(*)
+        integer(c_int) :: rc
+        integer :: n1, k
+        real(c_double), allocatable :: buf(:)
+        rc = MGPU_OK
+        n = 0
+        if (.not. F%has_rsv) return
+        if (.not. F%rsv_on(ia + 1)) return
+        n1 = F%n1(ia + 1)
+        if (F%device_build) then
+            allocate(buf(3 * n1 * max(1, F%rsv_total(ia + 1, replica + 1))))
+            rc = mgpu_replica_get_reservoir(F%engine, replica, int(F%res_type(ia + 1), c_int), n, buf)
+            if (rc /= MGPU_OK .or. n > cap) return
+            off(1:3 * n1 * n) = buf(1:3 * n1 * n)
+        else
+            n = F%rsv_n(ia + 1, replica + 1)
+            if (n > cap) return
+            do k = 1, n
+                off(3 * n1 * (k - 1) + 1:3 * n1 * k) = F%rsv(1:3 * n1, k, ia + 1, replica + 1)
+            end do
+        end if
+    end function mfarm_get_reservoir
 
 end module mc_farm

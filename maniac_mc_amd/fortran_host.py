@@ -57,6 +57,8 @@ def lib():
         L.mfarm_create.restype = C.c_int
         L.mfarm_run.restype = C.c_int
         L.mfarm_set_gcmc.restype = C.c_int
+        L.mfarm_set_reservoir.restype = C.c_int
+        L.mfarm_get_reservoir.restype = C.c_int
         _host = L
     return _host
 
@@ -67,6 +69,9 @@ class FortranFarm:
     NVT by default (translation / rotation).  ``gcmc=dict(p_translation=..., p_rotation=..., fugacity=...)``
     switches insertion / deletion on: ``fugacity`` in molecules per cubic Angstrom, scalar, per active
     type, or (n_active, R) for an isotherm sweep; ``mol_capacity`` bounds the molecule count per type.
+    ``reservoir={t: off (n, n1, 3)}`` gives every chain a reservoir of residue type t (MANIAC's ``-r reservoir.data``;
+    ``io_maniac.reservoir_offsets`` reads one): insertions of t copy a reservoir molecule unrotated and take it out of the
+    reservoir, deletions put the box's last molecule of t into it, and an insertion from an empty reservoir is skipped.
     """
 
     _live = None          # the farm created last that is still open (tests close leftovers through it)
@@ -77,7 +82,7 @@ class FortranFarm:
                  translation_step: float = 0.3, rotation_step: float = 0.3, p_translation: float = 0.5,
                  rng_kind: int = 1, n_threads: int = 8, mol_capacity=None, gcmc=None,
                  n_lanes: int = 2, n_drivers: int = 1, device_build: bool = False, device_accept: bool = False,
-                 window: bool = False, window_depth: int = 2):
+                 window: bool = False, window_depth: int = 2, reservoir=None):
         self.H = lib()
         # mc_farm.f90 keeps up to MAX_FARMS farms; every call below selects this farm's slot first
         free = [k for k in range(FortranFarm.MAX_FARMS) if k not in FortranFarm._slots]
@@ -170,6 +175,10 @@ class FortranFarm:
                                        fug.ctypes.data_as(_dp))
             if rc:
                 raise ValueError(f"mfarm_set_gcmc: bad probabilities / fugacity (code {rc})")
+        for t, off in (reservoir or {}).items():
+            n1 = int(topo.atoms_in_res[t])
+            off = np.ascontiguousarray(np.asarray(off, dtype=np.float64).reshape(-1, n1, 3))
+            _lib.check(self.H.mfarm_set_reservoir(C.c_int(int(t)), C.c_int(off.shape[0]), off.ctypes.data_as(_dp)))
 
     def _select(self):
         self.H.mfarm_select(C.c_int(self.slot))
@@ -243,6 +252,19 @@ class FortranFarm:
         self.H.mfarm_get_molecule(C.c_int(replica), C.c_int(ia), C.c_int(slot), com.ctypes.data_as(_dp),
                                   off.ctypes.data_as(_dp))
         return com, off
+
+    def reservoir(self, replica: int, ia: int):
+        """chain `replica`'s reservoir of active type ia: offsets (n, n1, 3) -- the driver's mirror (host-built farms) or the
+        engine's (device-built)"""
+        n1 = int(self.sys.topo.atoms_in_res[int(self.active[ia])])
+        cap = self.mol_capacity[int(self.active[ia])] + 4096
+        off = np.zeros((cap, n1, 3))
+        n = C.c_int()
+        self._select()
+        _lib.check(self.H.mfarm_get_reservoir(C.c_int(replica), C.c_int(ia), C.c_int(cap), C.byref(n), off.ctypes.data_as(_dp)))
+        if n.value > cap:
+            raise RuntimeError("reservoir larger than the buffer")
+        return off[: n.value].copy()
 
     @property
     def trials(self):

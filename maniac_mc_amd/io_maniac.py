@@ -595,6 +595,20 @@ def load_system(maniac_path, data_path, inc_path, with_data=False):
     return system, inp
 
 
+def reservoir_offsets(path, inp: ManiacInput):
+    """A MANIAC reservoir data file (`-r reservoir.data`) -> {residue type (0-based): offsets (n, n1, 3)} for every type
+    the file holds molecules of: exactly the offsets the single-chain front end hands to mchain_set_reservoir_residue
+    (run.py), in the form Engine.set_reservoir and FortranFarm take them.  The reservoir's centres are not returned (only
+    reservoir.lammpstrj reads them)."""
+    rdat = read_lammps_data(path, inp)
+    out = {}
+    for t, r in enumerate(inp.residues):
+        off = np.ascontiguousarray(np.asarray(rdat["off"][t], dtype=np.float64).reshape(-1, r.nb_atoms, 3))
+        if off.shape[0]:
+            out[t] = off
+    return out
+
+
 # ---- log.maniac header --------------------------------------------------------------------------
 
 MANIAC_VERSION = "v0.3.0-beta"      # the reference version this front end mirrors (its version_module string)

@@ -11,6 +11,8 @@ import os
 import sys
 import time
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
@@ -26,6 +28,8 @@ def main():
     ap.add_argument("--workload", default="spce", choices=("spce", "co2_gcmc", "adsorbate24"),
                     help="spce: the 10 125-atom box, translation / rotation; co2_gcmc: bench.py's 50 A CO2 box, insertion / deletion only; "
                          "adsorbate24: bench.py's 64 rigid 24-site adsorbates in a 60 A box, translation / rotation")
+    ap.add_argument("--reservoir", action="store_true",
+                    help="co2_gcmc: every chain draws its insertions from a reservoir of 400 random rotations of CO2 (mfarm_set_reservoir)")
     ap.add_argument("--json", default="")
     args = ap.parse_args()
     from maniac_mc_amd import synth
@@ -40,6 +44,18 @@ def main():
         s = synth.co2_box(64, seed=13)
         kw = dict(translation_step=1.0, rotation_step=0.6, mol_capacity=[400],
                   gcmc=dict(p_translation=0.0, p_rotation=0.0, fugacity=100.0 / 50.0 ** 3))
+    rsv = None
+    if args.reservoir:
+        if args.workload != "co2_gcmc":
+            ap.error("--reservoir goes with --workload co2_gcmc")
+        rng = np.random.default_rng(5)
+        q = rng.normal(size=(400, 4))
+        q /= np.linalg.norm(q, axis=1)[:, None]
+        w, x, y, z = q.T
+        rot = np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], -1),
+                        np.stack([2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)], -1),
+                        np.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1)], 1)
+        rsv = {0: np.einsum("mij,aj->mai", rot, s.offsets[0][0])}
     rows = []
     for R in [int(x) for x in args.replicas.split(",")]:
         for mode in args.modes.split(","):
@@ -49,7 +65,7 @@ def main():
                 window = mode.startswith("w")
                 depth = int(mode[1:]) if window else 1
                 farm = FortranFarm(s, R, seed=77, n_threads=max(args.threads, drivers), n_lanes=lanes, n_drivers=drivers, device_build=True,
-                                   window=window, window_depth=depth, **kw)
+                                   window=window, window_depth=depth, reservoir=rsv, **kw)
                 try:
                     farm.run(20)
                     chunk = (400 if R <= 64 else 200) if window else 50       # (see bench.py replicas_sweep: a chunk ends with a synchronise)
