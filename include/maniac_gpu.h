@@ -254,6 +254,19 @@ int mgpu_recip_energy_candidates(mgpu_engine *e, int n_candidates, const int *re
 #define MGPU_RECIP_FORM_PER_K 4             /* recip_kernel: one k per thread, the sites a tile at a time */
 int mgpu_recip_form(const mgpu_engine *e, int n1_max, int kind, int out[4]);
 
+/* The layout of the pair sweeps the engine chose at creation from its topology (host only, no device work).
+ * out[0] = 1 where pair_flat_kernel is in use, else 0 (pair_sweep_kernel);
+ * out[1], out[2] = atom-type groups of all frozen residues together (limit 32) and planes (limit 64: a frozen type counts
+ *   mol_capacity x its groups, every other type its atoms_in_res) of the frozen layout -- the counts the flat kernel's
+ *   eligibility is judged on, whether or not it is wanted (it also needs an orthorhombic box and no active type of 64 or
+ *   more sites);
+ * out[3] = the frozen residue type whose framework batched trials sweep with pair_frozen_kernel as the engine stands now
+ *   (flat kernels, orthorhombic box, exactly one frozen type, the same in every replica, holding a molecule), -1 for none;
+ * out[4 + t] = residue type t's layout: 0 plane-major, 1 site-major, 2 frozen (site-major, sites sorted by atom type);
+ *   -1 for t >= n_res.  A frozen residue is an inactive one of 64 or more sites while the flat kernel is in use. */
+#define MGPU_PAIR_LAYOUT_LEN 12
+int mgpu_pair_layout(const mgpu_engine *e, int out[MGPU_PAIR_LAYOUT_LEN]);
+
 /* ComputeEwaldSelfInteractionSingleMol (ewald_energy.f90:308-336); configuration independent. */
 int mgpu_self_energy(const mgpu_engine *e, int t, double *e_self);
 

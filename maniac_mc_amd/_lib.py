@@ -23,6 +23,7 @@ KERNEL_PAIR, KERNEL_RECIP, KERNEL_COMMIT, KERNEL_SFACTOR = 0, 1, 2, 3
 RECIP_TRIAL, RECIP_COMMIT = 0, 1
 # mgpu_recip_form's forms of the reciprocal update
 RECIP_FORMS = ("rows", "wide-vector", "wide-mfma", "wide-mfma-tiled", "per-k")
+PAIR_LAYOUT_LEN = 12     # include/maniac_gpu.h MGPU_PAIR_LAYOUT_LEN
 
 # every symbol include/maniac_gpu.h declares (tests check the library exports each of them)
 EXPORTS = [
@@ -31,7 +32,7 @@ EXPORTS = [
     "mgpu_engine_get_kvectors", "mgpu_replica_set_molecules", "mgpu_replica_get_molecules",
     "mgpu_replica_num_molecules", "mgpu_replica_copy", "mgpu_system_energy", "mgpu_init_structure_factor",
     "mgpu_get_structure_factor", "mgpu_set_structure_factor", "mgpu_structure_factor_add", "mgpu_pair_energy_candidates",
-    "mgpu_recip_energy_candidates", "mgpu_recip_form", "mgpu_self_energy", "mgpu_intra_energy_candidates",
+    "mgpu_recip_energy_candidates", "mgpu_recip_form", "mgpu_pair_layout", "mgpu_self_energy", "mgpu_intra_energy_candidates",
     "mgpu_trial_energy_candidates", "mgpu_commit_candidates", "mgpu_trial_submit", "mgpu_trial_wait",
     "mgpu_commit_submit", "mgpu_lane_site_buffer", "mgpu_set_host_team", "mgpu_replica_set_frames", "mgpu_replica_get_frames", "mgpu_replica_set_reservoir", "mgpu_replica_get_reservoir", "mgpu_move_trial_submit", "mgpu_move_trial_decide_submit", "mgpu_gcmc_trial_decide_submit", "mgpu_trial_decide_wait", "mgpu_gcmc_trial_submit", "mgpu_gcmc_trial_wait", "mgpu_replica_replace_molecule",
     "mgpu_replica_set_num_molecules", "mgpu_chain_window_capacity", "mgpu_chain_window", "mgpu_chain_set_margin",

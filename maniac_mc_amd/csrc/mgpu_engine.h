@@ -233,6 +233,7 @@ struct mgpu_engine {
     std::vector<std::vector<int>> site_perm;
     std::vector<char> frozen;        // [n_res]
     bool any_frozen = false;
+    int flat_groups = 0, flat_planes = 0;   // of the frozen layout: what pair_flat_kernel's eligibility was judged on
     int *d_atom_ty = nullptr;        // [Ncap] 0-based atom type of every slot (pair_flat_kernel fetches it per lane)
     // A frozen framework is normally the SAME in every replica (a farm copies replica 0): frozen_ref[t] = the coordinates
     // replica 0 was given (engine site order), frozen_same[r * n_res + t] = replica r holds exactly those, frozen_diff[t] =

@@ -398,7 +398,8 @@ int mgpu_engine_create(mgpu_engine **out, int device, int n_replicas, int n_res,
         for (int t = 0; t < n_res; ++t) framework = framework || (tp.n1[t] >= 64 && is_active[t] == 0);
         bool want_flat = framework;
         if (const char *ov = std::getenv("MGPU_PAIR_FLAT")) want_flat = std::atoi(ov) != 0;
-        build_layout(want_flat);
+        // eligibility is judged on the frozen layout whether or not the flat kernel is wanted (mgpu_pair_layout reports it)
+        build_layout(true);
         bool ok = e->box_type != 3 && (int)grp_tab.size() <= kMaxGrp;
         int planes = 0;                        // one lane of a wave builds one plane's record
         for (int t = 0; t < n_res; ++t) {
@@ -406,6 +407,8 @@ int mgpu_engine_create(mgpu_engine **out, int device, int n_replicas, int n_res,
             planes += tp.site_major[t] == 2 ? tp.cap[t] * tp.n_grp[t] : tp.n1[t];
         }
         if (planes > kFlatMaxPlanes) ok = false;
+        e->flat_groups = (int)grp_tab.size();
+        e->flat_planes = planes;
         e->pair_flat = want_flat && ok;
         if (!e->pair_flat && e->any_frozen) build_layout(false);
         for (size_t g = 0; g < (size_t)kMaxGrp; ++g) {

@@ -4,6 +4,18 @@
 
 extern "C" {
 
+// The frozen residue type whose framework batched trials sweep with pair_frozen_kernel right now, -1 for none: the flat
+// kernels in use in an orthorhombic box, exactly one frozen type, identical in every replica and holding a molecule
+// (trial_submit_impl dispatches by it, mgpu_pair_layout reports it).
+static int frozen_batch_type(const mgpu_engine *e) {
+    if (!e->pair_flat || !e->frozen_batch || e->bx.triclinic) return -1;
+    int nf = 0, t_frozen = -1;
+    for (int tt = 0; tt < e->tp.n_res; ++tt)
+        if (e->frozen[tt]) { ++nf; t_frozen = tt; }
+    if (nf != 1 || e->frozen_diff[t_frozen] != 0 || e->h_nmol[t_frozen] < 1) return -1;
+    return t_frozen;
+}
+
 // ---- batched candidates ----------------------------------------------------------------------
 
 int mgpu_pair_energy_candidates(mgpu_engine *e, int n, const int *replica, const int *t, const int *m,
@@ -113,6 +125,16 @@ int mgpu_recip_form(const mgpu_engine *e, int n1_max, int kind, int out[4]) {
         case MGPU_RECIP_FORM_PER_K: out[1] = 2 * p.tile; out[3] = (n1_max + p.tile - 1) / p.tile; break;
         default: out[1] = p.mfma_tile; out[3] = (((2 * n1_max + 3) & ~3) + p.mfma_tile - 1) / p.mfma_tile; break;
     }
+    return MGPU_OK;
+}
+
+int mgpu_pair_layout(const mgpu_engine *e, int out[MGPU_PAIR_LAYOUT_LEN]) {
+    if (!e || !out) return set_error(MGPU_ERR_INVALID_ARG, "mgpu_pair_layout: null argument");
+    out[0] = e->pair_flat ? 1 : 0;
+    out[1] = e->flat_groups;
+    out[2] = e->flat_planes;
+    out[3] = frozen_batch_type(e);
+    for (int t = 0; t < kMaxRes; ++t) out[4 + t] = t < e->tp.n_res ? e->tp.site_major[t] : -1;
     return MGPU_OK;
 }
 
@@ -273,13 +295,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
     // Framework boxes: one frozen residue type, identical in every replica, flat kernels in use, an active residue type of
     // <= 5 sites -> the type's items go to pair_frozen_kernel (candidates in the lanes; framework atoms as scalars, then the
     // replica's few other atoms per lane); their sums arrive as ONE extra record per entry behind the other results
-    int t_frozen = -1;
-    if (e->pair_flat && e->frozen_batch && !e->bx.triclinic) {
-        int nf = 0;
-        for (int tt = 0; tt < e->tp.n_res; ++tt)
-            if (e->frozen[tt]) { ++nf; t_frozen = tt; }
-        if (nf != 1 || e->frozen_diff[t_frozen] != 0 || e->h_nmol[t_frozen] < 1) t_frozen = -1;
-    }
+    const int t_frozen = frozen_batch_type(e);
     auto type_batched = [&](int ty, int n1) { return t_frozen >= 0 && ty != t_frozen && n1 <= kMaxFusedSitesWide; };
     const int n_atoms_f = t_frozen >= 0 ? e->h_nmol[t_frozen] * e->tp.n1[t_frozen] : 0;
     const int n_chunks_f = t_frozen >= 0 ? (n_atoms_f + frozen_chunk_atoms(e, n_atoms_f) - 1) / frozen_chunk_atoms(e, n_atoms_f) : 0;

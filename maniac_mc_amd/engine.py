@@ -347,6 +347,15 @@ class Engine:
         check(self.L.mgpu_recip_form(self.h, C.c_int(int(n1_max)), C.c_int(_lib.RECIP_COMMIT if commit else _lib.RECIP_TRIAL), _i(out)))
         return dict(form=_lib.RECIP_FORMS[int(out[0])], site_states=int(out[1]), rows_per_tile=int(out[2]), site_tiles=int(out[3]))
 
+    def pair_layout(self):
+        """mgpu_pair_layout: dict(flat= pair_flat_kernel in use, groups= / planes= of the frozen layout its eligibility was
+        judged on, frozen_batch= the residue type pair_frozen_kernel batches now (-1: none), site_major= per residue type:
+        0 plane-major, 1 site-major, 2 frozen)."""
+        out = np.zeros(_lib.PAIR_LAYOUT_LEN, np.int32)
+        check(self.L.mgpu_pair_layout(self.h, _i(out)))
+        return dict(flat=bool(out[0]), groups=int(out[1]), planes=int(out[2]), frozen_batch=int(out[3]),
+                    site_major=[int(v) for v in out[4:4 + self.topo.n_res]])
+
     def self_energy(self, t):
         e = C.c_double()
         check(self.L.mgpu_self_energy(self.h, C.c_int(t), C.byref(e)))
