@@ -349,6 +349,18 @@ int mgpu_move_trial_submit(mgpu_engine *e, int lane, int n_candidates, const int
  * not NULL (n = 0 where there is no reservoir). */
 int mgpu_replica_set_reservoir(mgpu_engine *e, int replica, int t, int n, int cap, const double *off);
 int mgpu_replica_get_reservoir(mgpu_engine *e, int replica, int t, int *n, double *off);
+/* Farm snapshot: the state the output files of a block need, for the replicas replicas[0..n-1], in ONE launch on one stream.
+ * It is ordered after the last commit of every lane (farm windows included: the lanes are drained and A(k) put back in its
+ * primary buffer, as the per-replica getters do), gathers on the device and copies the block into a pinned host buffer the
+ * engine owns.  Values are copied bit for bit, unwrapped.  mgpu_farm_snapshot_wait waits for it and returns the buffer
+ * (valid until the next submit or the engine's destruction) and its size.  Layout, for item k = i * n_res + t (replica
+ * replicas[i], residue type t): first n * n_res records of four int64 {molecule count, reservoir count, index of the
+ * item's frames, index of its reservoir} (indices count doubles from the start of the buffer; -1: none), then per item the
+ * frames com [n][3] followed by the offsets [n][n1][3] -- mgpu_replica_get_frames' layout; types without frames have none --
+ * and the reservoir offsets [nr][n1][3] (mgpu_replica_get_reservoir's).  The caller chunks large farms by the replica list.
+ * One snapshot at a time per engine. */
+int mgpu_farm_snapshot_submit(mgpu_engine *e, int n, const int *replicas, long long *bytes);
+int mgpu_farm_snapshot_wait(mgpu_engine *e, const void **data, long long *bytes);
 /* The same trials with the ACCEPTANCE TEST ON THE DEVICE.  The k sweep is the last kernel of a trial, one workgroup per
  * candidate; once it has summed the candidate's reciprocal energies its first thread holds everything
  * mc_acceptance_probability (src/monte_carlo_utils.f90:184-226) needs, so it applies the rule itself,

@@ -278,6 +278,12 @@ struct mgpu_engine {
            &d_partials = lanes[0].d_partials, &d_out = lanes[0].d_out;
     HostBuf &h_out = lanes[0].h_out;
     HostBuf h_stage;
+    // farm snapshots (mgpu_farm_snapshot_submit / _wait): the item table, the gathered block on the device and its pinned
+    // host copy, which the caller reads after the wait
+    DevBuf d_snap, d_snap_items;
+    HostBuf h_snap, h_snap_items;
+    size_t snap_bytes = 0;
+    bool snap_pending = false;
     // single-chain windows (mgpu_chain_window): pinned, host-coherent blocks the kernel reads its candidates from and
     // writes its results to (no copies, no stream synchronisation: the host polls the tag), and device scratch
     struct Chain {

@@ -248,6 +248,49 @@ double self_energy_host(const mgpu_engine *e, int t) {
     return s * kEps0InvEvA / kKbEvK;
 }
 
+// ---- farm snapshots (mgpu_farm_snapshot_submit): one (replica, residue type) per item ----
+struct SnapItem {
+    const double *rsv;            // the reservoir block [rsv_cap][n1][3] of (replica, t); null: none
+    long long com_src, off_src;   // x plane of the type's slots of the replica in d_com / d_off
+    long long hdr[4];             // the item's header record as written out (hdr[1], the reservoir count, by the kernel)
+    int n, n1, cap, site_major, rsv_idx, rsv_cap;
+};
+
+// Gathers the frames of one item -- com [n][3] and offsets [n][n1][3], the layout mgpu_replica_get_frames returns -- and its
+// reservoir [nr][n1][3] into one contiguous block.  A copy, bit for bit: no arithmetic on the values.  Consecutive lanes store
+// consecutive doubles of the output (whole molecule records, coalesced); the loads come from the x / y / z planes of the slots.
+// gridDim.y workgroups share a large item.
+__global__ __launch_bounds__(kBlock) void farm_snapshot_kernel(const SnapItem *__restrict__ items, const double *__restrict__ com,
+                                                               const double *__restrict__ off, long long com_plane, long long off_plane,
+                                                               const int *__restrict__ rsv_nc, double *__restrict__ out) {
+    const SnapItem &it = items[blockIdx.x];
+    const int nr = it.rsv ? min(max(rsv_nc[2 * it.rsv_idx], 0), it.rsv_cap) : 0;
+    if (blockIdx.y == 0 && threadIdx.x < 4) {
+        long long *hdr = reinterpret_cast<long long *>(out) + 4ll * blockIdx.x;
+        hdr[threadIdx.x] = threadIdx.x == 1 ? (long long)nr : it.hdr[threadIdx.x];
+    }
+    const unsigned stride = gridDim.y * blockDim.x, q0 = blockIdx.y * blockDim.x + threadIdx.x;
+    if (it.hdr[2] >= 0) {
+        double *dst = out + it.hdr[2];
+        const unsigned nc = 3u * (unsigned)it.n;
+        for (unsigned q = q0; q < nc; q += stride) {
+            const unsigned m = q / 3u, d = q - 3u * m;
+            dst[q] = com[it.com_src + d * com_plane + m];
+        }
+        dst += nc;
+        const unsigned rec = 3u * (unsigned)it.n1, no = rec * (unsigned)it.n;
+        for (unsigned q = q0; q < no; q += stride) {
+            const unsigned m = q / rec, k = q - rec * m, a = k / 3u, d = k - 3u * a;
+            const unsigned j = it.site_major ? m * (unsigned)it.n1 + a : a * (unsigned)it.cap + m;
+            dst[q] = off[it.off_src + d * off_plane + j];
+        }
+    }
+    if (it.hdr[3] >= 0) {
+        double *dst = out + it.hdr[3];
+        const unsigned nq = 3u * (unsigned)it.n1 * (unsigned)nr;
+        for (unsigned q = q0; q < nq; q += stride) dst[q] = it.rsv[q];
+    }
+}
 
 }  // namespace mgpu
 
@@ -625,6 +668,10 @@ int mgpu_engine_destroy(mgpu_engine *e) {
     for (void *p : {(void *)e->d_rsv, (void *)e->d_rsv_nc})
         if (p) (void)hipFree(p);
     e->h_stage.release();
+    e->h_snap.release();
+    e->h_snap_items.release();
+    e->d_snap.release();
+    e->d_snap_items.release();
     for (void *p : {(void *)e->chain.h_out, (void *)e->chain.h_tag})
         if (p) (void)hipHostFree(p);
     for (void *p : {(void *)e->chain.d_res, (void *)e->chain.d_part, (void *)e->chain.d_ticket, (void *)e->chain.d_topo, (void *)e->chain.d_alt,
@@ -973,6 +1020,86 @@ int mgpu_replica_get_reservoir(mgpu_engine *e, int replica, int t, int *n, doubl
     HIP_TRY(hipMemcpy(n, e->d_rsv_nc + 2 * idx, sizeof(int), hipMemcpyDeviceToHost));
     if (off && *n > 0)
         HIP_TRY(hipMemcpy(off, e->rsv_ptr[idx], (size_t)*n * e->tp.n1[t] * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return MGPU_OK;
+}
+
+int mgpu_farm_snapshot_submit(mgpu_engine *e, int n, const int *replicas, long long *bytes) {
+    if (n < 0 || (n > 0 && !replicas)) return set_error(MGPU_ERR_INVALID_ARG, "farm_snapshot: bad replica list");
+    if (e && e->snap_pending) return set_error(MGPU_ERR_STATE, "farm_snapshot: the last snapshot was not waited for");
+    for (int i = 0; i < n; ++i)
+        if (int rc = check_replica_t(e, replicas[i], 0)) return rc;
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc;
+    if ((rc = use_device(e))) return rc;
+    // after the last commit of every lane (farm windows: the commits behind the host tag), A(k) back in its primary buffer:
+    // the state the per-replica getters read
+    if ((rc = sync_all_lanes(e))) return rc;
+    const Topo &tp = e->tp;
+    const size_t n_items = (size_t)n * tp.n_res;
+    if ((rc = e->h_snap_items.reserve(std::max<size_t>(1, n_items) * sizeof(SnapItem)))) return rc;
+    SnapItem *items = (SnapItem *)e->h_snap_items.p;
+    size_t at = 4 * n_items, most = 0;          // (in doubles: the header records come first)
+    for (int i = 0; i < n; ++i)
+        for (int t = 0; t < tp.n_res; ++t) {
+            const size_t idx = (size_t)replicas[i] * tp.n_res + t;
+            SnapItem &it = items[(size_t)i * tp.n_res + t];
+            it.n = e->h_nmol[idx];
+            it.n1 = tp.n1[t];
+            it.cap = tp.cap[t];
+            it.site_major = tp.site_major[t] ? 1 : 0;
+            it.com_src = (long long)replicas[i] * 3 * tp.n_mol_slots + tp.mol_off[t];
+            it.off_src = (long long)replicas[i] * 3 * tp.n_cap_atoms + tp.seg_off[t];
+            it.hdr[0] = it.n;
+            it.hdr[1] = 0;
+            it.hdr[2] = it.hdr[3] = -1;
+            size_t len = 0;
+            if (e->d_com && e->frames_ok[idx] && !e->frozen[t]) {
+                it.hdr[2] = (long long)at;
+                len = 3 * (size_t)it.n * (1 + it.n1);
+                at += len;
+            }
+            it.rsv = nullptr;
+            it.rsv_idx = (int)idx;
+            it.rsv_cap = 0;
+            if (has_reservoir(e, idx)) {
+                it.rsv = e->rsv_ptr[idx];
+                it.rsv_cap = e->rsv_cap[idx];
+                it.hdr[3] = (long long)at;
+                at += 3 * (size_t)it.rsv_cap * it.n1;
+                len = std::max(len, 3 * (size_t)it.rsv_cap * it.n1);
+            }
+            most = std::max(most, len);
+        }
+    const size_t nbytes = at * sizeof(double);
+    if (most >= (size_t)1 << 31) return set_error(MGPU_ERR_CAPACITY, "farm_snapshot: one residue type's block exceeds 2^31 values");
+    if ((rc = e->d_snap.reserve(std::max<size_t>(nbytes, 8)))) return rc;
+    if ((rc = e->h_snap.reserve(std::max<size_t>(nbytes, 8)))) return rc;
+    if (n_items > 0) {
+        if ((rc = e->d_snap_items.reserve(n_items * sizeof(SnapItem)))) return rc;
+        hipStream_t s = e->lanes[0].stream;
+        HIP_TRY(hipMemcpyAsync(e->d_snap_items.p, items, n_items * sizeof(SnapItem), hipMemcpyHostToDevice, s));
+        const unsigned split = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (most + 8 * kBlock - 1) / (8 * kBlock)));
+        hipLaunchKernelGGL(farm_snapshot_kernel, dim3((unsigned)n_items, split), dim3(kBlock), 0, s,
+                           (const SnapItem *)e->d_snap_items.p, e->d_com, e->d_off, (long long)tp.n_mol_slots,
+                           (long long)tp.n_cap_atoms, e->d_rsv_nc, (double *)e->d_snap.p);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(e->h_snap.p, e->d_snap.p, nbytes, hipMemcpyDeviceToHost, s));
+    }
+    e->snap_bytes = nbytes;
+    e->snap_pending = true;
+    if (bytes) *bytes = (long long)nbytes;
+    return MGPU_OK;
+}
+
+int mgpu_farm_snapshot_wait(mgpu_engine *e, const void **data, long long *bytes) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    if (!e->snap_pending) return set_error(MGPU_ERR_STATE, "farm_snapshot_wait: no snapshot submitted");
+    int rc;
+    if ((rc = use_device(e))) return rc;
+    e->snap_pending = false;
+    HIP_TRY(hipStreamSynchronize(e->lanes[0].stream));
+    if (data) *data = e->h_snap.p;
+    if (bytes) *bytes = (long long)e->snap_bytes;
     return MGPU_OK;
 }
 

@@ -173,6 +173,50 @@ class Engine:
             check(self.L.mgpu_replica_get_reservoir(self.h, C.c_int(replica), C.c_int(t), C.byref(nr), _d(off)))
         return off
 
+    def farm_snapshot_raw(self, replicas):
+        """mgpu_farm_snapshot_submit + _wait for the replica list: (the engine's pinned block as a ctypes pointer, its length in
+        doubles).  The block stays valid until the next snapshot; its layout is include/maniac_gpu.h's."""
+        reps = _ints(replicas)
+        nbytes = C.c_longlong()
+        check(self.L.mgpu_farm_snapshot_submit(self.h, C.c_int(reps.shape[0]), _i(reps), C.byref(nbytes)))
+        ptr = C.c_void_p()
+        check(self.L.mgpu_farm_snapshot_wait(self.h, C.byref(ptr), C.byref(nbytes)))
+        return ptr, nbytes.value // 8
+
+    def farm_snapshot(self, replicas, chunk=None):
+        """The frames and reservoirs of the listed replicas in one launch per chunk of `chunk` replicas (default: chunks of
+        about 256 MB at the types' capacities).  Returns (counts (n, n_res) int32, com, off, rsv): com[i][t] (n, 3) and
+        off[i][t] (n, n1, 3) are what get_frames(replicas[i], t) returns (None for a type without frames), rsv[i][t] the
+        offsets get_reservoir returns (None without a reservoir)."""
+        reps = [int(r) for r in np.atleast_1d(np.asarray(replicas, dtype=np.int64))]
+        n_res = self.topo.n_res
+        n1s = [int(self.topo.atoms_in_res[t]) for t in range(n_res)]
+        if chunk is None:
+            per = sum(3 * (1 + n1s[t]) * int(self.mol_capacity[t]) * 8 for t in range(n_res))
+            chunk = max(1, (256 << 20) // max(1, per))
+        counts = np.zeros((len(reps), n_res), dtype=np.int32)
+        com, off, rsv = [], [], []
+        for c0 in range(0, max(1, len(reps)), int(chunk)):
+            part = reps[c0:c0 + int(chunk)]
+            if not part:
+                break
+            ptr, n_dbl = self.farm_snapshot_raw(part)
+            block = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_double)), shape=(n_dbl,))
+            hdr = block[: 4 * len(part) * n_res].view(np.int64).reshape(len(part), n_res, 4)
+            for i in range(len(part)):
+                ci, oi, ri = [], [], []
+                for t in range(n_res):
+                    n, nr, at, rat = (int(v) for v in hdr[i, t])
+                    counts[c0 + i, t] = n
+                    if at >= 0:
+                        ci.append(block[at: at + 3 * n].reshape(n, 3).copy())
+                        oi.append(block[at + 3 * n: at + 3 * n * (1 + n1s[t])].reshape(n, n1s[t], 3).copy())
+                    else:
+                        ci.append(None); oi.append(None)
+                    ri.append(block[rat: rat + 3 * nr * n1s[t]].reshape(nr, n1s[t], 3).copy() if rat >= 0 else None)
+                com.append(ci); off.append(oi); rsv.append(ri)
+        return counts, com, off, rsv
+
     def move_trial(self, replica, t, m, move, u, translation_step, rotation_step, lane=0):
         """Device-built trials (mgpu_move_trial_submit + wait): (old[n,5], new[n,5])."""
         m = _ints(m); n = m.shape[0]

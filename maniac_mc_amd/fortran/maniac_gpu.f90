@@ -241,6 +241,22 @@ module maniac_gpu
             real(c_double), intent(out) :: off(*)
             integer(c_int) :: rc
         end function
+        ! farm snapshot: frames and reservoirs of a list of replicas in one launch (layout: include/maniac_gpu.h)
+        function mgpu_farm_snapshot_submit(e, n, replicas, bytes) bind(C, name="mgpu_farm_snapshot_submit") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_long_long), intent(out) :: bytes
+            integer(c_int) :: rc
+        end function
+        function mgpu_farm_snapshot_wait(e, data, bytes) bind(C, name="mgpu_farm_snapshot_wait") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            type(c_ptr), intent(out) :: data
+            integer(c_long_long), intent(out) :: bytes
+            integer(c_int) :: rc
+        end function
         function mgpu_move_trial_submit(e, lane, n, replica, t, m, move, u, translation_step, rotation_step) &
                 bind(C, name="mgpu_move_trial_submit") result(rc)
             import :: c_ptr, c_int, c_double

@@ -25,7 +25,7 @@ module maniac_output
 
     private
     public :: residue_block, box_block, chain_block
-    public :: log_line, log_box_line, log_rule, log_start_mc, log_status, log_final_report
+    public :: log_line, log_text, log_box_line, log_rule, log_start_mc, log_status, log_final_report
     public :: write_trajectory, write_energy_and_count, write_topology, update_files, wrap_into_box
     public :: KB_KCALMOL_OUT, BOX_WIDTH, mout_format_fixed
 
@@ -121,6 +121,28 @@ contains
         write(ch%log_unit, *) trim(msg)                 ! list-directed, like LogMessage (output_utils.f90:30-36)
         flush(ch%log_unit)
     end subroutine log_line
+
+    ! text = messages separated by line feeds, one log_line each (an empty last message included)
+    subroutine log_text(ch, text)
+        type(chain_block), intent(in) :: ch
+        character(*), intent(in) :: text
+        integer :: a, b, n
+        n = len(text)
+        a = 1
+        do while (a <= n + 1)
+            b = index(text(min(a, n):n), achar(10))
+            if (a > n) then
+                call log_line(ch, '')
+                exit
+            end if
+            if (b == 0) then
+                call log_line(ch, text(a:n))
+                exit
+            end if
+            call log_line(ch, text(a:a + b - 2))
+            a = a + b
+        end do
+    end subroutine log_text
 
     subroutine log_rule(ch)
         type(chain_block), intent(in) :: ch

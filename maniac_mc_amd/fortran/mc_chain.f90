@@ -35,6 +35,7 @@ module mc_chain
     use, intrinsic :: iso_fortran_env, only: real64
     use maniac_gpu
     use maniac_output
+    use mc_farm, only: mfarm_set_output_template
 
     implicit none
 
@@ -43,7 +44,8 @@ module mc_chain
               mchain_set_moves, mchain_set_reservoir_box, mchain_set_reservoir_residue, mchain_run, &
               mchain_get_energy, mchain_get_counters, mchain_get_counts, mchain_get_molecule, mchain_get_steps, &
               mchain_set_mode, mchain_set_as_written, mchain_set_log_header, mchain_write_log_header, &
-              mchain_set_speculation, mchain_set_chain_windows, mchain_get_loop_seconds, mchain_get_times
+              mchain_set_speculation, mchain_set_chain_windows, mchain_get_loop_seconds, mchain_get_times, &
+              mchain_export_template
 
     real(real64), parameter :: PI = 3.14159265358979323846_real64, TWOPI = 2.0_real64 * PI
     real(real64), parameter :: zero = 0.0_real64, one = 1.0_real64, half = 0.5_real64, three = 3.0_real64
@@ -400,24 +402,15 @@ contains
     ! every header message through the reference's list-directed write (LogMessage, output_utils.f90:30-36)
     subroutine write_log_header(ch)
         type(chain_block), intent(in) :: ch
-        integer :: a, b, n
-        if (.not. allocated(log_header)) return
-        n = len(log_header)
-        a = 1
-        do while (a <= n + 1)
-            b = index(log_header(min(a, n):n), achar(10))
-            if (a > n) then
-                call log_line(ch, '')
-                exit
-            end if
-            if (b == 0) then
-                call log_line(ch, log_header(a:n))
-                exit
-            end if
-            call log_line(ch, log_header(a:a + b - 2))
-            a = a + b
-        end do
+        if (allocated(log_header)) call log_text(ch, log_header)
     end subroutine write_log_header
+
+    ! The chain's static description (box, residue templates and inactive residues, bonded lists, masses, reservoir box) as
+    ! the output template of the selected farm (mfarm_write_block): a farm of replicas of this input writes its files with
+    ! this chain's writers
+    subroutine mchain_export_template() bind(C, name="mchain_export_template")
+        call mfarm_set_output_template(S)
+    end subroutine mchain_export_template
 
     ! Test hook (no engine needed): write the header alone to `path`
     subroutine mchain_write_log_header(path) bind(C, name="mchain_write_log_header")

@@ -41,6 +41,8 @@ module mc_farm
     use, intrinsic :: iso_fortran_env, only: real64, int64
     use omp_lib
     use maniac_gpu
+    use maniac_output, only: chain_block, log_text, log_start_mc, log_status, log_final_report, write_trajectory, &
+                             write_energy_and_count, write_topology, IE_TOTAL
 
     implicit none
 
@@ -49,6 +51,7 @@ module mc_farm
     public :: mfarm_get_timers, mfarm_set_gcmc, mfarm_get_counts, mfarm_get_counters, mfarm_set_triclinic
     public :: mfarm_rng_sample, mfarm_set_drivers, mfarm_configure, mfarm_select, mfarm_exchange_block
     public :: mfarm_window_mode, mfarm_set_window_depth, mfarm_set_reservoir, mfarm_get_reservoir
+    public :: mfarm_get_chain_counters, mfarm_set_output_template, mfarm_set_log_header, mfarm_write_block
 
     real(real64), parameter :: PI = 3.14159265358979323846_real64
     real(real64), parameter :: TWOPI = 2.0_real64 * PI
@@ -97,6 +100,10 @@ module mc_farm
         integer(int64) :: trials = 0, accepted = 0, skipped = 0, counters(8) = 0, ticks(7) = 0
     end type lane_buffers
 
+    type :: text_block
+        character(len=:), allocatable :: s
+    end type text_block
+
     type :: farm_state
         type(c_ptr) :: engine = c_null_ptr
         integer :: n_replicas = 0, n_active = 0, max_n1 = 0, cap_total = 0
@@ -115,6 +122,8 @@ module mc_farm
         logical :: gcmc = .false.
         integer(int64) :: trials = 0, accepted = 0
         integer(int64) :: counters(8) = 0   ! trial/accepted: translations, rotations, creations, deletions
+        ! the same per chain, (8, R): updated where the lanes count (lanes own disjoint chains); summed over R = counters
+        integer(int64), allocatable :: chain_counters(:, :)
         integer(int64) :: skipped = 0                      ! no-op selections (empty type, full type)
         type(lane_buffers) :: lane(0:MGPU_LANES - 1)
         logical :: ready = .false.
@@ -146,6 +155,10 @@ module mc_farm
         integer, allocatable :: rsv_total(:, :)            ! (n_active, R)
         integer, allocatable :: rsv_n(:, :)                ! (n_active, R) host-built: reservoir counts
         real(real64), allocatable :: rsv(:, :, :, :)       ! (3 * max_n1, rsv_cap, n_active, R) host-built: offsets
+        ! Output files (mfarm_write_block): the input's static description (mc_chain's, mchain_export_template) -- the chain
+        ! block the single chain's writers are handed, replica by replica -- and every replica's log.maniac header
+        type(chain_block) :: out
+        type(text_block), allocatable :: log_header(:)     ! (R)
     end type farm_state
 
     ! Several farms may exist in one process (one per engine: different boxes, force fields or GPUs); the entry points act
@@ -300,7 +313,8 @@ contains
             rc = MGPU_OK
         end if
         if (.not. F%device_build) call alloc_mirror(3 + 3 * max_n1, tot, int(n_replicas))
-        allocate(F%energy(5, n_replicas))
+        allocate(F%energy(5, n_replicas), F%chain_counters(8, n_replicas))
+        F%chain_counters = 0
         F%n_threads = max(1, int(n_threads))
         ! n_lanes groups of replicas, one per engine lane (<= 0: the default of two)
         F%n_lanes = n_lanes
@@ -466,6 +480,9 @@ contains
             nullify(F%mol)
         end if
         if (allocated(F%energy)) deallocate(F%energy)
+        if (allocated(F%chain_counters)) deallocate(F%chain_counters)
+        if (allocated(F%log_header)) deallocate(F%log_header)
+        if (allocated(F%out%res)) deallocate(F%out%res)
         if (allocated(F%cxs)) deallocate(F%cxs)
         if (allocated(F%rsv_on)) deallocate(F%rsv_on, F%rsv_total)
         if (allocated(F%rsv_n)) deallocate(F%rsv_n)
@@ -814,6 +831,7 @@ contains
                 case default
                     k_rt = k_rt + 1
                 end select
+                call count_chain(r, L%move(j), .false.)
                 yes = L%accept(j) /= 0
             else
             select case (L%move(j))
@@ -834,10 +852,12 @@ contains
                 probability = min(1.0_real64, exp(-delta_e / F%temperature))
                 k_rt = k_rt + 1
             end select
+            call count_chain(r, L%move(j), .false.)
             yes = L%u(9, i) <= probability
             end if
             if (yes) then
                 L%accept(j) = 1
+                call count_chain(r, L%move(j), .true.)
                 slot = L%m(j) + 1
                 select case (L%move(j))
                 case (MV_CREATION)
@@ -895,6 +915,25 @@ contains
         L%ticks(4) = L%ticks(4) + (c2 - c1)
         L%ticks(5) = L%ticks(5) + (c3 - c2)
     end function resolve_and_commit
+
+    ! chain r's own counters (F%chain_counters): the trial of move mv, or its acceptance
+    subroutine count_chain(r, mv, accepted)
+        integer, intent(in) :: r, mv
+        logical, intent(in) :: accepted
+        integer :: k
+        select case (mv)
+        case (MV_TRANSLATION)
+            k = 1
+        case (MV_ROTATION)
+            k = 3
+        case (MV_CREATION)
+            k = 5
+        case default
+            k = 7
+        end select
+        if (accepted) k = k + 1
+        F%chain_counters(k, r) = F%chain_counters(k, r) + 1
+    end subroutine count_chain
 
     !---------------------------------------------------------------------------
     ! Window mode.  Move selection for chain r from its draws u and its counts: monte_carlo.f90:50-75, exactly
@@ -1149,7 +1188,9 @@ contains
             case default
                 k_rt = k_rt + 1
             end select
+            call count_chain(r, mv, .false.)
             if (v == 1) then
+                call count_chain(r, mv, .true.)
                 select case (mv)
                 case (MV_CREATION)
                     F%cnt(ia, r) = F%cnt(ia, r) + 1
@@ -1428,6 +1469,164 @@ contains
 
     ! trial / accepted counts: translations, rotations, creations, deletions (counter_type,
     ! src/simulation_state.f90:19-31)
+    !---------------------------------------------------------------------------
+    ! Output files of a farm: each replica writes what one MANIAC run writes, into its own directory, through the
+    ! single chain's writers (maniac_output).
+    !---------------------------------------------------------------------------
+    subroutine mfarm_set_output_template(ch)
+        type(chain_block), intent(in) :: ch
+        F%out = ch
+        F%out%engine = c_null_ptr
+        ! the farm's reservoirs hold offsets only (the reference places a reservoir molecule at a random centre, a draw the
+        ! farm does not make): no reservoir.lammpstrj
+        F%out%has_reservoir = .false.
+    end subroutine mfarm_set_output_template
+
+    ! replica's (0-based) log.maniac header: messages separated by line feeds (io_maniac.log_header_lines)
+    subroutine mfarm_set_log_header(replica, text, n) bind(C, name="mfarm_set_log_header")
+        integer(c_int), value :: replica, n
+        character(kind=c_char), intent(in) :: text(*)
+        integer :: i
+        if (.not. allocated(F%log_header)) allocate(F%log_header(F%n_replicas))
+        if (allocated(F%log_header(replica + 1)%s)) deallocate(F%log_header(replica + 1)%s)
+        allocate(character(len=n) :: F%log_header(replica + 1)%s)
+        do i = 1, n
+            F%log_header(replica + 1)%s(i:i) = text(i)
+        end do
+    end subroutine mfarm_set_log_header
+
+    ! The files of block `block` for the replicas reps(1:n) (0-based), in mchain_run's order: block 0 creates log.maniac (header,
+    ! "Started Monte Carlo Loop"), energy.dat, number_<res>.dat and moves.dat; a later block adds its status to log.maniac and
+    ! a record to each file.  final /= 0 (after the last block): the final report, and nothing else but what(i).
+    ! what(i): 1 trajectory.lammpstrj, 2 topology.data, 3 both, 0 neither.  The molecules come from the host mirror (host-built
+    ! farms) or, where snap is given, from mgpu_farm_snapshot's block (snap_len doubles) of the replicas with what(i) /= 0,
+    ! in order.  outroot ends with '/'; replica r writes into outroot // 'replica_NNNN/', which must exist.
+    ! Returns 8 if the snapshot disagrees with the farm's counts or is too short, 9 if a file cannot be opened.
+    function mfarm_write_block(block, nb_block, nb_step, final, n, reps, what, snap, snap_len, outroot) &
+            bind(C, name="mfarm_write_block") result(rc)
+        integer(c_int), value :: block, nb_block, nb_step, final, n
+        integer(c_int), intent(in) :: reps(*), what(*)
+        type(c_ptr), value :: snap
+        integer(c_long_long), value :: snap_len
+        character(kind=c_char), intent(in) :: outroot(*)
+        integer(c_int) :: rc
+        character(len=512) :: root
+        type(chain_block), pointer :: W
+        integer(int64), pointer :: hdr(:, :)
+        real(real64), pointer :: buf(:)
+        real(real64), allocatable :: grown(:, :), grown_off(:, :, :)
+        integer :: i, k, r, ia, t, m, nt, n1, cnt, ios, item
+        integer(int64) :: at
+        rc = MGPU_OK
+        if (.not. F%ready .or. .not. allocated(F%out%res)) then
+            rc = 5
+            return
+        end if
+        root = ''
+        do i = 1, len(root)
+            if (outroot(i) == c_null_char) exit
+            root(i:i) = outroot(i)
+        end do
+        W => F%out
+        nt = W%n_res
+        if (c_associated(snap)) then
+            call c_f_pointer(snap, hdr, [4_int64, snap_len / 4])
+            call c_f_pointer(snap, buf, [snap_len])
+        end if
+        W%nb_block = nb_block
+        W%nb_step = nb_step
+        W%translation_step = F%translation_step
+        W%rotation_step = F%rotation_step
+        k = 0
+        do i = 1, n
+            r = reps(i) + 1
+            write(W%outdir, '(A,"replica_",I4.4,"/")') trim(root), r - 1
+            W%current_block = block
+            W%energy(1:5) = F%energy(:, r)
+            W%energy(IE_TOTAL) = F%energy(1, r) + F%energy(2, r) + F%energy(3, r) + F%energy(4, r) + F%energy(5, r)
+            W%counter = int(F%chain_counters(:, r))
+            W%box%num_atoms = 0
+            do t = 1, nt
+                ia = findloc(F%res_type, t - 1, dim=1)
+                if (ia > 0) then
+                    cnt = F%cnt(ia, r)
+                    W%res(t)%count = cnt
+                    if (what(i) /= 0) then
+                        n1 = W%res(t)%n1
+                        if (size(W%res(t)%com, 2) < cnt) then
+                            allocate(grown(3, cnt), grown_off(3, n1, cnt))
+                            call move_alloc(grown, W%res(t)%com)
+                            call move_alloc(grown_off, W%res(t)%off)
+                        end if
+                        if (c_associated(snap)) then
+                            item = k * nt + t
+                            if (int(item, int64) > snap_len / 4) then
+                                rc = 8
+                                return
+                            end if
+                            at = hdr(3, item)
+                            if (hdr(1, item) /= cnt .or. at < 0 .or. at + 3_int64 * cnt * (1 + n1) > snap_len) then
+                                rc = 8
+                                return
+                            end if
+                            do m = 1, cnt
+                                W%res(t)%com(:, m) = buf(at + 3 * (m - 1) + 1:at + 3 * m)
+                            end do
+                            at = at + 3_int64 * cnt
+                            do m = 1, cnt
+                                W%res(t)%off(:, :, m) = reshape(buf(at + 3_int64 * n1 * (m - 1) + 1:at + 3_int64 * n1 * m), [3, n1])
+                            end do
+                        else if (.not. F%device_build) then
+                            do m = 1, cnt
+                                W%res(t)%com(:, m) = F%mol(1:3, F%first(ia) + m, r)
+                                W%res(t)%off(:, :, m) = reshape(F%mol(4:3 + 3 * n1, F%first(ia) + m, r), [3, n1])
+                            end do
+                        else
+                            rc = 8                           ! device-built farm: the molecules are on the device only
+                            return
+                        end if
+                    end if
+                end if
+                W%box%num_atoms = W%box%num_atoms + W%res(t)%count * W%res(t)%n1
+            end do
+            if (what(i) /= 0) k = k + 1
+            if (block == 0 .and. final == 0) then
+                open(newunit=W%log_unit, file=trim(W%outdir) // 'log.maniac', status='replace', action='write', iostat=ios)
+            else
+                open(newunit=W%log_unit, file=trim(W%outdir) // 'log.maniac', status='old', action='write', &
+                     position='append', iostat=ios)
+            end if
+            if (ios /= 0) then
+                rc = 9
+                return
+            end if
+            if (final /= 0) then
+                if (iand(what(i), 2) /= 0) call write_topology(W)
+                W%current_block = nb_block + 1           ! as mchain_run: one past the last block
+                call log_final_report(W)
+            else
+                if (block == 0) then
+                    if (allocated(F%log_header)) then
+                        if (allocated(F%log_header(r)%s)) call log_text(W, F%log_header(r)%s)
+                    end if
+                    call log_start_mc(W)
+                else
+                    call log_status(W)
+                end if
+                if (iand(what(i), 1) /= 0) call write_trajectory(W, W%res, W%box, 'trajectory.lammpstrj', block > 0)
+                call write_energy_and_count(W)
+                if (iand(what(i), 2) /= 0) call write_topology(W)
+            end if
+            close(W%log_unit)
+        end do
+    end function mfarm_write_block
+
+    ! every chain's own counters, c(8, R) in the order of mfarm_get_counters
+    subroutine mfarm_get_chain_counters(c) bind(C, name="mfarm_get_chain_counters")
+        real(c_double), intent(out) :: c(8, F%n_replicas)
+        c = real(F%chain_counters, real64)
+    end subroutine mfarm_get_chain_counters
+
     subroutine mfarm_get_counters(c) bind(C, name="mfarm_get_counters")
         real(c_double), intent(out) :: c(8)
         c = real(F%counters, real64)

@@ -18,7 +18,7 @@ from .system import System
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmaniac_host.so")
-FSRC = [os.path.join(_HERE, "fortran", f) for f in ("maniac_gpu.f90", "mc_farm.f90", "maniac_output.f90", "mc_chain.f90")]
+FSRC = [os.path.join(_HERE, "fortran", f) for f in ("maniac_gpu.f90", "maniac_output.f90", "mc_farm.f90", "mc_chain.f90")]
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -59,6 +59,7 @@ def lib():
         L.mfarm_set_gcmc.restype = C.c_int
         L.mfarm_set_reservoir.restype = C.c_int
         L.mfarm_get_reservoir.restype = C.c_int
+        L.mfarm_write_block.restype = C.c_int
         _host = L
     return _host
 
@@ -218,6 +219,13 @@ class FortranFarm:
         names = ("trial_translations", "translations", "trial_rotations", "rotations", "trial_creations",
                  "creations", "trial_deletions", "deletions")
         return dict(zip(names, c.astype(np.int64).tolist()))
+
+    def chain_counters(self):
+        """Every chain's own counters, shape (R, 8), in the order of counters(); summed over the chains they are counters()."""
+        c = np.zeros((self.R, 8))
+        self._select()
+        self.H.mfarm_get_chain_counters(c.ctypes.data_as(_dp))
+        return c.astype(np.int64)
 
     def counts(self):
         """Current molecule counts, shape (R, n_active)."""

@@ -1,0 +1,212 @@
+"""A MANIAC input run as a farm of R independent replicas on one GPU, each writing the files one MANIAC run writes.
+
+    run_replicas("input.maniac", "topology.data", "parameters.inc", "outputs/", replicas=64)
+
+loads the reference's three input files (io_maniac), builds one FortranFarm of R chains of that system and runs the input's
+nb_block blocks of nb_step steps per replica.  After every block the farm's Fortran writer (mfarm_write_block, with the
+single chain's writers of maniac_output.f90) adds the block's records to every replica's energy.dat, number_<res>.dat,
+moves.dat and log.maniac under <outdir>/replica_NNNN/; the replicas of the `frames` set also get trajectory.lammpstrj and
+topology.data every block, and every replica gets its final topology.data (a restartable MANIAC input).  Where the engine
+holds the coordinates (device-built and window farms) they come back in one snapshot launch per chunk of replicas
+(Engine.farm_snapshot_raw).  <outdir>/replicas.dat holds, per block and fugacity group, the mean and standard error over the
+replicas of the total energy and of every active type's molecule count.
+
+Step-size recalibration, where the input asks for it, is farm-wide: the pooled counters after every block.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import dataclasses
+import os
+
+import numpy as np
+
+from . import _lib, fortran_host, io_maniac
+from .fortran_host import FortranFarm
+from .run import header_text, set_chain_state
+from .system import KB_KCALMOL, NB_MAX_MOLECULE
+
+MODES = ("auto", "windows", "device", "device_accept", "host")
+SNAPSHOT_BYTES = 256 << 20          # a snapshot chunk's size at the types' capacities
+
+
+def parse_frames(text, n_replicas):
+    """--frames: "0,3,7" | "all" | "none" -> the sorted replica indices; ValueError on anything else or out of range."""
+    text = str(text).strip()
+    if text == "all":
+        return tuple(range(n_replicas))
+    if text == "none":
+        return ()
+    try:
+        out = sorted({int(v) for v in text.split(",")})
+    except ValueError:
+        raise ValueError(f"--frames: expected a list of replica indices, 'all' or 'none', got {text!r}") from None
+    if out and (out[0] < 0 or out[-1] >= n_replicas):
+        raise ValueError(f"--frames: replica indices must lie in [0, {n_replicas - 1}]")
+    return tuple(out)
+
+
+def parse_fugacities(text):
+    """--fugacities: "f1,f2,..." (the input's units, atm) -> list of positive floats."""
+    try:
+        out = [float(v) for v in str(text).split(",")]
+    except ValueError:
+        raise ValueError(f"--fugacities: expected comma-separated numbers, got {text!r}") from None
+    if not out or any(not (f > 0.0) for f in out):
+        raise ValueError("--fugacities: every fugacity must be positive")
+    return out
+
+
+def _with_fugacity(inp, f_atm):
+    """The input with every active residue's fugacity set to f_atm (atm)."""
+    res = [dataclasses.replace(r, fugacity_atm=float(f_atm)) if r.is_active == 1 else r for r in inp.residues]
+    return dataclasses.replace(inp, residues=res)
+
+
+def _stats(x):
+    x = np.asarray(x, dtype=np.float64)
+    sem = float(np.std(x, ddof=1) / np.sqrt(x.size)) if x.size > 1 else 0.0
+    return float(np.mean(x)), sem
+
+
+def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=None, fugacities=None, frames=(0,),
+                 mode="auto", device=0, nb_block=None, nb_step=None, mol_capacity=None, n_lanes=2, n_threads=8,
+                 chunk=None):
+    """Run `replicas` independent chains of the input; returns a dict with the final energies (R, 5) in K (non-Coulomb,
+    Coulomb, reciprocal, self, intramolecular), counts (R, n_active), chain counters (R, 8), the farm's counters, the
+    mode that ran and the block timings.
+
+    ``seed``: None -> the input's seed, else 1; replica r's stream is seeded from it and r.
+    ``fugacities``: [f1, ..., fk] in the input's units (atm): replica r runs at f[r % k] for every active type (GCMC inputs
+    only).  ``frames``: the replicas that write trajectory.lammpstrj and topology.data every block.
+    ``mode``: "auto" -> windows where the engine's one-launch path applies, else device-built batched steps, else (triclinic
+    boxes) host-built ones; "windows" | "device" | "device_accept" | "host" force one.
+    ``chunk``: replicas per snapshot launch (default: about SNAPSHOT_BYTES at the types' capacities).
+    """
+    import time
+    if mode not in MODES:
+        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+    R = int(replicas)
+    if R < 1:
+        raise ValueError("replicas must be at least 1")
+    system, inp, dat = io_maniac.load_system(maniac, data, inc, with_data=True)
+    rdat = io_maniac.read_lammps_data(reservoir_path, inp) if reservoir_path else None
+    topo = system.topo
+    n_res = topo.n_res
+    active = [t for t in range(n_res) if topo.is_active[t] == 1]
+    gcmc = inp.insertion_deletion_proba > 0.0
+    if inp.swap_proba > 0.0:
+        raise ValueError("replica farms have no swap moves: the input asks for swap_proba > 0")
+    if fugacities is not None and not gcmc:
+        raise ValueError("--fugacities needs a grand-canonical input (insertion_deletion_proba > 0)")
+    frames = tuple(sorted({int(r) for r in frames}))
+    if frames and (frames[0] < 0 or frames[-1] >= R):
+        raise ValueError(f"frames must lie in [0, {R - 1}]")
+    triclinic = system.is_triclinic()
+    if triclinic and mode in ("windows", "device", "device_accept"):
+        raise ValueError(f"mode {mode!r}: the engine builds no moves in triclinic boxes (use 'host' or 'auto')")
+    if mol_capacity is None:
+        mol_capacity = [NB_MAX_MOLECULE if topo.is_active[t] == 1 else max(1, int(system.n_mol[t])) for t in range(n_res)]
+    nb_block = inp.nb_block if nb_block is None else int(nb_block)
+    nb_step = inp.nb_step if nb_step is None else int(nb_step)
+    if seed is None:
+        seed = inp.seed if inp.has_seed and inp.seed > 0 else 1
+
+    group = np.zeros(R, dtype=np.int64)
+    if fugacities is not None:
+        fugacities = [float(f) for f in fugacities]
+        group = np.arange(R) % len(fugacities)
+        fug_grid = np.array([[_with_fugacity(inp, fugacities[g]).fugacity_per_A3()[t] for t in active] for g in group])
+    else:
+        fug_grid = np.tile(np.array([inp.fugacity_per_A3()[t] for t in active])[None, :], (R, 1)) if gcmc else None
+    gcmc_arg = dict(p_translation=inp.translation_proba, p_rotation=inp.rotation_proba, fugacity=fug_grid) if gcmc else None
+    reservoir = io_maniac.reservoir_offsets(reservoir_path, inp) if reservoir_path else None
+    device_build = not triclinic and mode != "host"
+    farm = FortranFarm(system, R, device=device, seed=int(seed), translation_step=inp.translation_step,
+                       rotation_step=inp.rotation_step_angle, p_translation=inp.translation_proba, n_threads=n_threads,
+                       mol_capacity=mol_capacity, gcmc=gcmc_arg, n_lanes=n_lanes, device_build=device_build,
+                       device_accept=mode == "device_accept", window=mode in ("auto", "windows"), reservoir=reservoir)
+    try:
+        ran = "host" if not farm.device_build else ("windows" if farm.window else
+                                                     ("device_accept" if farm.device_accept else "device"))
+        if mode == "windows" and ran != "windows":
+            raise ValueError("mode 'windows': the engine's one-launch farm window does not apply to this system")
+        H = fortran_host.lib()
+        farm._select()
+        hold = set_chain_state(H, farm.eng.h, system, inp, dat, mol_capacity, rdat)
+        H.mchain_export_template()
+        del hold
+        headers = {}
+        for r in range(R):
+            g = int(group[r])
+            if g not in headers:
+                inp_g = _with_fugacity(inp, fugacities[g]) if fugacities is not None else inp
+                headers[g] = header_text(inp_g, dat, maniac, data, inc, farm.eng, reservoir_path, rdat)
+            H.mfarm_set_log_header(C.c_int(r), headers[g], C.c_int(len(headers[g])))
+        root = os.path.join(outdir, "")
+        for r in range(R):
+            os.makedirs(os.path.join(root, f"replica_{r:04d}"), exist_ok=True)
+        if chunk is None:
+            per = sum(3 * (1 + int(topo.atoms_in_res[t])) * int(mol_capacity[t]) * 8 for t in active)
+            chunk = max(1, SNAPSHOT_BYTES // max(1, per))
+        in_frames = np.zeros(R, dtype=bool)
+        in_frames[list(frames)] = True
+        n_groups = len(fugacities) if fugacities is not None else 1
+        names = [inp.residues[t].name for t in active]
+        stats_path = os.path.join(root, "replicas.dat")
+        times = dict(run=0.0, write=0.0, snapshot=0.0)
+
+        def write(block, final):
+            t0 = time.perf_counter()
+            for c0 in range(0, R, int(chunk)):
+                reps = np.arange(c0, min(R, c0 + int(chunk)), dtype=np.int32)
+                what = np.full(reps.size, 2, dtype=np.int32) if final else np.where(in_frames[reps], 3, 0).astype(np.int32)
+                snap, n_dbl = None, 0
+                if farm.device_build and what.any():
+                    ts = time.perf_counter()
+                    snap, n_dbl = farm.eng.farm_snapshot_raw(reps[what != 0])
+                    times["snapshot"] += time.perf_counter() - ts
+                    farm._select()
+                rc = H.mfarm_write_block(C.c_int(block), C.c_int(nb_block), C.c_int(nb_step), C.c_int(1 if final else 0),
+                                         C.c_int(reps.size), reps.ctypes.data_as(C.POINTER(C.c_int)),
+                                         what.ctypes.data_as(C.POINTER(C.c_int)), snap, C.c_longlong(n_dbl),
+                                         root.encode())
+                if rc:
+                    raise RuntimeError(f"mfarm_write_block: code {rc} (block {block})")
+            if final:
+                times["write"] += time.perf_counter() - t0
+                return
+            e = np.array([farm.energy(r) for r in range(R)])
+            total = (e[:, 0] + e[:, 1] + e[:, 2] + e[:, 3] + e[:, 4]) * KB_KCALMOL
+            cnt = farm.counts()
+            with open(stats_path, "w" if block == 0 else "a") as f:
+                if block == 0:
+                    f.write("#     block  group   fugacity_atm  replicas      total_mean       total_sem"
+                            + "".join(f"  {('N_' + n):>14s}_mean  {('N_' + n):>14s}_sem" for n in names) + "\n")
+                for g in range(n_groups):
+                    sel = group == g
+                    f_atm = fugacities[g] if fugacities is not None else \
+                        (inp.residues[active[0]].fugacity_atm if active else 0.0)
+                    m, s = _stats(total[sel])
+                    line = f"{block:10d} {g:6d} {f_atm:14.6e} {int(sel.sum()):9d} {m:15.6f} {s:15.6f}"
+                    for k in range(len(active)):
+                        m, s = _stats(cnt[sel, k])
+                        line += f" {m:19.6f} {s:18.6f}"
+                    f.write(line + "\n")
+            times["write"] += time.perf_counter() - t0
+
+        write(0, False)
+        for block in range(1, nb_block + 1):
+            t0 = time.perf_counter()
+            farm.run(nb_step)
+            if inp.recalibrate_moves:
+                farm.recalibrate()
+            times["run"] += time.perf_counter() - t0
+            write(block, False)
+        write(nb_block, True)
+        _lib.check(0)
+        energies = np.array([farm.energy(r) for r in range(R)])
+        return dict(energy=energies, counts=farm.counts(), chain_counters=farm.chain_counters(), counters=farm.counters(),
+                    accepted=farm.accepted, mode=ran, seconds=times, group=group)
+    finally:
+        farm.close()

@@ -66,6 +66,54 @@ def header_text(inp, dat, maniac_path, data_path, inc_path, eng_or_ewald, reserv
     return "\n".join(lines).encode("utf-8")
 
 
+def set_chain_state(H, engine_h, system, inp, dat, mol_capacity, rdat=None):
+    """mc_chain's state from the loaded input: box, residues (templates, molecules, bonded lists), tables, move parameters
+    and, with a reservoir data file (rdat), the reservoir.  Returns the arrays the Fortran side was handed (keep them alive
+    while it runs)."""
+    topo = system.topo
+    n_res = topo.n_res
+    H.mchain_reset(engine_h, C.c_int(n_res), C.c_int(topo.n_atom_types), C.c_double(system.temperature))
+    keep, args = _box_args(dat)
+    H.mchain_set_box(*args)
+    fug = inp.fugacity_per_A3()
+    hold = []
+    for t in range(n_res):
+        n1 = int(topo.atoms_in_res[t])
+        com, off = _mol_arrays(system.com[t], system.offsets[t], n1)
+        types = np.ascontiguousarray(topo.atom_types[t, :n1], dtype=np.int32)
+        q = np.ascontiguousarray(topo.charges[t, :n1], dtype=np.float64)
+        hold += [com, off, types, q]
+        H.mchain_set_residue(C.c_int(t + 1), inp.residues[t].name.encode(), C.c_int(n1), C.c_int(int(topo.is_active[t])),
+                             C.c_int(int(mol_capacity[t])), C.c_int(com.shape[0]), types.ctypes.data_as(_ip),
+                             q.ctypes.data_as(_dp), com.ctypes.data_as(_dp), off.ctypes.data_as(_dp),
+                             C.c_double(float(fug[t])))
+        for kind, key in enumerate(("bonds", "angles", "dihedrals", "impropers"), start=1):
+            rows = dat["bonded_per_residue"][key][t]
+            tab = np.zeros((max(1, len(rows)), 5), dtype=np.int32)
+            for k, row in enumerate(rows):
+                tab[k, : len(row)] = row
+            hold.append(tab)
+            H.mchain_set_bonded(C.c_int(t + 1), C.c_int(kind), C.c_int(len(rows)), tab.ctypes.data_as(_ip))
+    masses = np.ascontiguousarray(dat["masses"], dtype=np.float64)
+    ntypes = np.array([dat["type_counts"][k] for k in ("bonds", "angles", "dihedrals", "impropers")], dtype=np.int32)
+    H.mchain_set_tables(masses.ctypes.data_as(_dp), ntypes.ctypes.data_as(_ip))
+    H.mchain_set_moves(C.c_double(inp.translation_step), C.c_double(inp.rotation_step_angle),
+                       C.c_double(inp.translation_proba), C.c_double(inp.rotation_proba),
+                       C.c_int(1 if inp.recalibrate_moves else 0))
+    if rdat is not None:
+        rkeep, rargs = _box_args(rdat)
+        any_bonded = np.array([1 if rdat["bonded_counts"][k] > 0 else 0
+                               for k in ("bonds", "angles", "dihedrals", "impropers")], dtype=np.int32)
+        H.mchain_set_reservoir_box(*rargs, any_bonded.ctypes.data_as(_ip))
+        for t in range(n_res):
+            n1 = int(topo.atoms_in_res[t])
+            com, off = _mol_arrays(rdat["com"][t], rdat["off"][t], n1)
+            hold += [com, off]
+            H.mchain_set_reservoir_residue(C.c_int(t + 1), C.c_int(n1), C.c_int(NB_MAX_MOLECULE), C.c_int(com.shape[0]),
+                                           com.ctypes.data_as(_dp), off.ctypes.data_as(_dp))
+    return hold + [keep] + ([rkeep] if rdat is not None else [])
+
+
 def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoir_path=None, device=0,
                    mol_capacity=None, nb_block=None, nb_step=None, seams=False, as_written=False, speculate=4,
                    chain_windows=True, chain_margin=None):
@@ -103,31 +151,7 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     H = fortran_host.lib()
     H.mchain_run.restype = C.c_int
     try:
-        H.mchain_reset(eng.h, C.c_int(n_res), C.c_int(topo.n_atom_types), C.c_double(system.temperature))
-        keep, args = _box_args(dat)
-        H.mchain_set_box(*args)
-        fug = inp.fugacity_per_A3()
-        hold = []
-        for t in range(n_res):
-            n1 = int(topo.atoms_in_res[t])
-            com, off = _mol_arrays(system.com[t], system.offsets[t], n1)
-            types = np.ascontiguousarray(topo.atom_types[t, :n1], dtype=np.int32)
-            q = np.ascontiguousarray(topo.charges[t, :n1], dtype=np.float64)
-            hold += [com, off, types, q]
-            H.mchain_set_residue(C.c_int(t + 1), inp.residues[t].name.encode(), C.c_int(n1), C.c_int(int(topo.is_active[t])),
-                                 C.c_int(int(mol_capacity[t])), C.c_int(com.shape[0]), types.ctypes.data_as(_ip),
-                                 q.ctypes.data_as(_dp), com.ctypes.data_as(_dp), off.ctypes.data_as(_dp),
-                                 C.c_double(float(fug[t])))
-            for kind, key in enumerate(("bonds", "angles", "dihedrals", "impropers"), start=1):
-                rows = dat["bonded_per_residue"][key][t]
-                tab = np.zeros((max(1, len(rows)), 5), dtype=np.int32)
-                for k, row in enumerate(rows):
-                    tab[k, : len(row)] = row
-                hold.append(tab)
-                H.mchain_set_bonded(C.c_int(t + 1), C.c_int(kind), C.c_int(len(rows)), tab.ctypes.data_as(_ip))
-        masses = np.ascontiguousarray(dat["masses"], dtype=np.float64)
-        ntypes = np.array([dat["type_counts"][k] for k in ("bonds", "angles", "dihedrals", "impropers")], dtype=np.int32)
-        H.mchain_set_tables(masses.ctypes.data_as(_dp), ntypes.ctypes.data_as(_ip))
+        hold = set_chain_state(H, eng.h, system, inp, dat, mol_capacity, rdat)
         H.mchain_set_mode(C.c_int(1 if seams else 0))
         H.mchain_set_as_written(C.c_int(1 if as_written else 0))
         H.mchain_set_speculation(C.c_int(1 if seams else max(1, int(speculate))))
@@ -135,20 +159,6 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
         H.mchain_get_loop_seconds.restype = C.c_double
         header = header_text(inp, dat, maniac_path, data_path, inc_path, eng, reservoir_path, rdat)
         H.mchain_set_log_header(header, C.c_int(len(header)))
-        H.mchain_set_moves(C.c_double(inp.translation_step), C.c_double(inp.rotation_step_angle),
-                           C.c_double(inp.translation_proba), C.c_double(inp.rotation_proba),
-                           C.c_int(1 if inp.recalibrate_moves else 0))
-        if reservoir_path:
-            rkeep, rargs = _box_args(rdat)
-            any_bonded = np.array([1 if rdat["bonded_counts"][k] > 0 else 0
-                                   for k in ("bonds", "angles", "dihedrals", "impropers")], dtype=np.int32)
-            H.mchain_set_reservoir_box(*rargs, any_bonded.ctypes.data_as(_ip))
-            for t in range(n_res):
-                n1 = int(topo.atoms_in_res[t])
-                com, off = _mol_arrays(rdat["com"][t], rdat["off"][t], n1)
-                hold += [com, off]
-                H.mchain_set_reservoir_residue(C.c_int(t + 1), C.c_int(n1), C.c_int(NB_MAX_MOLECULE), C.c_int(com.shape[0]),
-                                               com.ctypes.data_as(_dp), off.ctypes.data_as(_dp))
         if seed is None:
             seed = inp.seed if inp.has_seed else 0
         outdir = os.path.join(outdir, "")
@@ -181,7 +191,7 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
 def main(argv=None):
     """`python -m maniac_mc_amd.run -i input.maniac -d topology.data -p parameters.inc [-r reservoir.data] [-o outputs/]`
     -- the reference's command line (cli_utils.f90:36-83: -i, -d, -p mandatory, -r optional, -o defaults to
-    outputs/), plus --seed and --device."""
+    outputs/), plus --seed and --device; --replicas R runs R independent replicas on one GPU (maniac_mc_amd.replicas)."""
     import argparse
     import sys
     ap = argparse.ArgumentParser(prog="python -m maniac_mc_amd.run", description=main.__doc__)
@@ -198,11 +208,43 @@ def main(argv=None):
                     help="evaluate windows through the batched submit / wait calls instead of the one-launch path")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
+    ap.add_argument("--replicas", type=int, default=None,
+                    help="run R independent replicas of the input on one GPU, each writing its files to <out>/replica_NNNN/")
+    ap.add_argument("--fugacities", default=None,
+                    help="with --replicas, GCMC inputs: f1,f2,... (atm); replica r runs at f[r %% k] (an isotherm)")
+    ap.add_argument("--frames", default="0",
+                    help="with --replicas: replicas writing trajectory / topology every block: 0,3,7 | all | none (default 0)")
+    ap.add_argument("--farm-mode", default="auto", choices=("auto", "windows", "device", "device_accept", "host"),
+                    help="with --replicas: how the farm builds and decides its steps (default auto)")
     a = ap.parse_args(argv)
+    if a.replicas is None:
+        if a.fugacities is not None or a.frames != "0" or a.farm_mode != "auto":
+            ap.error("--fugacities, --frames and --farm-mode need --replicas")
+    else:
+        from . import replicas as farm_run
+        if a.as_written:
+            ap.error("--as-written cannot be combined with --replicas: the replica farm implements the intended physics only")
+        if a.replicas < 1:
+            ap.error("--replicas must be at least 1")
+        try:
+            frames = farm_run.parse_frames(a.frames, a.replicas)
+            fugacities = farm_run.parse_fugacities(a.fugacities) if a.fugacities is not None else None
+        except ValueError as err:
+            ap.error(str(err))
     for path, what in ((a.maniac, "Input"), (a.data, "Data"), (a.inc, "Parameter"), (a.reservoir, "Reservoir")):
         if path is not None and not os.path.isfile(path):
             print(f"{what} file not found: {path}", file=sys.stderr)
             return 1
+    if a.replicas is not None:
+        try:
+            res = farm_run.run_replicas(a.maniac, a.data, a.inc, a.out, a.replicas, seed=a.seed, reservoir_path=a.reservoir,
+                                        fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device)
+        except ValueError as err:
+            print(f"error: {err}", file=sys.stderr)
+            return 2
+        print(f"{a.replicas} replicas ({res['mode']}): {res['accepted']} accepted moves;  output in "
+              f"{os.path.join(a.out, '')}replica_NNNN/ and replicas.dat")
+        return 0
     res = run_simulation(a.maniac, a.data, a.inc, a.out, seed=a.seed, reservoir_path=a.reservoir, device=a.device,
                          as_written=a.as_written, speculate=a.speculate, chain_windows=not a.no_chain_windows)
     e = res["energy"]
