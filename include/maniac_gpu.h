@@ -313,18 +313,32 @@ int mgpu_commit_candidates(mgpu_engine *e, int n_candidates, const int *replica,
  * mgpu_replica_set_molecules (sites only) drops a residue type's frames again. */
 int mgpu_replica_set_frames(mgpu_engine *e, int replica, int t, int n_mol, const double *com, const double *off);
 int mgpu_replica_get_frames(mgpu_engine *e, int replica, int t, int *n_mol, double *com, double *off);
-/* One trial per candidate, its geometry built on the device from the resident frames (orthorhombic boxes):
+/* One trial per candidate, its geometry built on the device from the resident frames (orthorhombic boxes; triclinic ones
+ * once mgpu_set_triclinic_moves has switched them on, below):
  *   move[c] = 1  Translation      com <- ApplyPBC(com + (u[c][0..2] - 1/2) translation_step)      src/translation.f90:93-112
  *           = 2  Rotation         offsets rotated by (u[c][3] - 1/2) rotation_step about Cartesian axis int(3 u[c][4]) + 1
  *                                                                                                src/monte_carlo_utils.f90:30-92
  *           = 3  CreateMolecule   com <- lo + L u[c][0..2]; offsets of molecule 1 of the type rotated by 2 pi u[c][3]
  *                                 about that axis; m ignored                                       src/create_molecule.f90:166-207
  *           = 4  DeleteMolecule   the resident molecule m as it is
+ * In a triclinic cell (box_type 3) ApplyPBC is the reference's round trip through fractional coordinates, applied always
+ * (src/geometry_utils.f90:167-220): f = modulo(reciprocal (pos - lo), 1), com <- lo + matrix f; CreateMolecule places
+ * com <- lo + matrix u[c][0..2] (src/create_molecule.f90:180-184).  Both in the reference's doubles: no product is fused
+ * into the addition behind it.
  * u = n x 5 uniform numbers in [0, 1) drawn by the host (the random stream stays on the host, as the acceptance does).
  * Energies come back through mgpu_gcmc_trial_wait; mgpu_commit_submit(sites = NULL) on the same lane applies the accepted
  * candidates from the rows the device built, sites and frames. */
 int mgpu_move_trial_submit(mgpu_engine *e, int lane, int n_candidates, const int *replica, const int *t, const int *m,
                            const int *move, const double *u, double translation_step, double rotation_step);
+/* Device-built moves and farm windows in a TRICLINIC cell (the reference runs such a cell through the same loop as any
+ * other: src/geometry_utils.f90:167-220 ApplyPBC, :397-411 ComputeDistance, src/create_molecule.f90:180-184).  Off by
+ * default: mgpu_move_trial_submit and mgpu_move_trial_decide_submit then return MGPU_ERR_STATE for a triclinic engine and
+ * mgpu_farm_window_capacity reports 0 chains, as they always have.  on != 0: the two entry points build triclinic trials,
+ * and farm windows take the box where every active residue type is a molecule of <= 5 sites whose type takes the row form
+ * (a triclinic box with a larger active type keeps capacity 0: there is no wide window instance with the image search).
+ * On an orthorhombic engine the switch changes nothing.  Drains the lanes; call it between steps, not with trials or
+ * windows in flight on another thread. */
+int mgpu_set_triclinic_moves(mgpu_engine *e, int on);
 /* Reservoirs (MANIAC's `-r reservoir.data`; src/create_molecule.f90:117-128, :185-193, src/delete_molecule.f90:146-166): one
  * replica's molecules of one residue type held outside the box, offsets only (off[n][n1][3]; the reservoir's centres are
  * read by nothing but reservoir.lammpstrj).  Where (replica, t) has a reservoir, every DEVICE-BUILT step of the type
@@ -523,7 +537,8 @@ int mgpu_chain_get_timing(mgpu_engine *e, double us[15]);
  * that).  mgpu_farm_window_capacity: chains per launch and windows per lane in flight.  Chains: min(4096, replicas) where
  * every active residue type is a molecule of <= 5 sites whose type takes the row form, or a plane-major molecule of <= 63
  * sites whose type takes (mgpu_recip_form, for the type alone) the row form, the vector wide form or the untiled
- * matrix-unit wide form.  0 where the path does not apply: a triclinic box, a site-major type (64 sites or more), the per-k
+ * matrix-unit wide form.  0 where the path does not apply: a triclinic box without mgpu_set_triclinic_moves, or one with an
+ * active type of more than 5 sites; a site-major type (64 sites or more), the per-k
  * form, the tiled matrix-unit form, a Coulomb table over 64 KiB, or the windows' LDS beyond its budget.  Lanes may be
  * driven by different host threads (one thread per lane at a time), as the other per-lane entry points. */
 int mgpu_farm_window_capacity(const mgpu_engine *e, int *max_chains, int *max_in_flight);

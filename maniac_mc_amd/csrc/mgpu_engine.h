@@ -261,6 +261,7 @@ struct mgpu_engine {
     std::vector<char> rsv_tight;
     double **d_rsv = nullptr;
     int *d_rsv_nc = nullptr;
+    bool tri_moves = false;          // mgpu_set_triclinic_moves: a triclinic engine builds moves on the device and takes farm windows
     bool rsv_any = false;            // some reservoir was set: device-built rows carry the pick (reservoir_row_pick)
     // Register-site sweeps of this engine go through pair_flat_kernel (one software-pipelined loop over all units of
     // a work unit) instead of the plane-by-plane pair_sweep_kernel: chosen at creation for topologies with short planes

@@ -1106,7 +1106,8 @@ __global__ __launch_bounds__(kBlock, 2) void recip_rows_wide_kernel(
 //   move 4  deletion      nothing to build
 // One thread per candidate.  Row c of `rows` (row_stride "sites" of three doubles) receives the candidate's sites
 // com + off at [0, n1), its frame at [frame_at] (com) and [frame_at + 1, frame_at + 1 + n1) (offsets): the sweeps read
-// the sites, the commit writes sites AND frame back.  Orthorhombic boxes.
+// the sites, the commit writes sites AND frame back.  TRI: a triclinic cell -- moves 1 and 3 take trial_com_triclinic's centre
+// (mgpu_set_triclinic_moves).
 // ------------------------------------------------------------------------------------------
 // The construction in two pieces, shared with farm_window_kernel (every role of a window rebuilds the candidate it needs
 // from the same frames and numbers: the same functions, so the same bits):
@@ -1124,8 +1125,40 @@ template <bool RSV> struct TrialFrameR : TrialFrame {
     const double *rsv;            // a reservoir insertion: the offsets [n1][3] it copies, unrotated (else null)
 };
 template <> struct TrialFrameR<false> : TrialFrame {};
+// The centre of a candidate in a triclinic cell, the reference's doubles.
+// Every product is rounded before it is added -- the reference's object code holds no fused multiply-add here, and the
+// compiler would otherwise contract a * b + c.
+//   translation (geometry_utils.f90:167-220 ApplyPBC): v = (com + (u - 1/2) step) - lo; f = box%reciprocal v, each row summed
+//     left to right; f <- modulo(f, 1) ALWAYS (no "already inside" shortcut: the round trip through fractional coordinates
+//     changes the last bits of a centre inside the cell too); com = lo + box%matrix f
+//   insertion (create_molecule.f90:180-184): com = lo + box%matrix u
+__device__ __forceinline__ void trial_com_triclinic(const BoxDev &bx, int mv, const double *u, double t_step, double com[3]) {
+#pragma clang fp contract(off)
+    double f[3];
+    if (mv == 1) {
+        double v[3];
+        for (int d = 0; d < 3; ++d) {
+            const double s = (u[d] - 0.5) * t_step;
+            v[d] = (com[d] + s) - bx.lo[d];
+        }
+        for (int i = 0; i < 3; ++i) {
+            const double a = bx.rcp[3 * i] * v[0], b = bx.rcp[3 * i + 1] * v[1], c = bx.rcp[3 * i + 2] * v[2];
+            double r = fmod((a + b) + c, 1.0);                                // Fortran's modulo(f, 1)
+            if (r != 0.0 && r < 0.0) r = r + 1.0;
+            f[i] = r;
+        }
+    } else {
+        for (int i = 0; i < 3; ++i) f[i] = u[i];
+    }
+    for (int i = 0; i < 3; ++i) {
+        const double a = bx.m[3 * i] * f[0], b = bx.m[3 * i + 1] * f[1], c = bx.m[3 * i + 2] * f[2];
+        com[i] = bx.lo[i] + ((a + b) + c);
+    }
+}
 // RSV = false: the code of an engine that holds no reservoir (the farm windows' instances without one)
-template <bool RSV = true, class TopoT>
+// TRI: the triclinic form of the centre (trial_com_triclinic) -- a template parameter, not a branch on bx.triclinic: the
+// orthorhombic instances are the code they were
+template <bool RSV = true, bool TRI = false, class TopoT>
 __device__ __forceinline__ TrialFrameR<RSV> trial_frame(const TopoT &tp, const BoxDev &bx, int replica, int t, int m, int mv, const double *u,
                                                   double t_step, double r_step) {
     TrialFrameR<RSV> f;
@@ -1136,7 +1169,8 @@ __device__ __forceinline__ TrialFrameR<RSV> trial_frame(const TopoT &tp, const B
     f.p = 0; f.q = 0;
     f.cs = 1.0; f.sn = 0.0;
     f.rot = false;
-    if (mv == 1) {
+    if (TRI && (mv == 1 || mv == 3)) trial_com_triclinic(bx, mv, u, t_step, f.com);
+    if (!TRI && mv == 1) {
         for (int d = 0; d < 3; ++d) {
             // translation.f90:104-110, geometry_utils.f90:190: lo + modulo(pos - lo, L)
             double x = (f.com[d] + (u[d] - 0.5) * t_step) - bx.lo[d];
@@ -1154,7 +1188,7 @@ __device__ __forceinline__ TrialFrameR<RSV> trial_frame(const TopoT &tp, const B
         f.q = (axis + 1) % 3;
         f.rot = true;
     }
-    if (mv == 3)
+    if (!TRI && mv == 3)
         for (int d = 0; d < 3; ++d) f.com[d] = bx.lo[d] + bx.L[d] * u[d];     // create_molecule.f90:180-184
     if constexpr (RSV) {
     f.rsv = nullptr;
@@ -1192,6 +1226,7 @@ __device__ __forceinline__ void trial_offset(const TopoT &tp, const TrialFrameR<
     }
 }
 
+template <bool TRI = false>
 static __global__ void trial_build_kernel(Topo tp, BoxDev bx, const RecipItem *__restrict__ items, const int *__restrict__ move,
                                    const double *__restrict__ uu, double t_step, double r_step, double *__restrict__ rows,
                                    int row_stride, int frame_at, int n, int pick_at) {
@@ -1201,7 +1236,7 @@ static __global__ void trial_build_kernel(Topo tp, BoxDev bx, const RecipItem *_
     const int mv = move[c];
     if (mv == 4) return;
     const int n1 = tp.n1[it.t];
-    const auto f = trial_frame(tp, bx, it.replica, it.t, it.m, mv, uu + 5 * (size_t)c, t_step, r_step);
+    const auto f = trial_frame<true, TRI>(tp, bx, it.replica, it.t, it.m, mv, uu + 5 * (size_t)c, t_step, r_step);
     double *row = rows + (size_t)c * row_stride * 3;
     for (int d = 0; d < 3; ++d) row[(size_t)frame_at * 3 + d] = f.com[d];
     // (pick_at > 0: the engine holds reservoirs, and the row has room for the commit's reservoir_row_pick)

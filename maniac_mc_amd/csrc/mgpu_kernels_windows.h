@@ -41,6 +41,9 @@ constexpr int kChainMaxCand = 16;
 #ifndef MGPU_FARM_WIDE_MINWAVES
 #define MGPU_FARM_WIDE_MINWAVES 2   // farm_window_kernel<..., WIDE>: 140 VGPRs, no spills (at 4: 128 and 32 bytes of spills); DESIGN 4.4
 #endif
+#ifndef MGPU_FARM_TRI_MINWAVES
+#define MGPU_FARM_TRI_MINWAVES 2    // farm_window_kernel<false, false, false, RSV, true>: 169 VGPRs, no spills (at 4: 128 and 160 bytes of spills; at 3: 168, one workgroup per CU all the same); DESIGN 4.4
+#endif
 constexpr int kChainBlock = kPairBlock;          // 512 threads: 8 pair waves; the k role uses the first kBlock of them
 constexpr int kChainStamps = 8;                  // stage time stamps per role (k role of candidate 0, first pair workgroup, resolver)
 struct ChainResult {                             // what the k role of candidate c leaves for the resolving workgroup
@@ -317,7 +320,8 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_window_kernel(
 // one: nothing to do, as in the reference's drivers), prefactor phi V / (N + 1) or N / (phi V)
 // (src/monte_carlo.f90:50-75, src/monte_carlo_utils.f90:184-226).  The driver replays the same integer arithmetic with
 // its own counts when it collects the window.
-// Orthorhombic boxes, row-form k sweep, molecules of <= kMaxFusedSitesWide sites, frames resident.
+// Row-form k sweep, molecules of <= kMaxFusedSitesWide sites (the WIDE instances: up to 63), frames resident; orthorhombic
+// boxes, and triclinic ones through the TRI instances.
 // ------------------------------------------------------------------------------------------
 struct FarmRec {
     int replica, t, m, move;      // move 0: the chain does nothing this step; 1 translation, 2 rotation, 3 creation, 4 deletion
@@ -375,7 +379,7 @@ static __device__ long long g_farm_stamps[3][8];
 #endif
 
 // One chain resolved by ONE WAVE (all 64 lanes arrive): `scratch` = 4 nsplit + 4 doubles of LDS of its own.
-template <bool RSV>
+template <bool RSV, bool TRI = false>
 __device__ __forceinline__ void farm_resolve(const Topo &tp, const BoxDev &bx, double *__restrict__ pos, int *__restrict__ nmol,
                                              const FarmArgs &g, const FarmRec &rec, int c, int lane, double *scratch) {
     double *ho = g.host_out + (size_t)kFarmOut * c;
@@ -466,7 +470,7 @@ __device__ __forceinline__ void farm_resolve(const Topo &tp, const BoxDev &bx, d
     const int nm = nmol[rec.replica * tp.n_res + rec.t];
     if (kind != 2) {
         const int m = kind == 1 ? nm : rec.m;                 // appended at the first free slot (monte_carlo.f90:63, create_molecule.f90:64)
-        const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+        const auto f = trial_frame<RSV, TRI>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
         if (lane < n1) {
             double off[3];
             trial_offset<RSV>(tp, f, rec.replica, rec.t, lane, off);
@@ -607,8 +611,14 @@ __device__ __forceinline__ void farm_wide_k_role(const Topo &tp, const BoxDev &b
 // the thread form up to kIntraThreadMax sites and the wave form above, on the k workgroup's spare waves.  Chains of
 // <= kMaxFusedSitesWide sites take the narrow instance's code.
 // RSV: the engine holds reservoirs (mgpu_replica_set_reservoir); without them the instances are the code they were before.
-template <bool FLAT, bool FASTW, bool WIDE = false, bool RSV = false>
-__global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) void farm_window_kernel(
+// TRI: a triclinic box whose engine has device-built moves switched on (mgpu_set_triclinic_moves).  The roles build their
+// candidates with the triclinic form of trial_frame, and the pair role runs the register-site sweep with ComputeDistance's
+// image search, pair_sweep_item<NS, false, true, ...> with the engine's nsplit: the batched path's kernel for such a box and
+// chain_window_kernel<false, false, true>'s.  No FLAT, no FASTW and no WIDE form exists for such a box (launch_pair has none
+// either; a triclinic box with an active type of 6..63 sites keeps capacity 0).  The k role, the tickets, the resolver, the
+// hand-offs and RSV are the narrow instance's, unchanged.
+template <bool FLAT, bool FASTW, bool WIDE = false, bool RSV = false, bool TRI = false>
+__global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI ? MGPU_FARM_TRI_MINWAVES : 4)) void farm_window_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
@@ -692,7 +702,7 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) vo
             const int kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
             const int n1 = tp.n1[rec.t];
             if (kind != 2 && tid < n1) {
-                const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                const auto f = trial_frame<RSV, TRI>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                 double off[3];
                 trial_offset<RSV>(tp, f, rec.replica, rec.t, tid, off);
                 for (int d = 0; d < 3; ++d) s_cand[0][tid * 3 + d] = f.com[d] + off[d];
@@ -745,7 +755,7 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) vo
             } else if (ent == 0 ? kind != 1 : kind != 2) {
                 double *cand = &s_cand[wave][0];
                 if (ent == 1) {
-                    const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                    const auto f = trial_frame<RSV, TRI>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                     if (lane < n1) {
                         double off[3];
                         trial_offset<RSV>(tp, f, rec.replica, rec.t, lane, off);
@@ -762,7 +772,7 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) vo
                         pair_flat_item<NS, false, FASTW, true>(tp, bx, pos, nmol, res_q, res_atype, s_dyn, s_pair, s_grp,     \
                                                          s_plane + wave * kFlatMaxPlanes, it, cand, kMaxFusedSitesWide, split, ns, lane, 0, g.partials, wg); \
                     else                                                                                                 \
-                        pair_sweep_item<NS, false, false, false, FASTW, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, nullptr, \
+                        pair_sweep_item<NS, false, TRI, false, FASTW, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, nullptr, \
                                                                         nullptr, it, cand, kMaxFusedSitesWide, split, ns, lane, g.partials, wg);   \
                 } while (0)
                 switch (n1) {
@@ -798,7 +808,7 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : 4) vo
     MGPU_FSTAMP(tid == 0 && k_role && c_lo == 0, 0, 7);
     if (wave < n_c && s_resolve[wave]) {
         double *scratch = reinterpret_cast<double *>(s_dyn) + (size_t)wave * (4 * ns + 4);
-        farm_resolve<RSV>(tp, bx, pos, nmol, g, s_rec[wave], c_lo + wave, lane, scratch);
+        farm_resolve<RSV, TRI>(tp, bx, pos, nmol, g, s_rec[wave], c_lo + wave, lane, scratch);
     }
 }
 

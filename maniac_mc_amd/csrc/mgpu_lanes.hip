@@ -510,7 +510,9 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
         // the rows are written by the device: only [items | move codes | uniforms] travel
         HIP_TRY(hipMemcpyAsync((char *)ln.d_sites.p + site_bytes, (char *)ln.h_in.p + site_bytes, dec_at + dec_bytes - site_bytes,
                                hipMemcpyHostToDevice, ln.stream));
-        hipLaunchKernelGGL(trial_build_kernel, dim3((n + 127) / 128), dim3(128), 0, ln.stream, e->tp, e->bx,
+        // (a triclinic cell: the instance with trial_com_triclinic's centre; the entry points refuse one without the switch)
+        const auto build_kernel = e->bx.triclinic ? trial_build_kernel<true> : trial_build_kernel<false>;
+        hipLaunchKernelGGL(build_kernel, dim3((n + 127) / 128), dim3(128), 0, ln.stream, e->tp, e->bx,
                            (const RecipItem *)((char *)ln.d_sites.p + site_bytes + pit_cap), (const int *)((char *)ln.d_sites.p + build_at),
                            (const double *)((char *)ln.d_sites.p + build_at + build_mv), build->t_step, build->r_step,
                            (double *)ln.d_sites.p, site_stride, frame_at, n, e->rsv_any ? 2 * frame_at + 1 : 0);
@@ -913,7 +915,7 @@ int mgpu_move_trial_submit(mgpu_engine *e, int lane, int n, const int *replica, 
     int rc = check_lane(e, lane);
     if (rc) return rc;
     if (n <= 0 || !replica || !t || !m || !move || !u) return set_error(MGPU_ERR_INVALID_ARG, "move_trial_submit: bad argument");
-    if (e->bx.triclinic) return set_error(MGPU_ERR_STATE, "move_trial_submit: orthorhombic boxes only");
+    if (e->bx.triclinic && !e->tri_moves) return set_error(MGPU_ERR_STATE, "move_trial_submit: orthorhombic boxes only");
     if ((rc = use_device(e))) return rc;
     Lane &ln = e->lanes[lane];
     ln.build_kind.resize(n);
@@ -932,7 +934,7 @@ int mgpu_move_trial_decide_submit(mgpu_engine *e, int lane, int n, const int *re
     if (rc) return rc;
     if (n <= 0 || !replica || !t || !m || !move || !u || !accept_u || !accept_pref)
         return set_error(MGPU_ERR_INVALID_ARG, "move_trial_decide_submit: bad argument");
-    if (e->bx.triclinic) return set_error(MGPU_ERR_STATE, "move_trial_decide_submit: orthorhombic boxes only");
+    if (e->bx.triclinic && !e->tri_moves) return set_error(MGPU_ERR_STATE, "move_trial_decide_submit: orthorhombic boxes only");
     if ((rc = use_device(e))) return rc;
     Lane &ln = e->lanes[lane];
     ln.build_kind.resize(n);
@@ -1018,6 +1020,15 @@ int mgpu_commit_candidates(mgpu_engine *e, int n, const int *replica, const int 
     return sync_stream(e);
 }
 
+
+int mgpu_set_triclinic_moves(mgpu_engine *e, int on) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc = use_device(e);
+    if (rc) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;      // (no trial or window in flight sees the switch move)
+    e->tri_moves = on != 0;
+    return MGPU_OK;
+}
 
 int mgpu_set_host_team(mgpu_engine *e, int n_threads) {
     if (!e || n_threads < 1) return set_error(MGPU_ERR_INVALID_ARG, "set_host_team: bad argument");

@@ -283,7 +283,8 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
 // The k role a farm window gives a chain of residue type t -- the form recip_plan picks for the type alone, as the batched
 // path's per-type launches do (recip_groups) -- and the dynamic LDS that role needs.  false: windows do not take the type
 // (site-major types, i.e. molecules of kFarmWideSites sites or more; a molecule of <= kMaxFusedSitesWide sites whose type
-// does not take the row form; a larger one in a triclinic box, or whose type takes the per-k or the tiled matrix-unit form).
+// does not take the row form; a larger one in a triclinic box -- there is no WIDE instance with the image search -- or whose
+// type takes the per-k or the tiled matrix-unit form).
 struct FarmTypeForm {
     int form = kFarmFormRows, rpt = 0, nss = 0;
     size_t lds = 0;
@@ -331,10 +332,11 @@ static size_t farm_wide_lds(const mgpu_engine *e) {
     return lds;
 }
 
-// chains per launch the engine accepts, 0 where the path does not apply: a triclinic box, an active type windows do not take
-// (farm_type_form), a Coulomb table beyond 64 KiB, LDS beyond the budget
+// chains per launch the engine accepts, 0 where the path does not apply: a triclinic box whose engine has not switched
+// device-built moves on (mgpu_set_triclinic_moves), an active type windows do not take (farm_type_form: in a triclinic box
+// every type of more than kMaxFusedSitesWide sites), a Coulomb table beyond 64 KiB, LDS beyond the budget
 static int farm_max_chains(const mgpu_engine *e) {
-    if (e->bx.triclinic) return 0;
+    if (e->bx.triclinic && !e->tri_moves) return 0;
     bool wide = false;
     for (int t = 0; t < e->tp.n_res; ++t) {
         if (!e->is_active[t]) continue;
@@ -543,12 +545,21 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
                            e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, \
                            e->d_A, g);                                                                                     \
     } while (0)
+#define MGPU_LAUNCH_FARM_TRI(RS)                                                                                           \
+    do {                                                                                                                   \
+        hipLaunchKernelGGL((farm_window_kernel<false, false, false, RS, true>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, \
+                           e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks,     \
+                           e->d_rrows, e->n_rrows, e->d_A, g);                                                             \
+    } while (0)
     // (an engine without reservoirs runs the instances without their code)
 #define MGPU_LAUNCH_FARM(FL, FW, WI)                                                                                       \
     do {                                                                                                                   \
         if (e->rsv_any) MGPU_LAUNCH_FARM_RS(FL, FW, WI, true); else MGPU_LAUNCH_FARM_RS(FL, FW, WI, false);               \
     } while (0)
-    if (wide) {
+    if (e->bx.triclinic) {
+        // (farm_type_form admits no wide type here; the image search has no flat and no fast-fold form)
+        if (e->rsv_any) MGPU_LAUNCH_FARM_TRI(true); else MGPU_LAUNCH_FARM_TRI(false);
+    } else if (wide) {
         if (e->pair_flat) { if (ff) MGPU_LAUNCH_FARM(true, true, true); else MGPU_LAUNCH_FARM(true, false, true); }
         else { if (ff) MGPU_LAUNCH_FARM(false, true, true); else MGPU_LAUNCH_FARM(false, false, true); }
     } else {
@@ -557,6 +568,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     }
 #undef MGPU_LAUNCH_FARM
 #undef MGPU_LAUNCH_FARM_RS
+#undef MGPU_LAUNCH_FARM_TRI
     HIP_TRY(hipGetLastError());
     fw.pending.push_back(std::move(pd));
     e->farm.windows += 1;

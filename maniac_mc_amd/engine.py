@@ -76,7 +76,8 @@ class Engine:
     """One HIP device, R replicas of one (box, force field, k table)."""
 
     def __init__(self, topo: Topology, box_matrix, bounds_lo, real_space_cutoff, ewald_tolerance,
-                 n_replicas: int = 1, device: int = 0, mol_capacity: Optional[Sequence[int]] = None):
+                 n_replicas: int = 1, device: int = 0, mol_capacity: Optional[Sequence[int]] = None,
+                 triclinic_moves: bool = False):
         self.L = _lib.lib()
         self.topo = topo
         self.n_replicas = int(n_replicas)
@@ -98,17 +99,20 @@ class Engine:
         self.alpha, self.rc, self.tol, self.volume = alpha.value, rc.value, tol.value, vol.value
         self.kmax, self.nk, self.box_type = kmax, nk.value, bt.value
         self.max_n1 = int(topo.atoms_in_res.max())
+        if triclinic_moves:
+            self.set_triclinic_moves(True)
 
     @classmethod
     def from_system(cls, system: System, n_replicas: int = 1, device: int = 0, mol_capacity=None,
-                    extra_capacity: int = 8):
-        """Engine sized for ``system`` with every replica loaded with that configuration."""
+                    extra_capacity: int = 8, triclinic_moves: bool = False):
+        """Engine sized for ``system`` with every replica loaded with that configuration.  ``triclinic_moves``: device-built
+        moves and farm windows for a triclinic box (set_triclinic_moves)."""
         if mol_capacity is None:
             mol_capacity = [int(n) + (extra_capacity if system.topo.is_active[t] else 0)
                             for t, n in enumerate(system.n_mol)]
             mol_capacity = [max(1, c) for c in mol_capacity]
         eng = cls(system.topo, system.box_matrix, system.bounds_lo, system.real_space_cutoff,
-                  system.ewald_tolerance, n_replicas, device, mol_capacity)
+                  system.ewald_tolerance, n_replicas, device, mol_capacity, triclinic_moves)
         eng.load_system(system, 0)
         for r in range(1, n_replicas):
             eng.replica_copy(r, 0)
@@ -506,6 +510,11 @@ class Engine:
     def ComputeIntraResidueRealCoulombEnergySingleMol(self, residue_type, molecule_index, sites=None, replica=0):
         """ewald_energy.f90:371-411"""
         return float(self.intra_energy_candidates(replica, residue_type, molecule_index, sites)[0])
+
+    def set_triclinic_moves(self, on=True):
+        """Device-built moves (move_trial, move_trial_decide) and farm windows in a triclinic box: off by default, and then
+        refused / capacity 0 there.  Changes nothing for an orthorhombic engine."""
+        check(self.L.mgpu_set_triclinic_moves(self.h, C.c_int(1 if on else 0)))
 
     def set_host_team(self, n_threads):
         """Host threads the candidate loops inside submit / wait / commit may use (mgpu_set_host_team)."""

@@ -83,7 +83,7 @@ class FortranFarm:
                  translation_step: float = 0.3, rotation_step: float = 0.3, p_translation: float = 0.5,
                  rng_kind: int = 1, n_threads: int = 8, mol_capacity=None, gcmc=None,
                  n_lanes: int = 2, n_drivers: int = 1, device_build: bool = False, device_accept: bool = False,
-                 window: bool = False, window_depth: int = 2, reservoir=None):
+                 window: bool = False, window_depth: int = 2, reservoir=None, triclinic_moves: bool = False):
         self.H = lib()
         # mc_farm.f90 keeps up to MAX_FARMS farms; every call below selects this farm's slot first
         free = [k for k in range(FortranFarm.MAX_FARMS) if k not in FortranFarm._slots]
@@ -97,11 +97,14 @@ class FortranFarm:
             mol_capacity = [max(1, int(n)) for n in system.n_mol]
         self.mol_capacity = [int(c) for c in mol_capacity]
         self.eng = Engine(topo, system.box_matrix, system.bounds_lo, system.real_space_cutoff,
-                          system.ewald_tolerance, self.R, device, self.mol_capacity)
+                          system.ewald_tolerance, self.R, device, self.mol_capacity,
+                          triclinic_moves=bool(triclinic_moves) and system.is_triclinic())
         self.eng.load_system(system, 0)
         # device_build: the engine keeps the molecules' frames (com, offsets) and builds the trial moves itself; the
-        # Fortran driver then holds no mirror of the coordinates (orthorhombic boxes)
-        self.device_build = bool(device_build) and not system.is_triclinic()
+        # Fortran driver then holds no mirror of the coordinates (orthorhombic boxes; triclinic ones with triclinic_moves,
+        # Engine.set_triclinic_moves -- without it a triclinic system's moves are built on the host, as they always were)
+        self.triclinic_moves = bool(triclinic_moves) and system.is_triclinic()
+        self.device_build = bool(device_build) and (not system.is_triclinic() or self.triclinic_moves)
         if self.device_build:
             for tt in range(topo.n_res):
                 if topo.is_active[tt]:

@@ -80,7 +80,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     ``fugacities``: [f1, ..., fk] in the input's units (atm): replica r runs at f[r % k] for every active type (GCMC inputs
     only).  ``frames``: the replicas that write trajectory.lammpstrj and topology.data every block.
     ``mode``: "auto" -> windows where the engine's one-launch path applies, else device-built batched steps, else (triclinic
-    boxes) host-built ones; "windows" | "device" | "device_accept" | "host" force one.
+    boxes) host-built ones; "windows" | "device" | "device_accept" | "host" force one.  A triclinic input runs an explicit
+    "windows", "device" or "device_accept" with the engine's triclinic moves switched on (Engine.set_triclinic_moves);
+    "auto" keeps choosing "host" there.
     ``chunk``: replicas per snapshot launch (default: about SNAPSHOT_BYTES at the types' capacities).
     """
     import time
@@ -103,8 +105,7 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     if frames and (frames[0] < 0 or frames[-1] >= R):
         raise ValueError(f"frames must lie in [0, {R - 1}]")
     triclinic = system.is_triclinic()
-    if triclinic and mode in ("windows", "device", "device_accept"):
-        raise ValueError(f"mode {mode!r}: the engine builds no moves in triclinic boxes (use 'host' or 'auto')")
+    triclinic_moves = triclinic and mode in ("windows", "device", "device_accept")
     if mol_capacity is None:
         mol_capacity = [NB_MAX_MOLECULE if topo.is_active[t] == 1 else max(1, int(system.n_mol[t])) for t in range(n_res)]
     nb_block = inp.nb_block if nb_block is None else int(nb_block)
@@ -121,11 +122,12 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         fug_grid = np.tile(np.array([inp.fugacity_per_A3()[t] for t in active])[None, :], (R, 1)) if gcmc else None
     gcmc_arg = dict(p_translation=inp.translation_proba, p_rotation=inp.rotation_proba, fugacity=fug_grid) if gcmc else None
     reservoir = io_maniac.reservoir_offsets(reservoir_path, inp) if reservoir_path else None
-    device_build = not triclinic and mode != "host"
+    device_build = (not triclinic or triclinic_moves) and mode != "host"
     farm = FortranFarm(system, R, device=device, seed=int(seed), translation_step=inp.translation_step,
                        rotation_step=inp.rotation_step_angle, p_translation=inp.translation_proba, n_threads=n_threads,
                        mol_capacity=mol_capacity, gcmc=gcmc_arg, n_lanes=n_lanes, device_build=device_build,
-                       device_accept=mode == "device_accept", window=mode in ("auto", "windows"), reservoir=reservoir)
+                       device_accept=mode == "device_accept", window=mode in ("auto", "windows"), reservoir=reservoir,
+                       triclinic_moves=triclinic_moves)
     try:
         ran = "host" if not farm.device_build else ("windows" if farm.window else
                                                      ("device_accept" if farm.device_accept else "device"))

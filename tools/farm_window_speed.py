@@ -4,6 +4,11 @@
 step, mgpu_farm_window_submit), for several lane counts and windows in flight.
 
     python tools/farm_window_speed.py [--replicas 8,64,512] [--seconds 1.0] [--modes batched,w1,w2,w3] [--lanes 1,2,4]
+    python tools/farm_window_speed.py --workload spce_triclinic --lanes 1 --replicas 8,64,512 --modes host,batched,w1,w2
+
+--workload spce_triclinic: bench.py's sheared 10 125-atom box.  Mode `host` is the farm as it runs such a box by default (moves
+built on the host, batched evaluation); `batched` and `w1`.. switch the engine's triclinic moves on (FortranFarm
+triclinic_moves): device-built batched steps, and one launch per lane step.
 """
 import argparse
 import json
@@ -25,8 +30,9 @@ def main():
     ap.add_argument("--threads", type=int, default=2)
     ap.add_argument("--drivers", default="1", help="driver threads (each runs its own lanes' windows)")
     ap.add_argument("--side", type=int, default=15)
-    ap.add_argument("--workload", default="spce", choices=("spce", "co2_gcmc", "adsorbate24"),
-                    help="spce: the 10 125-atom box, translation / rotation; co2_gcmc: bench.py's 50 A CO2 box, insertion / deletion only; "
+    ap.add_argument("--workload", default="spce", choices=("spce", "spce_triclinic", "co2_gcmc", "adsorbate24"),
+                    help="spce: the 10 125-atom box, translation / rotation; spce_triclinic: the same box sheared (tilt 3.0 / -2.0 / 1.5 A, "
+                         "bench.py's), modes host | batched | w1..; co2_gcmc: bench.py's 50 A CO2 box, insertion / deletion only; "
                          "adsorbate24: bench.py's 64 rigid 24-site adsorbates in a 60 A box, translation / rotation")
     ap.add_argument("--reservoir", action="store_true",
                     help="co2_gcmc: every chain draws its insertions from a reservoir of 400 random rotations of CO2 (mfarm_set_reservoir)")
@@ -37,6 +43,14 @@ def main():
     if args.workload == "spce":
         s = synth.spce_box(args.side, seed=12345)
         kw = dict(translation_step=0.3, rotation_step=0.3, p_translation=0.5)
+    elif args.workload == "spce_triclinic":
+        s = synth.spce_box(args.side)
+        L = float(s.box_matrix[0, 0])
+        # bench.py's spce_triclinic: rows a = (lx, 0, 0), b = (xy, ly, 0), c = (xz, yz, lz), the centres sheared with the cell
+        s.box_matrix = np.array([[L, 0.0, 0.0], [3.0, L, 0.0], [-2.0, 1.5, L]])
+        frac = (s.com[0] - s.bounds_lo[None, :]) / L
+        s.com[0] = s.bounds_lo[None, :] + frac @ s.box_matrix.T
+        kw = dict(translation_step=0.3, rotation_step=0.3, p_translation=0.5, triclinic_moves=True)
     elif args.workload == "adsorbate24":
         s = synth.rigid_adsorbate_box(n_mol=64, L=60.0, seed=17)
         kw = dict(translation_step=0.3, rotation_step=0.3, p_translation=0.5)
@@ -64,8 +78,12 @@ def main():
                     continue
                 window = mode.startswith("w")
                 depth = int(mode[1:]) if window else 1
-                farm = FortranFarm(s, R, seed=77, n_threads=max(args.threads, drivers), n_lanes=lanes, n_drivers=drivers, device_build=True,
-                                   window=window, window_depth=depth, reservoir=rsv, **kw)
+                if mode == "host" and args.workload != "spce_triclinic":
+                    ap.error("mode host goes with --workload spce_triclinic")
+                farm = FortranFarm(s, R, seed=77, n_threads=max(args.threads, drivers), n_lanes=lanes, n_drivers=drivers,
+                                   device_build=mode != "host", window=window, window_depth=depth, reservoir=rsv, **kw)
+                if args.workload == "spce_triclinic":      # the switch took: no silent fall-back to the host construction
+                    assert farm.device_build == (mode != "host") and farm.window == window, (mode, farm.device_build, farm.window)
                 try:
                     farm.run(20)
                     chunk = (400 if R <= 64 else 200) if window else 50       # (see bench.py replicas_sweep: a chunk ends with a synchronise)
