@@ -19,6 +19,7 @@
 #include <string>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/maniac_gpu.h"
@@ -109,6 +110,14 @@ struct Lane {
     // row-form launch, one candidate per replica), under alt_owner stamp trial_stamp: a commit of it may switch buffers
     bool trial_alt = false;
     unsigned long long trial_stamp = 0;
+    // The site rows and items of the lane's previous trial are gone (overwritten, consumed by a commit, or built under rules
+    // that no longer hold): nothing may be committed "from the lane's resident rows", by mask or by switching, until the next trial.
+    void forget_trial() {
+        last_trial_n = 0;
+        d_trial_items = nullptr;
+        h_trial_items = nullptr;
+        trial_alt = false;
+    }
     // accepted share of the lane's last commit from its resident rows: the stores pay for every candidate, the switch saves
     // the commit pass of the accepted ones only (measured alone, 4096 candidates: k sweep 38 -> 69 us, commit 40 -> 6 us)
     double accept_share = 1.0;
@@ -178,6 +187,37 @@ struct Lane {
 constexpr int kLanes = 4;
 constexpr int kFarmDepth = 4;           // farm windows a lane may have in flight
 constexpr int kFarmMaxChains = 4096;   // chains per farm window
+
+// ---- From run-time values to template instances.  A launch site picks its kernel FAMILY with ordinary ifs, states the
+// family's argument list once in a generic lambda, and lets these expand the parameters that are free within the family:
+// exactly the instances the calls below can name are compiled, none besides.
+// with_bools(f, a, b, ...): f(std::bool_constant<a>{}, std::bool_constant<b>{}, ...)
+template <class F>
+void with_bools(F &&f) { f(); }
+template <class F, class... Rest>
+void with_bools(F &&f, bool first, Rest... rest) {
+    if (first) with_bools([&](auto... cs) { f(std::true_type{}, cs...); }, rest...);
+    else with_bools([&](auto... cs) { f(std::false_type{}, cs...); }, rest...);
+}
+// with_int<Lo, Hi>(v, f): f(std::integral_constant<int, v>{}) for Lo <= v <= Hi; false (f not called) outside the range --
+// a family's cap on a parameter is the range written at its call
+template <int Lo, int Hi, class F>
+bool with_int(int v, F &&f) {
+    if constexpr (Lo > Hi) return false;
+    else {
+        if (v == Lo) { f(std::integral_constant<int, Lo>{}); return true; }
+        return with_int<Lo + 1, Hi>(v, f);
+    }
+}
+// every instance a with_bools(f, ...) over sizeof...(Free) flags can reach, for what must be done to all of them
+// (hipFuncSetAttribute): the same f names them, so the two lists cannot differ
+template <class F, class... Done>
+void for_all_bools(F &&f, std::integral_constant<int, 0>, Done... done) { f(done...); }
+template <int N, class F, class... Done>
+void for_all_bools(F &&f, std::integral_constant<int, N>, Done... done) {
+    for_all_bools(f, std::integral_constant<int, N - 1>{}, done..., std::false_type{});
+    for_all_bools(f, std::integral_constant<int, N - 1>{}, done..., std::true_type{});
+}
 
 }  // namespace mgpu
 
@@ -352,6 +392,12 @@ double self_energy_host(const mgpu_engine *e, int t);
 int normalize_A(mgpu_engine *e);                // every replica's current A(k) back into d_A (mgpu_windows.hip)
 int alt_reserve(mgpu_engine *e);                // the A(k) double buffer (mgpu_windows.hip)
 void alt_forget(mgpu_engine *e, int replica);   // replica's other buffer holds nothing a commit may switch to (-1: every replica)
+// at most one of the n records per replica?  false: some replica (all within [0, n_replicas)) occurs twice
+bool one_record_per_replica(Lane &ln, int n_replicas, const int *replica, int n);
+// spin until each of the n pinned tags shows seq (then the results behind them are visible); from `first_check` spins on,
+// every `check_every`, make sure the stream is still alive.  `what` heads the error text.
+int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int n, unsigned long long seq, long long first_check,
+                 long long check_every, const char *what);
 int farm_clear_stall(mgpu_engine *e, int replica);   // the replica's state was rewritten: it waits for no decision (mgpu_windows.hip)
 int chain_topo(mgpu_engine *e, const Topo **d_topo);   // the engine's Topo in device memory (mgpu_windows.hip)
 // mgpu_launch.hip
@@ -361,19 +407,22 @@ int launch_pair(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, 
 int frozen_chunk_atoms(const mgpu_engine *e, int n_atoms);
 int launch_frozen(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, int n1, int site_stride, bool fused, bool fast_fold,
                   int t_frozen, double2 *d_scratch, double2 *d_extra);
-size_t recip_lds_bytes(const mgpu_engine *e, int n1_max);
-int recip_tile_sites(const mgpu_engine *e, int n1_max);
-size_t recip_rows_lds_bytes(const mgpu_engine *e, int n1_max);
+// the engine's dynamic-LDS sizes (the arithmetic: mgpu_internal.h)
+static_assert(sizeof(double2) == kLdsPhase && sizeof(int4) == kLdsRowRec, "mgpu_internal.h sizes the LDS tables with these");
+inline int recip_ktot(const mgpu_engine *e) { return recip_ktot(e->kmax); }
+inline size_t recip_rows_lds_bytes(const mgpu_engine *e, int n1_max) { return recip_rows_lds_bytes(recip_ktot(e), e->n_rrows, n1_max); }
+// the resolving waves' scratch of a farm window: four sums per split and four more, per wave
+inline size_t farm_resolver_scratch_bytes(int nsplit) { return (size_t)kPairWaves * (4 * nsplit + 4) * sizeof(double); }
 bool recip_by_rows(const mgpu_engine *e, int n1_max);
-int recip_wide_rows_per_tile(const mgpu_engine *e, int n1_max);   // 0: the wide row form does not apply
-bool recip_wide_mfma(const mgpu_engine *e, int n1_max);
-int recip_wide_mfma_tile(const mgpu_engine *e, int n1_max);       // site-states per LDS tile (0: the matrix-unit form does not apply)
 struct RecipPlan {
     int form = MGPU_RECIP_FORM_ROWS;   // MGPU_RECIP_FORM_*
     bool by_rows = true;
     int tile = 1;                      // row form: n1_max; per-k form: sites per LDS tile
     int mfma_tile = 0;                 // matrix-unit wide form: site-states per LDS tile (else 0)
     int wide_rpt = 0;                  // vector wide form: rows per XY tile (else 0)
+    int wide_nss = 0;                  // either wide form: site-states in LDS at a time (else 0)
+    size_t lds = 0;                    // dynamic LDS of the row / per-k kernel: beyond kLdsDefaultMax kmax is too large for the engine
+    size_t wide_lds = 0;               // dynamic LDS of the wide kernel (either wide form)
 };
 RecipPlan recip_plan(const mgpu_engine *e, int n1_max, bool wide_ok);
 void recip_groups(const mgpu_engine *e, const RecipItem *items, int n, std::vector<RecipGroup> &groups, std::vector<int> &order);

@@ -90,8 +90,18 @@ void finish_decided(mgpu_engine *e, Lane &ln) {
         frozen_changed(e, items[c].replica, items[c].t);
     }
     // the rows were consumed by the device's commit: nothing is left to commit "from the lane's resident rows"
-    ln.last_trial_n = 0;
-    ln.d_trial_items = nullptr;
+    ln.forget_trial();
+}
+
+bool one_record_per_replica(Lane &ln, int n_replicas, const int *replica, int n) {
+    if ((int)ln.mark.size() != n_replicas) ln.mark.assign(n_replicas, -1);
+    bool twice = false;
+    for (int c = 0; c < n; ++c) {
+        twice = twice || ln.mark[replica[c]] == -3;
+        ln.mark[replica[c]] = -3;
+    }
+    for (int c = 0; c < n; ++c) ln.mark[replica[c]] = -1;      // (the marks are scratch: reset whatever the answer)
+    return !twice;
 }
 
 // The sites or the count of a frozen (framework) residue type changed on one replica: it no longer equals the reference
@@ -212,7 +222,7 @@ bool any_frozen(const mgpu_engine *e, int n, const int *t) {
 
 int upload_sites(Lane &ln, const double *sites, int n_rows, int site_stride) {
     if (!sites || n_rows == 0) return MGPU_OK;
-    ln.last_trial_n = 0;
+    ln.forget_trial();
     const size_t bytes = (size_t)n_rows * site_stride * 3 * sizeof(double);
     int rc = ln.d_sites.reserve(bytes);
     if (rc) return rc;
@@ -573,7 +583,7 @@ int mgpu_engine_create(mgpu_engine **out, int device, int n_replicas, int n_res,
     HIP_TRY_E(hipSetDevice(device));
     for (auto &ln : e->lanes) HIP_TRY_E(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
     const size_t ncap = tp.n_cap_atoms, R = n_replicas;
-    const int ktot = e->kmax[0] + e->kmax[1] + e->kmax[2] + 3;
+    const int ktot = recip_ktot(e);
     HIP_TRY_E(hipMalloc(&e->d_pos, R * 3 * ncap * sizeof(double)));
     HIP_TRY_E(hipMemset(e->d_pos, 0, R * 3 * ncap * sizeof(double)));
     HIP_TRY_E(hipMalloc(&e->d_nmol, R * n_res * sizeof(int)));
@@ -941,10 +951,7 @@ static int reservoir_tables(mgpu_engine *e) {
     e->chain.topo_stale = true;
     // device-built rows carry the reservoir pick from now on: rows built before cannot be committed
     for (Lane &ln : e->lanes) {
-        ln.last_trial_n = 0;
-        ln.d_trial_items = nullptr;
-        ln.h_trial_items = nullptr;
-        ln.trial_alt = false;
+        ln.forget_trial();
     }
     return MGPU_OK;
 }

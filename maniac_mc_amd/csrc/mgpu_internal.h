@@ -2,6 +2,8 @@
 #ifndef MGPU_INTERNAL_H
 #define MGPU_INTERNAL_H
 
+#include <algorithm>
+#include <cstddef>
 #include <string>
 #include <vector>
 
@@ -39,6 +41,48 @@ static_assert(sizeof(CoulRow) == 48, "CoulRow must be three 16-byte LDS reads");
 constexpr int kCoulRowVec = sizeof(CoulRow) / 16;  // 16-byte LDS reads per row
 int build_coulomb_table(double alpha, double s_max, std::vector<CoulRow> &rows, int *idx_base);
 double coulomb_table_eval_host(const std::vector<CoulRow> &rows, int idx_base, double alpha, double s);
+
+// ---- Dynamic LDS of the reciprocal kernels: the one home of this arithmetic (plain integers: the host tests compile it
+// without a device).  The layouts these sizes describe are the kernels' (mgpu_kernels_recip.h); a size that disagrees with
+// them is an out-of-bounds LDS access, so nothing outside this block recomputes one.
+constexpr size_t kLdsDefaultMax = 64 * 1024;       // dynamic LDS a kernel gets without opting in to more
+constexpr size_t kLdsPhase = 16, kLdsRowRec = 16;  // a phase-table entry (double2), a row record of the matrix-unit form (int4)
+inline int recip_ktot(const int kmax[3]) { return kmax[0] + kmax[1] + kmax[2] + 3; }      // 1-D phases per site and state
+// recip_kernel / recip_rows_kernel: the 1-D phase tables of both states of n1 sites and the sites' charges ...
+inline size_t recip_lds_bytes(int ktot, int n1) { return (size_t)2 * n1 * ktot * kLdsPhase + (size_t)n1 * sizeof(double); }
+// ... and, row form, the XY table: every row of every site-state
+inline size_t recip_rows_lds_bytes(int ktot, int n_rrows, int n1) {
+    return recip_lds_bytes(ktot, n1) + (size_t)n_rrows * (2 * n1 * kLdsPhase);
+}
+// recip_rows_wide_kernel (and the WIDE farm windows' k role behind kFarmKFront): the 1-D tables and charges of `nss`
+// site-states, the XY table of `rpt` rows of them (vector form) or the row records (matrix-unit form)
+inline size_t recip_wide_lds_bytes(int ktot, int n_rrows, size_t nss, int rpt, bool mfma) {
+    return nss * ktot * kLdsPhase + (size_t)rpt * nss * kLdsPhase + nss * sizeof(double) + (mfma ? (size_t)n_rrows * kLdsRowRec : 0);
+}
+constexpr size_t kRecipTileBytes = 48 * 1024;       // per-k form: both table sets of a tile of sites
+constexpr size_t kRecipRowsLdsMax = 40 * 1024;      // row form: while everything fits this
+constexpr size_t kRecipWideTableBytes = 40 * 1024, kRecipWideLdsBytes = 60 * 1024;   // (dynamic LDS: 64 KiB with the static part)
+// sites per LDS tile of the per-k form: as many as fit kRecipTileBytes, at least one
+inline int recip_tile_sites(int ktot, int n1_max) {
+    return std::max(1, std::min(n1_max, (int)(kRecipTileBytes / recip_lds_bytes(ktot, 1))));
+}
+// vector wide form: rows per XY tile (0: tables beyond kRecipWideTableBytes, or fewer than eight rows per tile)
+inline int recip_wide_rows_per_tile(int ktot, int n_rrows, int n1_max) {
+    const size_t nss = (size_t)2 * n1_max, tables = recip_wide_lds_bytes(ktot, 0, nss, 0, false);
+    if (tables > kRecipWideTableBytes) return 0;
+    const int rpt = (int)((kRecipWideLdsBytes - tables) / (nss * kLdsPhase));
+    return rpt >= 8 ? std::min(rpt, n_rrows) : 0;
+}
+// matrix-unit wide form: site-states per tile, a multiple of four (0: not even four fit) -- the fewest tiles of at most
+// kRecipWideLdsBytes each, balanced
+inline int recip_wide_mfma_tile(int ktot, int n_rrows, int n1_max) {
+    const size_t nss = ((size_t)2 * n1_max + 3) & ~(size_t)3;
+    const size_t per_ss = recip_wide_lds_bytes(ktot, 0, 1, 0, false), fixed = recip_wide_lds_bytes(ktot, n_rrows, 0, 0, true);
+    if (fixed + 4 * per_ss > kRecipWideLdsBytes) return 0;
+    const size_t fit = ((kRecipWideLdsBytes - fixed) / per_ss) & ~(size_t)3;
+    const size_t n_tiles = (nss + fit - 1) / fit;
+    return (int)((((nss + n_tiles - 1) / n_tiles) + 3) & ~(size_t)3);
+}
 
 }  // namespace mgpu
 

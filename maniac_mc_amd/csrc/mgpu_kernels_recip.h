@@ -772,7 +772,7 @@ __global__ __launch_bounds__(kBlock, COMMIT ? MGPU_COMMIT_MINWAVES : MGPU_RECIP_
 // products and three reads for ONE in the per-k form (recip_kernel) that such molecules took before: measured round 5,
 // 1024 items of the 24-site adsorbate at Nk = 8936, 635 us per launch there (profiles/r05/recip_many_sites.txt).
 // Molecules whose phase tables alone exceed the budget (hundreds of sites) keep the per-k form with its site tiles.
-// Dynamic LDS: tab [nss][ktot] | xy [rows_per_tile][nss] | signed charges [nss].
+// Dynamic LDS: tab [nss][ktot] | xy [rows_per_tile][nss] | signed charges [nss] (its size: recip_wide_lds_bytes, mgpu_internal.h).
 // ------------------------------------------------------------------------------------------
 // MFMA: per item the row form's sums ARE four real matrix products [kz][site-state] x [site-state][row] (sac, sbd, sad, sbc
 // of the pass above), so each wave takes tiles of 16 rows x 16 kz through v_mfma_f64_16x16x4_f64, twelve steps of four

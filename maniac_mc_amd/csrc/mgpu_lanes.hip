@@ -114,8 +114,7 @@ int mgpu_recip_form(const mgpu_engine *e, int n1_max, int kind, int out[4]) {
     if (kind != MGPU_RECIP_TRIAL && kind != MGPU_RECIP_COMMIT) return set_error(MGPU_ERR_INVALID_ARG, "mgpu_recip_form: unknown kind");
     // (a trial and a commit take the same form: launch_recip decides by n1_max alone, so that they share the sum order)
     const RecipPlan p = recip_plan(e, n1_max, true);
-    const size_t lds = p.by_rows ? recip_rows_lds_bytes(e, n1_max) : recip_lds_bytes(e, p.tile);
-    if (lds > 64 * 1024) return set_error(MGPU_ERR_CAPACITY, "mgpu_recip_form: kmax too large for the LDS phase tables");
+    if (p.lds > kLdsDefaultMax) return set_error(MGPU_ERR_CAPACITY, "mgpu_recip_form: kmax too large for the LDS phase tables");
     out[0] = p.form;
     out[2] = 0;
     out[3] = 1;
@@ -212,15 +211,9 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
     if (decide) {
         if (!(decide->temperature > 0.0)) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: temperature must be positive");
         // one candidate per replica: the workgroups commit independently
-        if ((int)ln.mark.size() != e->n_replicas) ln.mark.assign(e->n_replicas, -1);
-        bool twice = false;
-        for (int c = 0; c < n; ++c) {
+        for (int c = 0; c < n; ++c)
             if (replica[c] < 0 || replica[c] >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: replica out of range");
-            twice = twice || ln.mark[replica[c]] == -3;
-            ln.mark[replica[c]] = -3;
-        }
-        for (int c = 0; c < n; ++c) ln.mark[replica[c]] = -1;
-        if (twice) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: more than one candidate for a replica");
+        if (!one_record_per_replica(ln, e->n_replicas, replica, n)) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: more than one candidate for a replica");
     }
     ln.decided_wait_n = 0;
     ln.dirty = true;
@@ -237,10 +230,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
     }
     // from here on the rows of the lane's previous trial are gone (the staging block below may be regrown and is
     // overwritten): a failed submit must not leave them committable "from the lane's resident rows"
-    ln.last_trial_n = 0;
-    ln.d_trial_items = nullptr;
-    ln.h_trial_items = nullptr;
-    ln.trial_alt = false;
+    ln.forget_trial();
     const size_t site_bytes = (size_t)n * site_stride * 3 * sizeof(double);
     const size_t pit_cap = 2 * (size_t)n * sizeof(PairItem), rit_bytes = (size_t)n * sizeof(RecipItem);
     const size_t iit_cap = (size_t)n * sizeof(PairItem);       // intra items
@@ -561,14 +551,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
         // candidate per replica (their stores would collide), molecules of at most 64 sites (commit_switch_kernel), and a
         // lane whose last commit accepted at least kSwitchMinShare of its candidates.
         bool alt = !e->commit_pass && ln.accept_share >= kSwitchMinShare && ln.recip_groups.size() == 1 && recip_by_rows(e, n1_max) && n1_max <= 64 && n <= 32 * kAcceptWords;
-        if (alt) {
-            if ((int)ln.mark.size() != e->n_replicas) ln.mark.assign(e->n_replicas, -1);
-            for (int c = 0; c < n; ++c) {
-                alt = alt && ln.mark[replica[c]] != -3;
-                ln.mark[replica[c]] = -3;
-            }
-            for (int c = 0; c < n; ++c) ln.mark[replica[c]] = -1;
-        }
+        alt = alt && one_record_per_replica(ln, e->n_replicas, replica, n);
         if (alt && (rc = alt_reserve(e))) return rc;
         if (alt) {
             ln.trial_stamp = ++e->trial_stamps;
@@ -820,9 +803,7 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         } else if ((rc = launch_recip(e, ln, ln.d_trial_items, n, ln.trial_n1_max, site_stride, true, e->d_A, nullptr, nullptr, &bits)))
             return rc;
         // applied once: a second commit_submit(sites = NULL) must not find these rows "resident" again
-        ln.last_trial_n = 0;
-        ln.d_trial_items = nullptr;
-        ln.h_trial_items = nullptr;
+        ln.forget_trial();
     } else {
         recip_groups(e, items, n_items, ln.recip_groups, ln.recip_order);
         if (!ln.recip_order.empty()) {
@@ -832,7 +813,7 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         if ((rc = ln.d_items2.reserve((size_t)n_items * sizeof(RecipItem)))) return rc;
         HIP_TRY(hipMemcpyAsync(ln.d_items2.p, items, (size_t)n_items * sizeof(RecipItem), hipMemcpyHostToDevice, ln.stream));
         if (any_sites && sites) {
-            ln.last_trial_n = 0;
+            ln.forget_trial();      // (their rows are about to be overwritten)
             std::memcpy(ln.h_commit.p, sites, site_bytes);
             if (any_frozen(e, n, t)) permute_frozen_rows(e, (double *)ln.h_commit.p, n, site_stride, t);
             if ((rc = ln.d_sites.reserve(site_bytes))) return rc;
@@ -880,9 +861,7 @@ int mgpu_lane_site_buffer(mgpu_engine *e, int lane, int n_max, int site_stride, 
     Lane &ln = e->lanes[lane];
     if (ln.n_submitted != 0) return set_error(MGPU_ERR_STATE, "lane_site_buffer: the lane holds an un-waited trial");
     // a regrown block would leave the previous trial's item image dangling
-    ln.last_trial_n = 0;
-    ln.d_trial_items = nullptr;
-    ln.h_trial_items = nullptr;
+    ln.forget_trial();
     // sized for the largest trial shape the lane accepts for n_max candidates: host rows of site_stride sites, or
     // device-built rows [sites | com | offsets] with their move codes and uniform numbers, acceptance records included
     const size_t built = trial_staging_bytes(n_max, 2 * site_stride + 2) + ((size_t)n_max * sizeof(int) + 8) + (size_t)5 * n_max * sizeof(double) + 16;

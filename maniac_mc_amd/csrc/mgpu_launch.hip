@@ -36,81 +36,46 @@ int launch_pair(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, 
     hipEvent_t a = nullptr, b = nullptr;
     rc = prof_begin(e, ln, MGPU_KERNEL_PAIR, &a, &b);
     if (rc) return rc;
-#define MGPU_LAUNCH_PAIR(NS, ORD, TRI, ...)                                                                             \
-    hipExtLaunchKernelGGL((pair_sweep_kernel<NS, ORD, TRI, ##__VA_ARGS__>), dim3(grid), dim3(kPairBlock), e->coul_bytes, ln.stream, \
-                          a, b, 0, e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab,     \
-                       d_items, (const double *)ln.d_sites.p, site_stride, nsplit, n_work, d_part)
+    // the sweeps' argument list (the flat kernels take skip_frozen behind it)
+    auto launch = [&](auto kernel, int grid_k, auto... tail) {
+        hipExtLaunchKernelGGL(kernel, dim3(grid_k), dim3(kPairBlock), e->coul_bytes, ln.stream, a, b, 0, e->tp, e->bx, e->d_pos, e->d_nmol,
+                              e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, d_items, (const double *)ln.d_sites.p, site_stride,
+                              nsplit, n_work, d_part, tail...);
+    };
     // fast_fold: every atom of the replicas involved lies within one box length of the cell centre (tracked on the
     // host), so the register-site kernels may fold separations with two instructions per axis (image_r2_fast)
     const bool ff = fast_fold && !ordered && !e->bx.triclinic && e->pair_fast_fold;
-#define MGPU_PAIR_FF(NS, FU)                                                                      \
-    do {                                                                                          \
-        if (ff) MGPU_LAUNCH_PAIR(NS, false, false, FU, true);                                     \
-        else MGPU_LAUNCH_PAIR(NS, false, false, FU, false);                                       \
-    } while (0)
+    // the plane-by-plane sweep with NS register sites, fused or not, either fold
+    auto sweep = [&](auto NS, auto FU) {
+        with_bools([&](auto FW) { launch(pair_sweep_kernel<decltype(NS)::value, false, false, decltype(FU)::value, decltype(FW)::value>, grid); }, ff);
+    };
     // flat kernels: as many workgroups per CU as their registers and the LDS tables allow
-#define MGPU_LAUNCH_FLAT_1(NS, FU, FW)                                                                                  \
-    do {                                                                                                               \
-        const int nb = resident_blocks<&pair_flat_kernel<NS, FU, FW>>(ln, e->coul_bytes);                                  \
-        const int grid_f = std::max(1, std::min((n_work + kPairWaves - 1) / kPairWaves, e->n_cu * nb));               \
-        hipExtLaunchKernelGGL((pair_flat_kernel<NS, FU, FW>), dim3(grid_f), dim3(kPairBlock), e->coul_bytes, ln.stream, a, b, 0, \
-                              e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab,   \
-                              d_items, (const double *)ln.d_sites.p, site_stride, nsplit, n_work, d_part, skip_frozen ? 1 : 0); \
-    } while (0)
-#define MGPU_LAUNCH_FLAT(NS, FU)                                                                                        \
-    do {                                                                                                               \
-        if (ff) MGPU_LAUNCH_FLAT_1(NS, FU, true);                                                                      \
-        else MGPU_LAUNCH_FLAT_1(NS, FU, false);                                                                        \
-    } while (0)
+    auto flat_sweep = [&](auto NS, auto FU) {
+        with_bools([&](auto FW) {
+            constexpr auto kernel = &pair_flat_kernel<decltype(NS)::value, decltype(FU)::value, decltype(FW)::value>;
+            const int nb = resident_blocks<kernel>(ln, e->coul_bytes);
+            launch(kernel, std::max(1, std::min((n_work + kPairWaves - 1) / kPairWaves, e->n_cu * nb)), skip_frozen ? 1 : 0);
+        }, ff);
+    };
+    // (fused items have at most kMaxFusedSites sites: checked above; flat ones at most kMaxFusedSitesWide: `flat`)
     const bool flat = e->pair_flat && !ordered && !e->bx.triclinic && common_n1 >= 1 && common_n1 <= kMaxFusedSitesWide;
     if (flat && fused) {
-        switch (common_n1) {
-            case 1: MGPU_LAUNCH_FLAT(1, true); break;
-            case 2: MGPU_LAUNCH_FLAT(2, true); break;
-            default: MGPU_LAUNCH_FLAT(3, true); break;      // (fused items have at most kMaxFusedSites sites: checked above)
-        }
+        with_int<1, kMaxFusedSites>(common_n1, [&](auto NS) { flat_sweep(NS, std::true_type{}); });
     } else if (flat) {
-        switch (common_n1) {
-            case 1: MGPU_LAUNCH_FLAT(1, false); break;
-            case 2: MGPU_LAUNCH_FLAT(2, false); break;
-            case 3: MGPU_LAUNCH_FLAT(3, false); break;
-            case 4: MGPU_LAUNCH_FLAT(4, false); break;
-            default: MGPU_LAUNCH_FLAT(5, false); break;
-        }
+        with_int<1, kMaxFusedSitesWide>(common_n1, [&](auto NS) { flat_sweep(NS, std::false_type{}); });
     } else if (fused) {
-        switch (common_n1) {
-            case 1: MGPU_PAIR_FF(1, true); break;
-            case 2: MGPU_PAIR_FF(2, true); break;
-            default: MGPU_PAIR_FF(3, true); break;
-        }
+        with_int<1, kMaxFusedSites>(common_n1, [&](auto NS) { sweep(NS, std::true_type{}); });
     } else if (e->bx.triclinic) {
         // triclinic boxes, round 5: the register-site sweeps with ComputeDistance's image search (image_r2_tri_lower / the full
         // 27); a move is two single-state items (trial_submit_impl)
-        if (ordered) MGPU_LAUNCH_PAIR(0, true, true);
-        else switch (common_n1) {
-            case 1: MGPU_LAUNCH_PAIR(1, false, true); break;
-            case 2: MGPU_LAUNCH_PAIR(2, false, true); break;
-            case 3: MGPU_LAUNCH_PAIR(3, false, true); break;
-            case 4: MGPU_LAUNCH_PAIR(4, false, true); break;
-            case 5: MGPU_LAUNCH_PAIR(5, false, true); break;
-            default: MGPU_LAUNCH_PAIR(0, false, true); break;
-        }
+        if (ordered) launch(pair_sweep_kernel<0, true, true>, grid);
+        else if (!with_int<1, kMaxFusedSitesWide>(common_n1, [&](auto NS) { launch(pair_sweep_kernel<decltype(NS)::value, false, true>, grid); }))
+            launch(pair_sweep_kernel<0, false, true>, grid);
     } else if (ordered) {
-        MGPU_LAUNCH_PAIR(0, true, false);
-    } else {
-        switch (common_n1) {
-            case 1: MGPU_PAIR_FF(1, false); break;
-            case 2: MGPU_PAIR_FF(2, false); break;
-            case 3: MGPU_PAIR_FF(3, false); break;
-            case 4: MGPU_PAIR_FF(4, false); break;
-            case 5: MGPU_PAIR_FF(5, false); break;
-            default: MGPU_LAUNCH_PAIR(0, false, false); break;
-        }
+        launch(pair_sweep_kernel<0, true, false>, grid);
+    } else if (!with_int<1, kMaxFusedSitesWide>(common_n1, [&](auto NS) { sweep(NS, std::false_type{}); })) {
+        launch(pair_sweep_kernel<0, false, false>, grid);      // mixed site counts, larger molecules: the LDS-staged sweep
     }
-#undef MGPU_PAIR_FF
-#undef MGPU_LAUNCH_FLAT
-#undef MGPU_LAUNCH_FLAT_1
-#undef MGPU_LAUNCH_PAIR
     rc = prof_end(e, ln, MGPU_KERNEL_PAIR, a, b);
     if (rc) return rc;
     // (The reduction stays a separate launch: letting the last wave of an item reduce the partials needs
@@ -154,105 +119,67 @@ int launch_frozen(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items
         if (ln.d_tickets.p != before) HIP_TRY(hipMemsetAsync(ln.d_tickets.p, 0, ln.d_tickets.bytes, ln.stream));
     }
     if ((rc = prof_begin(e, ln, MGPU_KERNEL_PAIR, &a, &b))) return rc;
-#define MGPU_LAUNCH_FROZEN_1(NS, FU, FW)                                                                                \
-    do {                                                                                                               \
-        const int nb = resident_blocks<&pair_frozen_kernel<NS, FU, FW>>(ln, e->coul_bytes);                                \
-        const int grid_f = std::max(1, std::min(n_wg_units, e->n_cu * nb));                                           \
-        hipExtLaunchKernelGGL((pair_frozen_kernel<NS, FU, FW>), dim3(grid_f), dim3(kPairBlock), e->coul_bytes, ln.stream, a, b, 0, \
-                              e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab,   \
-                              d_items, (const double *)ln.d_sites.p, site_stride, n_items, t_frozen, n_chunks, chunk_atoms, d_scratch,    \
-                              (int *)ln.d_tickets.p, d_extra, (const double *)e->d_atom_q_on, (const int *)e->tp.slot_ty);     \
-    } while (0)
-#define MGPU_LAUNCH_FROZEN(NS)                                                                                          \
-    do {                                                                                                               \
-        if (fused && ff) MGPU_LAUNCH_FROZEN_1(NS, true, true);                                                         \
-        else if (fused) MGPU_LAUNCH_FROZEN_1(NS, true, false);                                                         \
-        else if (ff) MGPU_LAUNCH_FROZEN_1(NS, false, true);                                                            \
-        else MGPU_LAUNCH_FROZEN_1(NS, false, false);                                                                   \
-    } while (0)
+    auto launch = [&](auto NS, auto FU) {
+        with_bools([&](auto FW) {
+            constexpr auto kernel = &pair_frozen_kernel<decltype(NS)::value, decltype(FU)::value, decltype(FW)::value>;
+            const int nb = resident_blocks<kernel>(ln, e->coul_bytes);
+            hipExtLaunchKernelGGL(kernel, dim3(std::max(1, std::min(n_wg_units, e->n_cu * nb))), dim3(kPairBlock), e->coul_bytes, ln.stream,
+                                  a, b, 0, e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab,
+                                  d_items, (const double *)ln.d_sites.p, site_stride, n_items, t_frozen, n_chunks, chunk_atoms, d_scratch,
+                                  (int *)ln.d_tickets.p, d_extra, (const double *)e->d_atom_q_on, (const int *)e->tp.slot_ty);
+        }, ff);
+    };
     // (fused items have at most kMaxFusedSites sites: trial_submit_impl sends larger molecules' moves as two single-state items)
-#define MGPU_LAUNCH_FROZEN_SINGLE(NS)                                                                                   \
-    do {                                                                                                               \
-        if (ff) MGPU_LAUNCH_FROZEN_1(NS, false, true);                                                                 \
-        else MGPU_LAUNCH_FROZEN_1(NS, false, false);                                                                   \
-    } while (0)
     if (fused && n1 > kMaxFusedSites) return set_error(MGPU_ERR_STATE, "launch_frozen: fused items have at most three sites");
-    switch (n1) {
-        case 1: MGPU_LAUNCH_FROZEN(1); break;
-        case 2: MGPU_LAUNCH_FROZEN(2); break;
-        case 3: MGPU_LAUNCH_FROZEN(3); break;
-        case 4: MGPU_LAUNCH_FROZEN_SINGLE(4); break;
-        default: MGPU_LAUNCH_FROZEN_SINGLE(5); break;
-    }
-#undef MGPU_LAUNCH_FROZEN_SINGLE
-#undef MGPU_LAUNCH_FROZEN
-#undef MGPU_LAUNCH_FROZEN_1
+    const bool took = fused ? with_int<1, kMaxFusedSites>(n1, [&](auto NS) { launch(NS, std::true_type{}); })
+                            : with_int<1, kMaxFusedSitesWide>(n1, [&](auto NS) { launch(NS, std::false_type{}); });
+    if (!took) return set_error(MGPU_ERR_STATE, "launch_frozen: items of one to five register sites only");
     if ((rc = prof_end(e, ln, MGPU_KERNEL_PAIR, a, b))) return rc;
     HIP_TRY(hipGetLastError());
     return MGPU_OK;
 }
-size_t recip_lds_bytes(const mgpu_engine *e, int n1_max) {
-    const int ktot = e->kmax[0] + e->kmax[1] + e->kmax[2] + 3;
-    return (size_t)2 * n1_max * ktot * sizeof(double2) + (size_t)n1_max * sizeof(double);
-}
 
-// sites per LDS tile of the per-k form: as many as fit kRecipTileBytes with both table sets, at least one
-constexpr size_t kRecipTileBytes = 48 * 1024;
-int recip_tile_sites(const mgpu_engine *e, int n1_max) {
-    const size_t per_site = recip_lds_bytes(e, 1);
-    return std::max(1, std::min(n1_max, (int)(kRecipTileBytes / per_site)));
-}
-
-size_t recip_rows_lds_bytes(const mgpu_engine *e, int n1_max) {
-    return recip_lds_bytes(e, n1_max) + (size_t)e->n_rrows * (2 * n1_max * sizeof(double2));
-}
-
-// d_u_old != nullptr: also return the energy of the unchanged A(k) from the same pass (trial moves)
 // row form while its XY table fits the LDS budget (molecules of a few sites), else the per-k form
 bool recip_by_rows(const mgpu_engine *e, int n1_max) {
-    return !e->recip_force_per_k && e->n_rtasks > 0 && recip_rows_lds_bytes(e, n1_max) <= 40 * 1024;
+    return !e->recip_force_per_k && e->n_rtasks > 0 && recip_rows_lds_bytes(e, n1_max) <= kRecipRowsLdsMax;
 }
 
 // The wide row form (recip_rows_wide_kernel): the phase tables of every site-state of the largest molecule of the launch
-// in LDS, the XY table a tile of rows at a time.  Rows per tile (0: does not apply -- no row structure, tables beyond
-// kRecipWideTableBytes, fewer than eight rows per tile).
-constexpr size_t kRecipWideTableBytes = 40 * 1024, kRecipWideLdsBytes = 60 * 1024;   // (dynamic LDS: 64 KiB with the static part)
-int recip_wide_rows_per_tile(const mgpu_engine *e, int n1_max) {
+// in LDS, the XY table a tile of rows at a time.  Rows per tile (0: does not apply -- no row structure, or
+// recip_wide_rows_per_tile's reasons).
+static int wide_rows_per_tile(const mgpu_engine *e, int n1_max) {
     if (e->recip_force_per_k || e->n_rtasks <= 0 || !e->d_row_first) return 0;
-    const int ktot = e->kmax[0] + e->kmax[1] + e->kmax[2] + 3;
-    const size_t nss = (size_t)2 * n1_max;
-    const size_t tables = nss * ktot * sizeof(double2) + nss * sizeof(double);
-    if (tables > kRecipWideTableBytes) return 0;
-    const int rpt = (int)((kRecipWideLdsBytes - tables) / (nss * sizeof(double2)));
-    return rpt >= 8 ? std::min(rpt, e->n_rrows) : 0;
+    return recip_wide_rows_per_tile(recip_ktot(e), e->n_rrows, n1_max);
 }
 
 // The matrix-unit form of the wide row sweep (recip_rows_wide_kernel<..., MFMA>): only the 1-D phase tables of a TILE of
-// site-states in LDS.  Site-states per tile (a multiple of four; 0: the form does not apply): the fewest tiles of at most
-// kRecipWideLdsBytes each, balanced -- one tile for a molecule of a few dozen sites; a molecule of any size otherwise, the four
-// sums of a task carried from tile to tile.  (Measured, 1024 candidates of 128 / 300 sites: tiles of 52-72 KB 147 / 456-466 us,
-// of 100-144 KB -- one workgroup per CU, opted in with hipFuncAttributeMaxDynamicSharedMemorySize -- 148-184 / 613-623 us.)
-int recip_wide_mfma_tile(const mgpu_engine *e, int n1_max) {
+// site-states in LDS.  Site-states per tile (recip_wide_mfma_tile; 0: the form does not apply): one tile for a molecule of a
+// few dozen sites; a molecule of any size otherwise, the four sums of a task carried from tile to tile.  (Measured, 1024
+// candidates of 128 / 300 sites: tiles of 52-72 KB 147 / 456-466 us, of 100-144 KB -- one workgroup per CU, opted in with
+// hipFuncAttributeMaxDynamicSharedMemorySize -- 148-184 / 613-623 us.)
+static int wide_mfma_tile(const mgpu_engine *e, int n1_max) {
     if (e->recip_force_per_k || e->recip_no_mfma || e->n_rtasks <= 0 || !e->d_row_first || !e->rows_contiguous) return 0;
-    const int ktot = e->kmax[0] + e->kmax[1] + e->kmax[2] + 3;
-    const size_t nss = ((size_t)2 * n1_max + 3) & ~(size_t)3;
-    const size_t per_ss = (size_t)ktot * sizeof(double2) + sizeof(double), fixed = (size_t)e->n_rrows * sizeof(int4);
-    if (fixed + 4 * per_ss > kRecipWideLdsBytes) return 0;
-    const size_t fit = ((kRecipWideLdsBytes - fixed) / per_ss) & ~(size_t)3;
-    const size_t n_tiles = (nss + fit - 1) / fit;
-    return (int)((((nss + n_tiles - 1) / n_tiles) + 3) & ~(size_t)3);
+    return recip_wide_mfma_tile(recip_ktot(e), e->n_rrows, n1_max);
 }
-bool recip_wide_mfma(const mgpu_engine *e, int n1_max) { return recip_wide_mfma_tile(e, n1_max) > 0; }
 
 // The kernel launch_recip takes for molecules of up to n1_max sites.  wide_ok = false: a commit by accept mask or the deciding
 // sweep, which have the row form only.
 RecipPlan recip_plan(const mgpu_engine *e, int n1_max, bool wide_ok) {
     RecipPlan p;
+    const int ktot = recip_ktot(e);
     p.by_rows = recip_by_rows(e, n1_max);
-    p.tile = p.by_rows ? n1_max : recip_tile_sites(e, n1_max);
+    // per-k form: the molecule's sites pass through LDS a tile at a time (recip_kernel), so no molecule is too large;
+    // the tile is the most sites whose two table sets fit kRecipTileBytes (a few-site molecule: one tile)
+    p.tile = p.by_rows ? n1_max : recip_tile_sites(ktot, n1_max);
+    p.lds = p.by_rows ? recip_rows_lds_bytes(e, n1_max) : recip_lds_bytes(ktot, p.tile);
     const bool wide = wide_ok && !p.by_rows;
-    p.mfma_tile = wide ? recip_wide_mfma_tile(e, n1_max) : 0;
-    p.wide_rpt = (wide && !p.mfma_tile) ? recip_wide_rows_per_tile(e, n1_max) : 0;
+    p.mfma_tile = wide ? wide_mfma_tile(e, n1_max) : 0;
+    p.wide_rpt = (wide && !p.mfma_tile) ? wide_rows_per_tile(e, n1_max) : 0;
+    if (p.mfma_tile || p.wide_rpt) {
+        // (matrix-unit form: the site-states of one LDS tile, a multiple of four)
+        p.wide_nss = p.mfma_tile ? p.mfma_tile : 2 * n1_max;
+        p.wide_lds = recip_wide_lds_bytes(ktot, e->n_rrows, p.wide_nss, p.wide_rpt, p.mfma_tile > 0);
+    }
     const int nss = ((2 * n1_max + 3) & ~3);
     if (p.by_rows) p.form = MGPU_RECIP_FORM_ROWS;
     else if (p.mfma_tile) p.form = p.mfma_tile < nss ? MGPU_RECIP_FORM_WIDE_MFMA_TILED : MGPU_RECIP_FORM_WIDE_MFMA;
@@ -322,77 +249,56 @@ int launch_recip(mgpu_engine *e, Lane &ln, const RecipItem *d_items, int n_items
     const double *d_cand = sites_override ? sites_override : (const double *)ln.d_sites.p;
     static const AcceptBits no_bits{};
     const AcceptBits &bits = accept ? *accept : no_bits;
-    const int use_accept = accept ? 1 : 0;
     if (accept && !by_rows) return set_error(MGPU_ERR_STATE, "commit by accept mask needs the row-form kernel");
     if (decide && (!by_rows || commit || !d_u_old)) return set_error(MGPU_ERR_STATE, "device-side acceptance needs the row-form old + new k sweep");
     const DecideArgs no_decide{};
-    // per-k form: the molecule's sites pass through LDS a tile at a time (recip_kernel), so no molecule is too large;
-    // the tile is the most sites whose two table sets fit kRecipTileBytes (a few-site molecule: one tile, as before)
-    const int tile = plan.tile;
-    const size_t lds = by_rows ? recip_rows_lds_bytes(e, n1_max) : recip_lds_bytes(e, tile);
-    if (lds > 64 * 1024)
+    if (plan.lds > kLdsDefaultMax)
         return set_error(MGPU_ERR_CAPACITY, "reciprocal update: kmax too large for the LDS phase tables (" +
-                                                std::to_string(lds) + " B > 64 KiB for one site)");
+                                                std::to_string(plan.lds) + " B > 64 KiB for one site)");
     hipEvent_t a = nullptr, b = nullptr;
     const int slot = commit ? MGPU_KERNEL_COMMIT : MGPU_KERNEL_RECIP;
     int rc = prof_begin(e, ln, slot, &a, &b);
     if (rc) return rc;
-#define MGPU_LAUNCH_RECIP(COMMIT, BOTH)                                                                              \
-    do {                                                                                                             \
-        if (by_rows)                                                                                                 \
-            hipExtLaunchKernelGGL((recip_rows_kernel<COMMIT, BOTH>), dim3(n_items), dim3(kBlock), lds, ln.stream, a, b, \
-                                  0, e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, \
-                               Ab, d_items, d_cand, site_stride, d_u, d_u_old,      \
-                                  bits, use_accept, no_decide);                                                     \
-        else                                                                                                         \
-            hipExtLaunchKernelGGL((recip_kernel<COMMIT, BOTH>), dim3(n_items), dim3(kBlock), lds, ln.stream, a, b, 0,   \
-                                  e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_kpack, e->d_kslot, e->d_kw, Ab, d_items,  \
-                               d_cand, site_stride, tile, d_u, d_u_old);                         \
-    } while (0)
-    const bool wide_mfma = plan.mfma_tile > 0;
-    const int wide_rpt = plan.wide_rpt;
-    if (wide_mfma || wide_rpt > 0) {
-        // (matrix-unit form: nss_max = the site-states of one LDS tile, a multiple of four)
-        const int ktot = e->kmax[0] + e->kmax[1] + e->kmax[2] + 3, nss_max = wide_mfma ? plan.mfma_tile : 2 * n1_max;
-        const size_t lds_w = (size_t)nss_max * ktot * sizeof(double2) + (size_t)wide_rpt * nss_max * sizeof(double2) + (size_t)nss_max * sizeof(double) +
-                             (wide_mfma ? (size_t)e->n_rrows * sizeof(int4) : 0);
+    // what a sweep does, as its kernels' <COMMIT, BOTH>: the new state's energy; that and the energy of the unchanged A(k) from
+    // the same pass (d_u_old, trial moves); the commit
+    auto with_pass = [&](auto &&f) {
+        if (commit) f(std::true_type{}, std::false_type{});
+        else with_bools([&](auto BOTH) { f(std::false_type{}, BOTH); }, d_u_old != nullptr);
+    };
+    // recip_rows_kernel's argument list
+    auto rows = [&](auto kernel, int use_accept, const DecideArgs &da) {
+        hipExtLaunchKernelGGL(kernel, dim3(n_items), dim3(kBlock), plan.lds, ln.stream, a, b, 0, e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q,
+                              e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, Ab, d_items, d_cand, site_stride, d_u, d_u_old, bits,
+                              use_accept, da);
+    };
+    if (plan.wide_lds) {
         // more than one tile of site-states: the tasks' four sums travel through a per-lane block [item][task][4]
         double *tile_sums = nullptr;
-        if (wide_mfma && nss_max < ((2 * n1_max + 3) & ~3)) {
+        if (plan.mfma_tile && plan.wide_nss < ((2 * n1_max + 3) & ~3)) {
             if ((rc = ln.d_recip_sums.reserve((size_t)n_items * e->n_rtasks * 4 * sizeof(double)))) return rc;
             tile_sums = (double *)ln.d_recip_sums.p;
         }
-#define MGPU_LAUNCH_WIDE_1(COMMIT, BOTH, MF, TI)                                                                     \
-        do {                                                                                                         \
-            hipExtLaunchKernelGGL((recip_rows_wide_kernel<COMMIT, BOTH, MF, TI>), dim3(n_items), dim3(kBlock), lds_w, ln.stream, a, b, 0, e->tp, \
-                                  e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->d_rrows, e->d_row_first, e->n_rrows, wide_rpt, \
-                                  nss_max, Ab, d_items, d_cand, site_stride, d_u, d_u_old, tile_sums, e->n_rtasks);     \
-        } while (0)
-#define MGPU_LAUNCH_WIDE(COMMIT, BOTH, MF)                                                                           \
-        do { if (MF && tile_sums) MGPU_LAUNCH_WIDE_1(COMMIT, BOTH, MF, true); else MGPU_LAUNCH_WIDE_1(COMMIT, BOTH, MF, false); } while (0)
-        if (wide_mfma) {
-            if (commit) MGPU_LAUNCH_WIDE(true, false, true);
-            else if (d_u_old) MGPU_LAUNCH_WIDE(false, true, true);
-            else MGPU_LAUNCH_WIDE(false, false, true);
-        } else {
-            if (commit) MGPU_LAUNCH_WIDE(true, false, false);
-            else if (d_u_old) MGPU_LAUNCH_WIDE(false, true, false);
-            else MGPU_LAUNCH_WIDE(false, false, false);
-        }
-#undef MGPU_LAUNCH_WIDE
-#undef MGPU_LAUNCH_WIDE_1
-    } else if (decide)
-        hipExtLaunchKernelGGL((recip_rows_kernel<false, true, true>), dim3(n_items), dim3(kBlock), lds, ln.stream, a, b, 0, e->tp,
-                              e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, Ab,
-                              d_items, d_cand, site_stride, d_u, d_u_old, bits, 0, *decide);
-    else if (store_alt)
-        hipExtLaunchKernelGGL((recip_rows_kernel<false, true, false, 1>), dim3(n_items), dim3(kBlock), lds, ln.stream, a, b, 0, e->tp,
-                              e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, Ab,
-                              d_items, d_cand, site_stride, d_u, d_u_old, bits, 0, no_decide);
-    else if (commit) MGPU_LAUNCH_RECIP(true, false);
-    else if (d_u_old) MGPU_LAUNCH_RECIP(false, true);
-    else MGPU_LAUNCH_RECIP(false, false);
-#undef MGPU_LAUNCH_RECIP
+        with_pass([&](auto COMMIT, auto BOTH) {
+            with_bools([&](auto MFMA, auto TILED) {
+                hipExtLaunchKernelGGL((recip_rows_wide_kernel<decltype(COMMIT)::value, decltype(BOTH)::value, decltype(MFMA)::value, decltype(TILED)::value>),
+                                      dim3(n_items), dim3(kBlock), plan.wide_lds, ln.stream, a, b, 0, e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q,
+                                      e->d_trj, e->d_tw, e->d_rrows, e->d_row_first, e->n_rrows, plan.wide_rpt, plan.wide_nss, Ab, d_items, d_cand,
+                                      site_stride, d_u, d_u_old, tile_sums, e->n_rtasks);
+            }, plan.mfma_tile > 0, tile_sums != nullptr);
+        });
+    } else if (decide) {
+        rows(recip_rows_kernel<false, true, true>, 0, *decide);
+    } else if (store_alt) {
+        rows(recip_rows_kernel<false, true, false, 1>, 0, no_decide);
+    } else if (by_rows) {
+        with_pass([&](auto COMMIT, auto BOTH) { rows(recip_rows_kernel<decltype(COMMIT)::value, decltype(BOTH)::value>, accept ? 1 : 0, no_decide); });
+    } else {
+        with_pass([&](auto COMMIT, auto BOTH) {
+            hipExtLaunchKernelGGL((recip_kernel<decltype(COMMIT)::value, decltype(BOTH)::value>), dim3(n_items), dim3(kBlock), plan.lds, ln.stream, a,
+                                  b, 0, e->tp, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_kpack, e->d_kslot, e->d_kw, Ab, d_items, d_cand,
+                                  site_stride, plan.tile, d_u, d_u_old);
+        });
+    }
     rc = prof_end(e, ln, slot, a, b);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());

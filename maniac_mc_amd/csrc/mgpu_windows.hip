@@ -65,6 +65,24 @@ int farm_clear_stall(mgpu_engine *e, int replica) {
     return MGPU_OK;
 }
 
+int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int n, unsigned long long seq, long long first_check,
+                 long long check_every, const char *what) {
+    long long spins = 0;
+    for (int c = 0; c < n; ++c) {
+        while (tag[c] != seq) {
+            __builtin_ia32_pause();
+            if (++spins >= first_check && (spins % check_every) == 0) {
+                // long past any window's run time: make sure the stream is still alive
+                const hipError_t q = hipStreamQuery(stream);
+                if (q == hipSuccess && tag[c] != seq) return set_error(MGPU_ERR_HIP, std::string(what) + ": the kernel finished without publishing its results");
+                if (q != hipSuccess && q != hipErrorNotReady) return set_error(MGPU_ERR_HIP, std::string(what) + ": " + hipGetErrorString(q));
+            }
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return MGPU_OK;
+}
+
 }  // namespace mgpu
 
 extern "C" {
@@ -81,9 +99,9 @@ static int chain_max_candidates(const mgpu_engine *e) {
         n1_max = std::max(n1_max, e->tp.n1[t]);
     }
     if (!recip_by_rows(e, n1_max)) return 0;
-    if (e->coul_bytes > 64 * 1024) return 0;
+    if (e->coul_bytes > kLdsDefaultMax) return 0;
     // the resolving workgroup stages every split partial of the window in LDS: 2 entries per candidate at most
-    const int by_lds = (int)((size_t)64 * 1024 / ((size_t)2 * e->pair_nsplit * sizeof(double2)));
+    const int by_lds = (int)(kLdsDefaultMax / ((size_t)2 * e->pair_nsplit * sizeof(double2)));
     return std::max(0, std::min(kChainMaxCand, by_lds));
 }
 
@@ -209,7 +227,7 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     }
     const int nsplit = e->pair_nsplit;
     const size_t lds = std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), (size_t)n_ent * nsplit * sizeof(double2));
-    if (lds > 64 * 1024) return set_error(MGPU_ERR_CAPACITY, "chain_window: the window does not fit the LDS budget");
+    if (lds > kLdsDefaultMax) return set_error(MGPU_ERR_CAPACITY, "chain_window: the window does not fit the LDS budget");
     ch.seq += 1;
     for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
     g.stamps = ch.timing ? 1 : 0;
@@ -220,36 +238,17 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     const int grid = n + (n_ent * nsplit + kPairWaves - 1) / kPairWaves;
     const bool ff = fast && e->pair_fast_fold;
     ln.dirty = true;
-    ln.last_trial_n = 0;
-    ln.d_trial_items = nullptr;
-    ln.h_trial_items = nullptr;
-#define MGPU_LAUNCH_CHAIN(FL, FW)                                                                                          \
-    hipLaunchKernelGGL((chain_window_kernel<FL, FW>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, \
-                       e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, \
-                       e->d_A, g)
-    if (e->bx.triclinic)
-        hipLaunchKernelGGL((chain_window_kernel<false, false, true>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos,
-                           e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows,
-                           e->n_rrows, e->d_A, g);
-    else if (e->pair_flat) { if (ff) MGPU_LAUNCH_CHAIN(true, true); else MGPU_LAUNCH_CHAIN(true, false); }
-    else { if (ff) MGPU_LAUNCH_CHAIN(false, true); else MGPU_LAUNCH_CHAIN(false, false); }
-#undef MGPU_LAUNCH_CHAIN
+    ln.forget_trial();
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype,
+                           e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, e->d_A, g);
+    };
+    // (the image search has no flat and no fast-fold form)
+    if (e->bx.triclinic) launch(chain_window_kernel<false, false, true>);
+    else with_bools([&](auto FLAT, auto FASTW) { launch(chain_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); }, e->pair_flat, ff);
     HIP_TRY(hipGetLastError());
     // ---- wait for the tag: the results are in host memory when it shows this window's number
-    {
-        volatile unsigned long long *tag = ch.h_tag;
-        long long spins = 0;
-        while (*tag != ch.seq) {
-            __builtin_ia32_pause();
-            if (++spins >= 20000 && (spins % 4096) == 0) {
-                // long past any window's run time: make sure the stream is still alive
-                const hipError_t q = hipStreamQuery(ln.stream);
-                if (q == hipSuccess && *tag != ch.seq) return set_error(MGPU_ERR_HIP, "chain_window: the kernel finished without publishing its results");
-                if (q != hipSuccess && q != hipErrorNotReady) return set_error(MGPU_ERR_HIP, std::string("chain_window: ") + hipGetErrorString(q));
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
+    if ((rc = wait_for_tag(ln.stream, ch.h_tag, 1, ch.seq, 20000, 4096, "chain_window"))) return rc;
     for (int c = 0; c < n; ++c) {
         std::memcpy(old_energy + 5 * (size_t)c, ch.h_out + 10 * (size_t)c, 5 * sizeof(double));
         std::memcpy(new_energy + 5 * (size_t)c, ch.h_out + 10 * (size_t)c + 5, 5 * sizeof(double));
@@ -300,18 +299,15 @@ static bool farm_type_form(const mgpu_engine *e, int t, FarmTypeForm &f) {
         return true;
     }
     if (e->bx.triclinic) return false;
-    const size_t ktot = (size_t)e->kmax[0] + e->kmax[1] + e->kmax[2] + 3;
     switch (p.form) {
         case MGPU_RECIP_FORM_ROWS:
             f.lds = kFarmKFront + recip_rows_lds_bytes(e, n1);
             return true;
-        case MGPU_RECIP_FORM_WIDE_VECTOR:                           // launch_recip's tables with nss_max = 2 n1
-            f.form = kFarmFormWideVector; f.rpt = p.wide_rpt; f.nss = 2 * n1;
-            f.lds = kFarmKFront + (size_t)f.nss * ktot * sizeof(double2) + (size_t)f.rpt * f.nss * sizeof(double2) + (size_t)f.nss * sizeof(double);
-            return true;
-        case MGPU_RECIP_FORM_WIDE_MFMA:                             // one tile of site-states
-            f.form = kFarmFormWideMfma; f.nss = p.mfma_tile;
-            f.lds = kFarmKFront + (size_t)f.nss * ktot * sizeof(double2) + (size_t)f.nss * sizeof(double) + (size_t)e->n_rrows * sizeof(int4);
+        case MGPU_RECIP_FORM_WIDE_VECTOR:                           // launch_recip's tables (2 n1 site-states)
+        case MGPU_RECIP_FORM_WIDE_MFMA:                             // ... one tile of site-states
+            f.form = p.mfma_tile ? kFarmFormWideMfma : kFarmFormWideVector;
+            f.rpt = p.wide_rpt; f.nss = p.wide_nss;
+            f.lds = kFarmKFront + p.wide_lds;
             return true;
         default:                                                    // the tiled matrix-unit form, the per-k form
             return false;
@@ -324,7 +320,7 @@ static bool farm_type_form(const mgpu_engine *e, int t, FarmTypeForm &f) {
 constexpr size_t kFarmWideStaticMax = 16 * 1024, kFarmWideLdsMax = 160 * 1024 - kFarmWideStaticMax;
 static size_t farm_wide_lds(const mgpu_engine *e) {
     size_t lds = ((e->coul_bytes + 15) & ~(size_t)15) + kFarmWidePairBytes;
-    lds = std::max(lds, (size_t)kPairWaves * (4 * e->pair_nsplit + 4) * sizeof(double));
+    lds = std::max(lds, farm_resolver_scratch_bytes(e->pair_nsplit));
     for (int t = 0; t < e->tp.n_res; ++t) {
         FarmTypeForm f;
         if (!e->frozen[t] && farm_type_form(e, t, f)) lds = std::max(lds, f.lds);      // (every type a chain may carry)
@@ -344,8 +340,8 @@ static int farm_max_chains(const mgpu_engine *e) {
         if (!farm_type_form(e, t, f)) return 0;
         wide = wide || e->tp.n1[t] > kMaxFusedSitesWide;
     }
-    if (e->coul_bytes > 64 * 1024) return 0;
-    if ((size_t)kPairWaves * (4 * e->pair_nsplit + 4) * sizeof(double) > 64 * 1024) return 0;      // the resolving waves' scratch
+    if (e->coul_bytes > kLdsDefaultMax) return 0;
+    if (farm_resolver_scratch_bytes(e->pair_nsplit) > kLdsDefaultMax) return 0;
     if (wide && farm_wide_lds(e) > kFarmWideLdsMax) return 0;
     return std::min(kFarmMaxChains, e->n_replicas);
 }
@@ -439,17 +435,12 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     FarmRec *recs = n <= kFarmInline ? g.inline_recs : fw.h_recs + (size_t)slot * fw.cap;
     bool fast = true;
     int n1_max = 1;
-    if ((int)ln.mark.size() != e->n_replicas) ln.mark.assign(e->n_replicas, -1);
-    bool twice = false;
     for (int c = 0; c < n; ++c) {
         FarmRec &r = recs[c];
         r = FarmRec{};
         const int mv = move[c];
-        // (every refusal breaks out of the loop: the replicas marked so far are unmarked below)
         if (mv < 0 || mv > 4) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: unknown move code"); break; }
         if (replica[c] < 0 || replica[c] >= e->n_replicas) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: replica out of range"); break; }
-        twice = twice || ln.mark[replica[c]] == -3;
-        ln.mark[replica[c]] = -3;
         r.replica = replica[c];
         if (mv == 0) continue;                                   // the chain does nothing this step
         if (t[c] < 0 || t[c] >= e->tp.n_res) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: residue type out of range"); break; }
@@ -489,10 +480,8 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         r.acc_u = accept_u[c];
         r.pref = accept_pref[c];
     }
-    for (int c = 0; c < n; ++c)
-        if (replica[c] >= 0 && replica[c] < e->n_replicas) ln.mark[replica[c]] = -1;
     if (rc) return rc;
-    if (twice) return set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: more than one chain record for a replica");
+    if (!one_record_per_replica(ln, e->n_replicas, replica, n)) return set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: more than one chain record for a replica");
     if (pd.counts_change && !fw.pending.empty())
         return set_error(MGPU_ERR_STATE, "farm_window_submit: a window with an insertion / deletion needs the lane's earlier windows collected "
                                          "(its molecule counts must be current)");
@@ -500,15 +489,26 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     // a chain of more than kMaxFusedSitesWide sites: the WIDE instance (its own LDS rule), else the narrow one
     const bool wide = n1_max > kMaxFusedSitesWide;
     const size_t lds = wide ? farm_wide_lds(e)
-                            : std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), (size_t)kPairWaves * (4 * nsplit + 4) * sizeof(double));
-    if (lds > (wide ? kFarmWideLdsMax : 64 * 1024)) return set_error(MGPU_ERR_CAPACITY, "farm_window_submit: the window does not fit the LDS budget");
-    if (lds > 64 * 1024) {
+                            : std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), farm_resolver_scratch_bytes(nsplit));
+    if (lds > (wide ? kFarmWideLdsMax : kLdsDefaultMax)) return set_error(MGPU_ERR_CAPACITY, "farm_window_submit: the window does not fit the LDS budget");
+    // The window kernel's families: with the image search (no flat form, no fast fold, no wide chains: farm_type_form), WIDE,
+    // narrow; within each the flags are free.  (An engine without reservoirs runs the instances without their code.)
+    auto tri_family = [](auto &&f, auto RSV) { f(farm_window_kernel<false, false, false, decltype(RSV)::value, true>); };
+    auto wide_family = [](auto &&f, auto FLAT, auto FASTW, auto RSV) {
+        f(farm_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value, true, decltype(RSV)::value>);
+    };
+    auto narrow_family = [](auto &&f, auto FLAT, auto FASTW, auto RSV) {
+        f(farm_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, decltype(RSV)::value>);
+    };
+    if (lds > kLdsDefaultMax) {
         // beyond 64 KiB of dynamic LDS a kernel opts in (gfx950: up to 160 KiB per workgroup); only the WIDE instances get here
-        const void *wide_kernels[8] = {(const void *)farm_window_kernel<false, false, true>, (const void *)farm_window_kernel<false, true, true>,
-                                       (const void *)farm_window_kernel<true, false, true>, (const void *)farm_window_kernel<true, true, true>,
-                                       (const void *)farm_window_kernel<false, false, true, true>, (const void *)farm_window_kernel<false, true, true, true>,
-                                       (const void *)farm_window_kernel<true, false, true, true>, (const void *)farm_window_kernel<true, true, true, true>};
-        for (const void *k : wide_kernels) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipError_t err = hipSuccess;
+        auto opt_in = [&](auto kernel) {
+            if (err == hipSuccess) err = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        };
+        for_all_bools([&](auto... flags) { wide_family(opt_in, flags...); }, std::integral_constant<int, 3>{});
+        if (err != hipSuccess)
+            return set_error(MGPU_ERR_HIP, std::string("hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds): ") + hipGetErrorString(err));
     }
     fw.seq += 1;
     for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
@@ -533,42 +533,16 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     const int grid = (n * wpc + kPairWaves - 1) / kPairWaves + n;
     const bool ff = fast && e->pair_fast_fold;
     ln.dirty = true;
-    ln.last_trial_n = 0;
-    ln.d_trial_items = nullptr;
-    ln.h_trial_items = nullptr;
-    ln.trial_alt = false;
+    ln.forget_trial();
     for (int c = 0; c < n; ++c) alt_forget(e, replica[c]);     // (the window's k role overwrites their other buffers)
     e->a_switched = true;
-#define MGPU_LAUNCH_FARM_RS(FL, FW, WI, RS)                                                                                \
-    do {                                                                                                                   \
-        hipLaunchKernelGGL((farm_window_kernel<FL, FW, WI, RS>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, \
-                           e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, \
-                           e->d_A, g);                                                                                     \
-    } while (0)
-#define MGPU_LAUNCH_FARM_TRI(RS)                                                                                           \
-    do {                                                                                                                   \
-        hipLaunchKernelGGL((farm_window_kernel<false, false, false, RS, true>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, \
-                           e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks,     \
-                           e->d_rrows, e->n_rrows, e->d_A, g);                                                             \
-    } while (0)
-    // (an engine without reservoirs runs the instances without their code)
-#define MGPU_LAUNCH_FARM(FL, FW, WI)                                                                                       \
-    do {                                                                                                                   \
-        if (e->rsv_any) MGPU_LAUNCH_FARM_RS(FL, FW, WI, true); else MGPU_LAUNCH_FARM_RS(FL, FW, WI, false);               \
-    } while (0)
-    if (e->bx.triclinic) {
-        // (farm_type_form admits no wide type here; the image search has no flat and no fast-fold form)
-        if (e->rsv_any) MGPU_LAUNCH_FARM_TRI(true); else MGPU_LAUNCH_FARM_TRI(false);
-    } else if (wide) {
-        if (e->pair_flat) { if (ff) MGPU_LAUNCH_FARM(true, true, true); else MGPU_LAUNCH_FARM(true, false, true); }
-        else { if (ff) MGPU_LAUNCH_FARM(false, true, true); else MGPU_LAUNCH_FARM(false, false, true); }
-    } else {
-        if (e->pair_flat) { if (ff) MGPU_LAUNCH_FARM(true, true, false); else MGPU_LAUNCH_FARM(true, false, false); }
-        else { if (ff) MGPU_LAUNCH_FARM(false, true, false); else MGPU_LAUNCH_FARM(false, false, false); }
-    }
-#undef MGPU_LAUNCH_FARM
-#undef MGPU_LAUNCH_FARM_RS
-#undef MGPU_LAUNCH_FARM_TRI
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype,
+                           e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, e->d_A, g);
+    };
+    if (e->bx.triclinic) with_bools([&](auto... flags) { tri_family(launch, flags...); }, e->rsv_any);
+    else if (wide) with_bools([&](auto... flags) { wide_family(launch, flags...); }, e->pair_flat, ff, e->rsv_any);
+    else with_bools([&](auto... flags) { narrow_family(launch, flags...); }, e->pair_flat, ff, e->rsv_any);
     HIP_TRY(hipGetLastError());
     fw.pending.push_back(std::move(pd));
     e->farm.windows += 1;
@@ -589,21 +563,11 @@ int mgpu_farm_window_wait(mgpu_engine *e, int lane, double *old_energy, double *
     const Lane::FarmWindow::Pending &pd = fw.pending.front();
     const int n = pd.n;
     const double *out = fw.h_out + (size_t)pd.slot * fw.cap * kFarmOut;
-    volatile unsigned long long *tag = fw.h_tag + (size_t)pd.slot * fw.cap;
-    long long spins = 0;
-    for (int c = 0; c < n; ++c) {
-        while (tag[c] != pd.seq) {
-            __builtin_ia32_pause();
-            if (++spins >= 200000 && (spins % 65536) == 0) {
-                // long past any window's run time: make sure the stream is still alive
-                const hipError_t q = hipStreamQuery(ln.stream);
-                // (either way the window is lost: it leaves the queue, so that the lane is not left waiting for it)
-                if (q == hipSuccess && tag[c] != pd.seq) { fw.pending.pop_front(); return set_error(MGPU_ERR_HIP, "farm_window_wait: the kernel finished without publishing its results"); }
-                if (q != hipSuccess && q != hipErrorNotReady) { fw.pending.pop_front(); return set_error(MGPU_ERR_HIP, std::string("farm_window_wait: ") + hipGetErrorString(q)); }
-            }
-        }
+    // (a window lost either way leaves the queue, so that the lane is not left waiting for it)
+    if ((rc = wait_for_tag(ln.stream, fw.h_tag + (size_t)pd.slot * fw.cap, n, pd.seq, 200000, 65536, "farm_window_wait"))) {
+        fw.pending.pop_front();
+        return rc;
     }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
     for (int c = 0; c < n; ++c) {
         const double *o = out + (size_t)kFarmOut * c;
         std::memcpy(old_energy + 5 * (size_t)c, o, 5 * sizeof(double));
