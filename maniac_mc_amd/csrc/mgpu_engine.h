@@ -94,8 +94,8 @@ struct Lane {
     int last_trial_n = 0, last_trial_stride = 0;   // shape of the site rows still resident in d_sites
     bool last_trial_built = false;                 // ... built on the device (rows carry the candidates' frames)
     int last_trial_frame = 0;                      // site index of the frame inside such a row
-    int n_pair_items = 0, n_partials = 0;   // reduced pair-energy entries of the trial in flight (2 per fused item + 1 per single) and its split partials
-    int n_fused = 0;                      // fused (old + new) items of the trial in flight, all site-count classes together
+    int n_pair_items = 0;                 // reduced pair-energy entries of the trial in flight (2 per fused item + 1 per single)
+    TrialResult result{};                 // layout of its result block in d_out / h_out (mgpu_internal.h)
     // reduced pair-energy entry i sums `n_split` partials starting at double ent_off[i] of the result block, ent_stride[i]
     // doubles apart (a fused item's partials are laid out [split][state], a single item's [split])
     std::vector<int> ent_off, ent_stride, ent_ns;     // ... ent_ns[i] of them
@@ -140,7 +140,6 @@ struct Lane {
     // with the energies; the engine's host mirrors (counts, range flags) follow when the lane is next synchronised
     int decided_n = 0;                        // candidates of such a trial not yet folded into the mirrors (0 = none)
     int decided_wait_n = 0;                   // ... whose outcomes the caller has not collected yet (mgpu_trial_decide_wait)
-    size_t decided_at = 0;                    // byte offset of the flags in h_out
     hipEvent_t commit_staged_ev = nullptr;                    // recorded behind the H2D copies that read h_commit
     bool commit_staged = false;
     // Farm windows (mgpu_farm_window_submit / _wait): up to kFarmDepth windows of this lane in flight.  The host-side blocks
@@ -383,6 +382,31 @@ bool sites_in_range(const mgpu_engine *e, const double *sites, int n_sites);
 bool replica_in_range(const mgpu_engine *e, int replica);
 // (replica, t) has a reservoir (mgpu_replica_set_reservoir): its insertions copy reservoir molecules, not slot 0's frame
 inline bool has_reservoir(const mgpu_engine *e, size_t idx) { return !e->rsv_ptr.empty() && e->rsv_ptr[idx] != nullptr; }
+// Admission of device-built candidate c (kind k, move code mv; idx = replica * n_res + type) to a batched trial or a farm window:
+// MGPU_OK, or the refusal's code with its text ("<who>: ... <noun> c") in `msg`.  `checks` picks the refusals to test, in this
+// order -- a farm window tests its molecule pick between the frames and the insertion, so it asks twice.  kAdmitRange: a built
+// candidate's centre lies in the cell (ApplyPBC / uniform insertion), so with tight frames its sites are within the fast fold's
+// range -- `ok` reports that, and `fast` is lowered with it.
+enum { kAdmitFrames = 1, kAdmitMove = 2, kAdmitInsertion = 4, kAdmitRange = 8, kAdmitAll = 15 };
+inline int admit_built(const mgpu_engine *e, size_t idx, int k, int mv, int checks, const char *who, const char *noun, int c,
+                       std::string &msg, char &ok, bool &fast) {
+    if ((checks & kAdmitFrames) && (!e->d_com || !e->frames_ok[idx])) {
+        msg = std::string(who) + ": no molecule frames for " + noun + " " + std::to_string(c) + " (mgpu_replica_set_frames)";
+        return MGPU_ERR_STATE;
+    }
+    if ((checks & kAdmitMove) && (mv < 1 || mv > 4 || (k == MGPU_MOVE) != (mv <= 2) || (k == MGPU_CREATION) != (mv == 3))) {
+        msg = std::string(who) + ": move code does not match the candidate kind";
+        return MGPU_ERR_INVALID_ARG;
+    }
+    // the insertion copies slot 0's frame whatever the count (create_molecule.f90:196-200), which a deletion leaves in place:
+    // there must be one (a type with a reservoir copies a reservoir molecule instead)
+    if ((checks & kAdmitInsertion) && k == MGPU_CREATION && !e->frames_held[idx] && !has_reservoir(e, idx)) {
+        msg = std::string(who) + ": an insertion copies the geometry of molecule 1 of its type, and this type has never held one on this replica";
+        return MGPU_ERR_STATE;
+    }
+    if ((checks & kAdmitRange) && k != MGPU_DELETION) { ok = e->frames_tight[idx]; fast = fast && ok; }
+    return MGPU_OK;
+}
 int engine_nsplit(const mgpu_engine *e);
 void permute_frozen_rows(const mgpu_engine *e, double *rows, int n_rows, int site_stride, const int *t);
 bool any_frozen(const mgpu_engine *e, int n, const int *t);
@@ -407,6 +431,14 @@ int launch_pair(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, 
 int frozen_chunk_atoms(const mgpu_engine *e, int n_atoms);
 int launch_frozen(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, int n1, int site_stride, bool fused, bool fast_fold,
                   int t_frozen, double2 *d_scratch, double2 *d_extra);
+// the lane blocks of a batched trial with the engine's record sizes (the arithmetic: mgpu_internal.h)
+static_assert((3 * sizeof(PairItem) + sizeof(RecipItem)) % 8 == 0, "the items end 8-byte aligned: TrialStaging::moves is their end");
+inline TrialStaging trial_staging(int n, int site_stride, bool built, bool reservoir_pick, bool decide) {
+    return trial_staging<sizeof(PairItem), sizeof(RecipItem), sizeof(DecideItem)>(n, site_stride, built, reservoir_pick, decide);
+}
+inline size_t lane_site_buffer_bytes(int n_max, int site_stride) {
+    return lane_site_buffer_bytes<sizeof(PairItem), sizeof(RecipItem), sizeof(DecideItem)>(n_max, site_stride);
+}
 // the engine's dynamic-LDS sizes (the arithmetic: mgpu_internal.h)
 static_assert(sizeof(double2) == kLdsPhase && sizeof(int4) == kLdsRowRec, "mgpu_internal.h sizes the LDS tables with these");
 inline int recip_ktot(const mgpu_engine *e) { return recip_ktot(e->kmax); }

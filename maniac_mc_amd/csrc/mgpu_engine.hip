@@ -79,7 +79,7 @@ int sync_all_lanes(mgpu_engine *e) {
 void finish_decided(mgpu_engine *e, Lane &ln) {
     const int n = ln.decided_n;
     ln.decided_n = 0;
-    const int *flags = (const int *)((const char *)ln.h_out.p + ln.decided_at);
+    const int *flags = (const int *)((const char *)ln.h_out.p + ln.result.flags_bytes());
     const RecipItem *items = ln.h_trial_items;
     for (int c = 0; c < n; ++c) {
         if (!flags[c]) continue;

@@ -84,6 +84,62 @@ inline int recip_wide_mfma_tile(int ktot, int n_rrows, int n1_max) {
     return (int)((((nss + n_tiles - 1) / n_tiles) + 3) & ~(size_t)3);
 }
 
+// ---- The two blocks of a batched trial on a lane (mgpu_lanes.hip): the one home of their layouts, plain integers as above.
+// trial_submit_impl, trial_wait_impl, finish_decided and the DecideItem offsets take every offset from here: a block that
+// disagrees between writer and reader gives a wrong energy, not a crash (tests/test_trial_layout.py).
+// The pinned staging block, copied to the device as it stands (byte offsets; PairB, RecipB, DecideB = sizeof PairItem, RecipItem,
+// DecideItem): [site rows | 2n pair items | n k items | n intra items | move codes (n ints) | 5n uniforms | n decide items].
+// Host rows have `site_stride` sites; a row built on the device is [sites | com | offsets (| reservoir pick)] of the largest
+// molecule (`site_stride` sites).  Move codes and uniforms: device-built trials only; decide items: the deciding form only;
+// both start 8-byte aligned.
+struct TrialStaging {
+    int row_sites, frame_at, pick_at;   // sites per row; built rows: site index of the frame (com) and of the reservoir pick (0: none)
+    size_t sites, pair_items, k_items, intra_items, moves, uniforms, decide_items, total;
+};
+template <size_t PairB, size_t RecipB, size_t DecideB>
+inline TrialStaging trial_staging(int n, int site_stride, bool built, bool reservoir_pick, bool decide) {
+    const auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+    TrialStaging s{};
+    s.row_sites = built ? 2 * site_stride + 1 + (reservoir_pick ? 1 : 0) : site_stride;
+    s.frame_at = built ? site_stride : 0;
+    s.pick_at = built && reservoir_pick ? 2 * site_stride + 1 : 0;
+    s.pair_items = (size_t)n * s.row_sites * 3 * sizeof(double);
+    s.k_items = s.pair_items + 2 * (size_t)n * PairB;
+    s.intra_items = s.k_items + (size_t)n * RecipB;
+    s.moves = up8(s.intra_items + (size_t)n * PairB);
+    s.uniforms = s.moves + up8((size_t)n * sizeof(int));
+    s.decide_items = up8(built ? s.uniforms + (size_t)5 * n * sizeof(double) : s.moves);
+    s.total = s.decide_items + (decide ? (size_t)n * DecideB : 0);
+    return s;
+}
+// What mgpu_lane_site_buffer reserves for n_max candidates of at most site_stride sites: the larger of the two shapes the lane
+// is promised for, host rows and device-built rows with the reservoir pick, both in the deciding form.  The margins are history
+// (16 bytes per shape; 16 more and unrounded move codes + 8 for the built one): they stay because a lent block is never
+// regrown and the pinned block's growth rule starts from this value.
+template <size_t PairB, size_t RecipB, size_t DecideB>
+inline size_t lane_site_buffer_bytes(int n_max, int site_stride) {
+    const TrialStaging host = trial_staging<PairB, RecipB, DecideB>(n_max, site_stride, false, false, true);
+    const TrialStaging built = trial_staging<PairB, RecipB, DecideB>(n_max, site_stride, true, true, true);
+    return std::max(host.total + 16, built.total + 32 + (size_t)n_max * sizeof(int) + 8 - (built.uniforms - built.moves));
+}
+// The result block, copied out once (offsets in doubles): [split partials of the pair sweep, 2 n_partials | u_old n | u_new n |
+// intra n | extra 2 n_pair (the framework part of every pair entry, pair_frozen_kernel; only where some segment has one) |
+// accept flags, n ints (deciding form only)]
+struct TrialResult {
+    size_t partials, u_old, u_new, intra, extra, flags, total;
+    size_t flags_bytes() const { return flags * sizeof(double); }
+};
+inline TrialResult trial_result(int n, int n_partials, int n_pair, bool frozen_extra, bool decide) {
+    TrialResult r{};
+    r.u_old = 2 * (size_t)n_partials;
+    r.u_new = r.u_old + n;
+    r.intra = r.u_new + n;
+    r.extra = r.intra + n;
+    r.flags = r.extra + (frozen_extra ? 2 * (size_t)n_pair : 0);
+    r.total = r.flags + (decide ? ((size_t)n + 1) / 2 : 0);
+    return r;
+}
+
 }  // namespace mgpu
 
 #endif

@@ -18,6 +18,25 @@ static int frozen_batch_type(const mgpu_engine *e) {
 
 // ---- batched candidates ----------------------------------------------------------------------
 
+// The items of mgpu_pair_energy_candidates / mgpu_intra_energy_candidates: candidate c is the resident molecule m[c] or row c
+// of `sites`.  `who` heads the null-sites error.
+static int candidate_pair_items(const mgpu_engine *e, int n, const int *replica, const int *t, const int *m, const int *use_resident,
+                                const double *sites, int site_stride, const char *who, std::vector<PairItem> &items, bool &any_sites) {
+    items.resize(n);
+    any_sites = false;
+    for (int c = 0; c < n; ++c) {
+        const bool res = use_resident && use_resident[c];
+        if (int rc = check_candidate(e, c, replica[c], t[c], m[c], res)) return rc;
+        if (!res) {
+            any_sites = true;
+            if (e->tp.n1[t[c]] > site_stride) return set_error(MGPU_ERR_INVALID_ARG, "site_stride smaller than atoms_in_res");
+        }
+        items[c] = PairItem{replica[c], t[c], m[c], res ? -1 : c, 0};
+    }
+    if (any_sites && !sites) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": sites is null");
+    return MGPU_OK;
+}
+
 int mgpu_pair_energy_candidates(mgpu_engine *e, int n, const int *replica, const int *t, const int *m,
                                 const int *use_resident, const double *sites, int site_stride, double *e_nc,
                                 double *e_c) {
@@ -27,18 +46,9 @@ int mgpu_pair_energy_candidates(mgpu_engine *e, int n, const int *replica, const
     int rc = use_device(e);
     if (rc) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    std::vector<PairItem> items(n);
-    bool any_sites = false;
-    for (int c = 0; c < n; ++c) {
-        const bool res = use_resident && use_resident[c];
-        if ((rc = check_candidate(e, c, replica[c], t[c], m[c], res))) return rc;
-        if (!res) {
-            any_sites = true;
-            if (e->tp.n1[t[c]] > site_stride) return set_error(MGPU_ERR_INVALID_ARG, "site_stride smaller than atoms_in_res");
-        }
-        items[c] = PairItem{replica[c], t[c], m[c], res ? -1 : c, 0};
-    }
-    if (any_sites && !sites) return set_error(MGPU_ERR_INVALID_ARG, "pair_energy_candidates: sites is null");
+    std::vector<PairItem> items;
+    bool any_sites;
+    if ((rc = candidate_pair_items(e, n, replica, t, m, use_resident, sites, site_stride, "pair_energy_candidates", items, any_sites))) return rc;
     if ((rc = e->d_items.reserve(n * sizeof(PairItem)))) return rc;
     if ((rc = e->d_out.reserve((size_t)2 * n * sizeof(double)))) return rc;
     if ((rc = e->h_out.reserve((size_t)2 * n * sizeof(double)))) return rc;
@@ -152,18 +162,9 @@ int mgpu_intra_energy_candidates(mgpu_engine *e, int n, const int *replica, cons
     int rc = use_device(e);
     if (rc) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    std::vector<PairItem> items(n);
-    bool any_sites = false;
-    for (int c = 0; c < n; ++c) {
-        const bool res = use_resident && use_resident[c];
-        if ((rc = check_candidate(e, c, replica[c], t[c], m[c], res))) return rc;
-        if (!res) {
-            any_sites = true;
-            if (e->tp.n1[t[c]] > site_stride) return set_error(MGPU_ERR_INVALID_ARG, "site_stride smaller than atoms_in_res");
-        }
-        items[c] = PairItem{replica[c], t[c], m[c], res ? -1 : c, 0};
-    }
-    if (any_sites && !sites) return set_error(MGPU_ERR_INVALID_ARG, "intra_energy_candidates: sites is null");
+    std::vector<PairItem> items;
+    bool any_sites;
+    if ((rc = candidate_pair_items(e, n, replica, t, m, use_resident, sites, site_stride, "intra_energy_candidates", items, any_sites))) return rc;
     if ((rc = e->d_items.reserve(n * sizeof(PairItem)))) return rc;
     if ((rc = e->d_out.reserve((size_t)n * sizeof(double)))) return rc;
     if ((rc = e->h_out.reserve((size_t)n * sizeof(double)))) return rc;
@@ -183,9 +184,8 @@ int mgpu_intra_energy_candidates(mgpu_engine *e, int n, const int *replica, cons
 //   MOVE      pair(resident) | pair(sites)          recip(A) | recip(A + new - old)
 //   CREATION  --             | pair(sites), intra   recip(A) | recip(A + new)         (m ignored)
 //   DELETION  pair(resident), intra | --            recip(A) | recip(A - old)
-// One pass over k per candidate yields both reciprocal energies.  Device output rows (doubles):
-//   lj[n_pair] c[n_pair] u_old[n] u_new[n] intra[n]; the lane remembers where each candidate's
-//   pair items are.
+// One pass over k per candidate yields both reciprocal energies.  The staging block and the result block: TrialStaging,
+// TrialResult (mgpu_internal.h); the lane remembers where each candidate's pair entries are.
 // build != nullptr: the candidate rows are built on the device (trial_build_kernel) from the molecule frames, the move
 // codes (1 translation, 2 rotation, 3 creation, 4 deletion) and five uniform numbers per candidate; `sites` is null and
 // site_stride is ignored (a row is [sites (n1_max) | com | offsets (n1_max)])
@@ -203,118 +203,88 @@ struct TrialDecide {
 // the accepted share of a lane's commits above which its trials store A + delta for a commit by switching (Lane::accept_share)
 constexpr double kSwitchMinShare = 0.5;
 
-static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica, const int *t, const int *m,
-                             const int *kind, const double *sites, int site_stride, const TrialBuild *build = nullptr,
-                             const TrialDecide *decide = nullptr) {
-    if (ln.n_submitted != 0) return set_error(MGPU_ERR_STATE, "trial_submit: the lane still holds an un-waited trial");
-    int rc;
-    if (decide) {
-        if (!(decide->temperature > 0.0)) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: temperature must be positive");
-        // one candidate per replica: the workgroups commit independently
-        for (int c = 0; c < n; ++c)
-            if (replica[c] < 0 || replica[c] >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: replica out of range");
-        if (!one_record_per_replica(ln, e->n_replicas, replica, n)) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: more than one candidate for a replica");
-    }
-    ln.decided_wait_n = 0;
-    ln.dirty = true;
-    ln.last_trial_built = false;
-    int frame_at = 0;
-    if (build) {
-        int n1_all = 1;
-        for (int c = 0; c < n; ++c) {
-            if (t[c] < 0 || t[c] >= e->tp.n_res) return set_error(MGPU_ERR_INVALID_ARG, "trial_submit: residue type out of range");
-            n1_all = std::max(n1_all, e->tp.n1[t[c]]);
-        }
-        frame_at = n1_all;
-        site_stride = 2 * n1_all + 1 + (e->rsv_any ? 1 : 0);     // (+ the reservoir pick, reservoir_row_pick)
-    }
-    // from here on the rows of the lane's previous trial are gone (the staging block below may be regrown and is
-    // overwritten): a failed submit must not leave them committable "from the lane's resident rows"
-    ln.forget_trial();
-    const size_t site_bytes = (size_t)n * site_stride * 3 * sizeof(double);
-    const size_t pit_cap = 2 * (size_t)n * sizeof(PairItem), rit_bytes = (size_t)n * sizeof(RecipItem);
-    const size_t iit_cap = (size_t)n * sizeof(PairItem);       // intra items
-    // device-built trials append [move codes (n ints) | uniforms (5 n doubles)] behind everything else, 8-byte aligned
-    const size_t build_at = (site_bytes + pit_cap + rit_bytes + iit_cap + 7) & ~(size_t)7;
-    const size_t build_mv = ((size_t)n * sizeof(int) + 7) & ~(size_t)7;
-    const size_t build_bytes = build ? build_mv + (size_t)5 * n * sizeof(double) : 0;
-    // ... and the deciding form its DecideItems behind that
-    const size_t dec_at = (build_at + build_bytes + 7) & ~(size_t)7;
-    const size_t dec_bytes = decide ? (size_t)n * sizeof(DecideItem) : 0;
-    if (sites && sites == ln.h_in.p && site_bytes + pit_cap + rit_bytes + iit_cap > ln.h_in.bytes)
-        return set_error(MGPU_ERR_INVALID_ARG, "trial_submit: more candidates than the lane's site buffer was sized for");
-    if (sites && sites == ln.h_in.p && dec_at + dec_bytes > ln.h_in.bytes)
-        return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: the lane's site buffer is too small for the acceptance records "
-                                               "(mgpu_lane_site_buffer sizes it for them)");
-    // a block lent to the caller is never regrown behind their back (they keep the pointer for the farm's lifetime)
-    if (ln.h_in_lent && dec_at + dec_bytes > ln.h_in.bytes)
-        return set_error(MGPU_ERR_STATE, "trial_submit: this trial needs a larger staging block than the one lent out by "
-                                         "mgpu_lane_site_buffer; call it again with the larger size first");
-    if ((rc = ln.h_in.reserve(dec_at + dec_bytes))) return rc;
-    double *h_sites = (double *)ln.h_in.p;
-    PairItem *pit = (PairItem *)((char *)ln.h_in.p + site_bytes);
-    RecipItem *rit = (RecipItem *)((char *)ln.h_in.p + site_bytes + pit_cap);
-    PairItem *iit = (PairItem *)((char *)ln.h_in.p + site_bytes + pit_cap + rit_bytes);
-    ln.pair_old.assign(n, -1);
-    ln.pair_new.assign(n, -1);
-    ln.intra_idx.assign(n, -1);
-    ln.kinds.assign(n, MGPU_MOVE);
-    ln.self_of.assign(n, 0.0);
-    int n1_max = 1, n_intra = 0;
-    // Candidates are grouped by residue type: every type gets its own pair-sweep launches with the register-site kernels
-    // of its size (a mixture of a 3-site and a 2-site species used to fall to the generic NS = 0 sweep for the whole
-    // launch), and which kernels a type's candidates take never depends on what else shares the launch.  Within a type,
-    // trial moves of molecules with a few sites are swept old + new together (fused items, two entries each);
-    // insertions, deletions and everything else are single-state items.
-    struct Seg { int n1, fused, first_item, n_items, first_entry, type, nsplit, first_partial; };
-    int cls_n1[kMaxRes], cls_moves[kMaxRes], cls_single[kMaxRes], cls_type[kMaxRes], n_cls = 0;
+// A batched trial between the stages of trial_submit_impl.  Candidates are grouped by residue type (a class): every type
+// gets its own pair-sweep launches with the register-site kernels of its size (a mixture of a 3-site and a 2-site species
+// used to fall to the generic NS = 0 sweep for the whole launch), and which kernels a type's candidates take never depends
+// on what else shares the launch.  Within a type, trial moves of molecules with a few sites are swept old + new together
+// (a fused segment: two entries per item); insertions, deletions and everything else are single-state items.
+struct Seg { int n1, fused, first_item, n_items, first_entry, n_entries, type, nsplit, first_partial, batched; };
+struct TrialPlan {
+    int n = 0, n_cls = 0;
+    int cls_n1[kMaxRes], cls_moves[kMaxRes], cls_single[kMaxRes], cls_type[kMaxRes];
+    int seg_fused[kMaxRes], seg_single[kMaxRes];        // per class: index of its fused / single segment (-1: none)
+    std::vector<Seg> segs;
+    int n_pair = 0, n_partials = 0, n_intra = 0, n1_max = 1;
+    bool fast = true;                 // all replicas of this trial within the fast fold's range
+    // Framework boxes: one frozen residue type, identical in every replica, flat kernels in use, an active residue type of
+    // <= 5 sites -> the type's segments are `batched`: their items go to pair_frozen_kernel (candidates in the lanes; framework
+    // atoms as scalars, then the replica's few other atoms per lane); their sums arrive as ONE extra record per entry behind
+    // the other results
+    int t_frozen = -1, n_chunks_f = 0;
+    size_t scratch_records = 0;       // chunk partials of those sweeps
+    TrialStaging in{};                // the two blocks (mgpu_internal.h)
+    TrialResult out{};
+};
+
+// Stage 1: the classes and their segments, with every segment's place among the items, entries and partials; the result block.
+static int trial_plan(const mgpu_engine *e, int n, const int *t, const int *kind, bool decide, TrialPlan &pl) {
     for (int c = 0; c < n; ++c) {
         const int k = kind ? kind[c] : MGPU_MOVE;
         if (k < MGPU_MOVE || k > MGPU_DELETION) return set_error(MGPU_ERR_INVALID_ARG, "trial_submit: unknown candidate kind");
         if (t[c] < 0 || t[c] >= e->tp.n_res) return set_error(MGPU_ERR_INVALID_ARG, "trial_submit: residue type out of range");
         const int n1 = e->tp.n1[t[c]];
         int ci = 0;
-        while (ci < n_cls && cls_type[ci] != t[c]) ++ci;
-        if (ci == n_cls) { cls_n1[ci] = n1; cls_moves[ci] = 0; cls_single[ci] = 0; cls_type[ci] = t[c]; ++n_cls; }   // <= n_res classes
+        while (ci < pl.n_cls && pl.cls_type[ci] != t[c]) ++ci;
+        if (ci == pl.n_cls) { pl.cls_n1[ci] = n1; pl.cls_moves[ci] = 0; pl.cls_single[ci] = 0; pl.cls_type[ci] = t[c]; ++pl.n_cls; }   // <= n_res classes
         // (triclinic boxes: two single-state items -- the image search's registers leave no room for 2 NS sites without spills;
         //  measured round 5, 10 125-atom box, 1024 moves: fused 267-391 us, two single-state sweeps 239 us)
         const bool fz = k == MGPU_MOVE && n1 <= kMaxFusedSites && !e->bx.triclinic;
-        if (fz) cls_moves[ci] += 1;
-        else cls_single[ci] += (k == MGPU_MOVE) ? 2 : 1;
+        if (fz) pl.cls_moves[ci] += 1;
+        else pl.cls_single[ci] += (k == MGPU_MOVE) ? 2 : 1;
     }
-    // Framework boxes: one frozen residue type, identical in every replica, flat kernels in use, an active residue type of
-    // <= 5 sites -> the type's items go to pair_frozen_kernel (candidates in the lanes; framework atoms as scalars, then the
-    // replica's few other atoms per lane); their sums arrive as ONE extra record per entry behind the other results
-    const int t_frozen = frozen_batch_type(e);
-    auto type_batched = [&](int ty, int n1) { return t_frozen >= 0 && ty != t_frozen && n1 <= kMaxFusedSitesWide; };
-    const int n_atoms_f = t_frozen >= 0 ? e->h_nmol[t_frozen] * e->tp.n1[t_frozen] : 0;
-    const int n_chunks_f = t_frozen >= 0 ? (n_atoms_f + frozen_chunk_atoms(e, n_atoms_f) - 1) / frozen_chunk_atoms(e, n_atoms_f) : 0;
-    const int nsplit_engine = e->pair_nsplit;
-    std::vector<Seg> segs;
-    int seg_fused[kMaxRes], seg_single[kMaxRes];        // per class: index of its fused / single segment (-1: none)
-    int n_items_total = 0, n_pair = 0, n_fused = 0, n_partials = 0;
-    for (int ci = 0; ci < n_cls; ++ci) {
-        seg_fused[ci] = seg_single[ci] = -1;
-        const int ns_seg = type_batched(cls_type[ci], cls_n1[ci]) ? 0 : nsplit_engine;      // batched: the extra record is all
-        if (cls_moves[ci]) {
-            seg_fused[ci] = (int)segs.size();
-            segs.push_back(Seg{cls_n1[ci], 1, n_items_total, 0, n_pair, cls_type[ci], ns_seg, n_partials});
-            n_items_total += cls_moves[ci];
-            n_pair += 2 * cls_moves[ci];
-            n_partials += 2 * cls_moves[ci] * ns_seg;
-            n_fused += cls_moves[ci];
-        }
-        if (cls_single[ci]) {
-            seg_single[ci] = (int)segs.size();
-            segs.push_back(Seg{cls_n1[ci], 0, n_items_total, 0, n_pair, cls_type[ci], ns_seg, n_partials});
-            n_items_total += cls_single[ci];
-            n_pair += cls_single[ci];
-            n_partials += cls_single[ci] * ns_seg;
-        }
+    pl.t_frozen = frozen_batch_type(e);
+    const int n_atoms_f = pl.t_frozen >= 0 ? e->h_nmol[pl.t_frozen] * e->tp.n1[pl.t_frozen] : 0;
+    pl.n_chunks_f = pl.t_frozen >= 0 ? (n_atoms_f + frozen_chunk_atoms(e, n_atoms_f) - 1) / frozen_chunk_atoms(e, n_atoms_f) : 0;
+    int n_items_total = 0;
+    for (int ci = 0; ci < pl.n_cls; ++ci) {
+        const int n1 = pl.cls_n1[ci], ty = pl.cls_type[ci];
+        const int batched = pl.t_frozen >= 0 && ty != pl.t_frozen && n1 <= kMaxFusedSitesWide;
+        const int ns_seg = batched ? 0 : e->pair_nsplit;      // batched: the extra record is all
+        auto add_seg = [&](int fused, int n_items, int &seg_of_class) {
+            seg_of_class = n_items ? (int)pl.segs.size() : -1;
+            if (!n_items) return;
+            const int n_entries = fused ? 2 * n_items : n_items;
+            pl.segs.push_back(Seg{n1, fused, n_items_total, n_items, pl.n_pair, n_entries, ty, ns_seg, pl.n_partials, batched});
+            n_items_total += n_items;
+            pl.n_pair += n_entries;
+            pl.n_partials += n_entries * ns_seg;
+            if (batched) pl.scratch_records += (size_t)n_entries * pl.n_chunks_f;
+        };
+        add_seg(1, pl.cls_moves[ci], pl.seg_fused[ci]);
+        add_seg(0, pl.cls_single[ci], pl.seg_single[ci]);
     }
-    ln.ent_off.assign(n_pair, 0);
-    ln.ent_stride.assign(n_pair, 2);
-    ln.ent_ns.assign(n_pair, 1);
+    pl.out = trial_result(n, pl.n_partials, pl.n_pair, pl.scratch_records != 0, decide);
+    return MGPU_OK;
+}
+
+// Stage 2: validate every candidate and write its pair, k and intra items into the staging block, the lane's per-candidate
+// rows beside them.  Two passes over the candidates, each cut into ranges run side by side (for_parts): the first validates
+// a candidate, fills what belongs to it alone and counts the items it will add to its class's segments; the second, knowing
+// every range's first item in every segment, writes the items -- in candidate order within a segment, as one loop would.
+static int trial_fill(mgpu_engine *e, Lane &ln, TrialPlan &pl, const int *replica, const int *t, const int *m, const int *kind,
+                      const double *sites, const TrialBuild *build, const TrialDecide *decide) {
+    const int n = pl.n, n_cls = pl.n_cls, site_stride = pl.in.row_sites, frame_at = pl.in.frame_at;
+    PairItem *pit = (PairItem *)((char *)ln.h_in.p + pl.in.pair_items), *iit = (PairItem *)((char *)ln.h_in.p + pl.in.intra_items);
+    RecipItem *rit = (RecipItem *)((char *)ln.h_in.p + pl.in.k_items);
+    ln.pair_old.assign(n, -1);
+    ln.pair_new.assign(n, -1);
+    ln.intra_idx.assign(n, -1);
+    ln.kinds.assign(n, MGPU_MOVE);
+    ln.self_of.assign(n, 0.0);
+    ln.ent_off.assign(pl.n_pair, 0);
+    ln.ent_stride.assign(pl.n_pair, 2);
+    ln.ent_ns.assign(pl.n_pair, 1);
+    ln.cand_ok.assign(n, 1);          // per candidate: would committing it keep its replica within the fast fold's range
     auto put_item = [&](const Seg &sg, int i, const PairItem &it) {     // item i of the segment; returns its first entry
         pit[sg.first_item + i] = it;
         const int e0 = sg.first_entry + (sg.fused ? 2 * i : i);
@@ -330,11 +300,6 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
         }
         return e0;
     };
-    bool fast = true;                 // all replicas of this trial within the fast fold's range
-    ln.cand_ok.assign(n, 1);          // and per candidate: would committing it keep its replica there
-    // Two passes over the candidates, each cut into ranges run side by side (for_parts): the first validates a candidate,
-    // fills what belongs to it alone and counts the items it will add to its class's segments; the second, knowing every
-    // range's first item in every segment, writes the items -- in candidate order within a segment, as one loop would.
     struct Part {
         int n1_max = 1, n_intra = 0;
         bool fast = true;
@@ -344,14 +309,14 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
     const int parts = host_parts(e, n);
     Part part_of[kMaxHostParts];
     PartError errs[kMaxHostParts];
-    auto class_of = [&](int ty) { int ci = 0; while (cls_type[ci] != ty) ++ci; return ci; };
+    auto class_of = [&](int ty) { int ci = 0; while (pl.cls_type[ci] != ty) ++ci; return ci; };
     // candidate c's pair and intra items at the places the running indices say
     auto place = [&](int c, int k, int mc, int ci, int *i_f, int *i_s, int &i_intra) {
-        if (k == MGPU_MOVE && seg_fused[ci] >= 0) {
-            const int e0 = put_item(segs[seg_fused[ci]], i_f[ci]++, PairItem{replica[c], t[c], mc, c, 0});
+        if (k == MGPU_MOVE && pl.seg_fused[ci] >= 0) {
+            const int e0 = put_item(pl.segs[pl.seg_fused[ci]], i_f[ci]++, PairItem{replica[c], t[c], mc, c, 0});
             ln.pair_old[c] = e0; ln.pair_new[c] = e0 + 1;
         } else {
-            const Seg &sg = segs[seg_single[ci]];
+            const Seg &sg = pl.segs[pl.seg_single[ci]];
             if (k != MGPU_CREATION) ln.pair_old[c] = put_item(sg, i_s[ci]++, PairItem{replica[c], t[c], mc, -1, 0});
             if (k != MGPU_DELETION) ln.pair_new[c] = put_item(sg, i_s[ci]++, PairItem{replica[c], t[c], mc, c, 0});
         }
@@ -363,6 +328,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
         for (int ci = 0; ci < n_cls; ++ci) P.n_fused[ci] = P.n_single[ci] = 0;
         int c0, c1;
         part_range(n, parts, q, c0, c1);
+        std::string why;
         for (int c = c0; c < c1; ++c) {
             const int k = kind ? kind[c] : MGPU_MOVE;
             const int mc = (k == MGPU_CREATION) ? -1 : m[c];
@@ -373,35 +339,18 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
             const int ci = class_of(t[c]);
             ln.kinds[c] = k;
             P.fast = P.fast && replica_in_range(e, replica[c]);
+            const size_t idx = (size_t)replica[c] * e->tp.n_res + t[c];
             if (build) {
-                const size_t idx = (size_t)replica[c] * e->tp.n_res + t[c];
-                if (!e->d_com || !e->frames_ok[idx]) {
-                    errs[q].set(c, MGPU_ERR_STATE, "move_trial_submit: no molecule frames for candidate " + std::to_string(c) +
-                                                       " (mgpu_replica_set_frames)");
+                if (const int r = admit_built(e, idx, k, build->move[c], kAdmitAll, "move_trial_submit", "candidate", c, why, ln.cand_ok[c], P.fast)) {
+                    errs[q].set(c, r, why);
                     return;
                 }
-                const int mv = build->move[c];
-                if (mv < 1 || mv > 4 || (k == MGPU_MOVE) != (mv <= 2) || (k == MGPU_CREATION) != (mv == 3)) {
-                    errs[q].set(c, MGPU_ERR_INVALID_ARG, "move_trial_submit: move code does not match the candidate kind");
-                    return;
-                }
-                // the insertion copies slot 0's frame whatever the count (create_molecule.f90:196-200): there must be one
-                // (a type with a reservoir copies a reservoir molecule instead)
-                if (k == MGPU_CREATION && !e->frames_held[idx] && !has_reservoir(e, idx)) {
-                    errs[q].set(c, MGPU_ERR_STATE, "move_trial_submit: an insertion copies the geometry of molecule 1 of its type, "
-                                                   "and this type has never held one on this replica");
-                    return;
-                }
-                // a built candidate's centre lies in the cell (ApplyPBC / uniform insertion); with tight frames its sites are
-                // within the fast fold's range
-                if (k != MGPU_DELETION) { ln.cand_ok[c] = e->frames_tight[idx]; P.fast = P.fast && ln.cand_ok[c]; }
             } else if (k != MGPU_DELETION) {
                 ln.cand_ok[c] = sites_in_range(e, sites + (size_t)c * site_stride * 3, n1) ? 1 : 0;
                 P.fast = P.fast && ln.cand_ok[c];          // the candidate's own sites are swept in this launch
             }
             if (k != MGPU_MOVE) ln.self_of[c] = e->self_of_type[t[c]];
             if (decide) {
-                const size_t idx = (size_t)replica[c] * e->tp.n_res + t[c];
                 if (k == MGPU_CREATION && e->h_nmol[idx] >= e->tp.cap[t[c]]) {
                     errs[q].set(c, MGPU_ERR_CAPACITY, "trial_decide_submit: residue type is at mol_capacity");
                     return;
@@ -416,28 +365,22 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
                 place(c, k, mc, ci, P.n_fused, P.n_single, P.n_intra);
                 continue;
             }
-            if (k == MGPU_MOVE && seg_fused[ci] >= 0) P.n_fused[ci] += 1;
+            if (k == MGPU_MOVE && pl.seg_fused[ci] >= 0) P.n_fused[ci] += 1;
             else P.n_single[ci] += (k != MGPU_CREATION) + (k != MGPU_DELETION);
             if (k != MGPU_MOVE) P.n_intra += 1;
         }
     });
-    if ((rc = report_first(errs, parts))) return rc;
-    {
-        int run_f[kMaxRes] = {0}, run_s[kMaxRes] = {0};
-        for (int q = 0; q < parts; ++q) {
-            Part &P = part_of[q];
-            n1_max = std::max(n1_max, P.n1_max);
-            fast = fast && P.fast;
-            P.at_intra = n_intra;
-            n_intra += P.n_intra;
-            for (int ci = 0; ci < n_cls; ++ci) {
-                P.at_fused[ci] = run_f[ci]; run_f[ci] += P.n_fused[ci];
-                P.at_single[ci] = run_s[ci]; run_s[ci] += P.n_single[ci];
-            }
-        }
+    if (int rc = report_first(errs, parts)) return rc;
+    int run_f[kMaxRes] = {0}, run_s[kMaxRes] = {0};
+    for (int q = 0; q < parts; ++q) {
+        Part &P = part_of[q];
+        pl.n1_max = std::max(pl.n1_max, P.n1_max);
+        pl.fast = pl.fast && P.fast;
+        P.at_intra = pl.n_intra;
+        pl.n_intra += P.n_intra;
         for (int ci = 0; ci < n_cls; ++ci) {
-            if (seg_fused[ci] >= 0) segs[seg_fused[ci]].n_items = run_f[ci];
-            if (seg_single[ci] >= 0) segs[seg_single[ci]].n_items = run_s[ci];
+            P.at_fused[ci] = run_f[ci]; run_f[ci] += P.n_fused[ci];
+            P.at_single[ci] = run_s[ci]; run_s[ci] += P.n_single[ci];
         }
     }
     if (parts > 1)
@@ -452,84 +395,92 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
                 place(c, k, (k == MGPU_CREATION) ? -1 : m[c], class_of(t[c]), i_f, i_s, i_intra);
             }
         });
+    return MGPU_OK;
+}
+
+// the deciding form's records: where the device finds each candidate's pair entries, intra result and constants
+static void trial_decide_items(Lane &ln, const TrialPlan &pl, const TrialDecide &decide) {
+    DecideItem *dit = (DecideItem *)((char *)ln.h_in.p + pl.in.decide_items);
+    for (int c = 0; c < pl.n; ++c) {
+        DecideItem d{0, 2, -1, -1, 0, 2, -1, -1, ln.intra_idx[c], ln.kinds[c], ln.self_of[c], decide.pref[c], decide.u[c]};
+        if (const int i = ln.pair_old[c]; i >= 0) {
+            d.old_off = ln.ent_off[i]; d.old_stride = ln.ent_stride[i]; d.old_ns = ln.ent_ns[i];
+            d.old_extra = ln.ent_extra[i] ? (int)(pl.out.extra + 2 * (size_t)i) : -1;
+        }
+        if (const int i = ln.pair_new[c]; i >= 0) {
+            d.new_off = ln.ent_off[i]; d.new_stride = ln.ent_stride[i]; d.new_ns = ln.ent_ns[i];
+            d.new_extra = ln.ent_extra[i] ? (int)(pl.out.extra + 2 * (size_t)i) : -1;
+        }
+        dit[c] = d;
+    }
+}
+
+// Stage 3: finish the staging block (site rows or the build's inputs, decide items), reserve the device blocks, and send the
+// staging block to the device -- one H2D copy; rows built on the device are written there by trial_build_kernel.
+static int trial_stage(mgpu_engine *e, Lane &ln, const TrialPlan &pl, const int *t, const double *sites, const TrialBuild *build,
+                       const TrialDecide *decide) {
+    const int n = pl.n;
+    char *h_in = (char *)ln.h_in.p;
     if (build) {
-        std::memcpy((char *)ln.h_in.p + build_at, build->move, (size_t)n * sizeof(int));
-        std::memcpy((char *)ln.h_in.p + build_at + build_mv, build->u, (size_t)5 * n * sizeof(double));
+        std::memcpy(h_in + pl.in.moves, build->move, (size_t)n * sizeof(int));
+        std::memcpy(h_in + pl.in.uniforms, build->u, (size_t)5 * n * sizeof(double));
     } else {
-        if (sites != h_sites) std::memcpy(h_sites, sites, site_bytes);    // rows built in place (mgpu_lane_site_buffer): no copy
-        if (any_frozen(e, n, t)) permute_frozen_rows(e, h_sites, n, site_stride, t);
+        if (sites != ln.h_in.p) std::memcpy(h_in, sites, pl.in.pair_items);    // rows built in place (mgpu_lane_site_buffer): no copy
+        if (any_frozen(e, n, t)) permute_frozen_rows(e, (double *)h_in, n, pl.in.row_sites, t);
     }
-    const size_t iit_bytes = (size_t)n_intra * sizeof(PairItem);
-    // results in device memory, copied out once: [split partials of the pair sweep (n_pair * nsplit complex-sized
-    // records, reduced on the host in trial_wait) | u_old | u_new | intra]
-    auto seg_batched = [&](const Seg &sg) { return type_batched(sg.type, sg.n1); };
-    ln.ent_extra.assign(n_pair, 0);
-    size_t scratch_records = 0;
-    for (const Seg &sg : segs)
-        if (seg_batched(sg)) {
-            const int ne = sg.n_items * (sg.fused ? 2 : 1);
-            for (int i = 0; i < ne; ++i) ln.ent_extra[sg.first_entry + i] = 1;
-            scratch_records += (size_t)ne * n_chunks_f;
-        }
-    const size_t extra_at = 2 * (size_t)n_partials + 3 * (size_t)n;          // doubles
-    const size_t acc_at = extra_at + (scratch_records ? 2 * (size_t)n_pair : 0);     // the deciding form's flags (ints)
-    const size_t out_doubles = acc_at + (decide ? ((size_t)n + 1) / 2 : 0);
+    ln.ent_extra.assign(pl.n_pair, 0);
+    for (const Seg &sg : pl.segs)
+        if (sg.batched) std::fill_n(ln.ent_extra.begin() + sg.first_entry, sg.n_entries, 1);
+    int rc;
     if (decide) {
-        if (!recip_by_rows(e, n1_max)) return set_error(MGPU_ERR_STATE, "trial_decide_submit: needs the row-form k sweep");
-        DecideItem *dit = (DecideItem *)((char *)ln.h_in.p + dec_at);
-        for (int c = 0; c < n; ++c) {
-            DecideItem d{0, 2, -1, -1, 0, 2, -1, -1, ln.intra_idx[c], ln.kinds[c], ln.self_of[c], decide->pref[c], decide->u[c]};
-            if (const int i = ln.pair_old[c]; i >= 0) {
-                d.old_off = ln.ent_off[i]; d.old_stride = ln.ent_stride[i]; d.old_ns = ln.ent_ns[i];
-                d.old_extra = ln.ent_extra[i] ? (int)(extra_at + 2 * (size_t)i) : -1;
-            }
-            if (const int i = ln.pair_new[c]; i >= 0) {
-                d.new_off = ln.ent_off[i]; d.new_stride = ln.ent_stride[i]; d.new_ns = ln.ent_ns[i];
-                d.new_extra = ln.ent_extra[i] ? (int)(extra_at + 2 * (size_t)i) : -1;
-            }
-            dit[c] = d;
-        }
+        if (!recip_by_rows(e, pl.n1_max)) return set_error(MGPU_ERR_STATE, "trial_decide_submit: needs the row-form k sweep");
+        trial_decide_items(ln, pl, *decide);
     }
-    if (scratch_records && (rc = ln.d_scratch.reserve(scratch_records * sizeof(double2)))) return rc;
-    // one staging block [sites | pair items (2n slots) | recip items | intra items] -> one H2D copy
-    const size_t in_bytes = site_bytes + pit_cap + rit_bytes + iit_bytes;
-    if ((rc = ln.d_sites.reserve(dec_at + dec_bytes))) return rc;
-    if ((rc = ln.d_out.reserve(out_doubles * sizeof(double)))) return rc;
-    if ((rc = ln.h_out.reserve(out_doubles * sizeof(double)))) return rc;
+    if (pl.scratch_records && (rc = ln.d_scratch.reserve(pl.scratch_records * sizeof(double2)))) return rc;
+    if ((rc = ln.d_sites.reserve(pl.in.total))) return rc;
+    if ((rc = ln.d_out.reserve(pl.out.total * sizeof(double)))) return rc;
+    if ((rc = ln.h_out.reserve(pl.out.total * sizeof(double)))) return rc;
+    char *d_in = (char *)ln.d_sites.p;
     if (build) {
-        // the rows are written by the device: only [items | move codes | uniforms] travel
-        HIP_TRY(hipMemcpyAsync((char *)ln.d_sites.p + site_bytes, (char *)ln.h_in.p + site_bytes, dec_at + dec_bytes - site_bytes,
-                               hipMemcpyHostToDevice, ln.stream));
+        // the rows are written by the device: only [items | move codes | uniforms | decide items] travel
+        HIP_TRY(hipMemcpyAsync(d_in + pl.in.pair_items, h_in + pl.in.pair_items, pl.in.total - pl.in.pair_items, hipMemcpyHostToDevice, ln.stream));
         // (a triclinic cell: the instance with trial_com_triclinic's centre; the entry points refuse one without the switch)
         const auto build_kernel = e->bx.triclinic ? trial_build_kernel<true> : trial_build_kernel<false>;
-        hipLaunchKernelGGL(build_kernel, dim3((n + 127) / 128), dim3(128), 0, ln.stream, e->tp, e->bx,
-                           (const RecipItem *)((char *)ln.d_sites.p + site_bytes + pit_cap), (const int *)((char *)ln.d_sites.p + build_at),
-                           (const double *)((char *)ln.d_sites.p + build_at + build_mv), build->t_step, build->r_step,
-                           (double *)ln.d_sites.p, site_stride, frame_at, n, e->rsv_any ? 2 * frame_at + 1 : 0);
+        hipLaunchKernelGGL(build_kernel, dim3((n + 127) / 128), dim3(128), 0, ln.stream, e->tp, e->bx, (const RecipItem *)(d_in + pl.in.k_items),
+                           (const int *)(d_in + pl.in.moves), (const double *)(d_in + pl.in.uniforms), build->t_step, build->r_step,
+                           (double *)d_in, pl.in.row_sites, pl.in.frame_at, n, pl.in.pick_at);
         HIP_TRY(hipGetLastError());
     } else {
-        HIP_TRY(hipMemcpyAsync(ln.d_sites.p, ln.h_in.p, in_bytes, hipMemcpyHostToDevice, ln.stream));
+        // (only the intra items in use travel)
+        HIP_TRY(hipMemcpyAsync(d_in, h_in, pl.in.intra_items + (size_t)pl.n_intra * sizeof(PairItem), hipMemcpyHostToDevice, ln.stream));
         if (decide)
-            HIP_TRY(hipMemcpyAsync((char *)ln.d_sites.p + dec_at, (char *)ln.h_in.p + dec_at, dec_bytes, hipMemcpyHostToDevice, ln.stream));
+            HIP_TRY(hipMemcpyAsync(d_in + pl.in.decide_items, h_in + pl.in.decide_items, pl.in.total - pl.in.decide_items, hipMemcpyHostToDevice, ln.stream));
     }
-    const PairItem *d_pit = (const PairItem *)((char *)ln.d_sites.p + site_bytes);
-    const RecipItem *d_rit = (const RecipItem *)((char *)ln.d_sites.p + site_bytes + pit_cap);
-    const PairItem *d_iit = (const PairItem *)((char *)ln.d_sites.p + site_bytes + pit_cap + rit_bytes);
-    double2 *d_part = (double2 *)ln.d_out.p;
-    double *d_uo = (double *)ln.d_out.p + 2 * (size_t)n_partials, *d_un = d_uo + n, *d_in = d_un + n;
-    // Kernel order: pair sweep first, k sweep second (the order the stand-alone commit of the other lanes overlaps best
-    // with; k sweep first was measured 10 % slower there).
+    return MGPU_OK;
+}
+
+// Stage 4: the sweeps.  Kernel order: pair sweep first, k sweep second (the order the stand-alone commit of the other lanes
+// overlaps best with; k sweep first was measured 10 % slower there), then intra; the deciding k sweep comes last: its
+// workgroups decide and commit (everything else of the trial has read the old state).
+static int trial_launch(mgpu_engine *e, Lane &ln, const TrialPlan &pl, const int *replica, const TrialDecide *decide) {
+    const int n = pl.n, site_stride = pl.in.row_sites;
+    int rc;
+    const char *d_in = (const char *)ln.d_sites.p;
+    const PairItem *d_pit = (const PairItem *)(d_in + pl.in.pair_items), *d_iit = (const PairItem *)(d_in + pl.in.intra_items);
+    const RecipItem *d_rit = (const RecipItem *)(d_in + pl.in.k_items), *rit = (const RecipItem *)((char *)ln.h_in.p + pl.in.k_items);
+    double *d_out = (double *)ln.d_out.p;
+    double2 *d_part = (double2 *)(d_out + pl.out.partials);
+    double *d_uo = d_out + pl.out.u_old, *d_un = d_out + pl.out.u_new, *d_intra = d_out + pl.out.intra;
     size_t scratch_at = 0;
-    for (const Seg &sg : segs) {
-        const bool fb = seg_batched(sg);
-        if (!fb && (rc = launch_pair(e, ln, d_pit + sg.first_item, sg.n_items, sg.n1, site_stride, sg.nsplit, nullptr, nullptr, false,
-                                     d_part + sg.first_partial, sg.fused != 0, fast)))
+    for (const Seg &sg : pl.segs) {
+        if (!sg.batched && (rc = launch_pair(e, ln, d_pit + sg.first_item, sg.n_items, sg.n1, site_stride, sg.nsplit, nullptr, nullptr, false,
+                                     d_part + sg.first_partial, sg.fused != 0, pl.fast)))
             return rc;
-        if (fb) {
-            if ((rc = launch_frozen(e, ln, d_pit + sg.first_item, sg.n_items, sg.n1, site_stride, sg.fused != 0, fast, t_frozen,
-                                    (double2 *)ln.d_scratch.p + scratch_at, (double2 *)((double *)ln.d_out.p + extra_at) + sg.first_entry)))
+        if (sg.batched) {
+            if ((rc = launch_frozen(e, ln, d_pit + sg.first_item, sg.n_items, sg.n1, site_stride, sg.fused != 0, pl.fast, pl.t_frozen,
+                                    (double2 *)ln.d_scratch.p + scratch_at, (double2 *)(d_out + pl.out.extra) + sg.first_entry)))
                 return rc;
-            scratch_at += (size_t)sg.n_items * (sg.fused ? 2 : 1) * n_chunks_f;
+            scratch_at += (size_t)sg.n_entries * pl.n_chunks_f;
         }
     }
     ln.recip_slot.clear();
@@ -539,6 +490,7 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
         recip_groups(e, rit, n, ln.recip_groups, ln.recip_order);
         const RecipItem *d_rit_k = d_rit;
         if (!ln.recip_order.empty()) {
+            const size_t rit_bytes = (size_t)n * sizeof(RecipItem);
             if ((rc = ln.h_recip_items.reserve(rit_bytes)) || (rc = ln.d_recip_items.reserve(rit_bytes))) return rc;
             RecipItem *h = (RecipItem *)ln.h_recip_items.p;
             ln.recip_slot.resize(n);
@@ -546,11 +498,11 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
             HIP_TRY(hipMemcpyAsync(ln.d_recip_items.p, h, rit_bytes, hipMemcpyHostToDevice, ln.stream));
             d_rit_k = (const RecipItem *)ln.d_recip_items.p;
         }
-        // A trial whose commit can switch A(k) buffers (commit_submit_impl): its k sweep also stores every candidate's A + delta
+        // A trial whose commit can switch A(k) buffers (commit_from_trial): its k sweep also stores every candidate's A + delta
         // into the replica's other buffer.  One row-form launch (the commit by accept mask's form, whose sums it shares), one
         // candidate per replica (their stores would collide), molecules of at most 64 sites (commit_switch_kernel), and a
         // lane whose last commit accepted at least kSwitchMinShare of its candidates.
-        bool alt = !e->commit_pass && ln.accept_share >= kSwitchMinShare && ln.recip_groups.size() == 1 && recip_by_rows(e, n1_max) && n1_max <= 64 && n <= 32 * kAcceptWords;
+        bool alt = !e->commit_pass && ln.accept_share >= kSwitchMinShare && ln.recip_groups.size() == 1 && recip_by_rows(e, pl.n1_max) && pl.n1_max <= 64 && n <= 32 * kAcceptWords;
         alt = alt && one_record_per_replica(ln, e->n_replicas, replica, n);
         if (alt && (rc = alt_reserve(e))) return rc;
         if (alt) {
@@ -563,30 +515,80 @@ static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica
                 return rc;
         ln.trial_alt = alt;
     }
-    if (n_intra && (rc = launch_intra(e, ln, d_iit, n_intra, (const double *)ln.d_sites.p, site_stride, d_in))) return rc;
+    if (pl.n_intra && (rc = launch_intra(e, ln, d_iit, pl.n_intra, (const double *)d_in, site_stride, d_intra))) return rc;
     if (decide) {
-        // the k sweep comes last: its workgroups decide and commit (everything else of the trial has read the old state)
-        const DecideArgs da{(const DecideItem *)((const char *)ln.d_sites.p + dec_at), (const double *)ln.d_out.p, d_in,
-                            (int *)((double *)ln.d_out.p + acc_at), decide->temperature};
-        if ((rc = launch_recip(e, ln, d_rit, n, n1_max, site_stride, false, e->d_A, d_un, d_uo, nullptr, nullptr, &da))) return rc;
+        const DecideArgs da{(const DecideItem *)(d_in + pl.in.decide_items), d_out, d_intra, (int *)(d_out + pl.out.flags), decide->temperature};
+        if ((rc = launch_recip(e, ln, d_rit, n, pl.n1_max, site_stride, false, e->d_A, d_un, d_uo, nullptr, nullptr, &da))) return rc;
+    }
+    return MGPU_OK;
+}
+
+// Stage 5: the copy-out, and everything the lane remembers of the trial in flight.
+static int trial_record(mgpu_engine *e, Lane &ln, const TrialPlan &pl, const int *replica, bool built, bool decided) {
+    const int n = pl.n;
+    ln.result = pl.out;
+    if (decided) {
         for (int c = 0; c < n; ++c) alt_forget(e, replica[c]);      // (its accepted candidates are committed in place)
         ln.decided_n = n;
         ln.decided_wait_n = n;
-        ln.decided_at = acc_at * sizeof(double);
     }
-    HIP_TRY(hipMemcpyAsync(ln.h_out.p, ln.d_out.p, out_doubles * sizeof(double), hipMemcpyDeviceToHost, ln.stream));
+    HIP_TRY(hipMemcpyAsync(ln.h_out.p, ln.d_out.p, pl.out.total * sizeof(double), hipMemcpyDeviceToHost, ln.stream));
     ln.n_submitted = n;
-    ln.n_pair_items = n_pair;
-    ln.n_fused = n_fused;
-    ln.n_partials = n_partials;
+    ln.n_pair_items = pl.n_pair;
     ln.last_trial_n = n;
-    ln.last_trial_stride = site_stride;
-    ln.last_trial_built = build != nullptr;
-    ln.last_trial_frame = frame_at;
-    ln.d_trial_items = d_rit;
-    ln.h_trial_items = rit;
-    ln.trial_n1_max = n1_max;
+    ln.last_trial_stride = pl.in.row_sites;
+    ln.last_trial_built = built;
+    ln.last_trial_frame = pl.in.frame_at;
+    ln.d_trial_items = (const RecipItem *)((const char *)ln.d_sites.p + pl.in.k_items);
+    ln.h_trial_items = (const RecipItem *)((const char *)ln.h_in.p + pl.in.k_items);
+    ln.trial_n1_max = pl.n1_max;
     return MGPU_OK;
+}
+
+static int trial_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica, const int *t, const int *m,
+                             const int *kind, const double *sites, int site_stride, const TrialBuild *build = nullptr,
+                             const TrialDecide *decide = nullptr) {
+    if (ln.n_submitted != 0) return set_error(MGPU_ERR_STATE, "trial_submit: the lane still holds an un-waited trial");
+    int rc;
+    if (decide) {
+        if (!(decide->temperature > 0.0)) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: temperature must be positive");
+        // one candidate per replica: the workgroups commit independently
+        for (int c = 0; c < n; ++c)
+            if (replica[c] < 0 || replica[c] >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: replica out of range");
+        if (!one_record_per_replica(ln, e->n_replicas, replica, n)) return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: more than one candidate for a replica");
+    }
+    ln.decided_wait_n = 0;
+    ln.dirty = true;
+    ln.last_trial_built = false;
+    if (build) {      // rows of the largest molecule's size; site_stride came in as 0
+        site_stride = 1;
+        for (int c = 0; c < n; ++c) {
+            if (t[c] < 0 || t[c] >= e->tp.n_res) return set_error(MGPU_ERR_INVALID_ARG, "trial_submit: residue type out of range");
+            site_stride = std::max(site_stride, e->tp.n1[t[c]]);
+        }
+    }
+    // from here on the rows of the lane's previous trial are gone (the staging block below may be regrown and is
+    // overwritten): a failed submit must not leave them committable "from the lane's resident rows"
+    ln.forget_trial();
+    TrialPlan pl;
+    pl.n = n;
+    pl.in = trial_staging(n, site_stride, build != nullptr, e->rsv_any, decide != nullptr);
+    // (up to the move codes: the rows and items every trial has)
+    if (sites && sites == ln.h_in.p && pl.in.moves > ln.h_in.bytes)
+        return set_error(MGPU_ERR_INVALID_ARG, "trial_submit: more candidates than the lane's site buffer was sized for");
+    if (sites && sites == ln.h_in.p && pl.in.total > ln.h_in.bytes)
+        return set_error(MGPU_ERR_INVALID_ARG, "trial_decide_submit: the lane's site buffer is too small for the acceptance records "
+                                               "(mgpu_lane_site_buffer sizes it for them)");
+    // a block lent to the caller is never regrown behind their back (they keep the pointer for the farm's lifetime)
+    if (ln.h_in_lent && pl.in.total > ln.h_in.bytes)
+        return set_error(MGPU_ERR_STATE, "trial_submit: this trial needs a larger staging block than the one lent out by "
+                                         "mgpu_lane_site_buffer; call it again with the larger size first");
+    if ((rc = ln.h_in.reserve(pl.in.total))) return rc;
+    if ((rc = trial_plan(e, n, t, kind, decide != nullptr, pl))) return rc;
+    if ((rc = trial_fill(e, ln, pl, replica, t, m, kind, sites, build, decide))) return rc;
+    if ((rc = trial_stage(e, ln, pl, t, sites, build, decide))) return rc;
+    if ((rc = trial_launch(e, ln, pl, replica, decide))) return rc;
+    return trial_record(e, ln, pl, replica, build != nullptr, decide != nullptr);
 }
 
 // ncomp = 3: non_coulomb, coulomb, recip_coulomb; ncomp = 5: + ewald_self, intra_coulomb
@@ -598,13 +600,13 @@ static int trial_wait_impl(mgpu_engine *e, Lane &ln, double *old_energy, double 
     if (accepted && ln.decided_wait_n != n) return set_error(MGPU_ERR_STATE, "trial_decide_wait: the lane's trial was not submitted with an acceptance test");
     ln.decided_wait_n = 0;
     ln.n_submitted = 0;
-    const size_t flags_at = ln.decided_at;
+    const TrialResult at = ln.result;
     int rc = sync_lane(e, ln);
     if (rc) return rc;
-    if (accepted) std::memcpy(accepted, (const char *)ln.h_out.p + flags_at, (size_t)n * sizeof(int));
+    if (accepted) std::memcpy(accepted, (const char *)ln.h_out.p + at.flags_bytes(), (size_t)n * sizeof(int));
     const int np = ln.n_pair_items;
     const double *h = (const double *)ln.h_out.p;
-    const double *uo = h + 2 * (size_t)ln.n_partials, *un = uo + n, *in = un + n, *ex = in + n;
+    const double *uo = h + at.u_old, *un = h + at.u_new, *in = h + at.intra, *ex = h + at.extra;
     // the ordered sum of the split partials and the Coulomb rescale e_coulomb * EPS0_INV_eVA / KB_eVK
     // (energy_utils.f90:440), exactly as pair_finalize_kernel does them.  Partials of a fused item are laid out
     // [split][state], those of a single item [split].
@@ -641,45 +643,53 @@ static int trial_wait_impl(mgpu_engine *e, Lane &ln, double *old_energy, double 
     return MGPU_OK;
 }
 
-// Queue the commit of the accepted candidates on a lane (no synchronisation).  The host-side
-// molecule counts are updated immediately; the device applies them in stream order.
-// reuse_sites: `sites` may be NULL, meaning "the rows the lane's last trial_submit uploaded" (same
-// candidates, same order), which are still resident in the lane's device scratch.
-static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica, const int *t, const int *m,
-                              const int *kind, const double *sites, int site_stride, const int *accept,
-                              bool reuse_sites = false) {
-    int rc;
-    const size_t site_bytes = sites ? (size_t)n * site_stride * 3 * sizeof(double) : 0;
-    if (ln.n_submitted != 0) return set_error(MGPU_ERR_STATE, "commit_submit: wait for the lane's trial first");
-    ln.dirty = true;
-    // committing a device-built trial from its resident rows: the rows carry the candidates' frames
-    const bool built = !sites && reuse_sites && ln.last_trial_built && n == ln.last_trial_n;
-    if (built) site_stride = ln.last_trial_stride;
-    // the pinned staging block may still feed the H2D copy of the lane's previous commit
-    if (ln.commit_staged) {
-        HIP_TRY(hipEventSynchronize(ln.commit_staged_ev));
-        ln.commit_staged = false;
+// What a range of commit_collect's candidates leaves for the commit's tail
+struct CommitPart {
+    int n_acc = 0, at = 0;
+    bool any_sites = false;
+    std::vector<int> new_counts;  // (index into h_nmol, value) pairs applied after validation
+    std::vector<int> range_lost;  // (replica, type) entries whose atoms leave the fast fold's range with this commit
+};
+
+// A refused commit_collect: take its stamps back (a repeat of the call must not look like a duplicate) and settle which error
+// the serial loop would have reported.  Two accepted candidates of one replica in DIFFERENT ranges are noticed by whichever
+// range came second in time: which candidate that is depends on the threads.  The serial loop reports the second of the pair
+// in candidate order, and it stops at the first refusal of any kind: scan for a duplicate below the refusal just found.
+static int commit_refused(mgpu_engine *e, Lane &ln, int n, const int *replica, const int *accept, const PartError *errs, int parts, int rc) {
+    auto unmark = [&] {
+        for (int c = 0; c < n; ++c)
+            if (accept[c] && replica[c] >= 0 && replica[c] < e->n_replicas) ln.commit_mark[replica[c]] = -1;
+    };
+    unmark();
+    if (parts == 1) return rc;
+    int first_bad = n;
+    for (int q = 0; q < parts; ++q)
+        if (errs[q].c >= 0) first_bad = std::min(first_bad, errs[q].c);
+    const int scan = ++ln.commit_stamp;
+    int dup = -1;
+    for (int c = 0; c < n && c <= first_bad && dup < 0; ++c) {
+        if (!accept[c] || replica[c] < 0 || replica[c] >= e->n_replicas) continue;
+        if (ln.commit_mark[replica[c]] == scan) dup = c;
+        ln.commit_mark[replica[c]] = scan;
     }
-    if ((rc = ln.h_commit.reserve(site_bytes + (size_t)n * sizeof(RecipItem)))) return rc;
-    RecipItem *items = (RecipItem *)((char *)ln.h_commit.p + site_bytes);
-    int n_items = 0;
+    unmark();
+    if (dup >= 0 && dup <= first_bad) return set_error(MGPU_ERR_INVALID_ARG, "commit: more than one accepted candidate for a replica");
+    return rc;
+}
+
+// Part 1 of a commit: validate the accepted candidates and write their items, in candidate order, into `items`.  Two passes
+// in ranges, as in trial_fill: count the accepted candidates of every range, then validate them and write their items at the
+// range's place.  `built`: the commit is from a device-built trial's resident rows, which carry the candidates' frames.
+static int commit_collect(mgpu_engine *e, Lane &ln, int n, const int *replica, const int *t, const int *m, const int *kind,
+                          const double *sites, int site_stride, const int *accept, bool built, int parts, CommitPart *part_of,
+                          RecipItem *items, int &n_items) {
     // one accepted candidate per replica: ln.commit_mark[replica] holds the stamp of the call that last committed there (a
     // fresh stamp per call instead of clearing n_replicas flags; exchanged atomically: the ranges below run side by side)
     if ((int)ln.commit_mark.size() != e->n_replicas) { ln.commit_mark.assign(e->n_replicas, -1); ln.commit_stamp = 0; }
     if (++ln.commit_stamp == 0x7fffffff) { std::fill(ln.commit_mark.begin(), ln.commit_mark.end(), -1); ln.commit_stamp = 1; }
     const int stamp = ln.commit_stamp;
-    bool any_sites = false;
-    // two passes in ranges, as in trial_submit_impl: count the accepted candidates of every range, then validate them and
-    // write their items at the range's place -- the items keep candidate order
-    struct Part {
-        int n_acc = 0, at = 0;
-        bool any_sites = false;
-        std::vector<int> new_counts;  // (index into h_nmol, value) pairs applied after validation
-        std::vector<int> range_lost;  // (replica, type) entries whose atoms leave the fast fold's range with this commit
-    };
-    const int parts = host_parts(e, n);
-    Part part_of[kMaxHostParts];
     PartError errs[kMaxHostParts];
+    n_items = 0;
     if (parts > 1) {
         for_parts(parts, [&](int q) {
             int c0, c1, k = 0;
@@ -690,7 +700,7 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         for (int q = 0; q < parts; ++q) { part_of[q].at = n_items; n_items += part_of[q].n_acc; }
     }
     for_parts(parts, [&](int q) {
-        Part &P = part_of[q];
+        CommitPart &P = part_of[q];
         int c0, c1, at = P.at;
         part_range(n, parts, q, c0, c1);
         for (int c = c0; c < c1; ++c) {
@@ -739,94 +749,114 @@ static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replic
         }
         if (parts == 1) n_items = at;        // (one range: counted as it went)
     });
-    if ((rc = report_first(errs, parts))) {
-        // (the stamps of this refused call must not make a repeat of it look like a duplicate)
-        for (int c = 0; c < n; ++c)
-            if (accept[c] && replica[c] >= 0 && replica[c] < e->n_replicas) ln.commit_mark[replica[c]] = -1;
-        if (parts > 1) {
-            // Two accepted candidates of one replica in DIFFERENT ranges are noticed by whichever range came second in time:
-            // which candidate that is depends on the threads.  The serial loop reports the second of the pair in candidate
-            // order, and it stops at the first refusal of any kind: scan for a duplicate below the refusal just found.
-            int first_bad = n;
-            for (int q = 0; q < parts; ++q)
-                if (errs[q].c >= 0) first_bad = std::min(first_bad, errs[q].c);
-            const int scan = ++ln.commit_stamp;
-            int dup = -1;
-            for (int c = 0; c < n && c <= first_bad && dup < 0; ++c) {
-                if (!accept[c] || replica[c] < 0 || replica[c] >= e->n_replicas) continue;
-                if (ln.commit_mark[replica[c]] == scan) dup = c;
-                ln.commit_mark[replica[c]] = scan;
-            }
-            for (int c = 0; c < n; ++c)
-                if (accept[c] && replica[c] >= 0 && replica[c] < e->n_replicas) ln.commit_mark[replica[c]] = -1;
-            if (dup >= 0 && dup <= first_bad) return set_error(MGPU_ERR_INVALID_ARG, "commit: more than one accepted candidate for a replica");
+    if (int rc = report_first(errs, parts)) return commit_refused(e, ln, n, replica, accept, errs, parts, rc);
+    return MGPU_OK;
+}
+
+// Part 2a: committing the lane's last trial from its resident rows.  The trial's items are still on the device too, so the
+// accept flags travel as a kernel argument and nothing is uploaded.
+static int commit_from_trial(mgpu_engine *e, Lane &ln, int n, const int *replica, const int *t, const int *m, const int *kind,
+                             int site_stride, const int *accept, int parts, int n_items) {
+    AcceptBits bits{};
+    bool same_of[kMaxHostParts];   // the caller promises the trial's candidates in the trial's order: verify
+    for_parts(parts, [&](int q) {  // (the ranges end on multiples of 32 candidates: a mask word belongs to one range)
+        bool same = true;
+        int c0, c1;
+        part_range(n, parts, q, c0, c1);
+        for (int c = c0; c < c1; ++c) {
+            if (!accept[c]) continue;
+            const RecipItem &ti = ln.h_trial_items[c];
+            same = same && ti.replica == replica[c] && ti.t == t[c] && ti.kind == kind[c] &&
+                   (kind[c] == MGPU_CREATION || ti.m == m[c]);
+            bits.w[c >> 5] |= 1u << (c & 31);
         }
+        same_of[q] = same;
+    });
+    bool same = true;
+    for (int q = 0; q < parts; ++q) same = same && same_of[q];
+    if (!same) return set_error(MGPU_ERR_INVALID_ARG, "commit_submit: candidates differ from the lane's last trial");
+    // The trial stored the A + delta of its candidates into their replicas' other buffers, and nothing has touched those
+    // since (alt_owner still holds the trial's stamp for every accepted one): switch buffers.  Otherwise A + delta again.
+    bool switch_ok = ln.trial_alt && !e->commit_pass;
+    for (int c = 0; c < n && switch_ok; ++c)
+        switch_ok = !accept[c] || __atomic_load_n(&e->alt_owner[replica[c]], __ATOMIC_RELAXED) == ln.trial_stamp;
+    ln.accept_share = (double)n_items / n;
+    int rc;
+    if (switch_ok) {
+        if ((rc = launch_commit_switch(e, ln, ln.d_trial_items, n, site_stride, bits))) return rc;
+        e->a_switched = true;
+    } else if ((rc = launch_recip(e, ln, ln.d_trial_items, n, ln.trial_n1_max, site_stride, true, e->d_A, nullptr, nullptr, &bits)))
         return rc;
+    // applied once: a second commit_submit(sites = NULL) must not find these rows "resident" again
+    ln.forget_trial();
+    return MGPU_OK;
+}
+
+// Part 2b: committing uploaded items (and, where the caller gave sites, uploaded rows).
+static int commit_from_items(mgpu_engine *e, Lane &ln, int n, const int *t, const double *sites, int site_stride, RecipItem *items,
+                             int n_items, bool any_sites) {
+    int rc;
+    recip_groups(e, items, n_items, ln.recip_groups, ln.recip_order);
+    if (!ln.recip_order.empty()) {
+        const std::vector<RecipItem> as_accepted(items, items + n_items);
+        for (int s = 0; s < n_items; ++s) items[s] = as_accepted[ln.recip_order[s]];
     }
+    if ((rc = ln.d_items2.reserve((size_t)n_items * sizeof(RecipItem)))) return rc;
+    HIP_TRY(hipMemcpyAsync(ln.d_items2.p, items, (size_t)n_items * sizeof(RecipItem), hipMemcpyHostToDevice, ln.stream));
+    if (any_sites && sites) {
+        const size_t site_bytes = (size_t)n * site_stride * 3 * sizeof(double);
+        ln.forget_trial();      // (their rows are about to be overwritten)
+        std::memcpy(ln.h_commit.p, sites, site_bytes);
+        if (any_frozen(e, n, t)) permute_frozen_rows(e, (double *)ln.h_commit.p, n, site_stride, t);
+        if ((rc = ln.d_sites.reserve(site_bytes))) return rc;
+        HIP_TRY(hipMemcpyAsync(ln.d_sites.p, ln.h_commit.p, site_bytes, hipMemcpyHostToDevice, ln.stream));
+    }
+    if (!ln.commit_staged_ev) HIP_TRY(hipEventCreateWithFlags(&ln.commit_staged_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ln.commit_staged_ev, ln.stream));
+    ln.commit_staged = true;
+    // each accepted candidate in the form of its own type, as in its trial (the items touch one replica each: any order)
+    for (const RecipGroup &g : ln.recip_groups)
+        if ((rc = launch_recip(e, ln, (const RecipItem *)ln.d_items2.p + g.first, g.n, g.n1_max, site_stride, true, e->d_A, nullptr)))
+            return rc;
+    return MGPU_OK;
+}
+
+// Queue the commit of the accepted candidates on a lane (no synchronisation).  The host-side
+// molecule counts are updated immediately; the device applies them in stream order.
+// reuse_sites: `sites` may be NULL, meaning "the rows the lane's last trial_submit uploaded" (same
+// candidates, same order), which are still resident in the lane's device scratch.
+static int commit_submit_impl(mgpu_engine *e, Lane &ln, int n, const int *replica, const int *t, const int *m,
+                              const int *kind, const double *sites, int site_stride, const int *accept,
+                              bool reuse_sites = false) {
+    int rc;
+    const size_t site_bytes = sites ? (size_t)n * site_stride * 3 * sizeof(double) : 0;
+    if (ln.n_submitted != 0) return set_error(MGPU_ERR_STATE, "commit_submit: wait for the lane's trial first");
+    ln.dirty = true;
+    const bool built = !sites && reuse_sites && ln.last_trial_built && n == ln.last_trial_n;
+    if (built) site_stride = ln.last_trial_stride;
+    // the pinned staging block may still feed the H2D copy of the lane's previous commit
+    if (ln.commit_staged) {
+        HIP_TRY(hipEventSynchronize(ln.commit_staged_ev));
+        ln.commit_staged = false;
+    }
+    if ((rc = ln.h_commit.reserve(site_bytes + (size_t)n * sizeof(RecipItem)))) return rc;
+    RecipItem *items = (RecipItem *)((char *)ln.h_commit.p + site_bytes);
+    const int parts = host_parts(e, n);
+    CommitPart part_of[kMaxHostParts];
+    int n_items;
+    if ((rc = commit_collect(e, ln, n, replica, t, m, kind, sites, site_stride, accept, built, parts, part_of, items, n_items))) return rc;
+    bool any_sites = false;
     for (int q = 0; q < parts; ++q) any_sites = any_sites || part_of[q].any_sites;
     if (n_items == 0) {
         if (!sites && reuse_sites) ln.accept_share = 0.0;
         return MGPU_OK;
     }
     if (any_sites && !sites && !reuse_sites) return set_error(MGPU_ERR_INVALID_ARG, "commit_candidates: sites is null");
-    // Committing the lane's last trial from its resident rows: the trial's items are still on the device too,
-    // so the accept flags travel as a kernel argument and nothing is uploaded.
-    if (!sites && reuse_sites && n == ln.last_trial_n && ln.d_trial_items && n <= 32 * kAcceptWords &&
-        recip_by_rows(e, ln.trial_n1_max)) {
-        AcceptBits bits{};
-        bool same_of[kMaxHostParts];   // the caller promises the trial's candidates in the trial's order: verify
-        for_parts(parts, [&](int q) {  // (the ranges end on multiples of 32 candidates: a mask word belongs to one range)
-            bool same = true;
-            int c0, c1;
-            part_range(n, parts, q, c0, c1);
-            for (int c = c0; c < c1; ++c) {
-                if (!accept[c]) continue;
-                const RecipItem &ti = ln.h_trial_items[c];
-                same = same && ti.replica == replica[c] && ti.t == t[c] && ti.kind == kind[c] &&
-                       (kind[c] == MGPU_CREATION || ti.m == m[c]);
-                bits.w[c >> 5] |= 1u << (c & 31);
-            }
-            same_of[q] = same;
-        });
-        bool same = true;
-        for (int q = 0; q < parts; ++q) same = same && same_of[q];
-        if (!same) return set_error(MGPU_ERR_INVALID_ARG, "commit_submit: candidates differ from the lane's last trial");
-        // The trial stored the A + delta of its candidates into their replicas' other buffers, and nothing has touched those
-        // since (alt_owner still holds the trial's stamp for every accepted one): switch buffers.  Otherwise A + delta again.
-        bool switch_ok = ln.trial_alt && !e->commit_pass;
-        for (int c = 0; c < n && switch_ok; ++c)
-            switch_ok = !accept[c] || __atomic_load_n(&e->alt_owner[replica[c]], __ATOMIC_RELAXED) == ln.trial_stamp;
-        ln.accept_share = (double)n_items / n;
-        if (switch_ok) {
-            if ((rc = launch_commit_switch(e, ln, ln.d_trial_items, n, site_stride, bits))) return rc;
-            e->a_switched = true;
-        } else if ((rc = launch_recip(e, ln, ln.d_trial_items, n, ln.trial_n1_max, site_stride, true, e->d_A, nullptr, nullptr, &bits)))
-            return rc;
-        // applied once: a second commit_submit(sites = NULL) must not find these rows "resident" again
-        ln.forget_trial();
-    } else {
-        recip_groups(e, items, n_items, ln.recip_groups, ln.recip_order);
-        if (!ln.recip_order.empty()) {
-            const std::vector<RecipItem> as_accepted(items, items + n_items);
-            for (int s = 0; s < n_items; ++s) items[s] = as_accepted[ln.recip_order[s]];
-        }
-        if ((rc = ln.d_items2.reserve((size_t)n_items * sizeof(RecipItem)))) return rc;
-        HIP_TRY(hipMemcpyAsync(ln.d_items2.p, items, (size_t)n_items * sizeof(RecipItem), hipMemcpyHostToDevice, ln.stream));
-        if (any_sites && sites) {
-            ln.forget_trial();      // (their rows are about to be overwritten)
-            std::memcpy(ln.h_commit.p, sites, site_bytes);
-            if (any_frozen(e, n, t)) permute_frozen_rows(e, (double *)ln.h_commit.p, n, site_stride, t);
-            if ((rc = ln.d_sites.reserve(site_bytes))) return rc;
-            HIP_TRY(hipMemcpyAsync(ln.d_sites.p, ln.h_commit.p, site_bytes, hipMemcpyHostToDevice, ln.stream));
-        }
-        if (!ln.commit_staged_ev) HIP_TRY(hipEventCreateWithFlags(&ln.commit_staged_ev, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(ln.commit_staged_ev, ln.stream));
-        ln.commit_staged = true;
-        // each accepted candidate in the form of its own type, as in its trial (the items touch one replica each: any order)
-        for (const RecipGroup &g : ln.recip_groups)
-            if ((rc = launch_recip(e, ln, (const RecipItem *)ln.d_items2.p + g.first, g.n, g.n1_max, site_stride, true, e->d_A, nullptr)))
-                return rc;
-    }
+    const bool from_trial = !sites && reuse_sites && n == ln.last_trial_n && ln.d_trial_items && n <= 32 * kAcceptWords &&
+                            recip_by_rows(e, ln.trial_n1_max);
+    if ((rc = from_trial ? commit_from_trial(e, ln, n, replica, t, m, kind, site_stride, accept, parts, n_items)
+                         : commit_from_items(e, ln, n, t, sites, site_stride, items, n_items, any_sites)))
+        return rc;
     // the committed replicas' other buffers hold no trial's A + delta for their new state
     for (int c = 0; c < n; ++c)
         if (accept[c]) alt_forget(e, replica[c]);
@@ -848,11 +878,6 @@ static int check_lane(const mgpu_engine *e, int lane) {
     return MGPU_OK;
 }
 
-static size_t trial_staging_bytes(int n, int site_stride) {
-    return (size_t)n * site_stride * 3 * sizeof(double) + 2 * (size_t)n * sizeof(PairItem) + (size_t)n * sizeof(RecipItem) +
-           (size_t)n * sizeof(PairItem) + 16 + (size_t)n * sizeof(DecideItem);   // + acceptance records
-}
-
 int mgpu_lane_site_buffer(mgpu_engine *e, int lane, int n_max, int site_stride, double **sites) {
     int rc = check_lane(e, lane);
     if (rc) return rc;
@@ -862,10 +887,8 @@ int mgpu_lane_site_buffer(mgpu_engine *e, int lane, int n_max, int site_stride, 
     if (ln.n_submitted != 0) return set_error(MGPU_ERR_STATE, "lane_site_buffer: the lane holds an un-waited trial");
     // a regrown block would leave the previous trial's item image dangling
     ln.forget_trial();
-    // sized for the largest trial shape the lane accepts for n_max candidates: host rows of site_stride sites, or
-    // device-built rows [sites | com | offsets] with their move codes and uniform numbers, acceptance records included
-    const size_t built = trial_staging_bytes(n_max, 2 * site_stride + 2) + ((size_t)n_max * sizeof(int) + 8) + (size_t)5 * n_max * sizeof(double) + 16;
-    if ((rc = ln.h_in.reserve(std::max(trial_staging_bytes(n_max, site_stride), built)))) return rc;
+    // sized for the largest trial shape the lane accepts for n_max candidates (lane_site_buffer_bytes, mgpu_internal.h)
+    if ((rc = ln.h_in.reserve(lane_site_buffer_bytes(n_max, site_stride)))) return rc;
     ln.h_in_lent = true;
     *sites = (double *)ln.h_in.p;
     return MGPU_OK;
@@ -889,6 +912,16 @@ int mgpu_gcmc_trial_submit(mgpu_engine *e, int lane, int n, const int *replica, 
     return trial_submit_impl(e, e->lanes[lane], n, replica, t, m, kind, sites, site_stride);
 }
 
+// the candidate kinds of a device-built trial from its move codes, into ln.build_kind; `who` heads the error
+static int build_kinds(Lane &ln, int n, const int *move, const char *who) {
+    ln.build_kind.resize(n);
+    for (int c = 0; c < n; ++c) {
+        if (move[c] < 1 || move[c] > 4) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": unknown move code");
+        ln.build_kind[c] = move[c] <= 2 ? MGPU_MOVE : (move[c] == 3 ? MGPU_CREATION : MGPU_DELETION);
+    }
+    return MGPU_OK;
+}
+
 int mgpu_move_trial_submit(mgpu_engine *e, int lane, int n, const int *replica, const int *t, const int *m, const int *move,
                            const double *u, double translation_step, double rotation_step) {
     int rc = check_lane(e, lane);
@@ -897,11 +930,7 @@ int mgpu_move_trial_submit(mgpu_engine *e, int lane, int n, const int *replica, 
     if (e->bx.triclinic && !e->tri_moves) return set_error(MGPU_ERR_STATE, "move_trial_submit: orthorhombic boxes only");
     if ((rc = use_device(e))) return rc;
     Lane &ln = e->lanes[lane];
-    ln.build_kind.resize(n);
-    for (int c = 0; c < n; ++c) {
-        if (move[c] < 1 || move[c] > 4) return set_error(MGPU_ERR_INVALID_ARG, "move_trial_submit: unknown move code");
-        ln.build_kind[c] = move[c] <= 2 ? MGPU_MOVE : (move[c] == 3 ? MGPU_CREATION : MGPU_DELETION);
-    }
+    if ((rc = build_kinds(ln, n, move, "move_trial_submit"))) return rc;
     const TrialBuild build{move, u, translation_step, rotation_step};
     return trial_submit_impl(e, ln, n, replica, t, m, ln.build_kind.data(), nullptr, 0, &build);
 }
@@ -916,11 +945,7 @@ int mgpu_move_trial_decide_submit(mgpu_engine *e, int lane, int n, const int *re
     if (e->bx.triclinic && !e->tri_moves) return set_error(MGPU_ERR_STATE, "move_trial_decide_submit: orthorhombic boxes only");
     if ((rc = use_device(e))) return rc;
     Lane &ln = e->lanes[lane];
-    ln.build_kind.resize(n);
-    for (int c = 0; c < n; ++c) {
-        if (move[c] < 1 || move[c] > 4) return set_error(MGPU_ERR_INVALID_ARG, "move_trial_decide_submit: unknown move code");
-        ln.build_kind[c] = move[c] <= 2 ? MGPU_MOVE : (move[c] == 3 ? MGPU_CREATION : MGPU_DELETION);
-    }
+    if ((rc = build_kinds(ln, n, move, "move_trial_decide_submit"))) return rc;
     const TrialBuild build{move, u, translation_step, rotation_step};
     const TrialDecide dec{accept_u, accept_pref, temperature};
     return trial_submit_impl(e, ln, n, replica, t, m, ln.build_kind.data(), nullptr, 0, &build, &dec);

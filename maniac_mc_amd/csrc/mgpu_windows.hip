@@ -435,6 +435,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     FarmRec *recs = n <= kFarmInline ? g.inline_recs : fw.h_recs + (size_t)slot * fw.cap;
     bool fast = true;
     int n1_max = 1;
+    std::string why;
     for (int c = 0; c < n; ++c) {
         FarmRec &r = recs[c];
         r = FarmRec{};
@@ -448,8 +449,8 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         FarmTypeForm tf;
         if (!farm_type_form(e, t[c], tf) || e->frozen[t[c]]) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: molecule too large for the one-launch path"); break; }
         const size_t idx = (size_t)replica[c] * e->tp.n_res + t[c];
-        if (!e->d_com || !e->frames_ok[idx]) { rc = set_error(MGPU_ERR_STATE, "farm_window_submit: no molecule frames for chain " + std::to_string(c) + " (mgpu_replica_set_frames)"); break; }
         const int k = mv <= 2 ? MGPU_MOVE : (mv == 3 ? MGPU_CREATION : MGPU_DELETION);
+        if ((rc = admit_built(e, idx, k, mv, kAdmitFrames, "farm_window_submit", "chain", c, why, pd.ok[c], fast))) { set_error(rc, why); break; }
         const int mc = k == MGPU_CREATION ? -1 : (slot_u ? 0 : m[c]);
         if (!slot_u) {
             // the caller picked the molecule: against the engine's counts, which must then be current
@@ -462,14 +463,10 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
             r.by_count = 1;
             r.sel_u = slot_u[c];
         }
-        // an insertion copies the offsets of molecule 1 of its type, whatever the count (create_molecule.f90:196-200): slot
-        // 0's frame, which a deletion leaves in place -- a type that never held a molecule on this replica has none
-        if (k == MGPU_CREATION && !e->frames_held[idx] && !has_reservoir(e, idx)) { rc = set_error(MGPU_ERR_STATE, "farm_window_submit: an insertion copies the geometry of molecule 1 of its type, and this type has never held one on this replica"); break; }
+        fast = fast && replica_in_range(e, replica[c]);
+        if ((rc = admit_built(e, idx, k, mv, kAdmitInsertion | kAdmitRange, "farm_window_submit", "chain", c, why, pd.ok[c], fast))) { set_error(rc, why); break; }
         n1_max = std::max(n1_max, n1);
         pd.kind[c] = k;
-        // a built candidate's centre lies in the cell; with tight frames its sites are within the fast fold's range
-        fast = fast && replica_in_range(e, replica[c]);
-        if (k != MGPU_DELETION) { pd.ok[c] = e->frames_tight[idx]; fast = fast && pd.ok[c]; }
         // windows still in flight behind this one must not take the fast fold if this step is accepted: the range flag is
         // lowered now, not when the window is collected (a rejected step costs the replica the fast fold and nothing else)
         if (k != MGPU_DELETION && !pd.ok[c]) e->in_range[idx] = 0;
