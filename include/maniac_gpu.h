@@ -468,8 +468,16 @@ int mgpu_replica_set_num_molecules(mgpu_engine *e, int replica, int t, int n_mol
  *               energies returned.  Every decision the device takes is therefore the host's decision.
  * mgpu_chain_window_capacity: the largest n (0: the one-launch path does not apply -- per-k reciprocal
  * form, active molecules of more than 5 sites -- use mgpu_gcmc_trial_submit / wait).  Lane 0's stream carries the launch:
- * no trial may be in flight on lane 0. */
+ * no trial may be in flight on lane 0.
+ * mgpu_chain_set_wide(e, 1): windows also take rigid molecules of 6 to 63 sites (off by default).  The capacity is then
+ * > 0 for an orthorhombic box whose active types of that size take the row form or an untiled wide form of the reciprocal
+ * update (mgpu_recip_form: "rows", "wide-vector", "wide-mfma"), and mgpu_chain_window accepts their rows at the caller's
+ * site_stride; a window with such a row reads its rows from pinned host memory (they do not fit the kernel's arguments).
+ * Still 0 / MGPU_ERR_INVALID_ARG: molecules of 64 sites or more, the per-k and the tiled matrix-unit form, a triclinic box
+ * with such an active type, a Coulomb table beyond 64 KiB.  Energies, decisions and committed state are those of the
+ * batched path (mgpu_gcmc_trial_submit / wait, mgpu_commit_*), bit for bit, with the switch on or off. */
 int mgpu_chain_window_capacity(const mgpu_engine *e, int *max_candidates);
+int mgpu_chain_set_wide(mgpu_engine *e, int on);
 int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const int *m, const int *kind, const int *link,
                       const double *sites, int site_stride, const double *accept_u, const double *accept_pref,
                       double temperature, double recip_energy, double *old_energy, double *new_energy,

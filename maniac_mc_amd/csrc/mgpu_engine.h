@@ -186,6 +186,7 @@ struct Lane {
 constexpr int kLanes = 4;
 constexpr int kFarmDepth = 4;           // farm windows a lane may have in flight
 constexpr int kFarmMaxChains = 4096;   // chains per farm window
+constexpr size_t kChainWideRowsBytes = (size_t)kChainMaxCand * kFarmWideSites * 3 * sizeof(double);   // one block of a wide window's rows
 
 // ---- From run-time values to template instances.  A launch site picks its kernel FAMILY with ordinary ifs, states the
 // family's argument list once in a generic lambda, and lets these expand the parameters that are free within the family:
@@ -339,6 +340,9 @@ struct mgpu_engine {
         double margin = 16.0 * 2.220446049250313e-16;   // relative band around the acceptance probability left to the host's exp
         long long windows = 0, undecided = 0;
         bool timing = false;                         // stage stamps wanted (mgpu_chain_set_timing)
+        bool wide = false;                           // windows take rows of 6..63 sites (mgpu_chain_set_wide)
+        double *h_rows = nullptr;                    // pinned [2][kChainMaxCand][kFarmWideSites][3]: such rows, the blocks taken in turn
+        size_t wide_lds_opted = 0;                   // dynamic LDS the WIDE instances have opted in to
     } chain;
     // The A(k) double buffer: the other buffer of every replica and which of the two is its current one (d_acur[r] = 1:
     // d_A_alt), allocated on first use (alt_reserve).  Farm windows and the batched trials store every candidate's A + delta into

@@ -682,7 +682,7 @@ int mgpu_engine_destroy(mgpu_engine *e) {
     e->h_snap_items.release();
     e->d_snap.release();
     e->d_snap_items.release();
-    for (void *p : {(void *)e->chain.h_out, (void *)e->chain.h_tag})
+    for (void *p : {(void *)e->chain.h_out, (void *)e->chain.h_tag, (void *)e->chain.h_rows})
         if (p) (void)hipHostFree(p);
     for (void *p : {(void *)e->chain.d_res, (void *)e->chain.d_part, (void *)e->chain.d_ticket, (void *)e->chain.d_topo, (void *)e->chain.d_alt,
                     (void *)e->d_A_alt, (void *)e->d_acur, (void *)e->farm.d_stalled})

@@ -84,6 +84,26 @@ inline int recip_wide_mfma_tile(int ktot, int n_rrows, int n1_max) {
     return (int)((((nss + n_tiles - 1) / n_tiles) + 3) & ~(size_t)3);
 }
 
+// ---- Dynamic LDS of a WIDE single-chain window (chain_window_kernel<..., WIDE>, mgpu_kernels_windows.h): a launch gets the
+// largest of its roles' needs.  A row of a type of more than five sites is staged in LDS with a stride of kWideRowSites sites.
+constexpr int kWideRowSites = 64;
+// k role of such a row: candidate row | the intra wave's two tiles of {x, y, z, q} | the tables of the type's form
+constexpr size_t wide_k_front_bytes() { return (size_t)kWideRowSites * 3 * sizeof(double) + 2 * (size_t)kWideRowSites * 4 * sizeof(double); }
+inline size_t chain_wide_k_lds_bytes(size_t form_bytes) { return wide_k_front_bytes() + form_bytes; }
+// pair role: the Coulomb table (rounded up to 16 bytes: chain_wide_pair_at), then per wave a candidate row, a slab of
+// site_chunk sites {x, y, z, q} and their atom types (the NS = 0 sweep's)
+inline size_t chain_wide_pair_at(size_t coul_bytes) { return (coul_bytes + 15) & ~(size_t)15; }
+constexpr size_t wide_pair_slab_bytes(int pair_waves, int site_chunk) {
+    return (size_t)pair_waves * (((size_t)kWideRowSites * 3 + (size_t)site_chunk * 4) * sizeof(double) + (size_t)site_chunk * sizeof(int));
+}
+inline size_t chain_wide_pair_lds_bytes(size_t coul_bytes, int pair_waves, int site_chunk) {
+    return chain_wide_pair_at(coul_bytes) + wide_pair_slab_bytes(pair_waves, site_chunk);
+}
+// resolving workgroup (every instance): the split partials {lj, coulomb} of the window's pair entries
+inline size_t chain_resolver_lds_bytes(int n_ent, int nsplit) { return (size_t)n_ent * nsplit * kLdsPhase; }
+// largest window the resolver's staging admits within the default budget: two entries per step
+inline int chain_window_steps_by_lds(int nsplit) { return (int)(kLdsDefaultMax / chain_resolver_lds_bytes(2, nsplit)); }
+
 // ---- The two blocks of a batched trial on a lane (mgpu_lanes.hip): the one home of their layouts, plain integers as above.
 // trial_submit_impl, trial_wait_impl, finish_decided and the DecideItem offsets take every offset from here: a block that
 // disagrees between writer and reader gives a wrong energy, not a crash (tests/test_trial_layout.py).

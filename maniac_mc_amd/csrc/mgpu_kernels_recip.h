@@ -786,7 +786,15 @@ __global__ __launch_bounds__(kBlock, COMMIT ? MGPU_COMMIT_MINWAVES : MGPU_RECIP_
 // Every thread of the workgroup must reach the barriers inside; the others run `spare()` once, right after the barrier that
 // ends phase 1 (farm_window_kernel's intra-molecular term).  s_tab: the dynamic LDS of the form (see below); sums: the item's
 // block [task][4] of carried sums (TILED only).  ALT = 1 (energy sweeps only): A + delta is ALSO stored into A_alt, with the
-// commit's arithmetic (recip_rows_pass's ALT).
+// commit's arithmetic (recip_rows_pass's ALT); ALT = 2: with `sc1` stores, for a reader in another workgroup of the launch
+// (chain_window_kernel<..., WIDE>, as recip_rows_pass's ALT = 2).
+__device__ __forceinline__ void recip_store_alt_sc1(double2 *A_alt, int t, const double2 vp, const double2 vm) {
+    double *d = reinterpret_cast<double *>(A_alt + 2 * t);
+    __hip_atomic_store(d + 0, vp.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(d + 1, vp.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(d + 2, vm.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(d + 3, vm.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 template <bool COMMIT, bool BOTH, bool MFMA, bool TILED, int ALT = 0, class Spare>
 __device__ __forceinline__ void recip_wide_sweep(
     const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q,
@@ -948,7 +956,10 @@ __device__ __forceinline__ void recip_wide_sweep(
                     A[2 * t + 1] = (rjv[i] & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0);
                 } else {
                     acc += fma(w.x, fma(npx, npx, npy * npy), w.y * fma(nmx, nmx, nmy * nmy));   // ewald_energy.f90:259-266
-                    if constexpr (ALT != 0) {   // the commit's stores above, to the other buffer
+                    if constexpr (ALT == 2) {
+                        recip_store_alt_sc1(A_alt, t, (rjv[i] & kTaskHasP) ? make_double2(npx, npy) : make_double2(0.0, 0.0),
+                                            (rjv[i] & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0));
+                    } else if constexpr (ALT != 0) {   // the commit's stores above, to the other buffer
                         A_alt[2 * t] = (rjv[i] & kTaskHasP) ? make_double2(npx, npy) : make_double2(0.0, 0.0);
                         A_alt[2 * t + 1] = (rjv[i] & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0);
                     }
@@ -1008,7 +1019,10 @@ __device__ __forceinline__ void recip_wide_sweep(
                 A[2 * t + 1] = (rj & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0);
             } else {
                 acc += fma(w.x, fma(npx, npx, npy * npy), w.y * fma(nmx, nmx, nmy * nmy));   // ewald_energy.f90:259-266
-                if constexpr (ALT != 0) {   // the commit's stores above, to the other buffer
+                if constexpr (ALT == 2) {
+                    recip_store_alt_sc1(A_alt, t, (rj & kTaskHasP) ? make_double2(npx, npy) : make_double2(0.0, 0.0),
+                                        (rj & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0));
+                } else if constexpr (ALT != 0) {   // the commit's stores above, to the other buffer
                     A_alt[2 * t] = (rj & kTaskHasP) ? make_double2(npx, npy) : make_double2(0.0, 0.0);
                     A_alt[2 * t + 1] = (rj & kTaskHasM) ? make_double2(nmx, nmy) : make_double2(0.0, 0.0);
                 }

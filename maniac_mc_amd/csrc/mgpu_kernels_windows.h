@@ -35,7 +35,9 @@ namespace mgpu {
 // kind 2 with link >= 0: the reference's deletion exactly as written (monte_carlo_utils.f90:301-309): the new
 // reciprocal energy is the creation-kind energy of row `link` (the molecule RemoveMolecule swaps into the slot) and an
 // accepted step adds THAT molecule's terms to A(k) while the coordinates lose slot m; row `link` itself is energy-only
-// (link = -2).  Orthorhombic boxes, row-form k sweep, molecules of <= kMaxFusedSitesWide sites.
+// (link = -2).  Row-form k sweep and molecules of <= kMaxFusedSitesWide sites (orthorhombic boxes, and triclinic ones through
+// the TRI instance); the WIDE instances (orthorhombic boxes) also take rows of molecules of up to kFarmWideSites - 1 = 63
+// sites, in the k form of the row's own type (see the kernel).
 // ------------------------------------------------------------------------------------------
 constexpr int kChainMaxCand = 16;
 #ifndef MGPU_FARM_WIDE_MINWAVES
@@ -44,6 +46,17 @@ constexpr int kChainMaxCand = 16;
 #ifndef MGPU_FARM_TRI_MINWAVES
 #define MGPU_FARM_TRI_MINWAVES 2    // farm_window_kernel<false, false, false, RSV, true>: 169 VGPRs, no spills (at 4: 128 and 160 bytes of spills; at 3: 168, one workgroup per CU all the same); DESIGN 4.4
 #endif
+// WIDE instances (launches with a molecule of more than kMaxFusedSitesWide sites, at most kFarmWideSites - 1): the k role's
+// form per residue type, as recip_plan picks it for the type alone
+constexpr int kFarmFormRows = 0, kFarmFormWideVector = 1, kFarmFormWideMfma = 2;
+constexpr int kFarmWideSites = 64;               // candidate row stride of a wide chain (plane-major types: n1 <= 63)
+// dynamic LDS of a wide chain's k role: candidate row | the intra wave's two site tiles | the form's tables
+constexpr size_t kFarmKFront = (size_t)kFarmWideSites * 3 * sizeof(double) + 2 * (size_t)kFarmWideSites * sizeof(double4);
+// dynamic LDS of the pair role behind the Coulomb table: per wave a candidate row, a site slab and a type slab (NS = 0 sweep)
+constexpr size_t kFarmWidePairBytes = (size_t)kPairWaves * ((kFarmWideSites * 3 + kSiteChunk * 4) * sizeof(double) + kSiteChunk * sizeof(int));
+// (the same layouts serve chain_window_kernel<..., WIDE>; their sizes as the host computes them: mgpu_internal.h)
+static_assert(kFarmWideSites == kWideRowSites && kFarmKFront == wide_k_front_bytes() &&
+              kFarmWidePairBytes == wide_pair_slab_bytes(kPairWaves, kSiteChunk), "mgpu_internal.h sizes the wide windows' LDS with these");
 constexpr int kChainBlock = kPairBlock;          // 512 threads: 8 pair waves; the k role uses the first kBlock of them
 constexpr int kChainStamps = 8;                  // stage time stamps per role (k role of candidate 0, first pair workgroup, resolver)
 struct ChainResult {                             // what the k role of candidate c leaves for the resolving workgroup
@@ -70,6 +83,16 @@ struct ChainArgs {
     signed char ent_old_of[kChainMaxCand], ent_new_of[kChainMaxCand];     // per candidate: its old / new pair entry, -1 none
     double u[kChainMaxCand], pref[kChainMaxCand];                          // acceptance draw, prefactor (1; phi V / N; (N + 1) / (phi V))
     double sites[kChainMaxCand][kMaxFusedSitesWide][3];                    // candidate rows, site stride kMaxFusedSitesWide
+    // the WIDE instances only (behind everything the others read): the rows of molecules of more than kMaxFusedSitesWide
+    // sites -- 24 KB at 16 rows of 63 sites, beyond the argument segment -- in pinned host memory the roles read (row c at
+    // wide_sites + c kFarmWideSites 3; rows of smaller molecules stay in `sites`), per residue type the k role's form and
+    // its tile, the rows' first tasks, and where the pair role's slabs start in dynamic LDS
+    const double *wide_sites;
+    const int *row_first;
+    int wide_at;                                 // bytes: the Coulomb table's, rounded up to 16
+    signed char kform[kMaxRes];                  // kFarmForm*
+    int wide_rpt[kMaxRes];                       // vector form: rows per tile
+    int wide_nss[kMaxRes];                       // site-states per tile (the layout of the form's tables)
 };
 static_assert(sizeof(BoxDev) + sizeof(ChainArgs) + 160 <= 4096, "a window must fit the kernel-argument segment");
 
@@ -78,7 +101,108 @@ static_assert(sizeof(BoxDev) + sizeof(ChainArgs) + 160 <= 4096, "a window must f
 // TRI: triclinic box -- the pair role runs the register-site sweeps with ComputeDistance's image search (the batched path's
 // kernels for such boxes: the same sums); everything else of a window is the same (the phase tables take the box's reciprocal
 // matrix either way).
-template <bool FLAT, bool FASTW, bool TRI = false>
+// ---- the WIDE instances' pieces for a row of a molecule of more than kMaxFusedSitesWide sites (farm_wide_pair_unit and
+// farm_wide_k_role are their models; here the row comes from the window's block and A + delta goes to the row's own buffer)
+// One pair work unit (entry, split) by ONE WAVE: the candidate row copied into the wave's row in dynamic LDS, then
+// pair_sweep_item<0, ...> with the wave's slabs: the batched path's NS = 0 sweep of the unit, the engine's nsplit.
+__device__ __forceinline__ void chain_wide_pair_unit(const Topo &tp, const BoxDev &bx, const double *pos, const int *nmol, const double *res_q,
+                                                     const int *res_atype, const double2 *pair_tab, const ChainArgs &g, int c, bool is_new,
+                                                     int split, char *s_dyn, const double2 *s_pair, int wave, int lane, int w) {
+    double *slab = reinterpret_cast<double *>(s_dyn + g.wide_at);
+    double *cand = slab + (size_t)wave * kFarmWideSites * 3;
+    double *w_site = slab + (size_t)kPairWaves * kFarmWideSites * 3 + (size_t)wave * kSiteChunk * 4;
+    int *w_sty = reinterpret_cast<int *>(slab + (size_t)kPairWaves * (kFarmWideSites * 3 + kSiteChunk * 4)) + wave * kSiteChunk;
+    const int t = g.t[c], kind = g.kind[c];
+    if (is_new) {
+        if (lane < tp.n1[t]) {
+            const double *row = g.wide_sites + ((size_t)c * kFarmWideSites + lane) * 3;
+            for (int d = 0; d < 3; ++d) cand[lane * 3 + d] = row[d];
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    // old state: the resident molecule; new state: the candidate row; an insertion excludes nothing
+    const PairItem it{g.replica, t, kind == 1 ? -1 : g.m[c], is_new ? 0 : -1, 0};
+    pair_sweep_item<0, false, false, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, w_site, w_sty, it, cand,
+                                                         kFarmWideSites, split, g.nsplit, lane, g.partials, w);
+}
+
+// The k role of such a row c (every thread of the workgroup): the row into LDS, the sweep of the type's form -- row form,
+// vector wide form or untiled matrix-unit wide form -- with A + delta into the row's buffer g.alt + c n_slots (`sc1` stores:
+// the resolving workgroup copies it), the intra term of an insertion / deletion on the spare waves meanwhile (one thread up
+// to kIntraThreadMax sites, one wave above: launch_intra's rule), and the energies into g.res[c].  Dynamic LDS: kFarmKFront
+// bytes of row and intra tiles, the form's tables behind them.
+__device__ __forceinline__ void chain_wide_k_role(const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q, const int *trj,
+                                                  const double2 *tw, int n_tasks, const RecipRow *rows, int n_rows, double2 *A,
+                                                  const ChainArgs &g, int c, char *s_dyn, double *s_red, int tid) {
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int t = g.t[c], kind = g.kind[c], link = g.link[c];
+    const int n1 = tp.n1[t];
+    double *cand = reinterpret_cast<double *>(s_dyn);
+    double4 *intra_a = reinterpret_cast<double4 *>(s_dyn + (size_t)kFarmWideSites * 3 * sizeof(double)), *intra_b = intra_a + kFarmWideSites;
+    double2 *tabs = reinterpret_cast<double2 *>(s_dyn + kFarmKFront);
+    if (kind != 2 && tid < n1) {
+        const double *row = g.wide_sites + ((size_t)c * kFarmWideSites + tid) * 3;
+        for (int d = 0; d < 3; ++d) cand[tid * 3 + d] = row[d];
+    }
+    __syncthreads();
+    double2 *A_other = g.alt + (size_t)c * bx.n_slots;
+    const RecipItem it{g.replica, t, g.m[c], kind, 0, 0, 0};
+    const bool active = tid < kBlock;
+    // ComputeIntraResidueRealCoulombEnergySingleMol of the inserted (candidate row) / deleted (resident) molecule
+    auto spare = [&] {
+        if (link == -2 || kind == 0) return;
+        const PairItem pit{g.replica, t, g.m[c], kind == 1 ? 0 : -1, 0};
+        if (n1 <= kIntraThreadMax) {
+            if (tid == kBlock)
+                __hip_atomic_store(&g.res[c].intra, intra_energy(tp, bx, pos, res_q, pit, cand, kFarmWideSites), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        } else if (wave == kWavesPerBlock) {
+            const double u = intra_energy_wave<kFarmWideSites>(tp, bx, pos, res_q, pit, cand, kFarmWideSites, lane, intra_a, intra_b, [] {
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            });
+            if (lane == 0) __hip_atomic_store(&g.res[c].intra, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    double acc = 0.0, acc0 = 0.0;
+    const int form = g.kform[t];
+    if (form == kFarmFormRows) {
+        const RecipLds v = recip_lds_view(tp, bx, it, n_rows, tabs);
+        RecipInFlight<kRecipTaskChunk> inflight;
+        recip_rows_tables(tp, bx, pos, res_q, rows, n_rows, it, cand, v, tid, active,
+                          [&] { recip_rows_prefetch<false>(inflight, trj, tw, n_tasks, A, tid); });
+        if (active) recip_rows_pass<false, true, kRecipTaskChunk, 2>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0, A_other);
+        else spare();
+    } else if (form == kFarmFormWideMfma) {
+        recip_wide_sweep<false, true, true, false, 2>(tp, bx, pos, res_q, trj, tw, rows, g.row_first, n_rows, 0, g.wide_nss[t], A, it, cand,
+                                                      nullptr, n_tasks, tabs, tid, active, acc, acc0, A_other, spare);
+    } else {
+        recip_wide_sweep<false, true, false, false, 2>(tp, bx, pos, res_q, trj, tw, rows, g.row_first, n_rows, g.wide_rpt[t], g.wide_nss[t], A,
+                                                       it, cand, nullptr, n_tasks, tabs, tid, active, acc, acc0, A_other, spare);
+    }
+    if (active) {
+        acc = wave_sum(acc);
+        acc0 = wave_sum(acc0);
+        if (lane == 0) { s_red[2 * wave] = acc; s_red[2 * wave + 1] = acc0; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double u = 0.0, u0 = 0.0;
+        for (int wv = 0; wv < kWavesPerBlock; ++wv) { u += s_red[2 * wv]; u0 += s_red[2 * wv + 1]; }
+        __hip_atomic_store(&g.res[c].u_new, u * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ewald_energy.f90:272
+        __hip_atomic_store(&g.res[c].u_old, u0 * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// WIDE: a window that carries a row of a molecule of 6..63 sites (orthorhombic boxes).  Such a row's pair
+// units run the LDS-staged NS = 0 sweep (the batched path's kernel for the size, the engine's nsplit: the resolver's split-order
+// sum is the batched path's) with its candidate row and slabs in dynamic LDS behind the Coulomb table; its k role takes the
+// form of its own type, storing A + delta into the row's own buffer; its intra term runs on the k workgroup's spare waves.
+// Rows of <= kMaxFusedSitesWide sites take the narrow instance's code; the ticket, the hand-offs, the resolver and the commit
+// (a copy of the accepted row's buffer, then recip_commit_tail, which fits one wave up to 63 sites) are the same code.
+template <bool FLAT, bool FASTW, bool TRI = false, bool WIDE = false>
 __global__ __launch_bounds__(kChainBlock, 1) void chain_window_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
@@ -112,6 +236,10 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_window_kernel(
     if ((int)blockIdx.x < n) {
         // ---------------- k role: candidate c
         const int c = blockIdx.x;
+        if (WIDE && tp.n1[g.t[c]] > kMaxFusedSitesWide) {
+            mark(my_role, 1);
+            chain_wide_k_role(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, A, g, c, s_dyn, s_red, tid);
+        } else {
         const int kind = g.kind[c], link = g.link[c];
         RecipItem it{g.replica, g.t[c], g.m[c], kind, c, 0, 0};
         const RecipLds v = recip_lds_view(tp, bx, it, n_rows, reinterpret_cast<double2 *>(s_dyn));
@@ -143,6 +271,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_window_kernel(
             __hip_atomic_store(&g.res[c].u_new, u * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ewald_energy.f90:272
             __hip_atomic_store(&g.res[c].u_old, u0 * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
+        }
         mark(my_role, 2);
     } else {
         // ---------------- pair role: one wave per (entry, split)
@@ -161,6 +290,9 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_window_kernel(
             // old state: the resident molecule; new state: the candidate row; an insertion excludes nothing
             const PairItem it{g.replica, t, kind == 1 ? -1 : g.m[c], g.ent_new[ent] ? c : -1, 0};
             const int n1 = tp.n1[t];
+            if (WIDE && n1 > kMaxFusedSitesWide) {
+                chain_wide_pair_unit(tp, bx, pos, nmol, res_q, res_atype, pair_tab, g, c, g.ent_new[ent] != 0, split, s_dyn, s_pair, wave, lane, w);
+            } else {
 #define MGPU_CHAIN_PAIR(NS)                                                                                              \
             do {                                                                                                         \
                 if constexpr (FLAT)                                                                                      \
@@ -178,6 +310,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_window_kernel(
                 default: MGPU_CHAIN_PAIR(5); break;
             }
 #undef MGPU_CHAIN_PAIR
+            }
         }
         mark(my_role, 2);
     }
@@ -282,7 +415,9 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_window_kernel(
         double *to = reinterpret_cast<double *>(A);
         for (int i = tid; i < 2 * bx.n_slots; i += kChainBlock) to[i] = load_sc1(from + i);
         mark(rs, 5);
-        if (tid < kBlock) recip_commit_tail(tp, pos, nmol, it, &g.sites[src][0][0], tid);
+        const double *row = &g.sites[src][0][0];
+        if (WIDE && tp.n1[g.t[first]] > kMaxFusedSitesWide) row = g.wide_sites + (size_t)src * kFarmWideSites * 3;
+        if (tid < kBlock) recip_commit_tail(tp, pos, nmol, it, row, tid);
         mark(rs, 6);
     }
 }
@@ -360,14 +495,6 @@ struct FarmArgs {
     int wide_nss[kMaxRes];                       // site-states per tile (the layout of the form's tables)
 };
 static_assert(sizeof(BoxDev) + sizeof(FarmArgs) + 160 <= 4096, "a farm window must fit the kernel-argument segment");
-// WIDE instances (launches with a molecule of more than kMaxFusedSitesWide sites, at most kFarmWideSites - 1): the k role's
-// form per residue type, as recip_plan picks it for the type alone
-constexpr int kFarmFormRows = 0, kFarmFormWideVector = 1, kFarmFormWideMfma = 2;
-constexpr int kFarmWideSites = 64;               // candidate row stride of a wide chain (plane-major types: n1 <= 63)
-// dynamic LDS of a wide chain's k role: candidate row | the intra wave's two site tiles | the form's tables
-constexpr size_t kFarmKFront = (size_t)kFarmWideSites * 3 * sizeof(double) + 2 * (size_t)kFarmWideSites * sizeof(double4);
-// dynamic LDS of the pair role behind the Coulomb table: per wave a candidate row, a site slab and a type slab (NS = 0 sweep)
-constexpr size_t kFarmWidePairBytes = (size_t)kPairWaves * ((kFarmWideSites * 3 + kSiteChunk * 4) * sizeof(double) + kSiteChunk * sizeof(int));
 
 // Diagnostic builds only (-DMGPU_FARM_STAMPS, tools/farm_stages.py; the shipped library has none of this): wall-clock stamps of
 // chain 0's k role (row 0), the launch's first pair workgroup (row 1) and chain 0's resolver (row 2).

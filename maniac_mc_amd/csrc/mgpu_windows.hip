@@ -87,22 +87,89 @@ int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int
 
 extern "C" {
 
+// ---- the k role of a window's row by its residue type (single-chain and farm windows) -------------
+// The k role a window (farm or, for a type of more than kMaxFusedSitesWide sites, single-chain) gives a row of residue type t -- the form recip_plan picks for the type alone, as the batched
+// path's per-type launches do (recip_groups) -- and the dynamic LDS that role needs.  false: windows do not take the type
+// (site-major types, i.e. molecules of kFarmWideSites sites or more; a molecule of <= kMaxFusedSitesWide sites whose type
+// does not take the row form; a larger one in a triclinic box -- there is no WIDE instance with the image search -- or whose
+// type takes the per-k or the tiled matrix-unit form).
+struct FarmTypeForm {
+    int form = kFarmFormRows, rpt = 0, nss = 0;
+    size_t lds = 0;
+};
+static bool farm_type_form(const mgpu_engine *e, int t, FarmTypeForm &f) {
+    const int n1 = e->tp.n1[t];
+    if (e->tp.site_major[t] || n1 >= kFarmWideSites) return false;
+    const RecipPlan p = recip_plan(e, n1, true);
+    f = FarmTypeForm{};
+    if (n1 <= kMaxFusedSitesWide) {                                 // the narrow instance's chains
+        if (p.form != MGPU_RECIP_FORM_ROWS) return false;
+        f.lds = recip_rows_lds_bytes(e, n1);
+        return true;
+    }
+    if (e->bx.triclinic) return false;
+    switch (p.form) {
+        case MGPU_RECIP_FORM_ROWS:
+            f.lds = kFarmKFront + recip_rows_lds_bytes(e, n1);
+            return true;
+        case MGPU_RECIP_FORM_WIDE_VECTOR:                           // launch_recip's tables (2 n1 site-states)
+        case MGPU_RECIP_FORM_WIDE_MFMA:                             // ... one tile of site-states
+            f.form = p.mfma_tile ? kFarmFormWideMfma : kFarmFormWideVector;
+            f.rpt = p.wide_rpt; f.nss = p.wide_nss;
+            f.lds = kFarmKFront + p.wide_lds;
+            return true;
+        default:                                                    // the tiled matrix-unit form, the per-k form
+            return false;
+    }
+}
+
 // ---- single-chain windows --------------------------------------------------------------------
 
-// largest window the engine accepts, 0 where the one-launch path does not apply (molecules of more than kMaxFusedSitesWide sites
-// among the active types, per-k reciprocal form)
+// Dynamic LDS of the WIDE instances for this engine (mgpu_internal.h): the larger of the pair role's (Coulomb table, then the
+// waves' candidate rows and slabs) and the k role's over the types a row may carry; a window adds its resolver's staging.
+// Beyond 64 KiB the instances opt in, up to the budget of the WIDE farm windows (kFarmWideLdsMax).
+constexpr size_t kFarmWideStaticMax = 16 * 1024, kFarmWideLdsMax = 160 * 1024 - kFarmWideStaticMax;
+static size_t chain_wide_lds(const mgpu_engine *e) {
+    size_t lds = chain_wide_pair_lds_bytes(e->coul_bytes, kPairWaves, kSiteChunk);
+    for (int t = 0; t < e->tp.n_res; ++t) {
+        FarmTypeForm f;
+        if (e->frozen[t] || !farm_type_form(e, t, f)) continue;
+        // (farm_type_form's size of a type of more than kMaxFusedSitesWide sites = kFarmKFront + its form's tables)
+        lds = std::max(lds, e->tp.n1[t] > kMaxFusedSitesWide ? chain_wide_k_lds_bytes(f.lds - kFarmKFront) : f.lds);
+    }
+    return lds;
+}
+
+// largest window the engine accepts, 0 where the one-launch path does not apply: a per-k reciprocal form, a Coulomb table
+// beyond 64 KiB, a site-major active type, and an active type of more than kMaxFusedSitesWide sites unless wide windows are on
+// (mgpu_chain_set_wide) and windows take the type (farm_type_form: an orthorhombic box, fewer than kFarmWideSites sites, the
+// row form or an untiled wide form)
 static int chain_max_candidates(const mgpu_engine *e) {
     int n1_max = 1;
+    bool wide = false;
     for (int t = 0; t < e->tp.n_res; ++t) {
         if (!e->is_active[t]) continue;
-        if (e->tp.n1[t] > kMaxFusedSitesWide || e->tp.site_major[t]) return 0;
+        if (e->tp.site_major[t]) return 0;
+        if (e->tp.n1[t] > kMaxFusedSitesWide) {
+            FarmTypeForm f;
+            if (!e->chain.wide || !farm_type_form(e, t, f)) return 0;
+            wide = true;
+            continue;
+        }
         n1_max = std::max(n1_max, e->tp.n1[t]);
     }
     if (!recip_by_rows(e, n1_max)) return 0;
     if (e->coul_bytes > kLdsDefaultMax) return 0;
+    if (wide && chain_wide_lds(e) > kFarmWideLdsMax) return 0;
     // the resolving workgroup stages every split partial of the window in LDS: 2 entries per candidate at most
-    const int by_lds = (int)(kLdsDefaultMax / ((size_t)2 * e->pair_nsplit * sizeof(double2)));
+    const int by_lds = chain_window_steps_by_lds(e->pair_nsplit);
     return std::max(0, std::min(kChainMaxCand, by_lds));
+}
+
+int mgpu_chain_set_wide(mgpu_engine *e, int on) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    e->chain.wide = on != 0;
+    return MGPU_OK;
 }
 
 int mgpu_chain_window_capacity(const mgpu_engine *e, int *max_candidates) {
@@ -180,6 +247,11 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
         HIP_TRY(hipMemset(ch.d_ticket, 0, sizeof(int)));
         HIP_TRY(hipDeviceSynchronize());
     }
+    if (ch.wide && !ch.h_rows) {
+        // the rows of wide windows: two blocks, taken in turn -- the kernel of the window before may still read its accepted
+        // row for the commit (behind the tag) while the next window's rows are written; the launches of a stream run in order
+        HIP_TRY(hipHostMalloc((void **)&ch.h_rows, 2 * kChainWideRowsBytes, hipHostMallocCoherent));
+    }
     const Topo *d_topo = nullptr;
     if ((rc = chain_topo(e, &d_topo))) return rc;
     if (e->a_switched && (rc = normalize_A(e))) return rc;      // (the window reads and writes d_A)
@@ -189,13 +261,18 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     bool fast = replica_in_range(e, replica);
     char cand_ok[kChainMaxCand];
     int n1_max = 1, n_ent = 0;
+    bool wide = false;
+    double *wide_rows = ch.h_rows ? ch.h_rows + ((ch.seq + 1) & 1) * (kChainWideRowsBytes / sizeof(double)) : nullptr;
     for (int c = 0; c < n; ++c) {
         const int k = kind[c];
         if (k < MGPU_MOVE || k > MGPU_DELETION) return set_error(MGPU_ERR_INVALID_ARG, "chain_window: unknown candidate kind");
         if (t[c] < 0 || t[c] >= e->tp.n_res) return set_error(MGPU_ERR_INVALID_ARG, "chain_window: residue type out of range");
         const int n1 = e->tp.n1[t[c]];
-        if (n1 > site_stride || n1 > kMaxFusedSitesWide || e->tp.site_major[t[c]])
+        const bool wide_row = n1 > kMaxFusedSitesWide;
+        FarmTypeForm tf;
+        if (n1 > site_stride || e->tp.site_major[t[c]] || (wide_row && (!ch.wide || !farm_type_form(e, t[c], tf))))
             return set_error(MGPU_ERR_INVALID_ARG, "chain_window: molecule too large for the one-launch path");
+        wide = wide || wide_row;
         const size_t idx = (size_t)replica * e->tp.n_res + t[c];
         if (e->d_com && e->frames_ok[idx])
             return set_error(MGPU_ERR_STATE, "chain_window: this replica holds molecule frames (mgpu_replica_set_frames)");
@@ -208,7 +285,7 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
         if ((rc = check_candidate(e, c, replica, t[c], mc, k != MGPU_CREATION))) return rc;
         if (k == MGPU_CREATION && lk != -2 && e->h_nmol[idx] >= e->tp.cap[t[c]])
             return set_error(MGPU_ERR_CAPACITY, "chain_window: residue type is at mol_capacity");
-        n1_max = std::max(n1_max, n1);
+        if (!wide_row) n1_max = std::max(n1_max, n1);
         g.t[c] = t[c]; g.m[c] = mc; g.kind[c] = (signed char)k; g.link[c] = (signed char)lk;
         g.u[c] = accept_u[c]; g.pref[c] = accept_pref[c];
         const double *row = sites + (size_t)c * site_stride * 3;
@@ -216,7 +293,7 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
         if (k != MGPU_DELETION) {
             // the engine's site order for a frozen type is not the caller's: such types are inactive and never move
             if (e->frozen[t[c]]) return set_error(MGPU_ERR_INVALID_ARG, "chain_window: frozen residue types do not move");
-            std::memcpy(&g.sites[c][0][0], row, (size_t)n1 * 3 * sizeof(double));
+            std::memcpy(wide_row ? wide_rows + (size_t)c * kFarmWideSites * 3 : &g.sites[c][0][0], row, (size_t)n1 * 3 * sizeof(double));
             cand_ok[c] = sites_in_range(e, row, n1) ? 1 : 0;
             if (lk != -2) fast = fast && cand_ok[c];
         }
@@ -226,8 +303,22 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
         if (k != MGPU_DELETION) { g.ent_new_of[c] = (signed char)n_ent; g.ent_c[n_ent] = (unsigned char)c; g.ent_new[n_ent] = 1; ++n_ent; }
     }
     const int nsplit = e->pair_nsplit;
-    const size_t lds = std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), (size_t)n_ent * nsplit * sizeof(double2));
-    if (lds > kLdsDefaultMax) return set_error(MGPU_ERR_CAPACITY, "chain_window: the window does not fit the LDS budget");
+    // a row of more than kMaxFusedSitesWide sites: the WIDE instance (its own LDS rule), else the narrow one
+    const size_t lds = std::max(wide ? chain_wide_lds(e) : std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)),
+                                chain_resolver_lds_bytes(n_ent, nsplit));
+    if (lds > (wide ? kFarmWideLdsMax : kLdsDefaultMax)) return set_error(MGPU_ERR_CAPACITY, "chain_window: the window does not fit the LDS budget");
+    auto wide_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, true>); };
+    if (lds > kLdsDefaultMax && lds > ch.wide_lds_opted) {
+        // beyond 64 KiB of dynamic LDS a kernel opts in (gfx950: up to 160 KiB per workgroup); only the WIDE instances get here
+        hipError_t err = hipSuccess;
+        auto opt_in = [&](auto kernel) {
+            if (err == hipSuccess) err = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        };
+        for_all_bools([&](auto... flags) { wide_family(opt_in, flags...); }, std::integral_constant<int, 2>{});
+        if (err != hipSuccess)
+            return set_error(MGPU_ERR_HIP, std::string("hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds): ") + hipGetErrorString(err));
+        ch.wide_lds_opted = lds;
+    }
     ch.seq += 1;
     for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
     g.stamps = ch.timing ? 1 : 0;
@@ -235,6 +326,16 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     g.host_out = ch.h_out; g.host_tag = ch.h_tag; g.seq = ch.seq;
     g.n = n; g.n_ent = n_ent; g.nsplit = nsplit; g.replica = replica;
     g.temperature = temperature; g.e_recip = recip_energy; g.margin = ch.margin;
+    if (wide) {
+        g.wide_sites = wide_rows;
+        g.row_first = e->d_row_first;
+        g.wide_at = (int)chain_wide_pair_at(e->coul_bytes);
+        for (int tt = 0; tt < e->tp.n_res; ++tt) {
+            FarmTypeForm f;
+            if (!farm_type_form(e, tt, f)) continue;              // (no row of such a type passed the checks above)
+            g.kform[tt] = (signed char)f.form; g.wide_rpt[tt] = f.rpt; g.wide_nss[tt] = f.nss;
+        }
+    }
     const int grid = n + (n_ent * nsplit + kPairWaves - 1) / kPairWaves;
     const bool ff = fast && e->pair_fast_fold;
     ln.dirty = true;
@@ -245,6 +346,7 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     };
     // (the image search has no flat and no fast-fold form)
     if (e->bx.triclinic) launch(chain_window_kernel<false, false, true>);
+    else if (wide) with_bools([&](auto... flags) { wide_family(launch, flags...); }, e->pair_flat, ff);
     else with_bools([&](auto FLAT, auto FASTW) { launch(chain_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); }, e->pair_flat, ff);
     HIP_TRY(hipGetLastError());
     // ---- wait for the tag: the results are in host memory when it shows this window's number
@@ -279,45 +381,9 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
 // kFarmDepth windows per lane may be in flight (a farm whose move selection does not depend on earlier outcomes -- NVT --
 // queues the next step before it has seen the last).
 
-// The k role a farm window gives a chain of residue type t -- the form recip_plan picks for the type alone, as the batched
-// path's per-type launches do (recip_groups) -- and the dynamic LDS that role needs.  false: windows do not take the type
-// (site-major types, i.e. molecules of kFarmWideSites sites or more; a molecule of <= kMaxFusedSitesWide sites whose type
-// does not take the row form; a larger one in a triclinic box -- there is no WIDE instance with the image search -- or whose
-// type takes the per-k or the tiled matrix-unit form).
-struct FarmTypeForm {
-    int form = kFarmFormRows, rpt = 0, nss = 0;
-    size_t lds = 0;
-};
-static bool farm_type_form(const mgpu_engine *e, int t, FarmTypeForm &f) {
-    const int n1 = e->tp.n1[t];
-    if (e->tp.site_major[t] || n1 >= kFarmWideSites) return false;
-    const RecipPlan p = recip_plan(e, n1, true);
-    f = FarmTypeForm{};
-    if (n1 <= kMaxFusedSitesWide) {                                 // the narrow instance's chains
-        if (p.form != MGPU_RECIP_FORM_ROWS) return false;
-        f.lds = recip_rows_lds_bytes(e, n1);
-        return true;
-    }
-    if (e->bx.triclinic) return false;
-    switch (p.form) {
-        case MGPU_RECIP_FORM_ROWS:
-            f.lds = kFarmKFront + recip_rows_lds_bytes(e, n1);
-            return true;
-        case MGPU_RECIP_FORM_WIDE_VECTOR:                           // launch_recip's tables (2 n1 site-states)
-        case MGPU_RECIP_FORM_WIDE_MFMA:                             // ... one tile of site-states
-            f.form = p.mfma_tile ? kFarmFormWideMfma : kFarmFormWideVector;
-            f.rpt = p.wide_rpt; f.nss = p.wide_nss;
-            f.lds = kFarmKFront + p.wide_lds;
-            return true;
-        default:                                                    // the tiled matrix-unit form, the per-k form
-            return false;
-    }
-}
-
 // Dynamic LDS of the WIDE instances for this engine: the larger of the pair role's (Coulomb table, then the waves' candidate
 // rows and slabs), the k role's over the active types, and the resolving waves' scratch.  gfx950 gives a workgroup up to
 // 160 KiB; the instances' static LDS takes up to kFarmWideStaticMax of it.
-constexpr size_t kFarmWideStaticMax = 16 * 1024, kFarmWideLdsMax = 160 * 1024 - kFarmWideStaticMax;
 static size_t farm_wide_lds(const mgpu_engine *e) {
     size_t lds = ((e->coul_bytes + 15) & ~(size_t)15) + kFarmWidePairBytes;
     lds = std::max(lds, farm_resolver_scratch_bytes(e->pair_nsplit));

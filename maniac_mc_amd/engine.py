@@ -453,6 +453,10 @@ class Engine:
     def chain_set_margin(self, rel):
         check(self.L.mgpu_chain_set_margin(self.h, C.c_double(rel)))
 
+    def chain_set_wide(self, on=True):
+        """mgpu_chain_set_wide: single-chain windows also take rigid molecules of 6 to 63 sites (off by default)."""
+        check(self.L.mgpu_chain_set_wide(self.h, C.c_int(1 if on else 0)))
+
     def chain_set_timing(self, on=True):
         check(self.L.mgpu_chain_set_timing(self.h, C.c_int(1 if on else 0)))
 

@@ -353,6 +353,13 @@ module maniac_gpu
             integer(c_int), intent(out) :: max_candidates
             integer(c_int) :: rc
         end function
+        ! windows also take rigid molecules of 6 to 63 sites (off by default)
+        function mgpu_chain_set_wide(e, on) bind(C, name="mgpu_chain_set_wide") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: on
+            integer(c_int) :: rc
+        end function
         function mgpu_chain_window(e, replica, n, t, m, kind, link, sites, site_stride, accept_u, accept_pref, temperature, &
                                    recip_energy, old_energy, new_energy, first_accepted, undecided) &
                 bind(C, name="mgpu_chain_window") result(rc)

@@ -44,7 +44,7 @@ module mc_chain
               mchain_set_moves, mchain_set_reservoir_box, mchain_set_reservoir_residue, mchain_run, &
               mchain_get_energy, mchain_get_counters, mchain_get_counts, mchain_get_molecule, mchain_get_steps, &
               mchain_set_mode, mchain_set_as_written, mchain_set_log_header, mchain_write_log_header, &
-              mchain_set_speculation, mchain_set_chain_windows, mchain_get_loop_seconds, mchain_get_times, &
+              mchain_set_speculation, mchain_set_chain_windows, mchain_set_wide_windows, mchain_get_loop_seconds, mchain_get_times, &
               mchain_export_template
 
     real(real64), parameter :: PI = 3.14159265358979323846_real64, TWOPI = 2.0_real64 * PI
@@ -82,6 +82,8 @@ module mc_chain
     ! committed) by this loop.  chain_windows: wanted (default); chain_cap: the engine's window capacity, 0 = the engine
     ! cannot (triclinic box, large molecules) and the window goes through mgpu_gcmc_trial_submit / wait as before.
     logical, save :: chain_windows = .true.
+    ! wide_windows: one-launch windows also for rigid molecules of 6 to 63 sites (mgpu_chain_set_wide); off unless asked for
+    logical, save :: wide_windows = .false.
     integer, save :: chain_cap = 0
     integer, parameter :: BY_HOST = -1, DEVICE_REJECTED = 0, DEVICE_ACCEPTED = 1
     ! time spent inside the Monte Carlo loop proper (no initial energy, no files), seconds
@@ -440,6 +442,11 @@ contains
         integer(c_int), value :: on
         chain_windows = on /= 0
     end subroutine mchain_set_chain_windows
+
+    subroutine mchain_set_wide_windows(on) bind(C, name="mchain_set_wide_windows")
+        integer(c_int), value :: on
+        wide_windows = on /= 0
+    end subroutine mchain_set_wide_windows
 
     function mchain_get_loop_seconds() bind(C, name="mchain_get_loop_seconds") result(sec)
         real(c_double) :: sec
@@ -1227,6 +1234,8 @@ contains
         ! the engine's one-launch window path, where it applies to this system (and the host wants it)
         chain_cap = 0
         if (fused .and. chain_windows) then
+            stat = mgpu_chain_set_wide(S%engine, merge(1_c_int, 0_c_int, wide_windows))
+            call note(stat)
             stat = mgpu_chain_window_capacity(S%engine, cap)
             call note(stat)
             if (stat == 0) chain_cap = int(cap)

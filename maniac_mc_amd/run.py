@@ -114,9 +114,14 @@ def set_chain_state(H, engine_h, system, inp, dat, mol_capacity, rdat=None):
     return hold + [keep] + ([rkeep] if rdat is not None else [])
 
 
+# one-launch windows for molecules of 6 to 63 sites: the default of run_simulation and of the command line.  Off until the path
+# has been timed against the batched windows (LABNOTES round 10): --wide-chain-windows / wide_chain_windows=True turn it on
+WIDE_CHAIN_WINDOWS_DEFAULT = False
+
+
 def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoir_path=None, device=0,
                    mol_capacity=None, nb_block=None, nb_step=None, seams=False, as_written=False, speculate=4,
-                   chain_windows=True, chain_margin=None):
+                   chain_windows=True, chain_margin=None, wide_chain_windows=WIDE_CHAIN_WINDOWS_DEFAULT):
     """Run the chain; returns a dict with the final energies (K), counters, molecule counts, step sizes.
 
     ``seed``: None -> the input file's ``seed`` if present, else the generator is left unseeded
@@ -135,7 +140,10 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     ``chain_windows``: True (default; batched mode only) -> a window is ONE kernel launch (mgpu_chain_window): the engine
     evaluates its steps, applies the acceptance rule to them in order with the loop's own draws and commits the first
     accepted one, leaving to the loop only the steps too close to call; where the engine cannot (triclinic box, molecules
-    of more than five sites) the loop falls back to the batched calls by itself.  False -> the batched calls always.
+    of more than five sites without ``wide_chain_windows``) the loop falls back to the batched calls by itself.  False -> the
+    batched calls always.
+    ``wide_chain_windows``: True -> one-launch windows also for rigid molecules of 6 to 63 sites (mgpu_chain_set_wide; an
+    orthorhombic box, the row form or an untiled wide form of the reciprocal update).  The files do not depend on it.
     ``chain_margin``: relative width of the band around an acceptance probability inside which the engine leaves the step to
     this loop's own exp (default: the engine's 16 ulp; tests widen it to drive the loop's side of that hand-over).
     """
@@ -156,6 +164,7 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
         H.mchain_set_as_written(C.c_int(1 if as_written else 0))
         H.mchain_set_speculation(C.c_int(1 if seams else max(1, int(speculate))))
         H.mchain_set_chain_windows(C.c_int(1 if chain_windows else 0))
+        H.mchain_set_wide_windows(C.c_int(1 if wide_chain_windows else 0))
         H.mchain_get_loop_seconds.restype = C.c_double
         header = header_text(inp, dat, maniac_path, data_path, inc_path, eng, reservoir_path, rdat)
         H.mchain_set_log_header(header, C.c_int(len(header)))
@@ -206,6 +215,10 @@ def main(argv=None):
                     help="speculative window: steps evaluated per engine call (same states and files; 1: one step per call)")
     ap.add_argument("--no-chain-windows", action="store_true",
                     help="evaluate windows through the batched submit / wait calls instead of the one-launch path")
+    ap.add_argument("--wide-chain-windows", dest="wide_chain_windows", action="store_true", default=WIDE_CHAIN_WINDOWS_DEFAULT,
+                    help="one-launch windows also for rigid molecules of 6 to 63 sites")
+    ap.add_argument("--no-wide-chain-windows", dest="wide_chain_windows", action="store_false",
+                    help="such molecules' windows through the batched calls")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
     ap.add_argument("--replicas", type=int, default=None,
@@ -246,7 +259,8 @@ def main(argv=None):
               f"{os.path.join(a.out, '')}replica_NNNN/ and replicas.dat")
         return 0
     res = run_simulation(a.maniac, a.data, a.inc, a.out, seed=a.seed, reservoir_path=a.reservoir, device=a.device,
-                         as_written=a.as_written, speculate=a.speculate, chain_windows=not a.no_chain_windows)
+                         as_written=a.as_written, speculate=a.speculate, chain_windows=not a.no_chain_windows,
+                         wide_chain_windows=a.wide_chain_windows)
     e = res["energy"]
     print(f"final energy (K): total {e['total']:.6f}  non_coulomb {e['non_coulomb']:.6f}  coulomb {e['coulomb']:.6f}  "
           f"recip {e['recip_coulomb']:.6f};  molecules {res['n_mol'].tolist()};  output in {os.path.join(a.out, '')}")
