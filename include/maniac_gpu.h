@@ -558,6 +558,65 @@ int mgpu_farm_window_flush(mgpu_engine *e);
 int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long long *undecided);
 
 /* ------------------------------------------------------------------------------------------
+ * Chain runs: launches of ONE chain queued back to back, each continuing from a step cursor in device memory.
+ * Replaces, for a block of NVT steps of one chain, MonteCarloLoop's body (src/monte_carlo.f90:40-86) without the host's
+ * turn-round between an accepted step and the next trial.  In such a block the random numbers of step i + 1 do not depend on
+ * the outcome of step i (src/monte_carlo.f90:50-75, src/translation.f90:93-112, src/rotation.f90, src/monte_carlo_utils.f90:
+ * 30-92): the driver draws the steps ahead as records, pushes them, queues launches and collects results in step order
+ * whenever it gets to them.  Every launch reads {cursor, pushed, stalled} from device memory, builds the next up to k steps
+ * as trials of the state it finds (the farm windows' construction from the resident frames, mgpu_replica_set_frames),
+ * evaluates them (the batched path's sums, bit for bit: the engine's nsplit), decides them in order (ComputeOldEnergy /
+ * ComputeNewEnergy, src/monte_carlo_utils.f90:275-395; mc_acceptance_probability, :184-226), commits the first accepted one
+ * (AcceptMove), advances the cursor by the steps it consumed and writes their results into pinned host memory.  The only
+ * ordering between launches is lane 0's stream.
+ *   capacity    max_k steps per launch, max_in_flight launches whose results nobody has looked at, ring_steps steps pushed and
+ *               not yet collected.  All 0 where the path does not apply: mgpu_farm_window_capacity's reasons (a site-major
+ *               type, the per-k or tiled matrix-unit form, a Coulomb table over 64 KiB) and, because no such instance of
+ *               the kernel exists, every triclinic box (with or without mgpu_set_triclinic_moves), every active type of
+ *               more than 5 sites, and an engine that holds reservoirs.  Orthorhombic boxes whose active types have <= 5
+ *               sites and take the row form, framework boxes included, are served.
+ *   open        replaces the block's set-up (src/monte_carlo.f90:40-48): cursor 0, the block's step sizes and temperature.
+ *               The replica needs resident frames of every active type, lane 0 must be idle, one run per engine
+ *               (MGPU_ERR_STATE otherwise).  Drains every lane.
+ *   push        n records behind those pushed so far: what PickRandomResidueType / PickRandomMoleculeIndex and the move
+ *               drivers draw (src/monte_carlo.f90:50-75) -- t, m, move (0 nothing to do, 1 translation, 2 rotation), u5[n][5]
+ *               (mgpu_move_trial_submit's), accept_u[n].  MGPU_ERR_INVALID_ARG: move 3 / 4 (insertions and deletions do
+ *               not ride in a run), a slot >= the type's count, more than ring_steps steps uncollected; a refused push
+ *               changes nothing.  One asynchronous copy per push (two where the ring wraps) and the new count, on lane 0's
+ *               stream: launches queued BEFORE a push do not see it.
+ *   launch      queues n_launches launches and never waits for one (it copies A(k) back first only if another path has
+ *               switched some replica's buffers since the run was opened).  A launch that finds no step of its own, or a
+ *               chain that waits for a decision, does nothing (a "void" launch).  MGPU_ERR_STATE beyond max_in_flight.
+ *   collect     results of the next steps in order, at most max_steps: old_energy / new_energy [n_got][5] as
+ *               mgpu_farm_window_wait fills them, verdict 0 rejected, 1 accepted and committed, 5 nothing to do.  wait = 0:
+ *               what is there; wait = 1: blocks until one step, or a stall, is there (MGPU_ERR_STATE if nothing in flight
+ *               can produce it).  An UNDECIDED step (the margin rule of mgpu_chain_set_margin, or a probability that is
+ *               not a number) ends the call: its row is the last one returned, with verdict 2, *stalled_at = its step
+ *               (else -1); nothing at or behind it has been committed, launches already queued do nothing, and collect
+ *               returns nothing more until mgpu_chain_run_force.
+ *   force       the driver's decision (its own exp) for the stalled step, and the launch that obeys it, clears the flag
+ *               and goes on with the steps behind it; the step is then collected again with its final verdict.
+ *   close       drains lane 0; A(k) is in its primary buffer (a run never leaves it).  MGPU_ERR_STATE while a step is
+ *               stalled and unforced (the run stays open); a reload of the replica (mgpu_replica_set_molecules, _set_frames,
+ *               _set_num_molecules, the destination of mgpu_replica_copy) clears the stall, as for farm windows.
+ *   get_stats   since the engine was created: launches seen, steps they consumed, void launches, launches that ended at an
+ *               undecided step.  get_launches: (first step, steps consumed) of the launches seen since open, oldest first
+ *               (the last 1024).
+ * An open run does not lock the engine: every synchronous entry point DRAINS it first -- it waits for the launches queued so
+ * far and sees the state they committed; their results stay collectable -- and a submit on lane 0 is ordered behind them by
+ * the stream.  Single-driver: one host thread at a time opens, pushes, launches, collects, forces and closes a run. */
+int mgpu_chain_run_capacity(const mgpu_engine *e, int *max_k, int *max_in_flight, int *ring_steps);
+int mgpu_chain_run_open(mgpu_engine *e, int replica, int k, double t_step, double r_step, double temperature);
+int mgpu_chain_run_push(mgpu_engine *e, int n, const int *t, const int *m, const int *move, const double *u5, const double *accept_u);
+int mgpu_chain_run_launch(mgpu_engine *e, int n_launches);
+int mgpu_chain_run_collect(mgpu_engine *e, int max_steps, int wait, double *old_energy, double *new_energy, int *verdict, int *n_got,
+                           int *stalled_at);
+int mgpu_chain_run_force(mgpu_engine *e, int step, int accept);
+int mgpu_chain_run_close(mgpu_engine *e);
+int mgpu_chain_run_get_stats(mgpu_engine *e, long long *launches, long long *steps, long long *void_launches, long long *undecided);
+int mgpu_chain_run_get_launches(mgpu_engine *e, int max_launches, int *first, int *consumed, int *n_got);
+
+/* ------------------------------------------------------------------------------------------
  * The path's one exchange step: replicas are farmed over the GPUs of a node, one process per GPU,
  * and never communicate while they run; once per block every rank contributes its chains' molecule-count histogram
  * (what the reference records per chain in number_<res>.dat, src/write_utils.f90:144-150) and a few running sums, and

@@ -186,6 +186,10 @@ struct Lane {
 constexpr int kLanes = 4;
 constexpr int kFarmDepth = 4;           // farm windows a lane may have in flight
 constexpr int kFarmMaxChains = 4096;   // chains per farm window
+constexpr int kRunRingSteps = 4096;     // chain runs: steps pushed and not yet collected
+constexpr int kRunMaxInFlight = 64;     // ... launches queued whose tags have not been read
+constexpr int kRunLaunchRing = 256;     // ... their slots in pinned memory
+constexpr int kRunLogMax = 1024;        // ... launches mgpu_chain_run_get_launches remembers
 constexpr size_t kChainWideRowsBytes = (size_t)kChainMaxCand * kFarmWideSites * 3 * sizeof(double);   // one block of a wide window's rows
 
 // ---- From run-time values to template instances.  A launch site picks its kernel FAMILY with ordinary ifs, states the
@@ -365,6 +369,29 @@ struct mgpu_engine {
         std::atomic<long long> windows{0}, undecided{0};   // (the lanes may be driven by different host threads)
         std::mutex mu;                                     // the engine-wide blocks' first allocation
     } farm;
+    // a chain run (mgpu_chain_run_*): launches of one chain queued back to back on lane 0, each continuing from the cursor in
+    // device memory (chain_run_kernel).  Single-driver: one host thread opens, pushes, launches, collects and closes a run.
+    struct Run {
+        bool open = false;
+        int replica = -1, k = 0;
+        double t_step = 0.0, r_step = 0.0, temperature = 0.0;
+        bool fast = false;                           // every record so far admits the fast fold
+        RunState *d_state = nullptr;
+        RunRec *d_ring = nullptr, *h_ring = nullptr; // device ring and its pinned image (the source of the pushes' copies)
+        int *h_pushed = nullptr;                     // pinned [kRunRingSteps]: the counts the pushes copy into d_state->pushed
+        double *h_out = nullptr;                     // pinned [kRunRingSteps][kRunOut]
+        unsigned long long *h_step_tag = nullptr;    // pinned [kRunRingSteps]
+        unsigned long long *h_launch = nullptr;      // pinned [2][kRunLaunchRing]: info | tag
+        double2 *d_part = nullptr, *d_alt = nullptr;
+        ChainResult *d_res = nullptr;
+        int *d_ticket = nullptr;
+        long long pushed = 0, collected = 0;         // steps
+        long long stalled_at = -1;                   // the undecided step collect has reported and force has not yet answered
+        bool dev_stalled = false;                    // the stall flag as the last launch seen left it
+        unsigned long long seq = 0, seq_done = 0;    // launches queued / whose tags have been read (never reset)
+        long long launches = 0, steps = 0, void_launches = 0, undecided = 0;
+        std::deque<std::pair<int, int>> log;         // (first, consumed) of the last launches seen since open
+    } run;
     // profiling
     bool profiling = false;
 };
@@ -428,6 +455,7 @@ int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int
                  long long check_every, const char *what);
 int farm_clear_stall(mgpu_engine *e, int replica);   // the replica's state was rewritten: it waits for no decision (mgpu_windows.hip)
 int chain_topo(mgpu_engine *e, const Topo **d_topo);   // the engine's Topo in device memory (mgpu_windows.hip)
+void chain_run_release(mgpu_engine *e);                // a chain run's blocks (mgpu_windows.hip)
 // mgpu_launch.hip
 int launch_pair(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, int common_n1, int site_stride,
                 int nsplit, double *d_lj, double *d_c, bool ordered = false, double2 *host_partials = nullptr,

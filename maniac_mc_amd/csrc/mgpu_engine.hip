@@ -687,6 +687,7 @@ int mgpu_engine_destroy(mgpu_engine *e) {
     for (void *p : {(void *)e->chain.d_res, (void *)e->chain.d_part, (void *)e->chain.d_ticket, (void *)e->chain.d_topo, (void *)e->chain.d_alt,
                     (void *)e->d_A_alt, (void *)e->d_acur, (void *)e->farm.d_stalled})
         if (p) (void)hipFree(p);
+    chain_run_release(e);
     for (auto &ln : e->lanes) {
         ln.release();
         for (auto &p : ln.pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }

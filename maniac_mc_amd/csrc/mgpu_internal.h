@@ -103,6 +103,8 @@ inline size_t chain_wide_pair_lds_bytes(size_t coul_bytes, int pair_waves, int s
 inline size_t chain_resolver_lds_bytes(int n_ent, int nsplit) { return (size_t)n_ent * nsplit * kLdsPhase; }
 // largest window the resolver's staging admits within the default budget: two entries per step
 inline int chain_window_steps_by_lds(int nsplit) { return (int)(kLdsDefaultMax / chain_resolver_lds_bytes(2, nsplit)); }
+// a chain-run launch of k steps (chain_run_kernel): its resolver stages both entries of every step
+inline size_t chain_run_resolver_lds_bytes(int k, int nsplit) { return chain_resolver_lds_bytes(2 * k, nsplit); }
 
 // ---- The two blocks of a batched trial on a lane (mgpu_lanes.hip): the one home of their layouts, plain integers as above.
 // trial_submit_impl, trial_wait_impl, finish_decided and the DecideItem offsets take every offset from here: a block that

@@ -939,6 +939,305 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI 
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Chain runs: launches of ONE chain queued back to back, each of which continues where the one before it stopped.
+//
+// A single-chain window ends at its first accepted step, and the next window cannot be drawn, built or launched before the
+// host has seen that outcome: the chain's period is the kernel plus the host's turn-round.  In an NVT
+// block the random numbers of step i + 1 do not depend on the outcome of step i (src/monte_carlo.f90:50-75,
+// src/translation.f90, src/rotation.f90): the driver draws a block's steps ahead as RECORDS -- residue type, molecule,
+// move, the five numbers of the construction, the acceptance draw -- pushes them into a ring in device memory and queues
+// launches without waiting for any.  A launch
+//   * reads the run's {cursor, pushed, stalled} from device memory (every workgroup's first act): steps
+//     [cursor, min(cursor + k, pushed)) are its own -- none, or a chain that waits for the host's decision: it does nothing;
+//   * front end, farm_window_kernel's: every role rebuilds its candidate from the resident frames and the record's numbers
+//     (trial_frame / trial_offset) as a trial of the state the launch FINDS; one wave per (step, state, split) of the pair
+//     sweep with the engine's nsplit, one k workgroup per step, which stores A + delta into the step's own buffer (`sc1`);
+//   * back end, chain_window_kernel's: one ticket per launch; the workgroup that draws the last one sums the split partials
+//     in split order, forms every step's totals and applies the rule as farm_resolve does, walks the steps in order, stores
+//     cursor += consumed (the steps up to and including the first accepted one, or up to an undecided one), the consumed
+//     steps' results into the pinned ring (indexed by absolute step: old[5] | new[5] | verdict, a tag per step behind
+//     them), the launch's tag last, and commits the accepted step: coordinates and frames as farm_resolve, A(k) by copying
+//     the step's buffer.
+// The only ordering between launches is the stream's; inside a launch nobody waits for anybody (the ticket).  An UNDECIDED
+// step (margin rule, NaN) is not consumed: its energies are published with verdict 2, `stalled` is set, and every launch
+// behind it does nothing until one arrives that carries the host's decision for exactly that step (force_step): it obeys,
+// clears the flag and goes on with the steps behind it.  Moves only (a run is an NVT block): kind 0, prefactor 1.
+// Instances: <FLAT, FASTW> -- orthorhombic boxes, molecules of <= kMaxFusedSitesWide sites in the row form, framework boxes
+// included: what farm_window_kernel<FLAT, FASTW> covers.  No WIDE, TRI or RSV instance exists (capacity 0).
+// ------------------------------------------------------------------------------------------
+struct RunState { int cursor, pushed, stalled, pad; };
+struct RunRec {
+    int t, m, move, pad;          // move 0: nothing to do; 1 translation, 2 rotation
+    double u[5];                  // the construction's uniform numbers (trial_build_kernel)
+    double acc_u;                 // the test's uniform number
+};
+constexpr int kRunRecWords = 8;
+static_assert(sizeof(RunRec) == 8 * kRunRecWords, "RunRec is read as 8-byte words");
+constexpr int kRunMaxK = kChainMaxCand;          // steps per launch
+constexpr int kRunOut = kFarmOut;                // doubles per step in the pinned ring: old[5] | new[5] | verdict
+constexpr int kRunTagStalled = 1, kRunTagVoid = 2;   // launch info: first << 16 | consumed << 8 | flags
+struct ChainRunArgs {
+    RunState *state;                             // device: the run's cursor
+    const RunRec *ring;                          // device [ring_steps]: step s at s % ring_steps
+    double2 *partials;                           // [k][2][nsplit] device scratch
+    ChainResult *res;                            // [k] device scratch
+    int *ticket;                                 // device counter, 0 between launches
+    double2 *alt;                                // [k][n_slots] device scratch: step c's k role leaves A + delta_c here
+    double *host_out;                            // pinned [ring_steps][kRunOut]
+    unsigned long long *step_tag;                // pinned [ring_steps]: (step + 1) << 1 | decided, behind the step's row
+    unsigned long long *launch_info, *launch_tag;   // pinned: this launch's slot; the tag (seq) is written last
+    unsigned long long seq;
+    int k, nsplit, replica, ring_steps;
+    int force_step, force_verdict;               // -1 / the stalled step the host has decided: 1 accept, 2 reject
+    double t_step, r_step, temperature, margin;
+};
+static_assert(sizeof(BoxDev) + sizeof(ChainRunArgs) + 160 <= 4096, "a chain-run launch must fit the kernel-argument segment");
+
+template <bool FLAT, bool FASTW>
+__global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
+    const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
+    const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
+    const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
+    double2 *__restrict__ A_base, const ChainRunArgs g) {
+    extern __shared__ __attribute__((aligned(16))) char s_dyn[];      // Coulomb table | phase tables | partials staging
+    __shared__ double2 s_pair[kMaxTypes * kMaxTypes];
+    __shared__ int4 s_grp[kMaxGrp];
+    __shared__ int4 s_plane[FLAT ? kPairWaves * kFlatMaxPlanes : 1];
+    __shared__ double s_red[2 * kWavesPerBlock];
+    __shared__ RunRec s_rec[kRunMaxK];                                 // the launch's steps
+    __shared__ double s_cand[kPairWaves][kMaxFusedSitesWide * 3];      // candidate rows: one per wave (pair role) / row 0 (k role)
+    __shared__ double s_ent[4 * kRunMaxK];                             // reduced pair entries {lj, cc} of the old / new state
+    __shared__ ChainResult s_res[kRunMaxK];
+    __shared__ double s_out[kRunMaxK][kRunOut];
+    __shared__ int s_hdr[3], s_flag;
+
+    const Topo &tp = *tpp;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int ns = g.nsplit, wpc = 2 * ns;
+    // ---- the cursor: which steps are this launch's
+    if (tid == 0) {
+        const int cursor = g.state->cursor, pushed = g.state->pushed, stalled = g.state->stalled;
+        int cnt = min(g.k, pushed - cursor), forced = 0;
+        if (stalled) {
+            if (g.force_step == cursor && g.force_verdict != 0) forced = g.force_verdict;
+            else cnt = 0;
+        }
+        s_hdr[0] = cursor; s_hdr[1] = max(cnt, 0); s_hdr[2] = forced;
+    }
+    __syncthreads();
+    const int first = s_hdr[0], cnt = s_hdr[1], forced = s_hdr[2];
+    const int n_pair_wg = (g.k * wpc + kPairWaves - 1) / kPairWaves;
+    const bool k_role = (int)blockIdx.x >= n_pair_wg;
+    if (tid < kRunRecWords * cnt) {
+        const int c = tid / kRunRecWords, wd = tid - c * kRunRecWords;
+        reinterpret_cast<double *>(s_rec)[tid] = reinterpret_cast<const double *>(g.ring + (first + c) % g.ring_steps)[wd];
+    }
+    if (!k_role && cnt > 0) {
+        for (int i = tid; i < (bx.coul_last_row + 1) * kCoulRowVec; i += kChainBlock)
+            reinterpret_cast<double2 *>(s_dyn)[i] = reinterpret_cast<const double2 *>(coul_tab_g)[i];
+        const int nt = tp.n_types;
+        for (int i = tid; i < nt * nt; i += kChainBlock) s_pair[i] = pair_tab[i];
+        if (FLAT && tid < kMaxGrp) s_grp[tid] = make_int4(tp.grp_start[tid], tp.grp_cnt[tid], tp.grp_ty[tid], 0);
+    }
+    __syncthreads();
+
+    if (k_role) {
+        // ---------------- k role: step c of the launch
+        const int c = (int)blockIdx.x - n_pair_wg;
+        if (c < cnt && s_rec[c].move != 0) {                           // (uniform per workgroup)
+            const RunRec &rec = s_rec[c];
+            const int n1 = tp.n1[rec.t];
+            if (tid < n1) {
+                const auto f = trial_frame<false, false>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                double off[3];
+                trial_offset<false>(tp, f, g.replica, rec.t, tid, off);
+                for (int d = 0; d < 3; ++d) s_cand[0][tid * 3 + d] = f.com[d] + off[d];
+            }
+            __syncthreads();
+            double2 *A = A_base + (size_t)g.replica * bx.n_slots;
+            RecipItem it{g.replica, rec.t, rec.m, 0, 0, 0, 0};
+            const RecipLds v = recip_lds_view(tp, bx, it, n_rows, reinterpret_cast<double2 *>(s_dyn));
+            const bool active = tid < kBlock;
+            RecipInFlight<kRecipTaskChunk> inflight;
+            recip_rows_tables(tp, bx, pos, res_q, rows, n_rows, it, &s_cand[0][0], v, tid, active,
+                              [&] { recip_rows_prefetch<false>(inflight, trj, tw, n_tasks, A, tid); });
+            double acc = 0.0, acc0 = 0.0;
+            if (active) recip_rows_pass<false, true, kRecipTaskChunk, 2>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0, g.alt + (size_t)c * bx.n_slots);
+            if (active) {
+                acc = wave_sum(acc);
+                acc0 = wave_sum(acc0);
+                if (lane == 0) { s_red[2 * wave] = acc; s_red[2 * wave + 1] = acc0; }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                double u = 0.0, u0 = 0.0;
+                for (int wv = 0; wv < kWavesPerBlock; ++wv) { u += s_red[2 * wv]; u0 += s_red[2 * wv + 1]; }
+                __hip_atomic_store(&g.res[c].u_new, u * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ewald_energy.f90:272
+                __hip_atomic_store(&g.res[c].u_old, u0 * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    } else {
+        // ---------------- pair role: one wave per (step, entry, split); entry 0 = the resident molecule, 1 = the candidate
+        const int wg = (int)blockIdx.x * kPairWaves + wave;
+        const int c = wg / wpc, j = wg - c * wpc;
+        if (c < cnt && s_rec[c].move != 0) {
+            const RunRec &rec = s_rec[c];
+            const int ent = j / ns, split = j - ent * ns;
+            const int n1 = tp.n1[rec.t];
+            double *cand = &s_cand[wave][0];
+            if (ent == 1) {
+                const auto f = trial_frame<false, false>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                if (lane < n1) {
+                    double off[3];
+                    trial_offset<false>(tp, f, g.replica, rec.t, lane, off);
+                    for (int d = 0; d < 3; ++d) cand[lane * 3 + d] = f.com[d] + off[d];
+                }
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+            // old state: the resident molecule; new state: the candidate row
+            const PairItem it{g.replica, rec.t, rec.m, ent == 1 ? 0 : -1, 0};
+#define MGPU_RUN_PAIR(NS)                                                                                                \
+            do {                                                                                                         \
+                if constexpr (FLAT)                                                                                      \
+                    pair_flat_item<NS, false, FASTW, true>(tp, bx, pos, nmol, res_q, res_atype, s_dyn, s_pair, s_grp,         \
+                                                     s_plane + wave * kFlatMaxPlanes, it, cand, kMaxFusedSitesWide, split, ns, lane, 0, g.partials, wg); \
+                else                                                                                                     \
+                    pair_sweep_item<NS, false, false, false, FASTW, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, nullptr, \
+                                                                    nullptr, it, cand, kMaxFusedSitesWide, split, ns, lane, g.partials, wg);   \
+            } while (0)
+            switch (n1) {
+                case 1: MGPU_RUN_PAIR(1); break;
+                case 2: MGPU_RUN_PAIR(2); break;
+                case 3: MGPU_RUN_PAIR(3); break;
+                case 4: MGPU_RUN_PAIR(4); break;
+                default: MGPU_RUN_PAIR(5); break;
+            }
+#undef MGPU_RUN_PAIR
+        }
+    }
+
+    // ---------------- ticket: the last workgroup to arrive resolves the launch (chain_window_kernel's hand-off: `sc1` stores,
+    // every storing wave waits for them, one lane per workgroup adds behind a barrier, the resolver loads with `sc1`)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) s_flag = (atomicAdd(g.ticket, 1) == (int)gridDim.x - 1) ? 1 : 0;
+    __syncthreads();
+    if (!s_flag) return;
+    // split partials of every step's two entries into LDS in one round trip, then one thread per (step, entry, component)
+    // adds them in split order -- the order trial_wait uses on the host
+    {
+        double *st = reinterpret_cast<double *>(s_dyn);
+        const int per = 4 * ns;
+        for (int i = tid; i < per * cnt; i += kChainBlock)
+            st[i] = s_rec[i / per].move != 0 ? load_sc1(reinterpret_cast<const double *>(g.partials) + i) : 0.0;
+        if (tid < 3 * cnt) reinterpret_cast<double *>(s_res)[tid] = s_rec[tid / 3].move != 0 ? load_sc1(reinterpret_cast<const double *>(g.res) + tid) : 0.0;
+        __syncthreads();
+        if (tid < 4 * cnt) {
+            const int c = tid >> 2, ent = (tid >> 1) & 1, comp = tid & 1;
+            double sum = 0.0;
+            for (int s2 = 0; s2 < ns; ++s2) sum += st[c * per + 2 * (ent * ns + s2) + comp];
+            if (comp) sum = sum * kEps0InvEvA / kKbEvK;                        // energy_utils.f90:440
+            s_ent[tid] = sum;
+        }
+        __syncthreads();
+    }
+    // every step's totals and verdict by its own thread, as farm_resolve forms them (a move: kind 0, prefactor 1)
+    if (tid < cnt) {
+        const int c = tid;
+        const RunRec &rec = s_rec[c];
+        double o[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, w[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+        int verdict = kFarmVerdictIdle;
+        if (rec.move != 0) {
+            o[0] = s_ent[4 * c]; o[1] = s_ent[4 * c + 1]; o[2] = s_res[c].u_old;
+            w[0] = s_ent[4 * c + 2]; w[1] = s_ent[4 * c + 3]; w[2] = s_res[c].u_new;
+            if (c == 0 && forced) {
+                verdict = forced == 1 ? kFarmVerdictAccepted : kFarmVerdictRejected;
+            } else {
+                // old%total, new%total and the rule as mc_farm.f90 resolve_and_commit forms them (monte_carlo_utils.f90:184-226)
+                double e_old = 0.0, e_new = 0.0;
+                for (int k = 0; k < 5; ++k) { e_old = e_old + o[k]; e_new = e_new + w[k]; }
+                const double x = 1.0 * exp(-(e_new - e_old) / g.temperature);
+                const double pr = x < 1.0 ? x : 1.0;                               // min(1, x)
+                if (!(x == x) || (x < 1.0 + g.margin && fabs(rec.acc_u - x) <= g.margin * x)) verdict = kFarmVerdictUndecided;
+                else verdict = rec.acc_u <= pr ? kFarmVerdictAccepted : kFarmVerdictRejected;
+            }
+        }
+        for (int k = 0; k < 5; ++k) { s_out[c][k] = o[k]; s_out[c][5 + k] = w[k]; }
+        s_out[c][10] = (double)verdict;
+    }
+    __syncthreads();
+    // the steps in order: the launch ends behind its first accepted step, or AT an undecided one
+    int consumed = 0, accepted = -1, stall = 0;
+    for (int c = 0; c < cnt; ++c) {
+        const int v = (int)s_out[c][10];
+        if (v == kFarmVerdictUndecided) { stall = 1; break; }
+        consumed = c + 1;
+        if (v == kFarmVerdictAccepted) { accepted = c; break; }
+    }
+    const int still = cnt == 0 ? g.state->stalled : stall;            // (a launch that does nothing leaves the flag as it found it)
+    if (tid == 0 && cnt > 0) {
+        g.state->cursor = first + consumed;
+        g.state->stalled = stall;
+    }
+    // ---- results into pinned host memory: rows (an undecided step's too: the host decides from them), a tag per step behind
+    // its row, the launch's tag behind everything (system-scope write-through stores, each waited for: farm_resolve's form)
+    const int n_out = consumed + stall;
+    if (tid < n_out * kRunOut) {
+        const int c = tid / kRunOut, k = tid - c * kRunOut;
+        __hip_atomic_store(g.host_out + (size_t)((first + c) % g.ring_steps) * kRunOut + k, s_out[c][k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid < n_out) {
+        const unsigned long long tag = ((unsigned long long)(first + tid + 1) << 1) | (tid < consumed ? 1ull : 0ull);
+        __hip_atomic_store(g.step_tag + (first + tid) % g.ring_steps, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned long long info = ((unsigned long long)(unsigned)first << 16) | ((unsigned long long)consumed << 8) |
+                                        (unsigned long long)((still ? kRunTagStalled : 0) | (cnt == 0 ? kRunTagVoid : 0));
+        __hip_atomic_store(g.launch_info, info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(g.launch_tag, g.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(g.ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (accepted < 0) return;
+    // ---------------- commit of the accepted step by this workgroup: A <- the buffer its k role filled with A + delta
+    // (chain_window_kernel's copy), coordinates and frames as farm_resolve writes them
+    {
+        const RunRec &rec = s_rec[accepted];
+        const double *from = reinterpret_cast<const double *>(g.alt + (size_t)accepted * bx.n_slots);
+        double *to = reinterpret_cast<double *>(A_base + (size_t)g.replica * bx.n_slots);
+        for (int i = tid; i < 2 * bx.n_slots; i += kChainBlock) to[i] = load_sc1(from + i);
+        if (wave == 0) {
+            const int n1 = tp.n1[rec.t];
+            double *px = pos + (size_t)g.replica * 3 * tp.n_cap_atoms;
+            double *py = px + tp.n_cap_atoms, *pz = py + tp.n_cap_atoms;
+            const size_t rep3 = (size_t)g.replica * 3;
+            double *fcom = tp.com + rep3 * tp.n_mol_slots + tp.mol_off[rec.t];
+            double *foff = tp.off + rep3 * tp.n_cap_atoms;
+            const auto f = trial_frame<false, false>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+            double off[3] = {0.0, 0.0, 0.0};
+            if (lane < n1) trial_offset<false>(tp, f, g.replica, rec.t, lane, off);
+            // (every lane has read the resident frame before any lane overwrites it)
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (lane < n1) {
+                const int j = atom_slot(tp, rec.t, rec.m, lane);
+                px[j] = f.com[0] + off[0]; py[j] = f.com[1] + off[1]; pz[j] = f.com[2] + off[2];
+                for (int d = 0; d < 3; ++d) foff[(size_t)d * tp.n_cap_atoms + j] = off[d];
+            }
+            // (selected, not indexed: a private array indexed by the lane would live in scratch)
+            if (lane < 3) fcom[(size_t)lane * tp.n_mol_slots + rec.m] = lane == 0 ? f.com[0] : (lane == 1 ? f.com[1] : f.com[2]);
+        }
+    }
+}
+
 // A(k) of every replica back into the engine's primary buffer (farm windows leave a replica's current A(k) in either):
 // one workgroup per replica.
 static __global__ __launch_bounds__(kBlock) void farm_normalize_kernel(int *__restrict__ acur, double2 *__restrict__ A_base,

@@ -62,7 +62,22 @@ void alt_forget(mgpu_engine *e, int replica) {
 // waits for no decision of an earlier step: its stall flag goes.  The callers have drained every lane.
 int farm_clear_stall(mgpu_engine *e, int replica) {
     if (e->farm.d_stalled) HIP_TRY(hipMemset(e->farm.d_stalled + replica, 0, sizeof(int)));
+    mgpu_engine::Run &rn = e->run;
+    if (rn.open && rn.replica == replica) {                   // an open chain run of the replica: the same
+        HIP_TRY(hipMemset(&rn.d_state->stalled, 0, sizeof(int)));
+        rn.stalled_at = -1;
+        rn.dev_stalled = false;
+    }
     return MGPU_OK;
+}
+
+void chain_run_release(mgpu_engine *e) {
+    mgpu_engine::Run &rn = e->run;
+    for (void *p : {(void *)rn.h_ring, (void *)rn.h_pushed, (void *)rn.h_out, (void *)rn.h_step_tag, (void *)rn.h_launch})
+        if (p) (void)hipHostFree(p);
+    for (void *p : {(void *)rn.d_state, (void *)rn.d_ring, (void *)rn.d_part, (void *)rn.d_alt, (void *)rn.d_res, (void *)rn.d_ticket})
+        if (p) (void)hipFree(p);
+    rn = mgpu_engine::Run{};
 }
 
 int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int n, unsigned long long seq, long long first_check,
@@ -646,6 +661,308 @@ int mgpu_farm_window_wait(mgpu_engine *e, int lane, double *old_energy, double *
         // (the range flag was lowered at submit)
     }
     fw.pending.pop_front();
+    return MGPU_OK;
+}
+
+// ---- chain runs --------------------------------------------------------------------------------
+// Launches of ONE chain queued back to back on lane 0, each continuing from the cursor in device memory (chain_run_kernel,
+// mgpu_kernels_windows.h).  Host state (e->run) is touched by the run's one driver thread only.
+
+// steps per launch the engine accepts, 0 where the path does not apply: mgpu_farm_window_capacity's reasons, and -- no such
+// instance of chain_run_kernel exists -- every triclinic box, every active type of more than kMaxFusedSitesWide sites, reservoirs
+static int run_max_k(const mgpu_engine *e) {
+    if (e->bx.triclinic || e->rsv_any) return 0;
+    for (int t = 0; t < e->tp.n_res; ++t) {
+        if (!e->is_active[t]) continue;
+        FarmTypeForm f;
+        if (e->tp.n1[t] > kMaxFusedSitesWide || !farm_type_form(e, t, f)) return 0;
+    }
+    if (e->coul_bytes > kLdsDefaultMax) return 0;
+    return std::max(0, std::min(kRunMaxK, chain_window_steps_by_lds(e->pair_nsplit)));
+}
+
+// the tags of the launches that have finished since the last look, in order: counters and the launch log
+static void run_poll(mgpu_engine *e) {
+    mgpu_engine::Run &rn = e->run;
+    const volatile unsigned long long *info = rn.h_launch, *tag = rn.h_launch + kRunLaunchRing;
+    while (rn.seq_done < rn.seq) {
+        const unsigned long long s = rn.seq_done + 1;
+        if (tag[s % kRunLaunchRing] != s) break;
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        const unsigned long long v = info[s % kRunLaunchRing];
+        const int first = (int)(v >> 16), consumed = (int)((v >> 8) & 0xff), flags = (int)(v & 0xff);
+        rn.launches += 1;
+        rn.steps += consumed;
+        if (flags & kRunTagVoid) rn.void_launches += 1;
+        else if (flags & kRunTagStalled) rn.undecided += 1;
+        rn.dev_stalled = (flags & kRunTagStalled) != 0;
+        rn.log.emplace_back(first, consumed);
+        if ((int)rn.log.size() > kRunLogMax) rn.log.pop_front();
+        rn.seq_done = s;
+    }
+}
+
+static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
+    mgpu_engine::Run &rn = e->run;
+    Lane &ln = e->lanes[0];
+    const Topo *d_topo = nullptr;
+    int rc = chain_topo(e, &d_topo);
+    if (rc) return rc;
+    const int nsplit = e->pair_nsplit;
+    int n1_max = 1;
+    for (int t = 0; t < e->tp.n_res; ++t)
+        if (e->is_active[t]) n1_max = std::max(n1_max, e->tp.n1[t]);
+    const size_t lds = std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), chain_run_resolver_lds_bytes(rn.k, nsplit));
+    if (lds > kLdsDefaultMax) return set_error(MGPU_ERR_CAPACITY, "chain_run_launch: the launch does not fit the LDS budget");
+    ChainRunArgs g{};
+    rn.seq += 1;
+    g.state = rn.d_state; g.ring = rn.d_ring; g.partials = rn.d_part; g.res = rn.d_res; g.ticket = rn.d_ticket; g.alt = rn.d_alt;
+    g.host_out = rn.h_out; g.step_tag = rn.h_step_tag;
+    g.launch_info = rn.h_launch + rn.seq % kRunLaunchRing;
+    g.launch_tag = rn.h_launch + kRunLaunchRing + rn.seq % kRunLaunchRing;
+    g.seq = rn.seq;
+    g.k = rn.k; g.nsplit = nsplit; g.replica = rn.replica; g.ring_steps = kRunRingSteps;
+    g.force_step = force_step; g.force_verdict = force_verdict;
+    g.t_step = rn.t_step; g.r_step = rn.r_step; g.temperature = rn.temperature; g.margin = e->chain.margin;
+    const int grid = (rn.k * 2 * nsplit + kPairWaves - 1) / kPairWaves + rn.k;
+    const bool ff = rn.fast && e->pair_fast_fold;
+    ln.dirty = true;
+    ln.forget_trial();
+    alt_forget(e, rn.replica);
+    with_bools([&](auto FLAT, auto FASTW) {
+        hipLaunchKernelGGL((chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo,
+                           e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks,
+                           e->d_rrows, e->n_rrows, e->d_A, g);
+    }, e->pair_flat, ff);
+    HIP_TRY(hipGetLastError());
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_capacity(const mgpu_engine *e, int *max_k, int *max_in_flight, int *ring_steps) {
+    if (!e || !max_k) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_capacity: null argument");
+    const int k = run_max_k(e);
+    *max_k = k;
+    if (max_in_flight) *max_in_flight = k ? kRunMaxInFlight : 0;
+    if (ring_steps) *ring_steps = k ? kRunRingSteps : 0;
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_open(mgpu_engine *e, int replica, int k, double t_step, double r_step, double temperature) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    mgpu_engine::Run &rn = e->run;
+    const int k_max = run_max_k(e);
+    if (k_max == 0) return set_error(MGPU_ERR_STATE, "chain_run_open: not available for this engine (mgpu_chain_run_capacity)");
+    if (rn.open) return set_error(MGPU_ERR_STATE, "chain_run_open: a run is open (one per engine)");
+    if (replica < 0 || replica >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_open: replica out of range");
+    if (k < 1 || k > k_max) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_open: steps per launch out of range");
+    if (!(temperature > 0.0)) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_open: temperature must be positive");
+    for (int t = 0; t < e->tp.n_res; ++t)
+        if (e->is_active[t] && (!e->d_com || !e->frames_ok[(size_t)replica * e->tp.n_res + t]))
+            return set_error(MGPU_ERR_STATE, "chain_run_open: no molecule frames for this replica (mgpu_replica_set_frames)");
+    int rc = use_device(e);
+    if (rc) return rc;
+    Lane &ln = e->lanes[0];
+    if (ln.n_submitted != 0 || !ln.farm.pending.empty())
+        return set_error(MGPU_ERR_STATE, "chain_run_open: lane 0 still holds an un-waited trial or farm window");
+    if ((rc = sync_all_lanes(e))) return rc;                    // (every replica's A(k) in its primary buffer: the run reads and writes d_A)
+    if (!rn.d_state) {
+        HIP_TRY(hipMalloc((void **)&rn.d_state, sizeof(RunState)));
+        HIP_TRY(hipMalloc((void **)&rn.d_ring, sizeof(RunRec) * kRunRingSteps));
+        HIP_TRY(hipHostMalloc((void **)&rn.h_ring, sizeof(RunRec) * kRunRingSteps, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void **)&rn.h_pushed, sizeof(int) * kRunRingSteps, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void **)&rn.h_out, sizeof(double) * kRunOut * kRunRingSteps, hipHostMallocCoherent));
+        HIP_TRY(hipHostMalloc((void **)&rn.h_step_tag, sizeof(unsigned long long) * kRunRingSteps, hipHostMallocCoherent));
+        HIP_TRY(hipHostMalloc((void **)&rn.h_launch, sizeof(unsigned long long) * 2 * kRunLaunchRing, hipHostMallocCoherent));
+        std::memset(rn.h_launch, 0, sizeof(unsigned long long) * 2 * kRunLaunchRing);
+        HIP_TRY(hipMalloc((void **)&rn.d_part, sizeof(double2) * 2 * kRunMaxK * (size_t)e->pair_nsplit));
+        HIP_TRY(hipMalloc((void **)&rn.d_res, sizeof(ChainResult) * kRunMaxK));
+        HIP_TRY(hipMalloc((void **)&rn.d_alt, sizeof(double2) * kRunMaxK * (size_t)e->n_slots));
+        HIP_TRY(hipMalloc((void **)&rn.d_ticket, sizeof(int)));
+        HIP_TRY(hipMemset(rn.d_ticket, 0, sizeof(int)));
+    }
+    const Topo *d_topo = nullptr;
+    if ((rc = chain_topo(e, &d_topo))) return rc;
+    HIP_TRY(hipMemset(rn.d_state, 0, sizeof(RunState)));
+    HIP_TRY(hipDeviceSynchronize());
+    std::memset(rn.h_step_tag, 0, sizeof(unsigned long long) * kRunRingSteps);
+    rn.open = true;
+    rn.replica = replica; rn.k = k;
+    rn.t_step = t_step; rn.r_step = r_step; rn.temperature = temperature;
+    rn.fast = replica_in_range(e, replica);
+    rn.pushed = rn.collected = 0;
+    rn.stalled_at = -1;
+    rn.dev_stalled = false;
+    rn.seq_done = rn.seq;
+    rn.log.clear();
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_push(mgpu_engine *e, int n, const int *t, const int *m, const int *move, const double *u5, const double *accept_u) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    mgpu_engine::Run &rn = e->run;
+    if (!rn.open) return set_error(MGPU_ERR_STATE, "chain_run_push: no run is open");
+    if (n < 0 || (n > 0 && (!t || !m || !move || !u5 || !accept_u))) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: bad argument");
+    if (n == 0) return MGPU_OK;
+    if (rn.pushed + n - rn.collected > kRunRingSteps)
+        return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: beyond the ring (steps pushed and not yet collected: mgpu_chain_run_capacity)");
+    if (rn.pushed + n >= (1ll << 30)) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: too many steps in one run");
+    int rc = use_device(e);
+    if (rc) return rc;
+    // every record is checked before any is written: a refused push leaves the run as it was
+    bool fast = rn.fast;
+    for (int c = 0; c < n; ++c) {
+        const int mv = move[c];
+        if (mv == 3 || mv == 4) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: insertions and deletions do not ride in a run (moves only)");
+        if (mv < 0 || mv > 4) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: unknown move code");
+        if (mv == 0) continue;
+        if (t[c] < 0 || t[c] >= e->tp.n_res || !e->is_active[t[c]] || e->frozen[t[c]])
+            return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: residue type out of range or not active");
+        if ((rc = check_candidate(e, c, rn.replica, t[c], m[c], true))) return rc;
+        fast = fast && e->frames_tight[(size_t)rn.replica * e->tp.n_res + t[c]];
+    }
+    for (int c = 0; c < n; ++c) {
+        RunRec &r = rn.h_ring[(rn.pushed + c) % kRunRingSteps];
+        r = RunRec{};
+        r.move = move[c];
+        if (r.move == 0) continue;
+        r.t = t[c]; r.m = m[c];
+        for (int d = 0; d < 5; ++d) r.u[d] = u5[5 * (size_t)c + d];
+        r.acc_u = accept_u[c];
+        // a step that is accepted may leave the fast fold's range: the flag is lowered now (mgpu_farm_window_submit's rule)
+        const size_t idx = (size_t)rn.replica * e->tp.n_res + t[c];
+        if (!e->frames_tight[idx]) e->in_range[idx] = 0;
+    }
+    rn.fast = fast;
+    Lane &ln = e->lanes[0];
+    ln.dirty = true;
+    // the records (the ring's image is the copies' source: a slot is rewritten only after its step has been collected), then
+    // the count, on the launches' stream and ahead of the launches that read them
+    const int s0 = (int)(rn.pushed % kRunRingSteps), n0 = std::min(n, kRunRingSteps - s0);
+    HIP_TRY(hipMemcpyAsync(rn.d_ring + s0, rn.h_ring + s0, sizeof(RunRec) * n0, hipMemcpyHostToDevice, ln.stream));
+    if (n > n0) HIP_TRY(hipMemcpyAsync(rn.d_ring, rn.h_ring, sizeof(RunRec) * (n - n0), hipMemcpyHostToDevice, ln.stream));
+    rn.pushed += n;
+    int *cnt = rn.h_pushed + rn.pushed % kRunRingSteps;
+    *cnt = (int)rn.pushed;
+    HIP_TRY(hipMemcpyAsync(&rn.d_state->pushed, cnt, sizeof(int), hipMemcpyHostToDevice, ln.stream));
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_launch(mgpu_engine *e, int n_launches) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    mgpu_engine::Run &rn = e->run;
+    if (!rn.open) return set_error(MGPU_ERR_STATE, "chain_run_launch: no run is open");
+    if (n_launches < 0) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_launch: negative count");
+    int rc = use_device(e);
+    if (rc) return rc;
+    run_poll(e);
+    if ((long long)(rn.seq - rn.seq_done) + n_launches > kRunMaxInFlight)
+        return set_error(MGPU_ERR_STATE, "chain_run_launch: too many launches in flight (mgpu_chain_run_capacity)");
+    if (e->lanes[0].n_submitted != 0) return set_error(MGPU_ERR_STATE, "chain_run_launch: lane 0 holds an un-waited trial");
+    // (another path has left some replica's A(k) in its other buffer since the run was opened: back into d_A, which the run uses)
+    if (e->a_switched && (rc = normalize_A(e))) return rc;
+    for (int i = 0; i < n_launches; ++i)
+        if ((rc = run_launch_one(e, -1, 0))) return rc;
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_force(mgpu_engine *e, int step, int accept) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    mgpu_engine::Run &rn = e->run;
+    if (!rn.open) return set_error(MGPU_ERR_STATE, "chain_run_force: no run is open");
+    if (rn.stalled_at < 0 || step != rn.stalled_at)
+        return set_error(MGPU_ERR_STATE, "chain_run_force: not the step the run waits for (mgpu_chain_run_collect reports it)");
+    int rc = use_device(e);
+    if (rc) return rc;
+    run_poll(e);
+    if ((long long)(rn.seq - rn.seq_done) + 1 > kRunMaxInFlight)
+        return set_error(MGPU_ERR_STATE, "chain_run_force: too many launches in flight (mgpu_chain_run_capacity)");
+    if (e->a_switched && (rc = normalize_A(e))) return rc;
+    // (the device writes this tag again, decided, behind the step's row)
+    __atomic_store_n(&rn.h_step_tag[step % kRunRingSteps], 0ull, __ATOMIC_RELEASE);
+    rn.stalled_at = -1;
+    return run_launch_one(e, step, accept ? 1 : 2);
+}
+
+int mgpu_chain_run_collect(mgpu_engine *e, int max_steps, int wait, double *old_energy, double *new_energy, int *verdict, int *n_got,
+                           int *stalled_at) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    mgpu_engine::Run &rn = e->run;
+    if (!rn.open) return set_error(MGPU_ERR_STATE, "chain_run_collect: no run is open");
+    if (max_steps < 0 || !n_got || !stalled_at || (max_steps > 0 && (!old_energy || !new_energy || !verdict)))
+        return set_error(MGPU_ERR_INVALID_ARG, "chain_run_collect: bad argument");
+    int rc = use_device(e);
+    if (rc) return rc;
+    *n_got = 0;
+    *stalled_at = rn.stalled_at >= 0 ? (int)rn.stalled_at : -1;
+    if (rn.stalled_at >= 0) return MGPU_OK;                   // nothing moves before mgpu_chain_run_force
+    const volatile unsigned long long *tags = rn.h_step_tag;
+    long long spins = 0;
+    int got = 0;
+    auto row = [&](long long step) {
+        const double *o = rn.h_out + (size_t)(step % kRunRingSteps) * kRunOut;
+        std::memcpy(old_energy + 5 * (size_t)got, o, 5 * sizeof(double));
+        std::memcpy(new_energy + 5 * (size_t)got, o + 5, 5 * sizeof(double));
+        verdict[got] = (int)o[10];
+        ++got;
+    };
+    while (got < max_steps && rn.collected < rn.pushed) {
+        const long long step = rn.collected;
+        const unsigned long long decided = ((unsigned long long)(step + 1) << 1) | 1ull, tag = tags[step % kRunRingSteps];
+        if (tag == decided || tag == (decided ^ 1ull)) {
+            __atomic_thread_fence(__ATOMIC_ACQUIRE);
+            row(step);
+            if (tag == decided) { rn.collected += 1; continue; }
+            rn.stalled_at = step;                                // undecided: its energies, verdict 2; the run waits for force
+            *stalled_at = (int)step;
+            break;
+        }
+        if (!wait || got > 0) break;
+        __builtin_ia32_pause();
+        if (++spins >= 200000 && (spins % 65536) == 0) {
+            // long past any launch's run time: is anything still going to write this tag?
+            const hipError_t q = hipStreamQuery(e->lanes[0].stream);
+            if (q != hipSuccess && q != hipErrorNotReady) return set_error(MGPU_ERR_HIP, std::string("chain_run_collect: ") + hipGetErrorString(q));
+            if (q == hipSuccess && tags[step % kRunRingSteps] == tag)
+                return set_error(MGPU_ERR_STATE, "chain_run_collect: nothing in flight will produce the next step (mgpu_chain_run_launch)");
+        }
+    }
+    *n_got = got;
+    run_poll(e);
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_close(mgpu_engine *e) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    mgpu_engine::Run &rn = e->run;
+    if (!rn.open) return set_error(MGPU_ERR_STATE, "chain_run_close: no run is open");
+    int rc = use_device(e);
+    if (rc) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;                    // drains lane 0; A(k) is in its primary buffer (the run never leaves it)
+    run_poll(e);
+    if (rn.dev_stalled) return set_error(MGPU_ERR_STATE, "chain_run_close: a step waits for the host's decision (mgpu_chain_run_force)");
+    rn.open = false;
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_get_stats(mgpu_engine *e, long long *launches, long long *steps, long long *void_launches, long long *undecided) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    mgpu_engine::Run &rn = e->run;
+    if (rn.h_launch) run_poll(e);
+    if (launches) *launches = rn.launches;
+    if (steps) *steps = rn.steps;
+    if (void_launches) *void_launches = rn.void_launches;
+    if (undecided) *undecided = rn.undecided;
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_get_launches(mgpu_engine *e, int max_launches, int *first, int *consumed, int *n_got) {
+    if (!e || !n_got || max_launches < 0 || (max_launches > 0 && (!first || !consumed)))
+        return set_error(MGPU_ERR_INVALID_ARG, "chain_run_get_launches: bad argument");
+    mgpu_engine::Run &rn = e->run;
+    if (rn.h_launch) run_poll(e);
+    const int n = std::min(max_launches, (int)rn.log.size());
+    for (int i = 0; i < n; ++i) { first[i] = rn.log[i].first; consumed[i] = rn.log[i].second; }
+    *n_got = n;
     return MGPU_OK;
 }
 

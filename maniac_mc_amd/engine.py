@@ -284,6 +284,54 @@ class Engine:
         check(self.L.mgpu_farm_window_get_stats(self.h, C.byref(w), C.byref(u)))
         return w.value, u.value
 
+    # ---- chain runs (mgpu_chain_run_*): launches of one chain queued back to back, continuing from a cursor on the device
+    def chain_run_capacity(self):
+        """(max_k, max_in_flight, ring_steps); all 0 where the path does not apply."""
+        k = C.c_int(0); d = C.c_int(0); r = C.c_int(0)
+        check(self.L.mgpu_chain_run_capacity(self.h, C.byref(k), C.byref(d), C.byref(r)))
+        return k.value, d.value, r.value
+
+    def chain_run_open(self, replica, k, translation_step, rotation_step, temperature):
+        check(self.L.mgpu_chain_run_open(self.h, C.c_int(replica), C.c_int(k), C.c_double(translation_step), C.c_double(rotation_step),
+                                         C.c_double(temperature)))
+
+    def chain_run_push(self, t, m, move, u, accept_u):
+        m = _ints(m); n = m.shape[0]
+        t = _ints(t, n); move = _ints(move, n)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(n, 5)
+        au = np.ascontiguousarray(accept_u, dtype=np.float64).reshape(n)
+        check(self.L.mgpu_chain_run_push(self.h, C.c_int(n), _i(t), _i(m), _i(move), _d(u), _d(au)))
+        return n
+
+    def chain_run_launch(self, n_launches=1):
+        check(self.L.mgpu_chain_run_launch(self.h, C.c_int(n_launches)))
+
+    def chain_run_collect(self, max_steps, wait=True):
+        """(old[n,5], new[n,5], verdict[n], stalled_at): the next steps in order; an undecided step is the last row (verdict 2)."""
+        old = np.zeros((max_steps, 5)); new = np.zeros((max_steps, 5)); v = np.zeros(max_steps, np.int32)
+        n = C.c_int(0); st = C.c_int(-1)
+        check(self.L.mgpu_chain_run_collect(self.h, C.c_int(max_steps), C.c_int(1 if wait else 0), _d(old), _d(new), _i(v), C.byref(n),
+                                            C.byref(st)))
+        return old[:n.value], new[:n.value], v[:n.value], st.value
+
+    def chain_run_force(self, step, accept):
+        check(self.L.mgpu_chain_run_force(self.h, C.c_int(step), C.c_int(1 if accept else 0)))
+
+    def chain_run_close(self):
+        check(self.L.mgpu_chain_run_close(self.h))
+
+    def chain_run_stats(self):
+        """(launches, steps, void_launches, undecided) since the engine was created."""
+        a = [C.c_longlong(0) for _ in range(4)]
+        check(self.L.mgpu_chain_run_get_stats(self.h, *[C.byref(x) for x in a]))
+        return tuple(x.value for x in a)
+
+    def chain_run_launches(self, max_launches=1024):
+        """[(first step, steps consumed)] of the launches seen since the run was opened, oldest first."""
+        f = np.zeros(max_launches, np.int32); c = np.zeros(max_launches, np.int32); n = C.c_int(0)
+        check(self.L.mgpu_chain_run_get_launches(self.h, C.c_int(max_launches), _i(f), _i(c), C.byref(n)))
+        return [(int(f[i]), int(c[i])) for i in range(n.value)]
+
     def gcmc_trial_decide(self, replica, t, m, kind, sites, accept_u, accept_pref, temperature, lane=0):
         """Host-built rows, decided and committed on the device: (old[n,5], new[n,5], accepted[n])."""
         n, replica, t, m, sites = self._cand(replica, t, m, sites)

@@ -217,6 +217,13 @@ module maniac_gpu
             integer(c_int) :: rc
         end function
         ! molecule frames (com, offsets) resident on the device and trial moves built from them there
+        function mgpu_replica_set_frames(e, replica, t, n_mol, com, off) bind(C, name="mgpu_replica_set_frames") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: replica, t, n_mol
+            real(c_double), intent(in) :: com(*), off(*)
+            integer(c_int) :: rc
+        end function
         function mgpu_replica_get_frames(e, replica, t, n_mol, com, off) bind(C, name="mgpu_replica_get_frames") result(rc)
             import :: c_ptr, c_int, c_double
             type(c_ptr), value :: e
@@ -312,6 +319,69 @@ module maniac_gpu
             integer(c_int), value :: lane
             real(c_double), intent(out) :: old_energy(*), new_energy(*)
             integer(c_int), intent(out) :: verdict(*)
+            integer(c_int) :: rc
+        end function
+        ! chain runs (include/maniac_gpu.h): launches of one chain queued back to back, continuing from a cursor on the device
+        function mgpu_chain_run_capacity(e, max_k, max_in_flight, ring_steps) bind(C, name="mgpu_chain_run_capacity") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), intent(out) :: max_k, max_in_flight, ring_steps
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_open(e, replica, k, t_step, r_step, temperature) bind(C, name="mgpu_chain_run_open") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: replica, k
+            real(c_double), value :: t_step, r_step, temperature
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_push(e, n, t, m, move, u5, accept_u) bind(C, name="mgpu_chain_run_push") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: t(*), m(*), move(*)
+            real(c_double), intent(in) :: u5(*), accept_u(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_launch(e, n_launches) bind(C, name="mgpu_chain_run_launch") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n_launches
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_collect(e, max_steps, wait, old_energy, new_energy, verdict, n_got, stalled_at) &
+                bind(C, name="mgpu_chain_run_collect") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: max_steps, wait
+            real(c_double), intent(out) :: old_energy(*), new_energy(*)
+            integer(c_int), intent(out) :: verdict(*)
+            integer(c_int), intent(out) :: n_got, stalled_at
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_force(e, step, accept) bind(C, name="mgpu_chain_run_force") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: step, accept
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_close(e) bind(C, name="mgpu_chain_run_close") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_get_stats(e, launches, steps, void_launches, undecided) bind(C, name="mgpu_chain_run_get_stats") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_long_long), intent(out) :: launches, steps, void_launches, undecided
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_get_launches(e, max_launches, first, consumed, n_got) bind(C, name="mgpu_chain_run_get_launches") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: max_launches
+            integer(c_int), intent(out) :: first(*), consumed(*)
+            integer(c_int), intent(out) :: n_got
             integer(c_int) :: rc
         end function
         ! pinned staging of a lane's next trial: candidate rows built in place are not copied again

@@ -45,7 +45,7 @@ module mc_chain
               mchain_get_energy, mchain_get_counters, mchain_get_counts, mchain_get_molecule, mchain_get_steps, &
               mchain_set_mode, mchain_set_as_written, mchain_set_log_header, mchain_write_log_header, &
               mchain_set_speculation, mchain_set_chain_windows, mchain_set_wide_windows, mchain_get_loop_seconds, mchain_get_times, &
-              mchain_export_template
+              mchain_export_template, mchain_set_chain_run, mchain_get_chain_run
 
     real(real64), parameter :: PI = 3.14159265358979323846_real64, TWOPI = 2.0_real64 * PI
     real(real64), parameter :: zero = 0.0_real64, one = 1.0_real64, half = 0.5_real64, three = 3.0_real64
@@ -85,6 +85,13 @@ module mc_chain
     ! wide_windows: one-launch windows also for rigid molecules of 6 to 63 sites (mgpu_chain_set_wide); off unless asked for
     logical, save :: wide_windows = .false.
     integer, save :: chain_cap = 0
+    ! Chain runs (mchain_set_chain_run; include/maniac_gpu.h mgpu_chain_run_*): an NVT block's steps are drawn ahead as records of
+    ! draws -- nothing is built here and nothing is ever rewound -- and the engine runs them in launches queued back to back,
+    ! each continuing from the cursor it finds; this loop keeps run_depth launches in flight and books the results in order.
+    ! run_k = 0: off (the default).  run_on: the mode applies to this run (set by mchain_run from the engine's capacity).
+    integer, save :: run_k = 0, run_depth = 3
+    logical, save :: run_on = .false.
+    integer(c_int), save :: run_ring = 0
     integer, parameter :: BY_HOST = -1, DEVICE_REJECTED = 0, DEVICE_ACCEPTED = 1
     ! time spent inside the Monte Carlo loop proper (no initial energy, no files), seconds
     real(real64), save :: loop_seconds = 0.0_real64
@@ -447,6 +454,20 @@ contains
         integer(c_int), value :: on
         wide_windows = on /= 0
     end subroutine mchain_set_wide_windows
+
+    ! k > 0: NVT blocks as chain runs of k steps per launch with `depth` launches in flight, where the engine takes them
+    ! (mgpu_chain_run_capacity) and the input has no insertions / deletions; elsewhere the loop keeps its windows.  0: off.
+    subroutine mchain_set_chain_run(k, depth) bind(C, name="mchain_set_chain_run")
+        integer(c_int), value :: k, depth
+        run_k = max(0, int(k))
+        run_depth = max(1, int(depth))
+    end subroutine mchain_set_chain_run
+
+    ! (on, k, depth) of the last mchain_run
+    subroutine mchain_get_chain_run(out) bind(C, name="mchain_get_chain_run")
+        integer(c_int), intent(out) :: out(3)
+        out = [merge(1_c_int, 0_c_int, run_on), int(run_k, c_int), int(run_depth, c_int)]
+    end subroutine mchain_get_chain_run
 
     function mchain_get_loop_seconds() bind(C, name="mchain_get_loop_seconds") result(sec)
         real(c_double) :: sec
@@ -1143,6 +1164,166 @@ contains
         done = max(done, 1)
     end function run_window
 
+    !---------------------------------------------------------------------------
+    ! One block of nb_step NVT steps as a chain run.  The draws are propose_step's statements in its order (type, molecule, move;
+    ! displacement | angle then axis; acceptance -- a translation or rotation with nothing to move draws nothing more), kept as
+    ! records; the engine builds the geometry (its construction is the one held to the reference; this loop's matmul contracts
+    ! where the reference's doubles do not), so the mirror S%res is NOT kept in step here: refresh_frames reloads it at the end.
+    ! Each collected step is booked as resolve_step books DEVICE_ACCEPTED / DEVICE_REJECTED; a step the engine left undecided is
+    ! decided here (decide, BY_HOST) and forced.
+    !---------------------------------------------------------------------------
+    subroutine run_block(nb_step)
+        integer, intent(in) :: nb_step
+        integer(c_int), allocatable :: rt(:), rm(:), rmove(:), verdict(:)
+        real(c_double), allocatable :: ru(:, :), rau(:), o(:, :), w(:, :)
+        integer, allocatable :: mtype(:)
+        integer :: j, t, m, n1, pushed, collected, queued, n, i, chunk
+        integer(c_int) :: rc, n_got, stalled_at
+        integer(c_long_long) :: seen0, seen, st_steps, st_void, st_und
+        real(real64) :: draw, trial(3), old(6), new(6)
+        logical :: yes
+        allocate(rt(nb_step), rm(nb_step), rmove(nb_step), mtype(nb_step), ru(5, nb_step), rau(nb_step))
+        chunk = 256
+        allocate(o(5, chunk), w(5, chunk), verdict(chunk))
+        rmove = 0; ru = zero; rau = zero; mtype = 0
+        do j = 1, nb_step
+            t = pick_residue_type()
+            m = pick_molecule_index(S%res(t)%count)
+            draw = rand_uniform()
+            n1 = S%res(t)%n1
+            rt(j) = t - 1
+            rm(j) = max(m - 1, 0)
+            if (draw <= S%p_translation) then
+                if (m /= 0) then
+                    call random_number(trial)
+                    ru(1:3, j) = trial
+                    rau(j) = rand_uniform()
+                    rmove(j) = 1
+                    mtype(j) = TYPE_TRANSLATION
+                end if
+            else
+                if (n1 /= 1 .and. m /= 0) then
+                    ru(4, j) = rand_uniform()                                ! ApplyRandomRotation: angle, then axis
+                    ru(5, j) = rand_uniform()
+                    rau(j) = rand_uniform()
+                    rmove(j) = 2
+                    mtype(j) = TYPE_ROTATION
+                end if
+            end if
+        end do
+        rc = mgpu_chain_run_get_stats(S%engine, seen0, st_steps, st_void, st_und)
+        call note(int(rc))
+        rc = mgpu_chain_run_open(S%engine, 0_c_int, int(run_k, c_int), S%translation_step, S%rotation_step, S%temperature)
+        call note(int(rc))
+        if (status /= 0) return
+        pushed = 0; collected = 0; queued = 0
+        do while (collected < nb_step .and. status == 0)
+            ! records as far ahead as the ring takes them, then launches up to the depth, then the next results in order
+            n = min(nb_step - pushed, int(run_ring) - (pushed - collected))
+            if (n > 0) then
+                rc = mgpu_chain_run_push(S%engine, int(n, c_int), rt(pushed + 1:), rm(pushed + 1:), rmove(pushed + 1:), &
+                                         ru(:, pushed + 1:), rau(pushed + 1:))
+                call note(int(rc))
+                pushed = pushed + n
+            end if
+            rc = mgpu_chain_run_get_stats(S%engine, seen, st_steps, st_void, st_und)
+            call note(int(rc))
+            n = run_depth - (queued - int(seen - seen0))
+            if (n > 0) then
+                rc = mgpu_chain_run_launch(S%engine, int(n, c_int))
+                call note(int(rc))
+                queued = queued + n
+            end if
+            if (status /= 0) exit
+            rc = mgpu_chain_run_collect(S%engine, int(min(chunk, nb_step - collected), c_int), 1_c_int, o, w, verdict, n_got, stalled_at)
+            call note(int(rc))
+            if (status /= 0) exit
+            do i = 1, int(n_got)
+                j = collected + 1
+                if (verdict(i) == 2) then
+                    ! too close to call on the device: this loop's own exp decides, and the engine obeys
+                    old = zero; new = zero
+                    old(1:3) = o(1:3, i); new(1:3) = w(1:3, i)
+                    old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP)
+                    new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP)
+                    yes = decide(old, new, int(rt(j)) + 1, mtype(j), rau(j), BY_HOST)
+                    rc = mgpu_chain_run_force(S%engine, stalled_at, merge(1_c_int, 0_c_int, yes))
+                    call note(int(rc))
+                    queued = queued + 1
+                    exit                                                     ! (collected again, with its final verdict)
+                end if
+                if (mtype(j) /= 0) call book_step(mtype(j), o(:, i), w(:, i), verdict(i) == DEVICE_ACCEPTED)
+                collected = j
+            end do
+        end do
+        rc = mgpu_chain_run_close(S%engine)
+        call note(int(rc))
+        call refresh_frames()
+    end subroutine run_block
+
+    ! counters and running energies of one decided translation / rotation, as resolve_step books them
+    subroutine book_step(move_type, o, w, accepted)
+        integer, intent(in) :: move_type
+        real(real64), intent(in) :: o(5), w(5)
+        logical, intent(in) :: accepted
+        real(real64) :: old(6), new(6)
+        old = zero
+        new = zero
+        if (move_type == TYPE_TRANSLATION) then
+            S%counter(C_TRIAL_T) = S%counter(C_TRIAL_T) + 1
+        else
+            S%counter(C_TRIAL_R) = S%counter(C_TRIAL_R) + 1
+        end if
+        if (.not. accepted) return
+        old(1:3) = o(1:3)
+        new(1:3) = w(1:3)
+        old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP)
+        new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP)
+        S%energy(IE_RECIP) = S%energy(IE_RECIP) + new(IE_RECIP) - old(IE_RECIP)
+        S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
+        S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
+        S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
+        if (move_type == TYPE_TRANSLATION) then
+            S%counter(C_T) = S%counter(C_T) + 1
+        else
+            S%counter(C_R) = S%counter(C_R) + 1
+        end if
+    end subroutine book_step
+
+    ! the mirror's frames of the active types from the engine, which built and committed the block's moves
+    subroutine refresh_frames()
+        integer :: t, n1
+        integer(c_int) :: rc, nm
+        real(c_double), allocatable :: com(:, :), off(:, :, :)
+        do t = 1, S%n_res
+            if (S%res(t)%active /= 1 .or. S%res(t)%count == 0) cycle
+            n1 = S%res(t)%n1
+            allocate(com(3, S%res(t)%count), off(3, n1, S%res(t)%count))
+            rc = mgpu_replica_get_frames(S%engine, 0_c_int, int(t - 1, c_int), nm, com, off)
+            call note(int(rc))
+            if (rc == MGPU_OK .and. int(nm) == S%res(t)%count) then
+                S%res(t)%com(:, 1:S%res(t)%count) = com
+                S%res(t)%off(:, 1:n1, 1:S%res(t)%count) = off
+            else if (rc == MGPU_OK) then
+                call note(4)
+            end if
+            deallocate(com, off)
+        end do
+    end subroutine refresh_frames
+
+    ! the engine's frames from the mirror (a chain run builds its moves from them)
+    subroutine upload_frames()
+        integer :: t, n1
+        integer(c_int) :: rc
+        do t = 1, S%n_res
+            if (S%res(t)%active /= 1) cycle
+            n1 = S%res(t)%n1
+            rc = mgpu_replica_set_frames(S%engine, 0_c_int, int(t - 1, c_int), int(S%res(t)%count, c_int), &
+                                         S%res(t)%com(:, 1:max(S%res(t)%count, 1)), S%res(t)%off(:, 1:n1, 1:max(S%res(t)%count, 1)))
+            call note(int(rc))
+        end do
+    end subroutine upload_frames
+
     ! AdjustMoveStepSizes, as written -- including the second branches that compare against +TOL and the
     ! rotation step that is multiplied by 1.95 and clamped from above by MIN_ROTATION_ANGLE
     subroutine adjust_move_step_sizes()
@@ -1207,7 +1388,7 @@ contains
         character(kind=c_char), intent(in) :: outdir(*)
         integer(c_int) :: rc
         integer :: i, t, m, stat, step
-        integer(c_int) :: cap
+        integer(c_int) :: cap, run_kmax, run_dmax
         integer(kind=8) :: c0, c1, crate
         real(real64) :: draw, e6(6)
 
@@ -1240,6 +1421,19 @@ contains
             call note(stat)
             if (stat == 0) chain_cap = int(cap)
         end if
+        ! chain runs, where the host wants them, the input draws no insertion / deletion and the engine takes this system;
+        ! elsewhere the windows above
+        run_on = .false.
+        if (fused .and. run_k > 0 .and. S%p_translation + S%p_rotation >= one .and. .not. S%has_reservoir) then
+            stat = mgpu_chain_run_capacity(S%engine, run_kmax, run_dmax, run_ring)
+            call note(stat)
+            if (stat == 0 .and. run_kmax > 0) then
+                run_on = .true.
+                run_k = min(run_k, int(run_kmax))
+                run_depth = min(run_depth, int(run_dmax))
+                call upload_frames()
+            end if
+        end if
         loop_seconds = 0.0_real64
 
         S%current_block = 0
@@ -1252,6 +1446,10 @@ contains
             S%current_block = S%current_block + 1
             step = 1
             call system_clock(c0, crate)
+            if (run_on) then
+                call run_block(int(nb_step))
+                step = nb_step + 1
+            end if
             do while (step <= nb_step)
                 if (fused .and. (spec_k > 1 .or. chain_cap > 0)) then
                     ! a window never crosses the end of a block (AdjustMoveStepSizes and the files come there)

@@ -64,6 +64,19 @@ def lib():
     return _host
 
 
+def set_chain_run(k: int = 0, depth: int = 3):
+    """mchain_set_chain_run: the single-chain driver (mc_chain.f90) runs NVT blocks as chain runs of k steps per launch with
+    `depth` launches in flight, where the engine takes them (Engine.chain_run_capacity); k = 0 switches the mode off."""
+    lib().mchain_set_chain_run(C.c_int(int(k)), C.c_int(int(depth)))
+
+
+def chain_run_mode():
+    """(on, k, depth) of the last mchain_run: on = the run's blocks were chain runs, k and depth as the engine's capacity cut them."""
+    out = np.zeros(3, dtype=np.int32)
+    lib().mchain_get_chain_run(out.ctypes.data_as(_ip))
+    return bool(out[0]), int(out[1]), int(out[2])
+
+
 class FortranFarm:
     """R chains of `system` on one GPU, advanced by the Fortran driver (mc_farm.f90).
 

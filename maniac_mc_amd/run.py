@@ -121,7 +121,7 @@ WIDE_CHAIN_WINDOWS_DEFAULT = False
 
 def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoir_path=None, device=0,
                    mol_capacity=None, nb_block=None, nb_step=None, seams=False, as_written=False, speculate=4,
-                   chain_windows=True, chain_margin=None, wide_chain_windows=WIDE_CHAIN_WINDOWS_DEFAULT):
+                   chain_windows=True, chain_margin=None, wide_chain_windows=WIDE_CHAIN_WINDOWS_DEFAULT, chain_run=None):
     """Run the chain; returns a dict with the final energies (K), counters, molecule counts, step sizes.
 
     ``seed``: None -> the input file's ``seed`` if present, else the generator is left unseeded
@@ -146,6 +146,12 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     orthorhombic box, the row form or an untiled wide form of the reciprocal update).  The files do not depend on it.
     ``chain_margin``: relative width of the band around an acceptance probability inside which the engine leaves the step to
     this loop's own exp (default: the engine's 16 ulp; tests widen it to drive the loop's side of that hand-over).
+    ``chain_run``: None (default) -> windows as above.  (k, depth) -> an input without insertions / deletions runs each block
+    as a CHAIN RUN (mgpu_chain_run_*): the block's steps are drawn ahead as records, the engine runs them in launches of up
+    to k steps queued back to back -- each continues from the step cursor it finds on the device -- and the loop keeps
+    ``depth`` launches in flight and books the results in order.  Same files.  Where the engine does not take the system
+    (Engine.chain_run_capacity) or the input is grand-canonical, the loop keeps its windows by itself; the result's
+    ``chain_run`` says which: dict(on, k, depth, launches, steps, void_launches, undecided).
     """
     system, inp, dat = io_maniac.load_system(maniac_path, data_path, inc_path, with_data=True)
     rdat = io_maniac.read_lammps_data(reservoir_path, inp) if reservoir_path else None
@@ -165,6 +171,8 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
         H.mchain_set_speculation(C.c_int(1 if seams else max(1, int(speculate))))
         H.mchain_set_chain_windows(C.c_int(1 if chain_windows else 0))
         H.mchain_set_wide_windows(C.c_int(1 if wide_chain_windows else 0))
+        k_run, depth_run = (0, 3) if chain_run is None or seams else (int(chain_run[0]), int(chain_run[1]))
+        fortran_host.set_chain_run(k_run, depth_run)
         H.mchain_get_loop_seconds.restype = C.c_double
         header = header_text(inp, dat, maniac_path, data_path, inc_path, eng, reservoir_path, rdat)
         H.mchain_set_log_header(header, C.c_int(len(header)))
@@ -187,6 +195,8 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
         times = np.zeros(3)
         H.mchain_get_times(times.ctypes.data_as(_dp))
         chain_stats = eng.chain_stats()
+        run_mode = fortran_host.chain_run_mode()
+        run_stats = dict(zip(("on", "k", "depth", "launches", "steps", "void_launches", "undecided"), run_mode + eng.chain_run_stats()))
         e_final = eng.system_energy(0)
     finally:
         eng.close()
@@ -194,7 +204,19 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     # loop_seconds: mchain_run as a whole (initial energy, Monte Carlo loop, every output file); mc_seconds: the Monte
     # Carlo steps alone; chain_windows: (one-launch windows, windows with a step left to the host's exp)
     return dict(energy=dict(zip(keys, e)), recomputed_energy=e_final, counters=cnt, n_mol=nm, loop_seconds=t_loop,
-                mc_seconds=mc_seconds, init_seconds=float(times[0]), file_seconds=float(times[2]), chain_windows=chain_stats, translation_step=st[0], rotation_step=st[1])
+                mc_seconds=mc_seconds, init_seconds=float(times[0]), file_seconds=float(times[2]), chain_windows=chain_stats, translation_step=st[0], rotation_step=st[1],
+                chain_run=run_stats)
+
+
+def parse_chain_run(text):
+    """--chain-run K[,DEPTH] -> (k, depth); depth defaults to 3."""
+    parts = [p.strip() for p in str(text).split(",")]
+    if len(parts) not in (1, 2) or not all(p.isdigit() for p in parts):
+        raise ValueError(f"--chain-run takes K or K,DEPTH (positive integers), not {text!r}")
+    k, depth = int(parts[0]), int(parts[1]) if len(parts) == 2 else 3
+    if k < 1 or depth < 1:
+        raise ValueError("--chain-run: K and DEPTH must be at least 1")
+    return k, depth
 
 
 def main(argv=None):
@@ -219,6 +241,8 @@ def main(argv=None):
                     help="one-launch windows also for rigid molecules of 6 to 63 sites")
     ap.add_argument("--no-wide-chain-windows", dest="wide_chain_windows", action="store_false",
                     help="such molecules' windows through the batched calls")
+    ap.add_argument("--chain-run", dest="chain_run", default=None, metavar="K[,DEPTH]",
+                    help="NVT inputs: run each block as a chain run of K steps per launch, DEPTH (default 3) launches in flight")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
     ap.add_argument("--replicas", type=int, default=None,
@@ -230,6 +254,12 @@ def main(argv=None):
     ap.add_argument("--farm-mode", default="auto", choices=("auto", "windows", "device", "device_accept", "host"),
                     help="with --replicas: how the farm builds and decides its steps (default auto)")
     a = ap.parse_args(argv)
+    try:
+        chain_run = parse_chain_run(a.chain_run) if a.chain_run is not None else None
+    except ValueError as err:
+        ap.error(str(err))
+    if chain_run is not None and a.replicas is not None:
+        ap.error("--chain-run is the single chain's mode: it cannot be combined with --replicas")
     if a.replicas is None:
         if a.fugacities is not None or a.frames != "0" or a.farm_mode != "auto":
             ap.error("--fugacities, --frames and --farm-mode need --replicas")
@@ -260,7 +290,7 @@ def main(argv=None):
         return 0
     res = run_simulation(a.maniac, a.data, a.inc, a.out, seed=a.seed, reservoir_path=a.reservoir, device=a.device,
                          as_written=a.as_written, speculate=a.speculate, chain_windows=not a.no_chain_windows,
-                         wide_chain_windows=a.wide_chain_windows)
+                         wide_chain_windows=a.wide_chain_windows, chain_run=chain_run)
     e = res["energy"]
     print(f"final energy (K): total {e['total']:.6f}  non_coulomb {e['non_coulomb']:.6f}  coulomb {e['coulomb']:.6f}  "
           f"recip {e['recip_coulomb']:.6f};  molecules {res['n_mol'].tolist()};  output in {os.path.join(a.out, '')}")

@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""Steps/s of the single-chain driver's Monte Carlo loop (mc_chain.f90, mchain_get_loop_seconds) in its default mode
+(speculate 4, one-launch windows) against chain runs (run_simulation(chain_run=(k, depth)): launches queued back to back that
+continue from the step cursor on the device).
+
+    python tools/chain_run_speed.py [--blocks 2] [--steps 2000] [--ks 1,2,4,8] [--depths 2,3,4] [--cases spce_10125_nvt,framework_nvt]
+
+Boxes: bench.py's 10 125-atom SPC/E box and its framework box (2208 framework atoms + 40 four-site waters), NVT, 50 %
+translations / 50 % rotations.  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
+build on one box in one session; per run: steps/s of the loop alone, mean steps per launch that did something, the share of
+void launches, undecided steps.  The output files of every mode must be those of the default mode (checked here).  A
+difference between two modes that is smaller than the spread between the two runs of one mode is no difference.
+"""
+import argparse
+import filecmp
+import os
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from maniac_mc_amd import io_maniac, run, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--ks", default="1,2,4,8")
+    ap.add_argument("--depths", default="2,3,4")
+    ap.add_argument("--cases", default="spce_10125_nvt,framework_nvt")
+    ap.add_argument("--rounds", type=int, default=2)
+    a = ap.parse_args()
+    tmp = tempfile.mkdtemp()
+    common = dict(nb_block=2, nb_step=100, translation_proba=0.5, rotation_proba=0.5)
+    cases = {
+        "spce_10125_nvt": (synth.spce_box(15), dict(translation_step=0.3, rotation_step_angle=0.3, masses=[15.9994, 1.008],
+                                                    atom_names=["OW", "HW"])),
+        "framework_nvt": (synth.framework_water_box(), dict(translation_step=0.5, rotation_step_angle=0.5,
+                                                            masses=[12.0] * 7 + [15.9994, 1.008, 1e-4], fugacity_atm=[1.0, 1.0])),
+    }
+    modes = [("default", None)] + [(f"run k={k} depth={d}", (k, d)) for k in map(int, a.ks.split(",")) for d in map(int, a.depths.split(","))]
+    n = a.blocks * a.steps
+    for name in a.cases.split(","):
+        system, kw = cases[name]
+        files = io_maniac.write_input_files(system, os.path.join(tmp, name + "_in"), **common, **kw)
+        rates = {label: [] for label, _ in modes}
+        base = None
+        for rnd in range(a.rounds):
+            for label, cr in modes:
+                out = os.path.join(tmp, f"{name}_{label.replace(' ', '_').replace('=', '')}_{rnd}") + "/"
+                res = run.run_simulation(*files, out, seed=5, nb_block=a.blocks, nb_step=a.steps, chain_run=cr)
+                rate = n / res["mc_seconds"]
+                rates[label].append(rate)
+                if base is None:
+                    base = out
+                diff = [f for f in sorted(os.listdir(out)) if f != "log.maniac" and not filecmp.cmp(os.path.join(out, f), os.path.join(base, f), shallow=False)]
+                c = res["counters"]
+                extra = f"windows {res['chain_windows'][0]}, left to the host {res['chain_windows'][1]}"
+                if cr is not None:
+                    r = res["chain_run"]
+                    work = max(1, r["launches"] - r["void_launches"])
+                    extra = (f"on {r['on']}, launches {r['launches']}, steps per working launch {r['steps'] / work:.2f}, "
+                             f"void {r['void_launches'] / max(1, r['launches']):.1%}, undecided {r['undecided']}")
+                print(f"{name:16s} round {rnd} {label:18s}: {rate:9.0f} steps/s (loop {res['mc_seconds']:.3f} s of {n} steps; {extra}; "
+                      f"acceptance {int(c[1] + c[3]) / n:.2f}; files as the first run's: {not diff}{' ' + str(diff) if diff else ''})", flush=True)
+        print(f"\n{name}: steps/s of the loop alone, the rounds side by side")
+        for label, _ in modes:
+            v = rates[label]
+            print(f"  {label:18s} {'  '.join(f'{x:9.0f}' for x in v)}   mean {sum(v) / len(v):9.0f}  spread {max(v) - min(v):8.0f}")
+        print(flush=True)
+
+
+if __name__ == "__main__":
+    main()
