@@ -572,9 +572,15 @@ int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long lo
  *   capacity    max_k steps per launch, max_in_flight launches whose results nobody has looked at, ring_steps steps pushed and
  *               not yet collected.  All 0 where the path does not apply: mgpu_farm_window_capacity's reasons (a site-major
  *               type, the per-k or tiled matrix-unit form, a Coulomb table over 64 KiB) and, because no such instance of
- *               the kernel exists, every triclinic box (with or without mgpu_set_triclinic_moves), every active type of
- *               more than 5 sites, and an engine that holds reservoirs.  Orthorhombic boxes whose active types have <= 5
- *               sites and take the row form, framework boxes included, are served.
+ *               the kernel exists, every active type of more than 5 sites and an engine that holds reservoirs.  Boxes whose
+ *               active types have <= 5 sites and take the row form are served: orthorhombic ones, framework boxes included,
+ *               always; a triclinic one only while BOTH mgpu_set_triclinic_moves and mgpu_chain_run_set_triclinic are on
+ *               (all 0 otherwise, as it always was).
+ *   set_triclinic  on = 1: a triclinic box takes runs (off at creation).  The launches then build every candidate with
+ *               ApplyPBC's triclinic form (src/geometry_utils.f90:167-220: through fractional coordinates, modulo(f, 1)
+ *               always) and sweep with ComputeDistance's image search (:397-411), as the farm windows of such a box do.
+ *               MGPU_ERR_STATE, and the switch stays as it was: an orthorhombic box, mgpu_set_triclinic_moves not on, a run
+ *               open.
  *   open        replaces the block's set-up (src/monte_carlo.f90:40-48): cursor 0, the block's step sizes and temperature.
  *               The replica needs resident frames of every active type, lane 0 must be idle, one run per engine
  *               (MGPU_ERR_STATE otherwise).  Drains every lane.
@@ -606,6 +612,7 @@ int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long lo
  * far and sees the state they committed; their results stay collectable -- and a submit on lane 0 is ordered behind them by
  * the stream.  Single-driver: one host thread at a time opens, pushes, launches, collects, forces and closes a run. */
 int mgpu_chain_run_capacity(const mgpu_engine *e, int *max_k, int *max_in_flight, int *ring_steps);
+int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on);
 int mgpu_chain_run_open(mgpu_engine *e, int replica, int k, double t_step, double r_step, double temperature);
 int mgpu_chain_run_push(mgpu_engine *e, int n, const int *t, const int *m, const int *move, const double *u5, const double *accept_u);
 int mgpu_chain_run_launch(mgpu_engine *e, int n_launches);

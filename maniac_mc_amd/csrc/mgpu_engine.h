@@ -373,6 +373,7 @@ struct mgpu_engine {
     // device memory (chain_run_kernel).  Single-driver: one host thread opens, pushes, launches, collects and closes a run.
     struct Run {
         bool open = false;
+        bool triclinic = false;                      // a triclinic box takes runs (mgpu_chain_run_set_triclinic; needs tri_moves)
         int replica = -1, k = 0;
         double t_step = 0.0, r_step = 0.0, temperature = 0.0;
         bool fast = false;                           // every record so far admits the fast fold

@@ -964,7 +964,11 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI 
 // behind it does nothing until one arrives that carries the host's decision for exactly that step (force_step): it obeys,
 // clears the flag and goes on with the steps behind it.  Moves only (a run is an NVT block): kind 0, prefactor 1.
 // Instances: <FLAT, FASTW> -- orthorhombic boxes, molecules of <= kMaxFusedSitesWide sites in the row form, framework boxes
-// included: what farm_window_kernel<FLAT, FASTW> covers.  No WIDE, TRI or RSV instance exists (capacity 0).
+// included: what farm_window_kernel<FLAT, FASTW> covers -- and <false, false, TRI = true>: a triclinic box whose engine has
+// switched both device-built moves and triclinic runs on (mgpu_chain_run_set_triclinic).  TRI changes what it changes in
+// farm_window_kernel and nothing else: every role and the commit build the candidate with the triclinic form of trial_frame
+// (trial_com_triclinic's centre, wrapped always), and the pair role runs the register-site sweep with ComputeDistance's
+// image search; no flat form, no fast fold.  No WIDE or RSV instance exists (capacity 0).
 // ------------------------------------------------------------------------------------------
 struct RunState { int cursor, pushed, stalled, pad; };
 struct RunRec {
@@ -994,12 +998,13 @@ struct ChainRunArgs {
 };
 static_assert(sizeof(BoxDev) + sizeof(ChainRunArgs) + 160 <= 4096, "a chain-run launch must fit the kernel-argument segment");
 
-template <bool FLAT, bool FASTW>
+template <bool FLAT, bool FASTW, bool TRI = false>
 __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
     double2 *__restrict__ A_base, const ChainRunArgs g) {
+    static_assert(!TRI || (!FLAT && !FASTW), "the image search has no flat form and no fast fold (farm_window_kernel's triclinic family)");
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];      // Coulomb table | phase tables | partials staging
     __shared__ double2 s_pair[kMaxTypes * kMaxTypes];
     __shared__ int4 s_grp[kMaxGrp];
@@ -1051,7 +1056,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             const RunRec &rec = s_rec[c];
             const int n1 = tp.n1[rec.t];
             if (tid < n1) {
-                const auto f = trial_frame<false, false>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                const auto f = trial_frame<false, TRI>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                 double off[3];
                 trial_offset<false>(tp, f, g.replica, rec.t, tid, off);
                 for (int d = 0; d < 3; ++d) s_cand[0][tid * 3 + d] = f.com[d] + off[d];
@@ -1089,7 +1094,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             const int n1 = tp.n1[rec.t];
             double *cand = &s_cand[wave][0];
             if (ent == 1) {
-                const auto f = trial_frame<false, false>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                const auto f = trial_frame<false, TRI>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                 if (lane < n1) {
                     double off[3];
                     trial_offset<false>(tp, f, g.replica, rec.t, lane, off);
@@ -1106,7 +1111,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
                     pair_flat_item<NS, false, FASTW, true>(tp, bx, pos, nmol, res_q, res_atype, s_dyn, s_pair, s_grp,         \
                                                      s_plane + wave * kFlatMaxPlanes, it, cand, kMaxFusedSitesWide, split, ns, lane, 0, g.partials, wg); \
                 else                                                                                                     \
-                    pair_sweep_item<NS, false, false, false, FASTW, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, nullptr, \
+                    pair_sweep_item<NS, false, TRI, false, FASTW, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, nullptr,   \
                                                                     nullptr, it, cand, kMaxFusedSitesWide, split, ns, lane, g.partials, wg);   \
             } while (0)
             switch (n1) {
@@ -1221,7 +1226,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             const size_t rep3 = (size_t)g.replica * 3;
             double *fcom = tp.com + rep3 * tp.n_mol_slots + tp.mol_off[rec.t];
             double *foff = tp.off + rep3 * tp.n_cap_atoms;
-            const auto f = trial_frame<false, false>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+            const auto f = trial_frame<false, TRI>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
             double off[3] = {0.0, 0.0, 0.0};
             if (lane < n1) trial_offset<false>(tp, f, g.replica, rec.t, lane, off);
             // (every lane has read the resident frame before any lane overwrites it)

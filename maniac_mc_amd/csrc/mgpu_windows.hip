@@ -669,9 +669,11 @@ int mgpu_farm_window_wait(mgpu_engine *e, int lane, double *old_energy, double *
 // mgpu_kernels_windows.h).  Host state (e->run) is touched by the run's one driver thread only.
 
 // steps per launch the engine accepts, 0 where the path does not apply: mgpu_farm_window_capacity's reasons, and -- no such
-// instance of chain_run_kernel exists -- every triclinic box, every active type of more than kMaxFusedSitesWide sites, reservoirs
+// instance of chain_run_kernel exists -- every active type of more than kMaxFusedSitesWide sites, reservoirs, and a triclinic
+// box unless both device-built moves and triclinic runs are on (mgpu_set_triclinic_moves, mgpu_chain_run_set_triclinic)
 static int run_max_k(const mgpu_engine *e) {
-    if (e->bx.triclinic || e->rsv_any) return 0;
+    if (e->rsv_any) return 0;
+    if (e->bx.triclinic && !(e->run.triclinic && e->tri_moves)) return 0;
     for (int t = 0; t < e->tp.n_res; ++t) {
         if (!e->is_active[t]) continue;
         FarmTypeForm f;
@@ -729,11 +731,16 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     ln.dirty = true;
     ln.forget_trial();
     alt_forget(e, rn.replica);
-    with_bools([&](auto FLAT, auto FASTW) {
-        hipLaunchKernelGGL((chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value>), dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo,
-                           e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype, e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks,
-                           e->d_rrows, e->n_rrows, e->d_A, g);
-    }, e->pair_flat, ff);
+    // The run kernel's families: with the image search (no flat form, no fast fold: farm_window_kernel's triclinic family), and
+    // the orthorhombic one, whose flags are free.
+    auto tri_family = [](auto &&f) { f(chain_run_kernel<false, false, true>); };
+    auto ortho_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); };
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype,
+                           e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, e->d_A, g);
+    };
+    if (e->bx.triclinic) tri_family(launch);
+    else with_bools([&](auto... flags) { ortho_family(launch, flags...); }, e->pair_flat, ff);
     HIP_TRY(hipGetLastError());
     return MGPU_OK;
 }
@@ -744,6 +751,16 @@ int mgpu_chain_run_capacity(const mgpu_engine *e, int *max_k, int *max_in_flight
     *max_k = k;
     if (max_in_flight) *max_in_flight = k ? kRunMaxInFlight : 0;
     if (ring_steps) *ring_steps = k ? kRunRingSteps : 0;
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    // every refusal leaves the switch as it was
+    if (!e->bx.triclinic) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: the box is orthorhombic");
+    if (!e->tri_moves) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: device-built triclinic moves are off (mgpu_set_triclinic_moves)");
+    if (e->run.open) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: a run is open");
+    e->run.triclinic = on != 0;
     return MGPU_OK;
 }
 

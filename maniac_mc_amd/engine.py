@@ -291,6 +291,11 @@ class Engine:
         check(self.L.mgpu_chain_run_capacity(self.h, C.byref(k), C.byref(d), C.byref(r)))
         return k.value, d.value, r.value
 
+    def chain_run_set_triclinic(self, on=True):
+        """mgpu_chain_run_set_triclinic: a triclinic box takes chain runs (off by default).  Refused (MgpuError, the switch
+        unchanged) for an orthorhombic box, without set_triclinic_moves, and while a run is open."""
+        check(self.L.mgpu_chain_run_set_triclinic(self.h, C.c_int(1 if on else 0)))
+
     def chain_run_open(self, replica, k, translation_step, rotation_step, temperature):
         check(self.L.mgpu_chain_run_open(self.h, C.c_int(replica), C.c_int(k), C.c_double(translation_step), C.c_double(rotation_step),
                                          C.c_double(temperature)))

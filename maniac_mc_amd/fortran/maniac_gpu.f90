@@ -328,6 +328,13 @@ module maniac_gpu
             integer(c_int), intent(out) :: max_k, max_in_flight, ring_steps
             integer(c_int) :: rc
         end function
+        ! a triclinic box takes runs (off by default; needs mgpu_set_triclinic_moves)
+        function mgpu_chain_run_set_triclinic(e, on) bind(C, name="mgpu_chain_run_set_triclinic") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: on
+            integer(c_int) :: rc
+        end function
         function mgpu_chain_run_open(e, replica, k, t_step, r_step, temperature) bind(C, name="mgpu_chain_run_open") result(rc)
             import :: c_ptr, c_int, c_double
             type(c_ptr), value :: e

@@ -1421,7 +1421,9 @@ contains
             call note(stat)
             if (stat == 0) chain_cap = int(cap)
         end if
-        ! chain runs, where the host wants them, the input draws no insertion / deletion and the engine takes this system;
+        ! chain runs, where the host wants them, the input draws no insertion / deletion and the engine takes this system (a
+        ! triclinic box: only where the caller has switched mgpu_chain_run_set_triclinic on -- the capacity says so, and the
+        ! block is then driven exactly as an orthorhombic one: the engine wraps the centres, refresh_frames reads them back);
         ! elsewhere the windows above
         run_on = .false.
         if (fused .and. run_k > 0 .and. S%p_translation + S%p_rotation >= one .and. .not. S%has_reservoir) then

@@ -66,7 +66,8 @@ def lib():
 
 def set_chain_run(k: int = 0, depth: int = 3):
     """mchain_set_chain_run: the single-chain driver (mc_chain.f90) runs NVT blocks as chain runs of k steps per launch with
-    `depth` launches in flight, where the engine takes them (Engine.chain_run_capacity); k = 0 switches the mode off."""
+    `depth` launches in flight, where the engine takes them (Engine.chain_run_capacity: a triclinic box only after
+    Engine.chain_run_set_triclinic); k = 0 switches the mode off."""
     lib().mchain_set_chain_run(C.c_int(int(k)), C.c_int(int(depth)))
 
 

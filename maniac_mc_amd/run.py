@@ -121,7 +121,8 @@ WIDE_CHAIN_WINDOWS_DEFAULT = False
 
 def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoir_path=None, device=0,
                    mol_capacity=None, nb_block=None, nb_step=None, seams=False, as_written=False, speculate=4,
-                   chain_windows=True, chain_margin=None, wide_chain_windows=WIDE_CHAIN_WINDOWS_DEFAULT, chain_run=None):
+                   chain_windows=True, chain_margin=None, wide_chain_windows=WIDE_CHAIN_WINDOWS_DEFAULT, chain_run=None,
+                   chain_run_triclinic=False):
     """Run the chain; returns a dict with the final energies (K), counters, molecule counts, step sizes.
 
     ``seed``: None -> the input file's ``seed`` if present, else the generator is left unseeded
@@ -152,6 +153,9 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     ``depth`` launches in flight and books the results in order.  Same files.  Where the engine does not take the system
     (Engine.chain_run_capacity) or the input is grand-canonical, the loop keeps its windows by itself; the result's
     ``chain_run`` says which: dict(on, k, depth, launches, steps, void_launches, undecided).
+    ``chain_run_triclinic``: True (with ``chain_run``) -> a TRICLINIC input's blocks are chain runs too: the engine is created
+    with device-built triclinic moves and takes runs (Engine.chain_run_set_triclinic).  False (default): a triclinic input
+    keeps its windows whatever ``chain_run`` says.  An orthorhombic input does not look at it.  ValueError without ``chain_run``.
     """
     system, inp, dat = io_maniac.load_system(maniac_path, data_path, inc_path, with_data=True)
     rdat = io_maniac.read_lammps_data(reservoir_path, inp) if reservoir_path else None
@@ -159,7 +163,12 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     n_res = topo.n_res
     if mol_capacity is None:
         mol_capacity = [NB_MAX_MOLECULE if topo.is_active[t] == 1 else max(1, int(system.n_mol[t])) for t in range(n_res)]
-    eng = Engine.from_system(system, n_replicas=1, device=device, mol_capacity=mol_capacity)
+    if chain_run_triclinic and chain_run is None:
+        raise ValueError("chain_run_triclinic needs chain_run=(k, depth)")
+    run_tri = bool(chain_run_triclinic) and not seams and system.is_triclinic()
+    eng = Engine.from_system(system, n_replicas=1, device=device, mol_capacity=mol_capacity, triclinic_moves=run_tri)
+    if run_tri:
+        eng.chain_run_set_triclinic(True)
     if chain_margin is not None:
         eng.chain_set_margin(float(chain_margin))
     H = fortran_host.lib()
@@ -243,6 +252,8 @@ def main(argv=None):
                     help="such molecules' windows through the batched calls")
     ap.add_argument("--chain-run", dest="chain_run", default=None, metavar="K[,DEPTH]",
                     help="NVT inputs: run each block as a chain run of K steps per launch, DEPTH (default 3) launches in flight")
+    ap.add_argument("--chain-run-triclinic", dest="chain_run_triclinic", action="store_true",
+                    help="with --chain-run: a triclinic input's blocks are chain runs too (off by default: such an input keeps its windows)")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
     ap.add_argument("--replicas", type=int, default=None,
@@ -258,6 +269,8 @@ def main(argv=None):
         chain_run = parse_chain_run(a.chain_run) if a.chain_run is not None else None
     except ValueError as err:
         ap.error(str(err))
+    if a.chain_run_triclinic and chain_run is None:
+        ap.error("--chain-run-triclinic needs --chain-run K[,DEPTH]")
     if chain_run is not None and a.replicas is not None:
         ap.error("--chain-run is the single chain's mode: it cannot be combined with --replicas")
     if a.replicas is None:
@@ -290,7 +303,8 @@ def main(argv=None):
         return 0
     res = run_simulation(a.maniac, a.data, a.inc, a.out, seed=a.seed, reservoir_path=a.reservoir, device=a.device,
                          as_written=a.as_written, speculate=a.speculate, chain_windows=not a.no_chain_windows,
-                         wide_chain_windows=a.wide_chain_windows, chain_run=chain_run)
+                         wide_chain_windows=a.wide_chain_windows, chain_run=chain_run,
+                         chain_run_triclinic=a.chain_run_triclinic)
     e = res["energy"]
     print(f"final energy (K): total {e['total']:.6f}  non_coulomb {e['non_coulomb']:.6f}  coulomb {e['coulomb']:.6f}  "
           f"recip {e['recip_coulomb']:.6f};  molecules {res['n_mol'].tolist()};  output in {os.path.join(a.out, '')}")

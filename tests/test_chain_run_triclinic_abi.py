@@ -1,0 +1,46 @@
+"""Triclinic chain runs' interface without a device: the C header, the Fortran binding and the Python loader name
+mgpu_chain_run_set_triclinic with the same argument list (tests/test_chain_run_abi.py's comparison), the ABI version is
+unchanged, and the command line takes --chain-run-triclinic together with --chain-run only."""
+import inspect
+import os
+
+import pytest
+
+from tests.test_chain_run_abi import ROOT, _c_args, _f_args
+
+NAME = "mgpu_chain_run_set_triclinic"
+
+
+def test_header_binding_and_loader_agree():
+    from maniac_mc_amd import _lib
+    header = open(os.path.join(ROOT, "include", "maniac_gpu.h")).read()
+    f90 = open(os.path.join(ROOT, "maniac_mc_amd", "fortran", "maniac_gpu.f90")).read()
+    assert NAME in _lib.EXPORTS
+    c, f = _c_args(header, NAME), _f_args(f90, NAME)
+    assert [(ct, cptr) for _, ct, cptr in c] == [("ptr", True), ("int", False)], c
+    assert len(c) == len(f), (c, f)
+    for (cn, ct, cptr), (fn, ft, fref) in zip(c, f):
+        if ct == "ptr":
+            assert ft == "ptr" and not fref, (cn, fn)
+        else:
+            assert ct == ft and cptr == fref, (cn, fn)
+    assert "MGPU_ABI_VERSION 2" in " ".join(header.split())
+    assert _lib.ABI_VERSION == 2
+
+
+def test_the_library_and_the_engine_class_carry_it():
+    from maniac_mc_amd import _lib
+    from maniac_mc_amd.engine import Engine
+    assert hasattr(_lib.lib(), NAME)
+    assert list(inspect.signature(Engine.chain_run_set_triclinic).parameters) == ["self", "on"]
+
+
+def test_the_command_line_flag_parses():
+    from maniac_mc_amd import run
+    assert inspect.signature(run.run_simulation).parameters["chain_run_triclinic"].default is False
+    # with --chain-run the parser takes the flag (the run stops at the missing input file, after parsing)
+    assert run.main(["-i", "/nonexistent.maniac", "-d", "x", "-p", "y", "--chain-run", "4,3", "--chain-run-triclinic"]) == 1
+    # alone it is an argument error
+    with pytest.raises(SystemExit) as ei:
+        run.main(["-i", "/nonexistent.maniac", "-d", "x", "-p", "y", "--chain-run-triclinic"])
+    assert ei.value.code == 2

@@ -4,9 +4,11 @@
 continue from the step cursor on the device).
 
     python tools/chain_run_speed.py [--blocks 2] [--steps 2000] [--ks 1,2,4,8] [--depths 2,3,4] [--cases spce_10125_nvt,framework_nvt]
+    python tools/chain_run_speed.py --workload spce_triclinic
 
 Boxes: bench.py's 10 125-atom SPC/E box and its framework box (2208 framework atoms + 40 four-site waters), NVT, 50 %
-translations / 50 % rotations.  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
+translations / 50 % rotations.  --workload spce_triclinic: bench.py's sheared 10 125-atom box (tilt 3.0 / -2.0 / 1.5 A) instead,
+its chain runs with chain_run_triclinic=True (the default mode is the windows such a box runs through without the switch).  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
 build on one box in one session; per run: steps/s of the loop alone, mean steps per launch that did something, the share of
 void launches, undecided steps.  The output files of every mode must be those of the default mode (checked here).  A
 difference between two modes that is smaller than the spread between the two runs of one mode is no difference.
@@ -16,6 +18,8 @@ import filecmp
 import os
 import sys
 import tempfile
+
+import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from maniac_mc_amd import io_maniac, run, synth  # noqa: E402
@@ -28,8 +32,11 @@ def main():
     ap.add_argument("--ks", default="1,2,4,8")
     ap.add_argument("--depths", default="2,3,4")
     ap.add_argument("--cases", default="spce_10125_nvt,framework_nvt")
+    ap.add_argument("--workload", default=None, choices=("spce", "framework", "spce_triclinic"), help="one box instead of --cases")
     ap.add_argument("--rounds", type=int, default=2)
     a = ap.parse_args()
+    if a.workload is not None:
+        a.cases = {"spce": "spce_10125_nvt", "framework": "framework_nvt", "spce_triclinic": "spce_triclinic_nvt"}[a.workload]
     tmp = tempfile.mkdtemp()
     common = dict(nb_block=2, nb_step=100, translation_proba=0.5, rotation_proba=0.5)
     cases = {
@@ -38,6 +45,13 @@ def main():
         "framework_nvt": (synth.framework_water_box(), dict(translation_step=0.5, rotation_step_angle=0.5,
                                                             masses=[12.0] * 7 + [15.9994, 1.008, 1e-4], fugacity_atm=[1.0, 1.0])),
     }
+    if "spce_triclinic_nvt" in a.cases.split(","):
+        # bench.py's spce_triclinic: rows a = (lx, 0, 0), b = (xy, ly, 0), c = (xz, yz, lz), the centres sheared with the cell
+        s = synth.spce_box(15)
+        L = float(s.box_matrix[0, 0])
+        s.box_matrix = np.array([[L, 0.0, 0.0], [3.0, L, 0.0], [-2.0, 1.5, L]])
+        s.com[0] = s.bounds_lo[None, :] + ((s.com[0] - s.bounds_lo[None, :]) / L) @ s.box_matrix.T
+        cases["spce_triclinic_nvt"] = (s, cases["spce_10125_nvt"][1])
     modes = [("default", None)] + [(f"run k={k} depth={d}", (k, d)) for k in map(int, a.ks.split(",")) for d in map(int, a.depths.split(","))]
     n = a.blocks * a.steps
     for name in a.cases.split(","):
@@ -48,7 +62,10 @@ def main():
         for rnd in range(a.rounds):
             for label, cr in modes:
                 out = os.path.join(tmp, f"{name}_{label.replace(' ', '_').replace('=', '')}_{rnd}") + "/"
-                res = run.run_simulation(*files, out, seed=5, nb_block=a.blocks, nb_step=a.steps, chain_run=cr)
+                res = run.run_simulation(*files, out, seed=5, nb_block=a.blocks, nb_step=a.steps, chain_run=cr,
+                                         chain_run_triclinic=cr is not None and system.is_triclinic())
+                if cr is not None and not res["chain_run"]["on"]:
+                    raise SystemExit(f"{name}: the engine did not take the chain run (Engine.chain_run_capacity)")
                 rate = n / res["mc_seconds"]
                 rates[label].append(rate)
                 if base is None:
