@@ -346,7 +346,6 @@ struct mgpu_engine {
         bool timing = false;                         // stage stamps wanted (mgpu_chain_set_timing)
         bool wide = false;                           // windows take rows of 6..63 sites (mgpu_chain_set_wide)
         double *h_rows = nullptr;                    // pinned [2][kChainMaxCand][kFarmWideSites][3]: such rows, the blocks taken in turn
-        size_t wide_lds_opted = 0;                   // dynamic LDS the WIDE instances have opted in to
     } chain;
     // The A(k) double buffer: the other buffer of every replica and which of the two is its current one (d_acur[r] = 1:
     // d_A_alt), allocated on first use (alt_reserve).  Farm windows and the batched trials store every candidate's A + delta into
@@ -369,6 +368,16 @@ struct mgpu_engine {
         std::atomic<long long> windows{0}, undecided{0};   // (the lanes may be driven by different host threads)
         std::mutex mu;                                     // the engine-wide blocks' first allocation
     } farm;
+    // What the one-launch paths make of every residue type (window_types_build, mgpu_windows.hip): built when the engine is
+    // created, from values fixed there (n1, site_major, the box, kmax, the row structure, MGPU_RECIP_NO_MFMA / _PER_K).
+    struct WindowTypes {
+        signed char take[kMaxRes];                   // kWindowNone / kWindowNarrow (<= kMaxFusedSitesWide sites, row form) / kWindowWide
+        signed char kform[kMaxRes];                  // the k role's form (kFarmForm*), its rows per tile and site-states
+        int wide_rpt[kMaxRes], wide_nss[kMaxRes];
+        size_t k_lds[kMaxRes];                       // the k role's dynamic LDS (window_k_lds_bytes)
+        size_t k_lds_one, k_lds_max;                 // ... of a one-site row (the floor of a narrow launch), over the types a row may carry
+        bool rows_one;                               // a one-site molecule takes the row form (single-chain windows without a narrow active type)
+    } win{};
     // a chain run (mgpu_chain_run_*): launches of one chain queued back to back on lane 0, each continuing from the cursor in
     // device memory (chain_run_kernel).  Single-driver: one host thread opens, pushes, launches, collects and closes a run.
     struct Run {
@@ -457,6 +466,8 @@ int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int
 int farm_clear_stall(mgpu_engine *e, int replica);   // the replica's state was rewritten: it waits for no decision (mgpu_windows.hip)
 int chain_topo(mgpu_engine *e, const Topo **d_topo);   // the engine's Topo in device memory (mgpu_windows.hip)
 void chain_run_release(mgpu_engine *e);                // a chain run's blocks (mgpu_windows.hip)
+enum { kWindowNone = 0, kWindowNarrow = 1, kWindowWide = 2 };
+void window_types_build(mgpu_engine *e);               // e->win, at the end of mgpu_engine_create (mgpu_windows.hip)
 // mgpu_launch.hip
 int launch_pair(mgpu_engine *e, Lane &ln, const PairItem *d_items, int n_items, int common_n1, int site_stride,
                 int nsplit, double *d_lj, double *d_c, bool ordered = false, double2 *host_partials = nullptr,
@@ -476,8 +487,7 @@ inline size_t lane_site_buffer_bytes(int n_max, int site_stride) {
 static_assert(sizeof(double2) == kLdsPhase && sizeof(int4) == kLdsRowRec, "mgpu_internal.h sizes the LDS tables with these");
 inline int recip_ktot(const mgpu_engine *e) { return recip_ktot(e->kmax); }
 inline size_t recip_rows_lds_bytes(const mgpu_engine *e, int n1_max) { return recip_rows_lds_bytes(recip_ktot(e), e->n_rrows, n1_max); }
-// the resolving waves' scratch of a farm window: four sums per split and four more, per wave
-inline size_t farm_resolver_scratch_bytes(int nsplit) { return (size_t)kPairWaves * (4 * nsplit + 4) * sizeof(double); }
+static_assert(kWindowPairWaves == kPairWaves && kWindowSiteChunk == kSiteChunk, "mgpu_internal.h sizes the windows' LDS with these");
 bool recip_by_rows(const mgpu_engine *e, int n1_max);
 struct RecipPlan {
     int form = MGPU_RECIP_FORM_ROWS;   // MGPU_RECIP_FORM_*

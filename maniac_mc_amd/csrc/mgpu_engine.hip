@@ -660,6 +660,7 @@ int mgpu_engine_create(mgpu_engine **out, int device, int n_replicas, int n_res,
 #undef HIP_TRY_E
     e->self_of_type.resize(n_res);
     for (int t = 0; t < n_res; ++t) e->self_of_type[t] = self_energy_host(e, t);
+    window_types_build(e);
     *out = e;
     return MGPU_OK;
 }

@@ -106,6 +106,33 @@ inline int chain_window_steps_by_lds(int nsplit) { return (int)(kLdsDefaultMax /
 // a chain-run launch of k steps (chain_run_kernel): its resolver stages both entries of every step
 inline size_t chain_run_resolver_lds_bytes(int k, int nsplit) { return chain_resolver_lds_bytes(2 * k, nsplit); }
 
+// ---- Dynamic LDS of a launch of the three one-launch paths (mgpu_windows.hip), narrow and WIDE: the largest of its roles'
+// needs.  The launch sites and the capacity rules take every size and both budget comparisons from here.
+enum WindowPath { kPathChain, kPathFarm, kPathRun };   // mgpu_chain_window, mgpu_farm_window_*, mgpu_chain_run_*
+constexpr int kWindowPairWaves = 8, kWindowSiteChunk = 32;   // kPairWaves, kSiteChunk (asserted in mgpu_engine.h)
+// gfx950 gives a workgroup up to 160 KiB; the WIDE instances, which opt in beyond 64 KiB, leave kFarmWideStaticMax to their static LDS
+constexpr size_t kFarmWideStaticMax = 16 * 1024, kFarmWideLdsMax = 160 * 1024 - kFarmWideStaticMax;
+inline size_t window_lds_budget(bool wide) { return wide ? kFarmWideLdsMax : kLdsDefaultMax; }
+// pair role: the Coulomb table, and behind it (WIDE) the waves' rows and slabs
+inline size_t window_pair_lds_bytes(bool wide, size_t coul_bytes) {
+    return wide ? chain_wide_pair_lds_bytes(coul_bytes, kWindowPairWaves, kWindowSiteChunk) : coul_bytes;
+}
+// k role of a row by its type's form: the row form's tables (recip_rows_lds_bytes) for a narrow row, the front and the form's
+// tables (row form, or recip_wide_lds_bytes) for a row of more than five sites
+inline size_t window_k_lds_bytes(bool wide_row, size_t form_bytes) { return wide_row ? chain_wide_k_lds_bytes(form_bytes) : form_bytes; }
+// the resolving waves' scratch of a farm window: four sums per split and four more, per wave
+inline size_t farm_resolver_scratch_bytes(int nsplit) { return (size_t)kWindowPairWaves * (4 * nsplit + 4) * sizeof(double); }
+// resolver: `count` = pair entries of a single-chain window, steps of a chain-run launch; a farm's does not depend on its chains
+inline size_t window_resolver_lds_bytes(WindowPath path, int count, int nsplit) {
+    return path == kPathChain ? chain_resolver_lds_bytes(count, nsplit)
+                              : (path == kPathFarm ? farm_resolver_scratch_bytes(nsplit) : chain_run_resolver_lds_bytes(count, nsplit));
+}
+// the launch: k_bytes = the largest k role (window_k_lds_bytes) among the rows it carries -- narrow -- or may carry -- WIDE
+inline size_t window_lds_bytes(WindowPath path, bool wide, size_t coul_bytes, size_t k_bytes, int count, int nsplit) {
+    return std::max(std::max(window_pair_lds_bytes(wide, coul_bytes), k_bytes), window_resolver_lds_bytes(path, count, nsplit));
+}
+inline bool window_lds_fits(bool wide, size_t lds) { return lds <= window_lds_budget(wide); }
+
 // ---- The two blocks of a batched trial on a lane (mgpu_lanes.hip): the one home of their layouts, plain integers as above.
 // trial_submit_impl, trial_wait_impl, finish_decided and the DecideItem offsets take every offset from here: a block that
 // disagrees between writer and reader gives a wrong energy, not a crash (tests/test_trial_layout.py).

@@ -3,6 +3,8 @@
 // memory the host polls.
 #include "mgpu_engine.h"
 
+#include <map>
+
 namespace mgpu {
 
 // The engine's Topo in device memory (the window kernels index it by residue types they LOAD: as a by-value kernel argument
@@ -98,88 +100,146 @@ int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int
     return MGPU_OK;
 }
 
+// ---- what the three one-launch paths take, and the launch they share --------------------------
+
+// e->win: the k role a window (farm or, for a type of more than kMaxFusedSitesWide sites, single-chain) gives a row of residue
+// type t -- the form recip_plan picks for the type alone, as the batched path's per-type launches do (recip_groups) -- and the
+// dynamic LDS that role needs.  kWindowNone: windows do not take the type (site-major types, i.e. molecules of kFarmWideSites
+// sites or more, frozen ones among them; a molecule of <= kMaxFusedSitesWide sites whose type does not take the row form; a larger
+// one in a triclinic box -- there is no WIDE instance with the image search -- or whose type takes the per-k or the tiled
+// matrix-unit form).  Everything read here is fixed when the engine is created.
+void window_types_build(mgpu_engine *e) {
+    mgpu_engine::WindowTypes &w = e->win;
+    w = mgpu_engine::WindowTypes{};
+    w.k_lds_one = recip_rows_lds_bytes(e, 1);
+    w.rows_one = recip_by_rows(e, 1);
+    for (int t = 0; t < e->tp.n_res; ++t) {
+        const int n1 = e->tp.n1[t];
+        const bool wide = n1 > kMaxFusedSitesWide;
+        if (!wide) w.k_lds[t] = window_k_lds_bytes(false, recip_rows_lds_bytes(e, n1));   // (a narrow row's k role is the row form's)
+        if (e->tp.site_major[t] || n1 >= kFarmWideSites || (wide && e->bx.triclinic)) continue;
+        const RecipPlan p = recip_plan(e, n1, true);
+        if (p.form == MGPU_RECIP_FORM_ROWS) {
+            w.k_lds[t] = window_k_lds_bytes(wide, recip_rows_lds_bytes(e, n1));
+        } else if (wide && (p.form == MGPU_RECIP_FORM_WIDE_VECTOR || p.form == MGPU_RECIP_FORM_WIDE_MFMA)) {
+            // launch_recip's tables (2 n1 site-states), or one tile of site-states
+            w.kform[t] = (signed char)(p.mfma_tile ? kFarmFormWideMfma : kFarmFormWideVector);
+            w.wide_rpt[t] = p.wide_rpt; w.wide_nss[t] = p.wide_nss;
+            w.k_lds[t] = window_k_lds_bytes(true, p.wide_lds);
+        } else {
+            continue;
+        }
+        w.take[t] = wide ? kWindowWide : kWindowNarrow;
+        w.k_lds_max = std::max(w.k_lds_max, w.k_lds[t]);         // (every type a row may carry)
+    }
+}
+
+// What a path admits, from e->win and the switches laid over it (mgpu_chain_set_wide, mgpu_set_triclinic_moves,
+// mgpu_chain_run_set_triclinic, reservoirs).  capacity: candidates of a single-chain window, chains of a farm window, steps of a
+// chain-run launch; 0 where the path does not apply --
+//   every path: an active type it does not take (a narrow type off the row form, a site-major one, one of more than
+//     kMaxFusedSitesWide sites unless the path has WIDE instances, they are on and windows take the type), a Coulomb table or a
+//     resolver beyond 64 KiB, WIDE LDS beyond its budget;
+//   farm windows and chain runs: a triclinic box whose engine has not switched device-built moves on;
+//   chain runs (no such instance of chain_run_kernel exists): reservoirs, and a triclinic box unless triclinic runs are on.
+// rides[t]: a record of type t may travel (a single-chain window takes any row of <= kMaxFusedSitesWide sites; a run any active type).
+struct WindowAdmission {
+    int capacity = 0;
+    bool rides[kMaxRes] = {};
+};
+static WindowAdmission window_admission(const mgpu_engine *e, WindowPath path) {
+    const mgpu_engine::WindowTypes &w = e->win;
+    const bool wide_on = path == kPathFarm || (path == kPathChain && e->chain.wide);
+    WindowAdmission a;
+    bool ok = true, wide = false;
+    for (int t = 0; t < e->tp.n_res; ++t) {
+        const bool takes = w.take[t] == kWindowNarrow || (w.take[t] == kWindowWide && wide_on);
+        a.rides[t] = path == kPathRun ? e->is_active[t] != 0 : (takes || (path == kPathChain && e->tp.n1[t] <= kMaxFusedSitesWide));
+        if (!e->is_active[t]) continue;
+        ok = ok && takes;
+        wide = wide || w.take[t] == kWindowWide;
+    }
+    if (path != kPathChain && e->bx.triclinic && !e->tri_moves) ok = false;
+    if (path == kPathRun && (e->rsv_any || (e->bx.triclinic && !e->run.triclinic))) ok = false;
+    if (path == kPathChain && !w.rows_one) ok = false;
+    const int nsplit = e->pair_nsplit;
+    if (!window_lds_fits(false, window_lds_bytes(path, false, e->coul_bytes, 0, 0, nsplit))) ok = false;
+    if (wide && !window_lds_fits(true, window_lds_bytes(path, true, e->coul_bytes, w.k_lds_max, 0, nsplit))) ok = false;
+    if (!ok) return a;
+    // (single-chain windows, runs: the resolving workgroup stages every split partial in LDS, 2 entries per step at most)
+    a.capacity = path == kPathFarm ? std::min(kFarmMaxChains, e->n_replicas)
+                                   : std::max(0, std::min(path == kPathChain ? kChainMaxCand : kRunMaxK, chain_window_steps_by_lds(nsplit)));
+    return a;
+}
+
+// a launch's dynamic LDS (mgpu_internal.h): `k_rows` = the largest k role among the narrow rows it carries; a WIDE launch takes
+// the largest over every type a row may carry
+static size_t window_lds(const mgpu_engine *e, WindowPath path, bool wide, size_t k_rows, int count) {
+    const size_t k_bytes = wide ? e->win.k_lds_max : std::max(e->win.k_lds_one, k_rows);
+    return window_lds_bytes(path, wide, e->coul_bytes, k_bytes, count, e->pair_nsplit);
+}
+
+// what the WIDE instances read besides: the k role's form per residue type and its tile, the rows' first tasks, where the pair
+// role's slabs start in dynamic LDS
+static void wide_args(const mgpu_engine *e, const int **row_first, int *wide_at, signed char *kform, int *wide_rpt, int *wide_nss) {
+    *row_first = e->d_row_first;
+    *wide_at = (int)chain_wide_pair_at(e->coul_bytes);
+    std::memcpy(kform, e->win.kform, sizeof(e->win.kform));
+    std::memcpy(wide_rpt, e->win.wide_rpt, sizeof(e->win.wide_rpt));
+    std::memcpy(wide_nss, e->win.wide_nss, sizeof(e->win.wide_nss));
+}
+
+// Beyond 64 KiB of dynamic LDS a kernel opts in (gfx950: up to 160 KiB per workgroup); only the WIDE instances get here.  The
+// limit belongs to the kernel function, not to an engine: the most each family has asked for on each device is kept for the
+// whole process, and only a larger size sets the attribute again.  each(f) calls f(kernel) for every instance of the family.
+enum LdsFamily { kLdsChainWide, kLdsFarmWide, kLdsFamilies };
+static std::mutex g_lds_opt_mu;
+static std::map<int, size_t> g_lds_opted[kLdsFamilies];       // [family][device]
+template <class Each>
+static int lds_opt_in(int device, LdsFamily family, size_t lds, Each &&each) {
+    if (lds <= kLdsDefaultMax) return MGPU_OK;
+    std::lock_guard<std::mutex> lock(g_lds_opt_mu);
+    size_t &opted = g_lds_opted[family][device];
+    if (lds <= opted) return MGPU_OK;
+    hipError_t err = hipSuccess;
+    each([&](auto kernel) {
+        if (err == hipSuccess) err = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    });
+    if (err != hipSuccess)
+        return set_error(MGPU_ERR_HIP, std::string("hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds): ") + hipGetErrorString(err));
+    opted = lds;
+    return MGPU_OK;
+}
+
+// the launch of any instance of the three kernels: the engine's arguments, then the path's own
+template <class Kernel, class Args>
+static void window_launch(Kernel kernel, const mgpu_engine *e, const Topo *d_topo, int grid, size_t lds, hipStream_t stream, const Args &g) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kChainBlock), lds, stream, d_topo, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype,
+                       e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, e->d_A, g);
+}
+
+// a result row "five old | five new" (non_coulomb, coulomb, recip_coulomb, ewald_self, intra_coulomb) into the caller's row c
+static void copy_energy_rows(double *old_energy, double *new_energy, size_t c, const double *row) {
+    std::memcpy(old_energy + 5 * c, row, 5 * sizeof(double));
+    std::memcpy(new_energy + 5 * c, row + 5, 5 * sizeof(double));
+}
+
+// the device has committed (or is committing, behind the tag) a step of `kind` on (replica, t): the host mirrors follow.
+// in_range_ok = false: the new sites may lie outside the fast fold's range (an as-written deletion moves resident atoms only:
+// the range flag stands)
+static void mirror_accepted(mgpu_engine *e, int replica, int t, int kind, bool in_range_ok) {
+    const size_t idx = (size_t)replica * e->tp.n_res + t;
+    if (kind == MGPU_CREATION) e->h_nmol[idx] += 1;
+    if (kind == MGPU_DELETION) e->h_nmol[idx] -= 1;
+    if (kind != MGPU_DELETION && !in_range_ok) e->in_range[idx] = 0;
+    frozen_changed(e, replica, t);
+}
+
 }  // namespace mgpu
 
 extern "C" {
 
-// ---- the k role of a window's row by its residue type (single-chain and farm windows) -------------
-// The k role a window (farm or, for a type of more than kMaxFusedSitesWide sites, single-chain) gives a row of residue type t -- the form recip_plan picks for the type alone, as the batched
-// path's per-type launches do (recip_groups) -- and the dynamic LDS that role needs.  false: windows do not take the type
-// (site-major types, i.e. molecules of kFarmWideSites sites or more; a molecule of <= kMaxFusedSitesWide sites whose type
-// does not take the row form; a larger one in a triclinic box -- there is no WIDE instance with the image search -- or whose
-// type takes the per-k or the tiled matrix-unit form).
-struct FarmTypeForm {
-    int form = kFarmFormRows, rpt = 0, nss = 0;
-    size_t lds = 0;
-};
-static bool farm_type_form(const mgpu_engine *e, int t, FarmTypeForm &f) {
-    const int n1 = e->tp.n1[t];
-    if (e->tp.site_major[t] || n1 >= kFarmWideSites) return false;
-    const RecipPlan p = recip_plan(e, n1, true);
-    f = FarmTypeForm{};
-    if (n1 <= kMaxFusedSitesWide) {                                 // the narrow instance's chains
-        if (p.form != MGPU_RECIP_FORM_ROWS) return false;
-        f.lds = recip_rows_lds_bytes(e, n1);
-        return true;
-    }
-    if (e->bx.triclinic) return false;
-    switch (p.form) {
-        case MGPU_RECIP_FORM_ROWS:
-            f.lds = kFarmKFront + recip_rows_lds_bytes(e, n1);
-            return true;
-        case MGPU_RECIP_FORM_WIDE_VECTOR:                           // launch_recip's tables (2 n1 site-states)
-        case MGPU_RECIP_FORM_WIDE_MFMA:                             // ... one tile of site-states
-            f.form = p.mfma_tile ? kFarmFormWideMfma : kFarmFormWideVector;
-            f.rpt = p.wide_rpt; f.nss = p.wide_nss;
-            f.lds = kFarmKFront + p.wide_lds;
-            return true;
-        default:                                                    // the tiled matrix-unit form, the per-k form
-            return false;
-    }
-}
-
 // ---- single-chain windows --------------------------------------------------------------------
-
-// Dynamic LDS of the WIDE instances for this engine (mgpu_internal.h): the larger of the pair role's (Coulomb table, then the
-// waves' candidate rows and slabs) and the k role's over the types a row may carry; a window adds its resolver's staging.
-// Beyond 64 KiB the instances opt in, up to the budget of the WIDE farm windows (kFarmWideLdsMax).
-constexpr size_t kFarmWideStaticMax = 16 * 1024, kFarmWideLdsMax = 160 * 1024 - kFarmWideStaticMax;
-static size_t chain_wide_lds(const mgpu_engine *e) {
-    size_t lds = chain_wide_pair_lds_bytes(e->coul_bytes, kPairWaves, kSiteChunk);
-    for (int t = 0; t < e->tp.n_res; ++t) {
-        FarmTypeForm f;
-        if (e->frozen[t] || !farm_type_form(e, t, f)) continue;
-        // (farm_type_form's size of a type of more than kMaxFusedSitesWide sites = kFarmKFront + its form's tables)
-        lds = std::max(lds, e->tp.n1[t] > kMaxFusedSitesWide ? chain_wide_k_lds_bytes(f.lds - kFarmKFront) : f.lds);
-    }
-    return lds;
-}
-
-// largest window the engine accepts, 0 where the one-launch path does not apply: a per-k reciprocal form, a Coulomb table
-// beyond 64 KiB, a site-major active type, and an active type of more than kMaxFusedSitesWide sites unless wide windows are on
-// (mgpu_chain_set_wide) and windows take the type (farm_type_form: an orthorhombic box, fewer than kFarmWideSites sites, the
-// row form or an untiled wide form)
-static int chain_max_candidates(const mgpu_engine *e) {
-    int n1_max = 1;
-    bool wide = false;
-    for (int t = 0; t < e->tp.n_res; ++t) {
-        if (!e->is_active[t]) continue;
-        if (e->tp.site_major[t]) return 0;
-        if (e->tp.n1[t] > kMaxFusedSitesWide) {
-            FarmTypeForm f;
-            if (!e->chain.wide || !farm_type_form(e, t, f)) return 0;
-            wide = true;
-            continue;
-        }
-        n1_max = std::max(n1_max, e->tp.n1[t]);
-    }
-    if (!recip_by_rows(e, n1_max)) return 0;
-    if (e->coul_bytes > kLdsDefaultMax) return 0;
-    if (wide && chain_wide_lds(e) > kFarmWideLdsMax) return 0;
-    // the resolving workgroup stages every split partial of the window in LDS: 2 entries per candidate at most
-    const int by_lds = chain_window_steps_by_lds(e->pair_nsplit);
-    return std::max(0, std::min(kChainMaxCand, by_lds));
-}
 
 int mgpu_chain_set_wide(mgpu_engine *e, int on) {
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
@@ -189,7 +249,7 @@ int mgpu_chain_set_wide(mgpu_engine *e, int on) {
 
 int mgpu_chain_window_capacity(const mgpu_engine *e, int *max_candidates) {
     if (!e || !max_candidates) return set_error(MGPU_ERR_INVALID_ARG, "chain_window_capacity: null argument");
-    *max_candidates = chain_max_candidates(e);
+    *max_candidates = window_admission(e, kPathChain).capacity;
     return MGPU_OK;
 }
 
@@ -240,7 +300,8 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
     if (!t || !m || !kind || !link || !sites || !accept_u || !accept_pref || !old_energy || !new_energy || !first_accepted || !undecided)
         return set_error(MGPU_ERR_INVALID_ARG, "chain_window: null argument");
-    const int n_max = chain_max_candidates(e);
+    const WindowAdmission adm = window_admission(e, kPathChain);
+    const int n_max = adm.capacity;
     if (n_max == 0) return set_error(MGPU_ERR_STATE, "chain_window: not available for this engine (mgpu_chain_window_capacity)");
     if (n < 1 || n > n_max) return set_error(MGPU_ERR_INVALID_ARG, "chain_window: window size out of range");
     if (replica < 0 || replica >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, "chain_window: replica out of range");
@@ -275,7 +336,8 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     ChainArgs g{};
     bool fast = replica_in_range(e, replica);
     char cand_ok[kChainMaxCand];
-    int n1_max = 1, n_ent = 0;
+    int n_ent = 0;
+    size_t k_rows = 0;
     bool wide = false;
     double *wide_rows = ch.h_rows ? ch.h_rows + ((ch.seq + 1) & 1) * (kChainWideRowsBytes / sizeof(double)) : nullptr;
     for (int c = 0; c < n; ++c) {
@@ -284,8 +346,7 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
         if (t[c] < 0 || t[c] >= e->tp.n_res) return set_error(MGPU_ERR_INVALID_ARG, "chain_window: residue type out of range");
         const int n1 = e->tp.n1[t[c]];
         const bool wide_row = n1 > kMaxFusedSitesWide;
-        FarmTypeForm tf;
-        if (n1 > site_stride || e->tp.site_major[t[c]] || (wide_row && (!ch.wide || !farm_type_form(e, t[c], tf))))
+        if (n1 > site_stride || !adm.rides[t[c]])
             return set_error(MGPU_ERR_INVALID_ARG, "chain_window: molecule too large for the one-launch path");
         wide = wide || wide_row;
         const size_t idx = (size_t)replica * e->tp.n_res + t[c];
@@ -300,7 +361,7 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
         if ((rc = check_candidate(e, c, replica, t[c], mc, k != MGPU_CREATION))) return rc;
         if (k == MGPU_CREATION && lk != -2 && e->h_nmol[idx] >= e->tp.cap[t[c]])
             return set_error(MGPU_ERR_CAPACITY, "chain_window: residue type is at mol_capacity");
-        if (!wide_row) n1_max = std::max(n1_max, n1);
+        if (!wide_row) k_rows = std::max(k_rows, e->win.k_lds[t[c]]);
         g.t[c] = t[c]; g.m[c] = mc; g.kind[c] = (signed char)k; g.link[c] = (signed char)lk;
         g.u[c] = accept_u[c]; g.pref[c] = accept_pref[c];
         const double *row = sites + (size_t)c * site_stride * 3;
@@ -318,22 +379,14 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
         if (k != MGPU_DELETION) { g.ent_new_of[c] = (signed char)n_ent; g.ent_c[n_ent] = (unsigned char)c; g.ent_new[n_ent] = 1; ++n_ent; }
     }
     const int nsplit = e->pair_nsplit;
-    // a row of more than kMaxFusedSitesWide sites: the WIDE instance (its own LDS rule), else the narrow one
-    const size_t lds = std::max(wide ? chain_wide_lds(e) : std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)),
-                                chain_resolver_lds_bytes(n_ent, nsplit));
-    if (lds > (wide ? kFarmWideLdsMax : kLdsDefaultMax)) return set_error(MGPU_ERR_CAPACITY, "chain_window: the window does not fit the LDS budget");
+    // a row of more than kMaxFusedSitesWide sites: the WIDE instance, else the narrow one
+    const size_t lds = window_lds(e, kPathChain, wide, k_rows, n_ent);
+    if (!window_lds_fits(wide, lds)) return set_error(MGPU_ERR_CAPACITY, "chain_window: the window does not fit the LDS budget");
     auto wide_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, true>); };
-    if (lds > kLdsDefaultMax && lds > ch.wide_lds_opted) {
-        // beyond 64 KiB of dynamic LDS a kernel opts in (gfx950: up to 160 KiB per workgroup); only the WIDE instances get here
-        hipError_t err = hipSuccess;
-        auto opt_in = [&](auto kernel) {
-            if (err == hipSuccess) err = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        };
-        for_all_bools([&](auto... flags) { wide_family(opt_in, flags...); }, std::integral_constant<int, 2>{});
-        if (err != hipSuccess)
-            return set_error(MGPU_ERR_HIP, std::string("hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds): ") + hipGetErrorString(err));
-        ch.wide_lds_opted = lds;
-    }
+    if ((rc = lds_opt_in(e->device, kLdsChainWide, lds, [&](auto &&f) {
+             for_all_bools([&](auto... flags) { wide_family(f, flags...); }, std::integral_constant<int, 2>{});
+         })))
+        return rc;
     ch.seq += 1;
     for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
     g.stamps = ch.timing ? 1 : 0;
@@ -343,22 +396,13 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     g.temperature = temperature; g.e_recip = recip_energy; g.margin = ch.margin;
     if (wide) {
         g.wide_sites = wide_rows;
-        g.row_first = e->d_row_first;
-        g.wide_at = (int)chain_wide_pair_at(e->coul_bytes);
-        for (int tt = 0; tt < e->tp.n_res; ++tt) {
-            FarmTypeForm f;
-            if (!farm_type_form(e, tt, f)) continue;              // (no row of such a type passed the checks above)
-            g.kform[tt] = (signed char)f.form; g.wide_rpt[tt] = f.rpt; g.wide_nss[tt] = f.nss;
-        }
+        wide_args(e, &g.row_first, &g.wide_at, g.kform, g.wide_rpt, g.wide_nss);
     }
     const int grid = n + (n_ent * nsplit + kPairWaves - 1) / kPairWaves;
     const bool ff = fast && e->pair_fast_fold;
     ln.dirty = true;
     ln.forget_trial();
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype,
-                           e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, e->d_A, g);
-    };
+    auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
     // (the image search has no flat and no fast-fold form)
     if (e->bx.triclinic) launch(chain_window_kernel<false, false, true>);
     else if (wide) with_bools([&](auto... flags) { wide_family(launch, flags...); }, e->pair_flat, ff);
@@ -366,25 +410,14 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     HIP_TRY(hipGetLastError());
     // ---- wait for the tag: the results are in host memory when it shows this window's number
     if ((rc = wait_for_tag(ln.stream, ch.h_tag, 1, ch.seq, 20000, 4096, "chain_window"))) return rc;
-    for (int c = 0; c < n; ++c) {
-        std::memcpy(old_energy + 5 * (size_t)c, ch.h_out + 10 * (size_t)c, 5 * sizeof(double));
-        std::memcpy(new_energy + 5 * (size_t)c, ch.h_out + 10 * (size_t)c + 5, 5 * sizeof(double));
-    }
+    for (int c = 0; c < n; ++c) copy_energy_rows(old_energy, new_energy, c, ch.h_out + 10 * (size_t)c);
     const int *hi = (const int *)(ch.h_out + 10 * (size_t)kChainMaxCand);
     const int first = hi[0], und = hi[1];
     *first_accepted = first;
     *undecided = und;
     ch.windows += 1;
     if (und >= 0) ch.undecided += 1;
-    if (first >= 0) {
-        // the device is committing candidate `first` behind the tag: the host mirrors follow
-        const size_t idx = (size_t)replica * e->tp.n_res + t[first];
-        if (kind[first] == MGPU_CREATION) e->h_nmol[idx] += 1;
-        if (kind[first] == MGPU_DELETION) e->h_nmol[idx] -= 1;
-        if (kind[first] != MGPU_DELETION && !cand_ok[first]) e->in_range[idx] = 0;
-        // (an as-written deletion moves resident atoms only: the range flag stands)
-        frozen_changed(e, replica, t[first]);
-    }
+    if (first >= 0) mirror_accepted(e, replica, t[first], kind[first], cand_ok[first] != 0);
     return MGPU_OK;
 }
 
@@ -396,40 +429,9 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
 // kFarmDepth windows per lane may be in flight (a farm whose move selection does not depend on earlier outcomes -- NVT --
 // queues the next step before it has seen the last).
 
-// Dynamic LDS of the WIDE instances for this engine: the larger of the pair role's (Coulomb table, then the waves' candidate
-// rows and slabs), the k role's over the active types, and the resolving waves' scratch.  gfx950 gives a workgroup up to
-// 160 KiB; the instances' static LDS takes up to kFarmWideStaticMax of it.
-static size_t farm_wide_lds(const mgpu_engine *e) {
-    size_t lds = ((e->coul_bytes + 15) & ~(size_t)15) + kFarmWidePairBytes;
-    lds = std::max(lds, farm_resolver_scratch_bytes(e->pair_nsplit));
-    for (int t = 0; t < e->tp.n_res; ++t) {
-        FarmTypeForm f;
-        if (!e->frozen[t] && farm_type_form(e, t, f)) lds = std::max(lds, f.lds);      // (every type a chain may carry)
-    }
-    return lds;
-}
-
-// chains per launch the engine accepts, 0 where the path does not apply: a triclinic box whose engine has not switched
-// device-built moves on (mgpu_set_triclinic_moves), an active type windows do not take (farm_type_form: in a triclinic box
-// every type of more than kMaxFusedSitesWide sites), a Coulomb table beyond 64 KiB, LDS beyond the budget
-static int farm_max_chains(const mgpu_engine *e) {
-    if (e->bx.triclinic && !e->tri_moves) return 0;
-    bool wide = false;
-    for (int t = 0; t < e->tp.n_res; ++t) {
-        if (!e->is_active[t]) continue;
-        FarmTypeForm f;
-        if (!farm_type_form(e, t, f)) return 0;
-        wide = wide || e->tp.n1[t] > kMaxFusedSitesWide;
-    }
-    if (e->coul_bytes > kLdsDefaultMax) return 0;
-    if (farm_resolver_scratch_bytes(e->pair_nsplit) > kLdsDefaultMax) return 0;
-    if (wide && farm_wide_lds(e) > kFarmWideLdsMax) return 0;
-    return std::min(kFarmMaxChains, e->n_replicas);
-}
-
 int mgpu_farm_window_capacity(const mgpu_engine *e, int *max_chains, int *max_in_flight) {
     if (!e || !max_chains) return set_error(MGPU_ERR_INVALID_ARG, "farm_window_capacity: null argument");
-    *max_chains = farm_max_chains(e);
+    *max_chains = window_admission(e, kPathFarm).capacity;
     if (max_in_flight) *max_in_flight = kFarmDepth;
     return MGPU_OK;
 }
@@ -487,7 +489,8 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     Lane &ln = *lp;
     if (!replica || !t || !m || !move || !u5 || !accept_u || !accept_pref)
         return set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: null argument");
-    const int n_max = farm_max_chains(e);
+    const WindowAdmission adm = window_admission(e, kPathFarm);
+    const int n_max = adm.capacity;
     if (n_max == 0) return set_error(MGPU_ERR_STATE, "farm_window_submit: not available for this engine (mgpu_farm_window_capacity)");
     if (n < 1 || n > n_max) return set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: number of chains out of range");
     if (!(temperature > 0.0)) return set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: temperature must be positive");
@@ -514,8 +517,8 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     pd.ok.assign(n, 1);
     FarmArgs g{};
     FarmRec *recs = n <= kFarmInline ? g.inline_recs : fw.h_recs + (size_t)slot * fw.cap;
-    bool fast = true;
-    int n1_max = 1;
+    bool fast = true, wide = false;
+    size_t k_rows = 0;
     std::string why;
     for (int c = 0; c < n; ++c) {
         FarmRec &r = recs[c];
@@ -526,9 +529,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         r.replica = replica[c];
         if (mv == 0) continue;                                   // the chain does nothing this step
         if (t[c] < 0 || t[c] >= e->tp.n_res) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: residue type out of range"); break; }
-        const int n1 = e->tp.n1[t[c]];
-        FarmTypeForm tf;
-        if (!farm_type_form(e, t[c], tf) || e->frozen[t[c]]) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: molecule too large for the one-launch path"); break; }
+        if (!adm.rides[t[c]]) { rc = set_error(MGPU_ERR_INVALID_ARG, "farm_window_submit: molecule too large for the one-launch path"); break; }
         const size_t idx = (size_t)replica[c] * e->tp.n_res + t[c];
         const int k = mv <= 2 ? MGPU_MOVE : (mv == 3 ? MGPU_CREATION : MGPU_DELETION);
         if ((rc = admit_built(e, idx, k, mv, kAdmitFrames, "farm_window_submit", "chain", c, why, pd.ok[c], fast))) { set_error(rc, why); break; }
@@ -546,7 +547,8 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         }
         fast = fast && replica_in_range(e, replica[c]);
         if ((rc = admit_built(e, idx, k, mv, kAdmitInsertion | kAdmitRange, "farm_window_submit", "chain", c, why, pd.ok[c], fast))) { set_error(rc, why); break; }
-        n1_max = std::max(n1_max, n1);
+        wide = wide || e->win.take[t[c]] == kWindowWide;
+        k_rows = std::max(k_rows, e->win.k_lds[t[c]]);
         pd.kind[c] = k;
         // windows still in flight behind this one must not take the fast fold if this step is accepted: the range flag is
         // lowered now, not when the window is collected (a rejected step costs the replica the fast fold and nothing else)
@@ -564,12 +566,10 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         return set_error(MGPU_ERR_STATE, "farm_window_submit: a window with an insertion / deletion needs the lane's earlier windows collected "
                                          "(its molecule counts must be current)");
     const int nsplit = e->pair_nsplit;
-    // a chain of more than kMaxFusedSitesWide sites: the WIDE instance (its own LDS rule), else the narrow one
-    const bool wide = n1_max > kMaxFusedSitesWide;
-    const size_t lds = wide ? farm_wide_lds(e)
-                            : std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), farm_resolver_scratch_bytes(nsplit));
-    if (lds > (wide ? kFarmWideLdsMax : kLdsDefaultMax)) return set_error(MGPU_ERR_CAPACITY, "farm_window_submit: the window does not fit the LDS budget");
-    // The window kernel's families: with the image search (no flat form, no fast fold, no wide chains: farm_type_form), WIDE,
+    // a chain of more than kMaxFusedSitesWide sites: the WIDE instance, else the narrow one
+    const size_t lds = window_lds(e, kPathFarm, wide, k_rows, n);
+    if (!window_lds_fits(wide, lds)) return set_error(MGPU_ERR_CAPACITY, "farm_window_submit: the window does not fit the LDS budget");
+    // The window kernel's families: with the image search (no flat form, no fast fold, no wide chains: window_types_build), WIDE,
     // narrow; within each the flags are free.  (An engine without reservoirs runs the instances without their code.)
     auto tri_family = [](auto &&f, auto RSV) { f(farm_window_kernel<false, false, false, decltype(RSV)::value, true>); };
     auto wide_family = [](auto &&f, auto FLAT, auto FASTW, auto RSV) {
@@ -578,16 +578,10 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     auto narrow_family = [](auto &&f, auto FLAT, auto FASTW, auto RSV) {
         f(farm_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, decltype(RSV)::value>);
     };
-    if (lds > kLdsDefaultMax) {
-        // beyond 64 KiB of dynamic LDS a kernel opts in (gfx950: up to 160 KiB per workgroup); only the WIDE instances get here
-        hipError_t err = hipSuccess;
-        auto opt_in = [&](auto kernel) {
-            if (err == hipSuccess) err = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        };
-        for_all_bools([&](auto... flags) { wide_family(opt_in, flags...); }, std::integral_constant<int, 3>{});
-        if (err != hipSuccess)
-            return set_error(MGPU_ERR_HIP, std::string("hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds): ") + hipGetErrorString(err));
-    }
+    if ((rc = lds_opt_in(e->device, kLdsFarmWide, lds, [&](auto &&f) {
+             for_all_bools([&](auto... flags) { wide_family(f, flags...); }, std::integral_constant<int, 3>{});
+         })))
+        return rc;
     fw.seq += 1;
     for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
     g.recs = fw.h_recs + (size_t)slot * fw.cap;
@@ -599,13 +593,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     g.n = n; g.nsplit = nsplit;
     g.t_step = t_step; g.r_step = r_step; g.temperature = temperature; g.margin = e->chain.margin;
     if (wide) {
-        g.row_first = e->d_row_first;
-        g.wide_at = (int)((e->coul_bytes + 15) & ~(size_t)15);
-        for (int tt = 0; tt < e->tp.n_res; ++tt) {
-            FarmTypeForm f;
-            if (!farm_type_form(e, tt, f)) continue;              // (no chain of such a type passed the checks above)
-            g.kform[tt] = (signed char)f.form; g.wide_rpt[tt] = f.rpt; g.wide_nss[tt] = f.nss;
-        }
+        wide_args(e, &g.row_first, &g.wide_at, g.kform, g.wide_rpt, g.wide_nss);
     }
     const int wpc = 2 * nsplit;
     const int grid = (n * wpc + kPairWaves - 1) / kPairWaves + n;
@@ -614,10 +602,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     ln.forget_trial();
     for (int c = 0; c < n; ++c) alt_forget(e, replica[c]);     // (the window's k role overwrites their other buffers)
     e->a_switched = true;
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype,
-                           e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, e->d_A, g);
-    };
+    auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
     if (e->bx.triclinic) with_bools([&](auto... flags) { tri_family(launch, flags...); }, e->rsv_any);
     else if (wide) with_bools([&](auto... flags) { wide_family(launch, flags...); }, e->pair_flat, ff, e->rsv_any);
     else with_bools([&](auto... flags) { narrow_family(launch, flags...); }, e->pair_flat, ff, e->rsv_any);
@@ -648,17 +633,12 @@ int mgpu_farm_window_wait(mgpu_engine *e, int lane, double *old_energy, double *
     }
     for (int c = 0; c < n; ++c) {
         const double *o = out + (size_t)kFarmOut * c;
-        std::memcpy(old_energy + 5 * (size_t)c, o, 5 * sizeof(double));
-        std::memcpy(new_energy + 5 * (size_t)c, o + 5, 5 * sizeof(double));
+        copy_energy_rows(old_energy, new_energy, c, o);
         const int v = (int)o[10];
         verdict[c] = v;
         if (v == kFarmVerdictUndecided) e->farm.undecided += 1;
         if (v != kFarmVerdictAccepted) continue;
-        // the device has committed the step: the host mirrors follow
-        const size_t idx = (size_t)pd.rep[c] * e->tp.n_res + pd.t[c];
-        if (pd.kind[c] == MGPU_CREATION) e->h_nmol[idx] += 1;
-        if (pd.kind[c] == MGPU_DELETION) e->h_nmol[idx] -= 1;
-        // (the range flag was lowered at submit)
+        mirror_accepted(e, pd.rep[c], pd.t[c], pd.kind[c], true);   // (the range flag was lowered at submit)
     }
     fw.pending.pop_front();
     return MGPU_OK;
@@ -667,21 +647,6 @@ int mgpu_farm_window_wait(mgpu_engine *e, int lane, double *old_energy, double *
 // ---- chain runs --------------------------------------------------------------------------------
 // Launches of ONE chain queued back to back on lane 0, each continuing from the cursor in device memory (chain_run_kernel,
 // mgpu_kernels_windows.h).  Host state (e->run) is touched by the run's one driver thread only.
-
-// steps per launch the engine accepts, 0 where the path does not apply: mgpu_farm_window_capacity's reasons, and -- no such
-// instance of chain_run_kernel exists -- every active type of more than kMaxFusedSitesWide sites, reservoirs, and a triclinic
-// box unless both device-built moves and triclinic runs are on (mgpu_set_triclinic_moves, mgpu_chain_run_set_triclinic)
-static int run_max_k(const mgpu_engine *e) {
-    if (e->rsv_any) return 0;
-    if (e->bx.triclinic && !(e->run.triclinic && e->tri_moves)) return 0;
-    for (int t = 0; t < e->tp.n_res; ++t) {
-        if (!e->is_active[t]) continue;
-        FarmTypeForm f;
-        if (e->tp.n1[t] > kMaxFusedSitesWide || !farm_type_form(e, t, f)) return 0;
-    }
-    if (e->coul_bytes > kLdsDefaultMax) return 0;
-    return std::max(0, std::min(kRunMaxK, chain_window_steps_by_lds(e->pair_nsplit)));
-}
 
 // the tags of the launches that have finished since the last look, in order: counters and the launch log
 static void run_poll(mgpu_engine *e) {
@@ -711,11 +676,11 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     int rc = chain_topo(e, &d_topo);
     if (rc) return rc;
     const int nsplit = e->pair_nsplit;
-    int n1_max = 1;
+    size_t k_rows = 0;
     for (int t = 0; t < e->tp.n_res; ++t)
-        if (e->is_active[t]) n1_max = std::max(n1_max, e->tp.n1[t]);
-    const size_t lds = std::max(std::max(e->coul_bytes, recip_rows_lds_bytes(e, n1_max)), chain_run_resolver_lds_bytes(rn.k, nsplit));
-    if (lds > kLdsDefaultMax) return set_error(MGPU_ERR_CAPACITY, "chain_run_launch: the launch does not fit the LDS budget");
+        if (e->is_active[t]) k_rows = std::max(k_rows, e->win.k_lds[t]);
+    const size_t lds = window_lds(e, kPathRun, false, k_rows, rn.k);
+    if (!window_lds_fits(false, lds)) return set_error(MGPU_ERR_CAPACITY, "chain_run_launch: the launch does not fit the LDS budget");
     ChainRunArgs g{};
     rn.seq += 1;
     g.state = rn.d_state; g.ring = rn.d_ring; g.partials = rn.d_part; g.res = rn.d_res; g.ticket = rn.d_ticket; g.alt = rn.d_alt;
@@ -735,10 +700,7 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     // the orthorhombic one, whose flags are free.
     auto tri_family = [](auto &&f) { f(chain_run_kernel<false, false, true>); };
     auto ortho_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); };
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kChainBlock), lds, ln.stream, d_topo, e->bx, e->d_pos, e->d_nmol, e->d_res_q, e->d_res_atype,
-                           e->d_pair_tab, e->d_coul_tab, e->d_trj, e->d_tw, e->n_rtasks, e->d_rrows, e->n_rrows, e->d_A, g);
-    };
+    auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
     if (e->bx.triclinic) tri_family(launch);
     else with_bools([&](auto... flags) { ortho_family(launch, flags...); }, e->pair_flat, ff);
     HIP_TRY(hipGetLastError());
@@ -747,7 +709,7 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
 
 int mgpu_chain_run_capacity(const mgpu_engine *e, int *max_k, int *max_in_flight, int *ring_steps) {
     if (!e || !max_k) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_capacity: null argument");
-    const int k = run_max_k(e);
+    const int k = window_admission(e, kPathRun).capacity;
     *max_k = k;
     if (max_in_flight) *max_in_flight = k ? kRunMaxInFlight : 0;
     if (ring_steps) *ring_steps = k ? kRunRingSteps : 0;
@@ -767,7 +729,7 @@ int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on) {
 int mgpu_chain_run_open(mgpu_engine *e, int replica, int k, double t_step, double r_step, double temperature) {
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
     mgpu_engine::Run &rn = e->run;
-    const int k_max = run_max_k(e);
+    const int k_max = window_admission(e, kPathRun).capacity;
     if (k_max == 0) return set_error(MGPU_ERR_STATE, "chain_run_open: not available for this engine (mgpu_chain_run_capacity)");
     if (rn.open) return set_error(MGPU_ERR_STATE, "chain_run_open: a run is open (one per engine)");
     if (replica < 0 || replica >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_open: replica out of range");
@@ -827,12 +789,13 @@ int mgpu_chain_run_push(mgpu_engine *e, int n, const int *t, const int *m, const
     if (rc) return rc;
     // every record is checked before any is written: a refused push leaves the run as it was
     bool fast = rn.fast;
+    const WindowAdmission adm = window_admission(e, kPathRun);
     for (int c = 0; c < n; ++c) {
         const int mv = move[c];
         if (mv == 3 || mv == 4) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: insertions and deletions do not ride in a run (moves only)");
         if (mv < 0 || mv > 4) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: unknown move code");
         if (mv == 0) continue;
-        if (t[c] < 0 || t[c] >= e->tp.n_res || !e->is_active[t[c]] || e->frozen[t[c]])
+        if (t[c] < 0 || t[c] >= e->tp.n_res || !adm.rides[t[c]])
             return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push: residue type out of range or not active");
         if ((rc = check_candidate(e, c, rn.replica, t[c], m[c], true))) return rc;
         fast = fast && e->frames_tight[(size_t)rn.replica * e->tp.n_res + t[c]];
@@ -917,8 +880,7 @@ int mgpu_chain_run_collect(mgpu_engine *e, int max_steps, int wait, double *old_
     int got = 0;
     auto row = [&](long long step) {
         const double *o = rn.h_out + (size_t)(step % kRunRingSteps) * kRunOut;
-        std::memcpy(old_energy + 5 * (size_t)got, o, 5 * sizeof(double));
-        std::memcpy(new_energy + 5 * (size_t)got, o + 5, 5 * sizeof(double));
+        copy_energy_rows(old_energy, new_energy, got, o);
         verdict[got] = (int)o[10];
         ++got;
     };
