@@ -590,6 +590,19 @@ int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long lo
  *               not ride in a run), a slot >= the type's count, more than ring_steps steps uncollected; a refused push
  *               changes nothing.  One asynchronous copy per push (two where the ring wraps) and the new count, on lane 0's
  *               stream: launches queued BEFORE a push do not see it.
+ *   set_gc      on = 1: the engine's runs are those of a grand-canonical block (off at creation): they take by-count records
+ *               through push_gc and launch the GC instances of the kernel.  MGPU_ERR_STATE, and the switch stays as it was: a
+ *               triclinic box, an engine that holds a reservoir (no such instance exists), a run open.  With the switch off
+ *               every entry point, refusal and kernel instance is what it was.  The capacity does not depend on it.
+ *   push_gc     (switch on; MGPU_ERR_STATE otherwise) n BY-COUNT records: t, move (0-4: 3 creation, 4 deletion), u5, accept_u as
+ *               push takes them, sel_u[n] the draw of PickRandomMoleculeIndex in [0, 1), phi_v[n] > 0 (moves 3 / 4).  The launch
+ *               that takes a record completes it from the molecule count it FINDS: slot = min(int(sel_u N), N - 1), prefactor
+ *               phi_v / (N + 1) of an insertion (appended at slot N), N / phi_v of a deletion (swap with the last molecule); a
+ *               move or deletion of an empty type and an insertion into a type at mol_capacity do nothing (verdict 5).  All
+ *               steps of a launch are trials of the state it finds, so one count completes them all.  An insertion needs a
+ *               frame to copy (mgpu_farm_window_submit's rule).  push itself still refuses moves 3 / 4; its records (slots
+ *               given by the caller) may be mixed with these.  The host's counts (mgpu_replica_get_num_molecules) follow an
+ *               accepted insertion / deletion when its step is collected, or at close.
  *   launch      queues n_launches launches and never waits for one (it copies A(k) back first only if another path has
  *               switched some replica's buffers since the run was opened).  A launch that finds no step of its own, or a
  *               chain that waits for a decision, does nothing (a "void" launch).  MGPU_ERR_STATE beyond max_in_flight.
@@ -615,6 +628,9 @@ int mgpu_chain_run_capacity(const mgpu_engine *e, int *max_k, int *max_in_flight
 int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on);
 int mgpu_chain_run_open(mgpu_engine *e, int replica, int k, double t_step, double r_step, double temperature);
 int mgpu_chain_run_push(mgpu_engine *e, int n, const int *t, const int *m, const int *move, const double *u5, const double *accept_u);
+int mgpu_chain_run_set_gc(mgpu_engine *e, int on);
+int mgpu_chain_run_push_gc(mgpu_engine *e, int n, const int *t, const int *move, const double *u5, const double *accept_u,
+                           const double *sel_u, const double *phi_v);
 int mgpu_chain_run_launch(mgpu_engine *e, int n_launches);
 int mgpu_chain_run_collect(mgpu_engine *e, int max_steps, int wait, double *old_energy, double *new_energy, int *verdict, int *n_got,
                            int *stalled_at);

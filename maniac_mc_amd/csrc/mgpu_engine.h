@@ -388,6 +388,9 @@ struct mgpu_engine {
         bool fast = false;                           // every record so far admits the fast fold
         RunState *d_state = nullptr;
         RunRec *d_ring = nullptr, *h_ring = nullptr; // device ring and its pinned image (the source of the pushes' copies)
+        bool gc = false;                             // grand-canonical runs (mgpu_chain_run_set_gc): by-count records, the GC instances
+        double2 *d_gc = nullptr, *h_gc = nullptr;    // ... their second ring {sel_u, phi V} and its pinned image (allocated with the first such run)
+        long long mirrored = 0;                      // steps whose accepted insertions / deletions the host's counts have followed
         int *h_pushed = nullptr;                     // pinned [kRunRingSteps]: the counts the pushes copy into d_state->pushed
         double *h_out = nullptr;                     // pinned [kRunRingSteps][kRunOut]
         unsigned long long *h_step_tag = nullptr;    // pinned [kRunRingSteps]

@@ -969,10 +969,23 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI 
 // farm_window_kernel and nothing else: every role and the commit build the candidate with the triclinic form of trial_frame
 // (trial_com_triclinic's centre, wrapped always), and the pair role runs the register-site sweep with ComputeDistance's
 // image search; no flat form, no fast fold.  No WIDE or RSV instance exists (capacity 0).
+// GC (mgpu_chain_run_set_gc, orthorhombic boxes without reservoirs: <FLAT, FASTW, false, true>): the run of a grand-canonical
+// block.  Which molecule a step picks and its prefactor depend on the molecule count, i.e. on the outcome of the steps before
+// it, so the driver pushes BY-COUNT records (RunRec::pad; the draw of PickRandomMoleculeIndex and phi V travel in a second
+// ring, ChainRunArgs::gc_ring, which these instances alone read) and every workgroup completes the launch's records from the
+// count the launch finds, with farm_window_kernel's integer arithmetic and prefactors: slot = min(int(u N), N - 1),
+// phi V / (N + 1) for an insertion, N / (phi V) for a deletion, and a move or deletion of an empty type or an insertion into a
+// full one does nothing (move 0, verdict 5).  A launch's steps are all trials of the state it finds and any acceptance ends
+// it, so ONE count completes every record of a launch.  The roles are farm_window_kernel's for the kinds: the k role builds
+// no candidate for a deletion and leaves the intra term of an insertion / deletion (thread kBlock) in res[c].intra; the pair
+// role has no old entry for an insertion (which excludes nothing) and no new entry for a deletion, and the resolver reads
+// the absent entries as zero -- they are never written.  Totals with self and intra terms, the prefactor in the rule and the
+// commit (append at slot N; swap with the last molecule) are farm_resolve's.
 // ------------------------------------------------------------------------------------------
 struct RunState { int cursor, pushed, stalled, pad; };
 struct RunRec {
-    int t, m, move, pad;          // move 0: nothing to do; 1 translation, 2 rotation
+    int t, m, move, pad;          // move 0: nothing to do; 1 translation, 2 rotation; GC runs: 3 creation, 4 deletion, and
+                                  // pad = 1: a by-count record (m and the prefactor follow from the count on the device)
     double u[5];                  // the construction's uniform numbers (trial_build_kernel)
     double acc_u;                 // the test's uniform number
 };
@@ -995,22 +1008,28 @@ struct ChainRunArgs {
     int k, nsplit, replica, ring_steps;
     int force_step, force_verdict;               // -1 / the stalled step the host has decided: 1 accept, 2 reject
     double t_step, r_step, temperature, margin;
+    // the GC instances only (behind everything the others read): per step {the draw of PickRandomMoleculeIndex, phi V} in a ring
+    // parallel to `ring`, and ewald_self per residue type
+    const double2 *gc_ring;                      // device [ring_steps]
+    double self_of_type[kMaxRes];
 };
 static_assert(sizeof(BoxDev) + sizeof(ChainRunArgs) + 160 <= 4096, "a chain-run launch must fit the kernel-argument segment");
 
-template <bool FLAT, bool FASTW, bool TRI = false>
+template <bool FLAT, bool FASTW, bool TRI = false, bool GC = false>
 __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
     double2 *__restrict__ A_base, const ChainRunArgs g) {
     static_assert(!TRI || (!FLAT && !FASTW), "the image search has no flat form and no fast fold (farm_window_kernel's triclinic family)");
+    static_assert(!(TRI && GC), "no grand-canonical run of a triclinic box (mgpu_chain_run_set_gc refuses it)");
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];      // Coulomb table | phase tables | partials staging
     __shared__ double2 s_pair[kMaxTypes * kMaxTypes];
     __shared__ int4 s_grp[kMaxGrp];
     __shared__ int4 s_plane[FLAT ? kPairWaves * kFlatMaxPlanes : 1];
     __shared__ double s_red[2 * kWavesPerBlock];
     __shared__ RunRec s_rec[kRunMaxK];                                 // the launch's steps
+    __shared__ double2 s_gc[GC ? kRunMaxK : 1];                        // GC: {sel_u, phi V}, then {prefactor, -} of the completed record
     __shared__ double s_cand[kPairWaves][kMaxFusedSitesWide * 3];      // candidate rows: one per wave (pair role) / row 0 (k role)
     __shared__ double s_ent[4 * kRunMaxK];                             // reduced pair entries {lj, cc} of the old / new state
     __shared__ ChainResult s_res[kRunMaxK];
@@ -1040,6 +1059,13 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
         const int c = tid / kRunRecWords, wd = tid - c * kRunRecWords;
         reinterpret_cast<double *>(s_rec)[tid] = reinterpret_cast<const double *>(g.ring + (first + c) % g.ring_steps)[wd];
     }
+    if constexpr (GC) {
+        // (the last wave: the records' loads above are the first waves')
+        if (tid >= kChainBlock - kRunMaxK && tid - (kChainBlock - kRunMaxK) < cnt) {
+            const int c = tid - (kChainBlock - kRunMaxK);
+            s_gc[c] = g.gc_ring[(first + c) % g.ring_steps];
+        }
+    }
     if (!k_role && cnt > 0) {
         for (int i = tid; i < (bx.coul_last_row + 1) * kCoulRowVec; i += kChainBlock)
             reinterpret_cast<double2 *>(s_dyn)[i] = reinterpret_cast<const double2 *>(coul_tab_g)[i];
@@ -1048,6 +1074,29 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
         if (FLAT && tid < kMaxGrp) s_grp[tid] = make_int4(tp.grp_start[tid], tp.grp_cnt[tid], tp.grp_ty[tid], 0);
     }
     __syncthreads();
+    if constexpr (GC) {
+        // complete the by-count records from the replica's molecule count as the launch finds it (farm_window_kernel's
+        // arithmetic); every workgroup does the same from the same count: nobody writes it before the last ticket is drawn
+        if (tid < cnt) {
+            RunRec &r = s_rec[tid];
+            double pref = 1.0;
+            if (r.pad && r.move != 0) {
+                const double sel_u = s_gc[tid].x, phi_v = s_gc[tid].y;
+                const int nm = nmol[g.replica * tp.n_res + r.t];
+                if (r.move == 3) {
+                    if (nm >= tp.cap[r.t]) r.move = 0;                      // full: nothing to do (monte_carlo.f90:63)
+                    else { r.m = 0; pref = phi_v / (double)(nm + 1); }      // phi V / (N + 1), N + 1 = the count after it
+                } else if (nm <= 0) {
+                    r.move = 0;                                             // PickRandomMoleculeIndex of an empty type: the drivers return
+                } else {
+                    r.m = min((int)(sel_u * nm), nm - 1);
+                    if (r.move == 4) pref = ((double)(nm - 1) + 1.0) / phi_v;   // (N' + 1) / (phi V), N' = the count after it
+                }
+            }
+            s_gc[tid].x = pref;
+        }
+        __syncthreads();
+    }
 
     if (k_role) {
         // ---------------- k role: step c of the launch
@@ -1055,7 +1104,11 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
         if (c < cnt && s_rec[c].move != 0) {                           // (uniform per workgroup)
             const RunRec &rec = s_rec[c];
             const int n1 = tp.n1[rec.t];
-            if (tid < n1) {
+            int kind = 0;                                               // GC: 1 insertion, 2 deletion (no candidate row)
+            if constexpr (GC) kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
+            bool build = tid < n1;
+            if constexpr (GC) build = build && kind != 2;
+            if (build) {
                 const auto f = trial_frame<false, TRI>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                 double off[3];
                 trial_offset<false>(tp, f, g.replica, rec.t, tid, off);
@@ -1064,6 +1117,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             __syncthreads();
             double2 *A = A_base + (size_t)g.replica * bx.n_slots;
             RecipItem it{g.replica, rec.t, rec.m, 0, 0, 0, 0};
+            if constexpr (GC) { it.m = kind == 1 ? -1 : rec.m; it.kind = kind; }
             const RecipLds v = recip_lds_view(tp, bx, it, n_rows, reinterpret_cast<double2 *>(s_dyn));
             const bool active = tid < kBlock;
             RecipInFlight<kRecipTaskChunk> inflight;
@@ -1071,6 +1125,14 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
                               [&] { recip_rows_prefetch<false>(inflight, trj, tw, n_tasks, A, tid); });
             double acc = 0.0, acc0 = 0.0;
             if (active) recip_rows_pass<false, true, kRecipTaskChunk, 2>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0, g.alt + (size_t)c * bx.n_slots);
+            if constexpr (GC) {
+                if (tid == kBlock && kind != 0) {
+                    // ComputeIntraResidueRealCoulombEnergySingleMol of the inserted (candidate row) / deleted (resident) molecule
+                    const PairItem pit{g.replica, rec.t, rec.m, kind == 1 ? 0 : -1, 0};
+                    __hip_atomic_store(&g.res[c].intra, intra_energy(tp, bx, pos, res_q, pit, &s_cand[0][0], kMaxFusedSitesWide), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
             if (active) {
                 acc = wave_sum(acc);
                 acc0 = wave_sum(acc0);
@@ -1088,7 +1150,14 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
         // ---------------- pair role: one wave per (step, entry, split); entry 0 = the resident molecule, 1 = the candidate
         const int wg = (int)blockIdx.x * kPairWaves + wave;
         const int c = wg / wpc, j = wg - c * wpc;
-        if (c < cnt && s_rec[c].move != 0) {
+        // (GC: an insertion has no old entry, a deletion no new one; they are never written, and the resolver reads them as zero)
+        int kind_w = 0;
+        bool work = c < cnt && s_rec[c].move != 0;
+        if constexpr (GC) {
+            if (work) kind_w = s_rec[c].move <= 2 ? 0 : (s_rec[c].move == 3 ? 1 : 2);
+            work = work && (j / ns == 0 ? kind_w != 1 : kind_w != 2);
+        }
+        if (work) {
             const RunRec &rec = s_rec[c];
             const int ent = j / ns, split = j - ent * ns;
             const int n1 = tp.n1[rec.t];
@@ -1103,8 +1172,9 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 __builtin_amdgcn_wave_barrier();
             }
-            // old state: the resident molecule; new state: the candidate row
-            const PairItem it{g.replica, rec.t, rec.m, ent == 1 ? 0 : -1, 0};
+            // old state: the resident molecule; new state: the candidate row; an insertion excludes nothing
+            PairItem it{g.replica, rec.t, rec.m, ent == 1 ? 0 : -1, 0};
+            if constexpr (GC) { if (kind_w == 1) it.m = -1; }
 #define MGPU_RUN_PAIR(NS)                                                                                                \
             do {                                                                                                         \
                 if constexpr (FLAT)                                                                                      \
@@ -1137,9 +1207,23 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
     {
         double *st = reinterpret_cast<double *>(s_dyn);
         const int per = 4 * ns;
+        if constexpr (GC) {
+            // (farm_resolve's `have`: an insertion's old entry, a deletion's new entry and a move's intra term were never written)
+            for (int i = tid; i < per * cnt; i += kChainBlock) {
+                const int mv = s_rec[i / per].move;
+                const bool have = mv != 0 && ((i % per) / (2 * ns) == 0 ? mv != 3 : mv != 4);
+                st[i] = have ? load_sc1(reinterpret_cast<const double *>(g.partials) + i) : 0.0;
+            }
+            if (tid < 3 * cnt) {
+                const int mv = s_rec[tid / 3].move;
+                const bool have = mv != 0 && (tid % 3 != 2 || mv >= 3);
+                reinterpret_cast<double *>(s_res)[tid] = have ? load_sc1(reinterpret_cast<const double *>(g.res) + tid) : 0.0;
+            }
+        } else {
         for (int i = tid; i < per * cnt; i += kChainBlock)
             st[i] = s_rec[i / per].move != 0 ? load_sc1(reinterpret_cast<const double *>(g.partials) + i) : 0.0;
         if (tid < 3 * cnt) reinterpret_cast<double *>(s_res)[tid] = s_rec[tid / 3].move != 0 ? load_sc1(reinterpret_cast<const double *>(g.res) + tid) : 0.0;
+        }
         __syncthreads();
         if (tid < 4 * cnt) {
             const int c = tid >> 2, ent = (tid >> 1) & 1, comp = tid & 1;
@@ -1150,7 +1234,8 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
         }
         __syncthreads();
     }
-    // every step's totals and verdict by its own thread, as farm_resolve forms them (a move: kind 0, prefactor 1)
+    // every step's totals and verdict by its own thread, as farm_resolve forms them (a move: kind 0, prefactor 1; GC: the
+    // self and intra terms of an insertion / deletion, the completed record's prefactor)
     if (tid < cnt) {
         const int c = tid;
         const RunRec &rec = s_rec[c];
@@ -1159,13 +1244,18 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
         if (rec.move != 0) {
             o[0] = s_ent[4 * c]; o[1] = s_ent[4 * c + 1]; o[2] = s_res[c].u_old;
             w[0] = s_ent[4 * c + 2]; w[1] = s_ent[4 * c + 3]; w[2] = s_res[c].u_new;
+            if constexpr (GC) {
+                if (rec.move == 3) { w[3] = g.self_of_type[rec.t]; w[4] = s_res[c].intra; }
+                if (rec.move == 4) { o[3] = g.self_of_type[rec.t]; o[4] = s_res[c].intra; }
+            }
             if (c == 0 && forced) {
                 verdict = forced == 1 ? kFarmVerdictAccepted : kFarmVerdictRejected;
             } else {
                 // old%total, new%total and the rule as mc_farm.f90 resolve_and_commit forms them (monte_carlo_utils.f90:184-226)
                 double e_old = 0.0, e_new = 0.0;
                 for (int k = 0; k < 5; ++k) { e_old = e_old + o[k]; e_new = e_new + w[k]; }
-                const double x = 1.0 * exp(-(e_new - e_old) / g.temperature);
+                double x = 1.0 * exp(-(e_new - e_old) / g.temperature);
+                if constexpr (GC) x = s_gc[c].x * exp(-(e_new - e_old) / g.temperature);
                 const double pr = x < 1.0 ? x : 1.0;                               // min(1, x)
                 if (!(x == x) || (x < 1.0 + g.margin && fabs(rec.acc_u - x) <= g.margin * x)) verdict = kFarmVerdictUndecided;
                 else verdict = rec.acc_u <= pr ? kFarmVerdictAccepted : kFarmVerdictRejected;
@@ -1219,13 +1309,43 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
         const double *from = reinterpret_cast<const double *>(g.alt + (size_t)accepted * bx.n_slots);
         double *to = reinterpret_cast<double *>(A_base + (size_t)g.replica * bx.n_slots);
         for (int i = tid; i < 2 * bx.n_slots; i += kChainBlock) to[i] = load_sc1(from + i);
-        if (wave == 0) {
+        bool swap_last = false;
+        if constexpr (GC) swap_last = rec.move == 4;
+        if (swap_last) {
+            if (wave == 0) {
+                // swap with the last molecule (delete_molecule.f90:107-114), as farm_resolve does: coordinates, frames, count
+                const int n1 = tp.n1[rec.t];
+                double *px = pos + (size_t)g.replica * 3 * tp.n_cap_atoms;
+                double *py = px + tp.n_cap_atoms, *pz = py + tp.n_cap_atoms;
+                const size_t rep3 = (size_t)g.replica * 3;
+                double *fcom = tp.com + rep3 * tp.n_mol_slots + tp.mol_off[rec.t];
+                double *foff = tp.off + rep3 * tp.n_cap_atoms;
+                const int last = nmol[g.replica * tp.n_res + rec.t] - 1;
+                if (last != rec.m) {
+                    if (lane < n1) {
+                        const int j = atom_slot(tp, rec.t, rec.m, lane), jl = atom_slot(tp, rec.t, last, lane);
+                        px[j] = px[jl]; py[j] = py[jl]; pz[j] = pz[jl];
+                        for (int d = 0; d < 3; ++d) foff[(size_t)d * tp.n_cap_atoms + j] = foff[(size_t)d * tp.n_cap_atoms + jl];
+                    }
+                    if (lane < 3) fcom[(size_t)lane * tp.n_mol_slots + rec.m] = fcom[(size_t)lane * tp.n_mol_slots + last];
+                }
+                // (every lane has read the count before lane 0 lowers it)
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                if (lane == 0) nmol[g.replica * tp.n_res + rec.t] = last;
+            }
+        } else if (wave == 0) {
             const int n1 = tp.n1[rec.t];
             double *px = pos + (size_t)g.replica * 3 * tp.n_cap_atoms;
             double *py = px + tp.n_cap_atoms, *pz = py + tp.n_cap_atoms;
             const size_t rep3 = (size_t)g.replica * 3;
             double *fcom = tp.com + rep3 * tp.n_mol_slots + tp.mol_off[rec.t];
             double *foff = tp.off + rep3 * tp.n_cap_atoms;
+            // an insertion is appended at the first free slot (monte_carlo.f90:63, create_molecule.f90:64)
+            int nm = 0, m_to = rec.m;
+            if constexpr (GC) {
+                if (rec.move == 3) { nm = nmol[g.replica * tp.n_res + rec.t]; m_to = nm; }
+            }
             const auto f = trial_frame<false, TRI>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
             double off[3] = {0.0, 0.0, 0.0};
             if (lane < n1) trial_offset<false>(tp, f, g.replica, rec.t, lane, off);
@@ -1233,12 +1353,15 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             __builtin_amdgcn_wave_barrier();
             if (lane < n1) {
-                const int j = atom_slot(tp, rec.t, rec.m, lane);
+                const int j = atom_slot(tp, rec.t, m_to, lane);
                 px[j] = f.com[0] + off[0]; py[j] = f.com[1] + off[1]; pz[j] = f.com[2] + off[2];
                 for (int d = 0; d < 3; ++d) foff[(size_t)d * tp.n_cap_atoms + j] = off[d];
             }
             // (selected, not indexed: a private array indexed by the lane would live in scratch)
-            if (lane < 3) fcom[(size_t)lane * tp.n_mol_slots + rec.m] = lane == 0 ? f.com[0] : (lane == 1 ? f.com[1] : f.com[2]);
+            if (lane < 3) fcom[(size_t)lane * tp.n_mol_slots + m_to] = lane == 0 ? f.com[0] : (lane == 1 ? f.com[1] : f.com[2]);
+            if constexpr (GC) {
+                if (rec.move == 3 && lane == 0) nmol[g.replica * tp.n_res + rec.t] = nm + 1;
+            }
         }
     }
 }

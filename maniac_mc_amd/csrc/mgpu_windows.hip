@@ -75,9 +75,9 @@ int farm_clear_stall(mgpu_engine *e, int replica) {
 
 void chain_run_release(mgpu_engine *e) {
     mgpu_engine::Run &rn = e->run;
-    for (void *p : {(void *)rn.h_ring, (void *)rn.h_pushed, (void *)rn.h_out, (void *)rn.h_step_tag, (void *)rn.h_launch})
+    for (void *p : {(void *)rn.h_ring, (void *)rn.h_gc, (void *)rn.h_pushed, (void *)rn.h_out, (void *)rn.h_step_tag, (void *)rn.h_launch})
         if (p) (void)hipHostFree(p);
-    for (void *p : {(void *)rn.d_state, (void *)rn.d_ring, (void *)rn.d_part, (void *)rn.d_alt, (void *)rn.d_res, (void *)rn.d_ticket})
+    for (void *p : {(void *)rn.d_state, (void *)rn.d_ring, (void *)rn.d_gc, (void *)rn.d_part, (void *)rn.d_alt, (void *)rn.d_res, (void *)rn.d_ticket})
         if (p) (void)hipFree(p);
     rn = mgpu_engine::Run{};
 }
@@ -142,6 +142,9 @@ void window_types_build(mgpu_engine *e) {
 //     resolver beyond 64 KiB, WIDE LDS beyond its budget;
 //   farm windows and chain runs: a triclinic box whose engine has not switched device-built moves on;
 //   chain runs (no such instance of chain_run_kernel exists): reservoirs, and a triclinic box unless triclinic runs are on.
+//     (Grand-canonical runs, mgpu_chain_run_set_gc, are admitted exactly where runs are: the switch is refused for a triclinic box
+//     and for an engine with a reservoir, and the GC instances' dynamic LDS is window_lds_bytes(kPathRun, ...) -- their k role, pair
+//     role and resolver stage what the NVT instances stage; what they add is 16 double2 of static LDS.)
 // rides[t]: a record of type t may travel (a single-chain window takes any row of <= kMaxFusedSitesWide sites; a run any active type).
 struct WindowAdmission {
     int capacity = 0;
@@ -669,6 +672,16 @@ static void run_poll(mgpu_engine *e) {
     }
 }
 
+// a decided step has been read: the host's counts follow an accepted insertion / deletion (once per step, in order)
+static void run_mirror(mgpu_engine *e, long long step) {
+    mgpu_engine::Run &rn = e->run;
+    if (step < rn.mirrored) return;
+    rn.mirrored = step + 1;
+    const RunRec &r = rn.h_ring[step % kRunRingSteps];
+    if (r.move < 3 || (int)rn.h_out[(size_t)(step % kRunRingSteps) * kRunOut + 10] != kFarmVerdictAccepted) return;
+    mirror_accepted(e, rn.replica, r.t, r.move == 3 ? MGPU_CREATION : MGPU_DELETION, true);   // (the range flag was lowered at the push)
+}
+
 static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     mgpu_engine::Run &rn = e->run;
     Lane &ln = e->lanes[0];
@@ -691,17 +704,23 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     g.k = rn.k; g.nsplit = nsplit; g.replica = rn.replica; g.ring_steps = kRunRingSteps;
     g.force_step = force_step; g.force_verdict = force_verdict;
     g.t_step = rn.t_step; g.r_step = rn.r_step; g.temperature = rn.temperature; g.margin = e->chain.margin;
+    if (rn.gc) {
+        g.gc_ring = rn.d_gc;
+        for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
+    }
     const int grid = (rn.k * 2 * nsplit + kPairWaves - 1) / kPairWaves + rn.k;
     const bool ff = rn.fast && e->pair_fast_fold;
     ln.dirty = true;
     ln.forget_trial();
     alt_forget(e, rn.replica);
-    // The run kernel's families: with the image search (no flat form, no fast fold: farm_window_kernel's triclinic family), and
-    // the orthorhombic one, whose flags are free.
+    // The run kernel's families: with the image search (no flat form, no fast fold: farm_window_kernel's triclinic family), the
+    // orthorhombic one, whose flags are free, and the grand-canonical one (orthorhombic; the run was opened with the switch on).
     auto tri_family = [](auto &&f) { f(chain_run_kernel<false, false, true>); };
     auto ortho_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); };
+    auto gc_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, true>); };
     auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
     if (e->bx.triclinic) tri_family(launch);
+    else if (rn.gc) with_bools([&](auto... flags) { gc_family(launch, flags...); }, e->pair_flat, ff);
     else with_bools([&](auto... flags) { ortho_family(launch, flags...); }, e->pair_flat, ff);
     HIP_TRY(hipGetLastError());
     return MGPU_OK;
@@ -723,6 +742,16 @@ int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on) {
     if (!e->tri_moves) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: device-built triclinic moves are off (mgpu_set_triclinic_moves)");
     if (e->run.open) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: a run is open");
     e->run.triclinic = on != 0;
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_set_gc(mgpu_engine *e, int on) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    // every refusal leaves the switch as it was
+    if (e->bx.triclinic) return set_error(MGPU_ERR_STATE, "chain_run_set_gc: the box is triclinic (no such instance of the run kernel)");
+    if (e->rsv_any) return set_error(MGPU_ERR_STATE, "chain_run_set_gc: the engine holds a reservoir (no such instance of the run kernel)");
+    if (e->run.open) return set_error(MGPU_ERR_STATE, "chain_run_set_gc: a run is open");
+    e->run.gc = on != 0;
     return MGPU_OK;
 }
 
@@ -759,6 +788,10 @@ int mgpu_chain_run_open(mgpu_engine *e, int replica, int k, double t_step, doubl
         HIP_TRY(hipMalloc((void **)&rn.d_ticket, sizeof(int)));
         HIP_TRY(hipMemset(rn.d_ticket, 0, sizeof(int)));
     }
+    if (rn.gc && !rn.d_gc) {
+        HIP_TRY(hipMalloc((void **)&rn.d_gc, sizeof(double2) * kRunRingSteps));
+        HIP_TRY(hipHostMalloc((void **)&rn.h_gc, sizeof(double2) * kRunRingSteps, hipHostMallocDefault));
+    }
     const Topo *d_topo = nullptr;
     if ((rc = chain_topo(e, &d_topo))) return rc;
     HIP_TRY(hipMemset(rn.d_state, 0, sizeof(RunState)));
@@ -768,11 +801,31 @@ int mgpu_chain_run_open(mgpu_engine *e, int replica, int k, double t_step, doubl
     rn.replica = replica; rn.k = k;
     rn.t_step = t_step; rn.r_step = r_step; rn.temperature = temperature;
     rn.fast = replica_in_range(e, replica);
-    rn.pushed = rn.collected = 0;
+    rn.pushed = rn.collected = rn.mirrored = 0;
     rn.stalled_at = -1;
     rn.dev_stalled = false;
     rn.seq_done = rn.seq;
     rn.log.clear();
+    return MGPU_OK;
+}
+
+// the records [pushed, pushed + n) of the ring's image (a slot is rewritten only after its step has been collected) to the
+// device, then the count, on the launches' stream and ahead of the launches that read them
+static int run_push_copy(mgpu_engine *e, int n, bool gc) {
+    mgpu_engine::Run &rn = e->run;
+    Lane &ln = e->lanes[0];
+    ln.dirty = true;
+    const int s0 = (int)(rn.pushed % kRunRingSteps), n0 = std::min(n, kRunRingSteps - s0);
+    HIP_TRY(hipMemcpyAsync(rn.d_ring + s0, rn.h_ring + s0, sizeof(RunRec) * n0, hipMemcpyHostToDevice, ln.stream));
+    if (n > n0) HIP_TRY(hipMemcpyAsync(rn.d_ring, rn.h_ring, sizeof(RunRec) * (n - n0), hipMemcpyHostToDevice, ln.stream));
+    if (gc) {
+        HIP_TRY(hipMemcpyAsync(rn.d_gc + s0, rn.h_gc + s0, sizeof(double2) * n0, hipMemcpyHostToDevice, ln.stream));
+        if (n > n0) HIP_TRY(hipMemcpyAsync(rn.d_gc, rn.h_gc, sizeof(double2) * (n - n0), hipMemcpyHostToDevice, ln.stream));
+    }
+    rn.pushed += n;
+    int *cnt = rn.h_pushed + rn.pushed % kRunRingSteps;
+    *cnt = (int)rn.pushed;
+    HIP_TRY(hipMemcpyAsync(&rn.d_state->pushed, cnt, sizeof(int), hipMemcpyHostToDevice, ln.stream));
     return MGPU_OK;
 }
 
@@ -813,18 +866,60 @@ int mgpu_chain_run_push(mgpu_engine *e, int n, const int *t, const int *m, const
         if (!e->frames_tight[idx]) e->in_range[idx] = 0;
     }
     rn.fast = fast;
-    Lane &ln = e->lanes[0];
-    ln.dirty = true;
-    // the records (the ring's image is the copies' source: a slot is rewritten only after its step has been collected), then
-    // the count, on the launches' stream and ahead of the launches that read them
-    const int s0 = (int)(rn.pushed % kRunRingSteps), n0 = std::min(n, kRunRingSteps - s0);
-    HIP_TRY(hipMemcpyAsync(rn.d_ring + s0, rn.h_ring + s0, sizeof(RunRec) * n0, hipMemcpyHostToDevice, ln.stream));
-    if (n > n0) HIP_TRY(hipMemcpyAsync(rn.d_ring, rn.h_ring, sizeof(RunRec) * (n - n0), hipMemcpyHostToDevice, ln.stream));
-    rn.pushed += n;
-    int *cnt = rn.h_pushed + rn.pushed % kRunRingSteps;
-    *cnt = (int)rn.pushed;
-    HIP_TRY(hipMemcpyAsync(&rn.d_state->pushed, cnt, sizeof(int), hipMemcpyHostToDevice, ln.stream));
-    return MGPU_OK;
+    return run_push_copy(e, n, false);
+}
+
+// By-count records of a grand-canonical run (mgpu_chain_run_set_gc): the device picks the molecule and forms the prefactor from
+// the count each launch finds (chain_run_kernel<..., GC>), so no slot is given and none is checked against the host's counts.
+int mgpu_chain_run_push_gc(mgpu_engine *e, int n, const int *t, const int *move, const double *u5, const double *accept_u,
+                           const double *sel_u, const double *phi_v) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    mgpu_engine::Run &rn = e->run;
+    if (!rn.open) return set_error(MGPU_ERR_STATE, "chain_run_push_gc: no run is open");
+    if (!rn.gc) return set_error(MGPU_ERR_STATE, "chain_run_push_gc: grand-canonical runs are off (mgpu_chain_run_set_gc)");
+    if (n < 0 || (n > 0 && (!t || !move || !u5 || !accept_u || !sel_u || !phi_v)))
+        return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push_gc: bad argument");
+    if (n == 0) return MGPU_OK;
+    if (rn.pushed + n - rn.collected > kRunRingSteps)
+        return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push_gc: beyond the ring (steps pushed and not yet collected: mgpu_chain_run_capacity)");
+    if (rn.pushed + n >= (1ll << 30)) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push_gc: too many steps in one run");
+    int rc = use_device(e);
+    if (rc) return rc;
+    // every record is checked before any is written: a refused push leaves the run as it was
+    bool fast = rn.fast;
+    const WindowAdmission adm = window_admission(e, kPathRun);
+    std::string why;
+    for (int c = 0; c < n; ++c) {
+        const int mv = move[c];
+        if (mv < 0 || mv > 4) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push_gc: unknown move code");
+        if (mv == 0) continue;
+        if (t[c] < 0 || t[c] >= e->tp.n_res || !adm.rides[t[c]])
+            return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push_gc: residue type out of range or not active");
+        if (!(sel_u[c] >= 0.0 && sel_u[c] < 1.0)) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push_gc: sel_u must lie in [0, 1)");
+        if (mv >= 3 && !(phi_v[c] > 0.0)) return set_error(MGPU_ERR_INVALID_ARG, "chain_run_push_gc: phi_v must be positive");
+        const size_t idx = (size_t)rn.replica * e->tp.n_res + t[c];
+        const int k = mv <= 2 ? MGPU_MOVE : (mv == 3 ? MGPU_CREATION : MGPU_DELETION);
+        char ok = 1;
+        if ((rc = admit_built(e, idx, k, mv, kAdmitFrames | kAdmitInsertion | kAdmitRange, "chain_run_push_gc", "step", c, why, ok, fast)))
+            return set_error(rc, why);
+    }
+    for (int c = 0; c < n; ++c) {
+        const size_t slot = (size_t)((rn.pushed + c) % kRunRingSteps);
+        RunRec &r = rn.h_ring[slot];
+        r = RunRec{};
+        rn.h_gc[slot] = double2{0.0, 0.0};
+        r.move = move[c];
+        if (r.move == 0) continue;
+        r.t = t[c]; r.m = 0; r.pad = 1;
+        for (int d = 0; d < 5; ++d) r.u[d] = u5[5 * (size_t)c + d];
+        r.acc_u = accept_u[c];
+        rn.h_gc[slot] = double2{sel_u[c], phi_v[c]};
+        // a step that is accepted may leave the fast fold's range: the flag is lowered now (mgpu_farm_window_submit's rule)
+        const size_t idx = (size_t)rn.replica * e->tp.n_res + t[c];
+        if (r.move != 4 && !e->frames_tight[idx]) e->in_range[idx] = 0;
+    }
+    rn.fast = fast;
+    return run_push_copy(e, n, true);
 }
 
 int mgpu_chain_run_launch(mgpu_engine *e, int n_launches) {
@@ -890,7 +985,7 @@ int mgpu_chain_run_collect(mgpu_engine *e, int max_steps, int wait, double *old_
         if (tag == decided || tag == (decided ^ 1ull)) {
             __atomic_thread_fence(__ATOMIC_ACQUIRE);
             row(step);
-            if (tag == decided) { rn.collected += 1; continue; }
+            if (tag == decided) { run_mirror(e, step); rn.collected += 1; continue; }
             rn.stalled_at = step;                                // undecided: its energies, verdict 2; the run waits for force
             *stalled_at = (int)step;
             break;
@@ -919,6 +1014,11 @@ int mgpu_chain_run_close(mgpu_engine *e) {
     if ((rc = sync_all_lanes(e))) return rc;                    // drains lane 0; A(k) is in its primary buffer (the run never leaves it)
     run_poll(e);
     if (rn.dev_stalled) return set_error(MGPU_ERR_STATE, "chain_run_close: a step waits for the host's decision (mgpu_chain_run_force)");
+    // (steps decided and never collected: the host's counts follow their insertions / deletions all the same)
+    for (long long step = rn.mirrored; step < rn.pushed; ++step) {
+        if (rn.h_step_tag[step % kRunRingSteps] != ((((unsigned long long)(step + 1)) << 1) | 1ull)) break;
+        run_mirror(e, step);
+    }
     rn.open = false;
     return MGPU_OK;
 }

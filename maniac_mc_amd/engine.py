@@ -308,6 +308,24 @@ class Engine:
         check(self.L.mgpu_chain_run_push(self.h, C.c_int(n), _i(t), _i(m), _i(move), _d(u), _d(au)))
         return n
 
+    def chain_run_set_gc(self, on=True):
+        """mgpu_chain_run_set_gc: the engine's runs are those of a grand-canonical block (off by default): by-count records
+        through chain_run_push_gc.  Refused (MgpuError, the switch unchanged) for a triclinic box, with a reservoir, and while
+        a run is open."""
+        check(self.L.mgpu_chain_run_set_gc(self.h, C.c_int(1 if on else 0)))
+
+    def chain_run_push_gc(self, t, move, u, accept_u, sel_u, phi_v):
+        """By-count records (moves 0-4): the launch that takes one picks slot min(int(sel_u N), N - 1) and forms the prefactor
+        phi_v / (N + 1) (insertion) or N / phi_v (deletion) from the count N it finds."""
+        move = _ints(move); n = move.shape[0]
+        t = _ints(t, n)
+        u = np.ascontiguousarray(u, dtype=np.float64).reshape(n, 5)
+        au = np.ascontiguousarray(accept_u, dtype=np.float64).reshape(n)
+        su = np.ascontiguousarray(np.broadcast_to(np.asarray(sel_u, dtype=np.float64), (n,)))
+        pv = np.ascontiguousarray(np.broadcast_to(np.asarray(phi_v, dtype=np.float64), (n,)))
+        check(self.L.mgpu_chain_run_push_gc(self.h, C.c_int(n), _i(t), _i(move), _d(u), _d(au), _d(su), _d(pv)))
+        return n
+
     def chain_run_launch(self, n_launches=1):
         check(self.L.mgpu_chain_run_launch(self.h, C.c_int(n_launches)))
 

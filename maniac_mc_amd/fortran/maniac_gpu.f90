@@ -350,6 +350,20 @@ module maniac_gpu
             real(c_double), intent(in) :: u5(*), accept_u(*)
             integer(c_int) :: rc
         end function
+        function mgpu_chain_run_set_gc(e, on) bind(C, name="mgpu_chain_run_set_gc") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: on
+            integer(c_int) :: rc
+        end function
+        function mgpu_chain_run_push_gc(e, n, t, move, u5, accept_u, sel_u, phi_v) bind(C, name="mgpu_chain_run_push_gc") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: t(*), move(*)
+            real(c_double), intent(in) :: u5(*), accept_u(*), sel_u(*), phi_v(*)
+            integer(c_int) :: rc
+        end function
         function mgpu_chain_run_launch(e, n_launches) bind(C, name="mgpu_chain_run_launch") result(rc)
             import :: c_ptr, c_int
             type(c_ptr), value :: e

@@ -45,7 +45,8 @@ module mc_chain
               mchain_get_energy, mchain_get_counters, mchain_get_counts, mchain_get_molecule, mchain_get_steps, &
               mchain_set_mode, mchain_set_as_written, mchain_set_log_header, mchain_write_log_header, &
               mchain_set_speculation, mchain_set_chain_windows, mchain_set_wide_windows, mchain_get_loop_seconds, mchain_get_times, &
-              mchain_export_template, mchain_set_chain_run, mchain_get_chain_run
+              mchain_export_template, mchain_set_chain_run, mchain_get_chain_run, mchain_set_chain_run_gcmc, &
+              mchain_get_chain_run_gcmc
 
     real(real64), parameter :: PI = 3.14159265358979323846_real64, TWOPI = 2.0_real64 * PI
     real(real64), parameter :: zero = 0.0_real64, one = 1.0_real64, half = 0.5_real64, three = 3.0_real64
@@ -91,6 +92,11 @@ module mc_chain
     ! run_k = 0: off (the default).  run_on: the mode applies to this run (set by mchain_run from the engine's capacity).
     integer, save :: run_k = 0, run_depth = 3
     logical, save :: run_on = .false.
+    ! Grand-canonical chain runs (mchain_set_chain_run_gcmc; mgpu_chain_run_set_gc, mgpu_chain_run_push_gc): a block with exchange
+    ! moves runs as a chain run of by-count records (run_block_gc).  run_gc_want: the host asked; run_gc: it applies to this run;
+    ! run_fallback: steps of the last mchain_run taken through the windows because the ahead-of-outcome rule failed.
+    logical, save :: run_gc_want = .false., run_gc = .false.
+    integer, save :: run_fallback = 0
     integer(c_int), save :: run_ring = 0
     integer, parameter :: BY_HOST = -1, DEVICE_REJECTED = 0, DEVICE_ACCEPTED = 1
     ! time spent inside the Monte Carlo loop proper (no initial energy, no files), seconds
@@ -462,6 +468,20 @@ contains
         run_k = max(0, int(k))
         run_depth = max(1, int(depth))
     end subroutine mchain_set_chain_run
+
+    ! Chain runs for blocks WITH insertions / deletions (off by default): with this and mchain_set_chain_run on, such a block runs as
+    ! a chain run of by-count records where the engine takes it (orthorhombic box, no reservoir) and the run is not --as-written
+    ! (whose `link` deletion has no device-built form); elsewhere, and without it, mchain_run decides as it always did.
+    subroutine mchain_set_chain_run_gcmc(on) bind(C, name="mchain_set_chain_run_gcmc")
+        integer(c_int), value :: on
+        run_gc_want = on /= 0
+    end subroutine mchain_set_chain_run_gcmc
+
+    ! (gcmc, fallback_steps) of the last mchain_run
+    subroutine mchain_get_chain_run_gcmc(out) bind(C, name="mchain_get_chain_run_gcmc")
+        integer(c_int), intent(out) :: out(2)
+        out = [merge(1_c_int, 0_c_int, run_gc), int(run_fallback, c_int)]
+    end subroutine mchain_get_chain_run_gcmc
 
     ! (on, k, depth) of the last mchain_run
     subroutine mchain_get_chain_run(out) bind(C, name="mchain_get_chain_run")
@@ -1261,6 +1281,290 @@ contains
         call refresh_frames()
     end subroutine run_block
 
+    !---------------------------------------------------------------------------
+    ! One block of nb_step steps of a GRAND-CANONICAL input as a chain run of by-count records.  The draws are propose_step's
+    ! statements in its order -- type, molecule (kept as the number itself: the launch that takes the record picks the slot from the
+    ! count it finds), move, insertion / deletion; then the displacement | the angle then the axis | the position, with its angle and
+    ! axis when n1 /= 1; the acceptance draw last -- kept as records.
+    ! How many numbers a step draws depends on the molecule count at its edges (pick_molecule_index draws nothing for an empty type,
+    ! the moves and the deletion return early for one, CheckMoleculeIndex aborts a creation into a full one), so a record is drawn
+    ! AHEAD OF THE OUTCOMES before it only while no count can reach an edge: with count_t from the verdicts collected so far and
+    ! I_t / D_t the insertion / deletion records pushed and not yet collected, count_t - D_t >= 1 and
+    ! count_t + I_t <= min(cap_t, NB_MAX_MOLECULE) - 1 for EVERY active type.  Where the rule fails with records outstanding they are
+    ! collected first; where it fails with none, the run is closed, the mirror refreshed, steps go through the window path until it
+    ! holds again (at least one; counted in run_fallback), the frames are uploaded and the run reopened.
+    ! Collected steps are booked as resolve_step books DEVICE_ACCEPTED / DEVICE_REJECTED; an undecided one is decided here (the
+    ! prefactor from this loop's own count) and forced.  A verdict 5 for a record that was not drawn as a no-op means the engine's
+    ! count is not this loop's: an engine-state error.
+    !---------------------------------------------------------------------------
+    subroutine run_block_gc(nb_step)
+        integer, intent(in) :: nb_step
+        integer(c_int), allocatable :: rt(:), rmove(:), verdict(:)
+        real(c_double), allocatable :: ru(:, :), rau(:), rsel(:), rphi(:), o(:, :), w(:, :)
+        integer, allocatable :: mtype(:), n_ins(:), n_del(:)
+        integer :: j, t, pushed, collected, queued, n, i, chunk, done, n0
+        integer(c_int) :: rc, n_got, stalled_at
+        integer(c_long_long) :: seen0, seen, st_steps, st_void, st_und
+        logical :: yes, is_open
+        allocate(rt(nb_step), rmove(nb_step), mtype(nb_step), ru(5, nb_step), rau(nb_step), rsel(nb_step), rphi(nb_step))
+        allocate(n_ins(S%n_res), n_del(S%n_res))
+        chunk = 256
+        allocate(o(5, chunk), w(5, chunk), verdict(chunk))
+        rt = 0; rmove = 0; ru = zero; rau = zero; rsel = zero; rphi = one; mtype = 0
+        n_ins = 0; n_del = 0
+        pushed = 0; collected = 0; queued = 0; seen0 = 0
+        is_open = .false.
+        do while (collected < nb_step .and. status == 0)
+            if (pushed == collected .and. .not. ahead_ok()) then
+                ! nothing outstanding and a count at an edge: the windows take over until the rule holds again
+                if (is_open) then
+                    rc = mgpu_chain_run_close(S%engine)
+                    call note(int(rc))
+                    is_open = .false.
+                    call refresh_frames()
+                end if
+                call drop_frames()
+                do while (collected < nb_step .and. status == 0)
+                    done = fallback_steps(nb_step - collected)
+                    collected = collected + done
+                    run_fallback = run_fallback + done
+                    if (ahead_ok()) exit
+                end do
+                pushed = collected
+                if (status == 0) call upload_frames()                       ! (the next run, of this block or the next, builds from them)
+                cycle
+            end if
+            if (.not. is_open) then
+                rc = mgpu_chain_run_get_stats(S%engine, seen0, st_steps, st_void, st_und)
+                call note(int(rc))
+                rc = mgpu_chain_run_open(S%engine, 0_c_int, int(run_k, c_int), S%translation_step, S%rotation_step, S%temperature)
+                call note(int(rc))
+                if (status /= 0) exit
+                is_open = .true.
+                queued = 0
+            end if
+            ! records as far ahead as the rule and the ring take them, then launches up to the depth, then the next results in order
+            n0 = pushed
+            do while (pushed < nb_step .and. pushed - collected < int(run_ring))
+                if (.not. ahead_ok()) exit
+                call draw_record(pushed + 1)
+                pushed = pushed + 1
+            end do
+            if (pushed > n0) then
+                rc = mgpu_chain_run_push_gc(S%engine, int(pushed - n0, c_int), rt(n0 + 1:), rmove(n0 + 1:), ru(:, n0 + 1:), rau(n0 + 1:), &
+                                            rsel(n0 + 1:), rphi(n0 + 1:))
+                call note(int(rc))
+            end if
+            rc = mgpu_chain_run_get_stats(S%engine, seen, st_steps, st_void, st_und)
+            call note(int(rc))
+            n = run_depth - (queued - int(seen - seen0))
+            if (n > 0) then
+                rc = mgpu_chain_run_launch(S%engine, int(n, c_int))
+                call note(int(rc))
+                queued = queued + n
+            end if
+            if (status /= 0) exit
+            rc = mgpu_chain_run_collect(S%engine, int(min(chunk, pushed - collected), c_int), 1_c_int, o, w, verdict, n_got, stalled_at)
+            call note(int(rc))
+            if (status /= 0) exit
+            do i = 1, int(n_got)
+                j = collected + 1
+                t = int(rt(j)) + 1
+                if (verdict(i) == 2) then
+                    ! too close to call on the device: this loop's own exp decides, and the engine obeys
+                    yes = decide_gc(mtype(j), t, o(:, i), w(:, i), rau(j))
+                    rc = mgpu_chain_run_force(S%engine, stalled_at, merge(1_c_int, 0_c_int, yes))
+                    call note(int(rc))
+                    queued = queued + 1
+                    exit                                                     ! (collected again, with its final verdict)
+                end if
+                if (mtype(j) /= 0) then
+                    if (verdict(i) /= DEVICE_ACCEPTED .and. verdict(i) /= DEVICE_REJECTED) then
+                        call note(4)                                         ! (verdict 5: the engine's count is not this loop's)
+                        exit
+                    end if
+                    call book_gc(mtype(j), t, o(:, i), w(:, i), verdict(i) == DEVICE_ACCEPTED)
+                    if (mtype(j) == TYPE_CREATION) n_ins(t) = n_ins(t) - 1
+                    if (mtype(j) == TYPE_DELETION) n_del(t) = n_del(t) - 1
+                end if
+                collected = j
+            end do
+        end do
+        if (is_open) then
+            rc = mgpu_chain_run_close(S%engine)
+            call note(int(rc))
+            call refresh_frames()                                            ! (the engine's counts must be this loop's: note(4) otherwise)
+        end if
+    contains
+        ! may one more record be drawn before the outstanding ones are decided?
+        function ahead_ok() result(ok)
+            logical :: ok
+            integer :: tt
+            ok = .true.
+            do tt = 1, S%n_res
+                if (S%res(tt)%active /= 1) cycle
+                if (S%res(tt)%count - n_del(tt) < 1) ok = .false.
+                if (S%res(tt)%count + n_ins(tt) > min(S%res(tt)%cap, NB_MAX_MOLECULE) - 1) ok = .false.
+            end do
+        end function ahead_ok
+
+        ! step jj's numbers, propose_step's statements in its order (every count is away from its edges: ahead_ok)
+        subroutine draw_record(jj)
+            integer, intent(in) :: jj
+            integer :: tt, nn1
+            real(real64) :: draw, trial(3)
+            tt = pick_residue_type()
+            rsel(jj) = rand_uniform()                                    ! PickRandomMoleculeIndex (the type is not empty)
+            draw = rand_uniform()
+            nn1 = S%res(tt)%n1
+            rt(jj) = tt - 1
+            if (draw <= S%p_translation) then
+                call random_number(trial)
+                ru(1:3, jj) = trial
+                rau(jj) = rand_uniform()
+                rmove(jj) = 1
+                mtype(jj) = TYPE_TRANSLATION
+            else if (draw <= S%p_rotation + S%p_translation) then
+                if (nn1 /= 1) then
+                    ru(4, jj) = rand_uniform()                           ! ApplyRandomRotation: angle, then axis
+                    ru(5, jj) = rand_uniform()
+                    rau(jj) = rand_uniform()
+                    rmove(jj) = 2
+                    mtype(jj) = TYPE_ROTATION
+                end if
+            else
+                rphi(jj) = S%res(tt)%fugacity * S%box%volume
+                if (rand_uniform() <= PROB_CREATE_DELETE) then
+                    call random_number(trial)
+                    ru(1:3, jj) = trial
+                    if (nn1 /= 1) then
+                        ru(4, jj) = rand_uniform()
+                        ru(5, jj) = rand_uniform()
+                    end if
+                    rau(jj) = rand_uniform()
+                    rmove(jj) = 3
+                    mtype(jj) = TYPE_CREATION
+                    n_ins(tt) = n_ins(tt) + 1
+                else
+                    rau(jj) = rand_uniform()
+                    rmove(jj) = 4
+                    mtype(jj) = TYPE_DELETION
+                    n_del(tt) = n_del(tt) + 1
+                end if
+            end if
+        end subroutine draw_record
+    end subroutine run_block_gc
+
+    ! steps of the block through the path the loop takes without chain runs: a window of up to `left` steps, or one plain step;
+    ! returns the number of steps taken
+    function fallback_steps(left) result(done)
+        integer, intent(in) :: left
+        integer :: done
+        if (fused .and. (spec_k > 1 .or. chain_cap > 0)) then
+            done = run_window(min(spec_k, left))
+        else
+            call plain_step()
+            done = 1
+        end if
+    end function fallback_steps
+
+    ! one step of MonteCarloLoop's body through the move drivers
+    subroutine plain_step()
+        integer :: t, m
+        real(real64) :: draw
+        t = pick_residue_type()
+        m = pick_molecule_index(S%res(t)%count)
+        draw = rand_uniform()
+        if (draw <= S%p_translation) then
+            call translation(t, m)
+        else if (draw <= S%p_rotation + S%p_translation) then
+            call rotation(t, m)
+        else
+            if (rand_uniform() <= PROB_CREATE_DELETE) then
+                m = S%res(t)%count + 1
+                call create_molecule(t, m)
+            else
+                call delete_molecule(t, m)
+            end if
+        end if
+    end subroutine plain_step
+
+    ! old / new as resolve_step forms them for the engine's rows of a step of a grand-canonical run
+    subroutine gc_states(move_type, o, w, old, new)
+        integer, intent(in) :: move_type
+        real(real64), intent(in) :: o(5), w(5)
+        real(real64), intent(out) :: old(6), new(6)
+        old = zero
+        new = zero
+        select case (move_type)
+        case (TYPE_CREATION)
+            old(IE_RECIP) = S%energy(IE_RECIP)
+            new(1:5) = w
+        case (TYPE_DELETION)
+            old(1:5) = o
+            old(IE_RECIP) = S%energy(IE_RECIP)
+            new(IE_RECIP) = w(IE_RECIP)
+        case default
+            old(1:3) = o(1:3)
+            new(1:3) = w(1:3)
+        end select
+        old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP) + old(IE_SELF) + old(IE_INTRA)
+        new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP) + new(IE_SELF) + new(IE_INTRA)
+    end subroutine gc_states
+
+    ! the rule for a step the engine left undecided, as resolve_step applies it (the count as the move drivers have it there)
+    function decide_gc(move_type, t, o, w, u) result(yes)
+        integer, intent(in) :: move_type, t
+        real(real64), intent(in) :: o(5), w(5), u
+        logical :: yes
+        real(real64) :: old(6), new(6)
+        integer :: dn
+        call gc_states(move_type, o, w, old, new)
+        dn = 0
+        if (move_type == TYPE_CREATION) dn = 1
+        if (move_type == TYPE_DELETION) dn = -1
+        S%res(t)%count = S%res(t)%count + dn
+        yes = decide(old, new, t, move_type, u, BY_HOST)
+        S%res(t)%count = S%res(t)%count - dn
+    end function decide_gc
+
+    ! counters, running energies and the count of one decided step of a grand-canonical run, as resolve_step books
+    ! DEVICE_ACCEPTED / DEVICE_REJECTED (the engine has applied the step; the mirror's frames follow at refresh_frames)
+    subroutine book_gc(move_type, t, o, w, accepted)
+        integer, intent(in) :: move_type, t
+        real(real64), intent(in) :: o(5), w(5)
+        logical, intent(in) :: accepted
+        real(real64) :: old(6), new(6)
+        integer :: n1
+        if (move_type == TYPE_TRANSLATION .or. move_type == TYPE_ROTATION) then
+            call book_step(move_type, o, w, accepted)
+            return
+        end if
+        n1 = S%res(t)%n1
+        call gc_states(move_type, o, w, old, new)
+        if (move_type == TYPE_CREATION) then
+            S%counter(C_TRIAL_C) = S%counter(C_TRIAL_C) + 1
+        else
+            S%counter(C_TRIAL_D) = S%counter(C_TRIAL_D) + 1
+        end if
+        if (.not. accepted) return
+        S%energy(IE_RECIP) = new(IE_RECIP)
+        S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
+        S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
+        S%energy(IE_SELF) = S%energy(IE_SELF) + new(IE_SELF) - old(IE_SELF)
+        S%energy(IE_INTRA) = S%energy(IE_INTRA) + new(IE_INTRA) - old(IE_INTRA)
+        S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
+        if (move_type == TYPE_CREATION) then
+            S%counter(C_C) = S%counter(C_C) + 1
+            S%res(t)%count = S%res(t)%count + 1
+            S%box%num_atoms = S%box%num_atoms + n1
+        else
+            S%counter(C_D) = S%counter(C_D) + 1
+            S%res(t)%count = S%res(t)%count - 1
+            S%box%num_atoms = S%box%num_atoms - n1
+        end if
+    end subroutine book_gc
+
     ! counters and running energies of one decided translation / rotation, as resolve_step books them
     subroutine book_step(move_type, o, w, accepted)
         integer, intent(in) :: move_type
@@ -1310,6 +1614,27 @@ contains
             deallocate(com, off)
         end do
     end subroutine refresh_frames
+
+    ! the engine's sites from the mirror, WITHOUT frames: the window path hands over rows built here, which an engine that holds
+    ! frames refuses (they would no longer mirror its sites); upload_frames gives them back
+    subroutine drop_frames()
+        integer :: t, n1, m, n
+        integer(c_int) :: rc
+        real(c_double), allocatable :: sites(:, :, :)
+        do t = 1, S%n_res
+            if (S%res(t)%active /= 1) cycle
+            n1 = S%res(t)%n1
+            n = S%res(t)%count
+            allocate(sites(3, n1, max(n, 1)))
+            sites = zero
+            do m = 1, n
+                call MoleculeSites(S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, sites(:, :, m))
+            end do
+            rc = mgpu_replica_set_molecules(S%engine, 0_c_int, int(t - 1, c_int), int(n, c_int), sites)
+            call note(int(rc))
+            deallocate(sites)
+        end do
+    end subroutine drop_frames
 
     ! the engine's frames from the mirror (a chain run builds its moves from them)
     subroutine upload_frames()
@@ -1390,7 +1715,8 @@ contains
         integer :: i, t, m, stat, step
         integer(c_int) :: cap, run_kmax, run_dmax
         integer(kind=8) :: c0, c1, crate
-        real(real64) :: draw, e6(6)
+        real(real64) :: e6(6)
+        logical :: want_gc
 
         S%outdir = ''
         do i = 1, len(S%outdir)
@@ -1425,12 +1751,22 @@ contains
         ! triclinic box: only where the caller has switched mgpu_chain_run_set_triclinic on -- the capacity says so, and the
         ! block is then driven exactly as an orthorhombic one: the engine wraps the centres, refresh_frames reads them back);
         ! elsewhere the windows above
+        ! A block WITH insertions / deletions: only where the host has asked for it (mchain_set_chain_run_gcmc), the run is not
+        ! --as-written and the engine takes the switch (orthorhombic box, no reservoir): run_block_gc.
         run_on = .false.
-        if (fused .and. run_k > 0 .and. S%p_translation + S%p_rotation >= one .and. .not. S%has_reservoir) then
+        run_gc = .false.
+        run_fallback = 0
+        want_gc = S%p_translation + S%p_rotation < one
+        if (fused .and. run_k > 0 .and. .not. S%has_reservoir .and. (.not. want_gc .or. (run_gc_want .and. .not. as_written))) then
             stat = mgpu_chain_run_capacity(S%engine, run_kmax, run_dmax, run_ring)
             call note(stat)
+            if (stat == 0 .and. run_kmax > 0 .and. want_gc) then
+                ! (a refusal -- a triclinic box -- is not an error of the run: it keeps its windows)
+                if (mgpu_chain_run_set_gc(S%engine, 1_c_int) /= MGPU_OK) run_kmax = 0
+            end if
             if (stat == 0 .and. run_kmax > 0) then
                 run_on = .true.
+                run_gc = want_gc
                 run_k = min(run_k, int(run_kmax))
                 run_depth = min(run_depth, int(run_dmax))
                 call upload_frames()
@@ -1449,7 +1785,11 @@ contains
             step = 1
             call system_clock(c0, crate)
             if (run_on) then
-                call run_block(int(nb_step))
+                if (run_gc) then
+                    call run_block_gc(int(nb_step))
+                else
+                    call run_block(int(nb_step))
+                end if
                 step = nb_step + 1
             end if
             do while (step <= nb_step)
@@ -1459,21 +1799,7 @@ contains
                     if (status /= 0) exit
                     cycle
                 end if
-                t = pick_residue_type()
-                m = pick_molecule_index(S%res(t)%count)
-                draw = rand_uniform()
-                if (draw <= S%p_translation) then
-                    call translation(t, m)
-                else if (draw <= S%p_rotation + S%p_translation) then
-                    call rotation(t, m)
-                else
-                    if (rand_uniform() <= PROB_CREATE_DELETE) then
-                        m = S%res(t)%count + 1
-                        call create_molecule(t, m)
-                    else
-                        call delete_molecule(t, m)
-                    end if
-                end if
+                call plain_step()
                 if (status /= 0) exit
                 step = step + 1
             end do

@@ -71,6 +71,20 @@ def set_chain_run(k: int = 0, depth: int = 3):
     lib().mchain_set_chain_run(C.c_int(int(k)), C.c_int(int(depth)))
 
 
+def set_chain_run_gcmc(on: bool = False):
+    """mchain_set_chain_run_gcmc: with set_chain_run on, blocks WITH insertions / deletions run as chain runs of by-count
+    records too, where the engine takes the switch (Engine.chain_run_set_gc) and the run is not as-written."""
+    lib().mchain_set_chain_run_gcmc(C.c_int(1 if on else 0))
+
+
+def chain_run_gcmc_mode():
+    """(gcmc, fallback_steps) of the last mchain_run: its blocks were grand-canonical chain runs; steps they took through the
+    windows because a molecule count stood at an edge."""
+    out = np.zeros(2, dtype=np.int32)
+    lib().mchain_get_chain_run_gcmc(out.ctypes.data_as(_ip))
+    return bool(out[0]), int(out[1])
+
+
 def chain_run_mode():
     """(on, k, depth) of the last mchain_run: on = the run's blocks were chain runs, k and depth as the engine's capacity cut them."""
     out = np.zeros(3, dtype=np.int32)

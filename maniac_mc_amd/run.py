@@ -122,7 +122,7 @@ WIDE_CHAIN_WINDOWS_DEFAULT = False
 def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoir_path=None, device=0,
                    mol_capacity=None, nb_block=None, nb_step=None, seams=False, as_written=False, speculate=4,
                    chain_windows=True, chain_margin=None, wide_chain_windows=WIDE_CHAIN_WINDOWS_DEFAULT, chain_run=None,
-                   chain_run_triclinic=False):
+                   chain_run_triclinic=False, chain_run_gcmc=False):
     """Run the chain; returns a dict with the final energies (K), counters, molecule counts, step sizes.
 
     ``seed``: None -> the input file's ``seed`` if present, else the generator is left unseeded
@@ -156,6 +156,13 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     ``chain_run_triclinic``: True (with ``chain_run``) -> a TRICLINIC input's blocks are chain runs too: the engine is created
     with device-built triclinic moves and takes runs (Engine.chain_run_set_triclinic).  False (default): a triclinic input
     keeps its windows whatever ``chain_run`` says.  An orthorhombic input does not look at it.  ValueError without ``chain_run``.
+    ``chain_run_gcmc``: True (with ``chain_run``) -> a GRAND-CANONICAL input's blocks are chain runs too, of by-count records
+    (Engine.chain_run_set_gc / chain_run_push_gc): the launch that takes a record picks the molecule and forms the prefactor
+    from the count it finds.  The loop draws a record ahead of the outcomes before it only while no count can reach 0 or the
+    capacity; where that rule fails it takes steps through its windows (``chain_run['fallback_steps']``).  Same files as the
+    windows.  Runs with ``as_written`` or a reservoir, and triclinic boxes, keep their windows (``on`` False); False
+    (default): a grand-canonical input keeps its windows whatever ``chain_run`` says.  ValueError without ``chain_run``.
+    ``chain_run`` in the result gains ``gcmc`` and ``fallback_steps``.
     """
     system, inp, dat = io_maniac.load_system(maniac_path, data_path, inc_path, with_data=True)
     rdat = io_maniac.read_lammps_data(reservoir_path, inp) if reservoir_path else None
@@ -165,6 +172,8 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
         mol_capacity = [NB_MAX_MOLECULE if topo.is_active[t] == 1 else max(1, int(system.n_mol[t])) for t in range(n_res)]
     if chain_run_triclinic and chain_run is None:
         raise ValueError("chain_run_triclinic needs chain_run=(k, depth)")
+    if chain_run_gcmc and chain_run is None:
+        raise ValueError("chain_run_gcmc needs chain_run=(k, depth)")
     run_tri = bool(chain_run_triclinic) and not seams and system.is_triclinic()
     eng = Engine.from_system(system, n_replicas=1, device=device, mol_capacity=mol_capacity, triclinic_moves=run_tri)
     if run_tri:
@@ -182,6 +191,7 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
         H.mchain_set_wide_windows(C.c_int(1 if wide_chain_windows else 0))
         k_run, depth_run = (0, 3) if chain_run is None or seams else (int(chain_run[0]), int(chain_run[1]))
         fortran_host.set_chain_run(k_run, depth_run)
+        fortran_host.set_chain_run_gcmc(bool(chain_run_gcmc) and not seams)
         H.mchain_get_loop_seconds.restype = C.c_double
         header = header_text(inp, dat, maniac_path, data_path, inc_path, eng, reservoir_path, rdat)
         H.mchain_set_log_header(header, C.c_int(len(header)))
@@ -206,6 +216,7 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
         chain_stats = eng.chain_stats()
         run_mode = fortran_host.chain_run_mode()
         run_stats = dict(zip(("on", "k", "depth", "launches", "steps", "void_launches", "undecided"), run_mode + eng.chain_run_stats()))
+        run_stats["gcmc"], run_stats["fallback_steps"] = fortran_host.chain_run_gcmc_mode()
         e_final = eng.system_energy(0)
     finally:
         eng.close()
@@ -254,6 +265,8 @@ def main(argv=None):
                     help="NVT inputs: run each block as a chain run of K steps per launch, DEPTH (default 3) launches in flight")
     ap.add_argument("--chain-run-triclinic", dest="chain_run_triclinic", action="store_true",
                     help="with --chain-run: a triclinic input's blocks are chain runs too (off by default: such an input keeps its windows)")
+    ap.add_argument("--chain-run-gcmc", dest="chain_run_gcmc", action="store_true",
+                    help="with --chain-run: a grand-canonical input's blocks are chain runs too (off by default: such an input keeps its windows)")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
     ap.add_argument("--replicas", type=int, default=None,
@@ -271,6 +284,8 @@ def main(argv=None):
         ap.error(str(err))
     if a.chain_run_triclinic and chain_run is None:
         ap.error("--chain-run-triclinic needs --chain-run K[,DEPTH]")
+    if a.chain_run_gcmc and chain_run is None:
+        ap.error("--chain-run-gcmc needs --chain-run K[,DEPTH]")
     if chain_run is not None and a.replicas is not None:
         ap.error("--chain-run is the single chain's mode: it cannot be combined with --replicas")
     if a.replicas is None:
@@ -304,7 +319,7 @@ def main(argv=None):
     res = run_simulation(a.maniac, a.data, a.inc, a.out, seed=a.seed, reservoir_path=a.reservoir, device=a.device,
                          as_written=a.as_written, speculate=a.speculate, chain_windows=not a.no_chain_windows,
                          wide_chain_windows=a.wide_chain_windows, chain_run=chain_run,
-                         chain_run_triclinic=a.chain_run_triclinic)
+                         chain_run_triclinic=a.chain_run_triclinic, chain_run_gcmc=a.chain_run_gcmc)
     e = res["energy"]
     print(f"final energy (K): total {e['total']:.6f}  non_coulomb {e['non_coulomb']:.6f}  coulomb {e['coulomb']:.6f}  "
           f"recip {e['recip_coulomb']:.6f};  molecules {res['n_mol'].tolist()};  output in {os.path.join(a.out, '')}")

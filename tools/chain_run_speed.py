@@ -5,10 +5,14 @@ continue from the step cursor on the device).
 
     python tools/chain_run_speed.py [--blocks 2] [--steps 2000] [--ks 1,2,4,8] [--depths 2,3,4] [--cases spce_10125_nvt,framework_nvt]
     python tools/chain_run_speed.py --workload spce_triclinic
+    python tools/chain_run_speed.py --workload co2_gcmc --chain-run-gcmc --ks 4,8 --depths 3
 
 Boxes: bench.py's 10 125-atom SPC/E box and its framework box (2208 framework atoms + 40 four-site waters), NVT, 50 %
 translations / 50 % rotations.  --workload spce_triclinic: bench.py's sheared 10 125-atom box (tilt 3.0 / -2.0 / 1.5 A) instead,
-its chain runs with chain_run_triclinic=True (the default mode is the windows such a box runs through without the switch).  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
+its chain runs with chain_run_triclinic=True (the default mode is the windows such a box runs through without the switch).
+--workload co2_gcmc / framework_gcmc (with --chain-run-gcmc: their chain runs are those of by-count records, chain_run_gcmc=True): a
+CO2 box (64 three-site molecules in 50 A) and the framework box with its waters, grand-canonical -- 30 % translations, 30 %
+rotations, 40 % insertions / deletions; per run also the steps the run took through the windows (fallback).  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
 build on one box in one session; per run: steps/s of the loop alone, mean steps per launch that did something, the share of
 void launches, undecided steps.  The output files of every mode must be those of the default mode (checked here).  A
 difference between two modes that is smaller than the spread between the two runs of one mode is no difference.
@@ -32,11 +36,15 @@ def main():
     ap.add_argument("--ks", default="1,2,4,8")
     ap.add_argument("--depths", default="2,3,4")
     ap.add_argument("--cases", default="spce_10125_nvt,framework_nvt")
-    ap.add_argument("--workload", default=None, choices=("spce", "framework", "spce_triclinic"), help="one box instead of --cases")
+    ap.add_argument("--workload", default=None, choices=("spce", "framework", "spce_triclinic", "co2_gcmc", "framework_gcmc"),
+                    help="one box instead of --cases")
+    ap.add_argument("--chain-run-gcmc", dest="chain_run_gcmc", action="store_true",
+                    help="the grand-canonical boxes' chain runs (chain_run_gcmc=True); without it such a box keeps its windows and the tool stops")
     ap.add_argument("--rounds", type=int, default=2)
     a = ap.parse_args()
     if a.workload is not None:
-        a.cases = {"spce": "spce_10125_nvt", "framework": "framework_nvt", "spce_triclinic": "spce_triclinic_nvt"}[a.workload]
+        a.cases = {"spce": "spce_10125_nvt", "framework": "framework_nvt", "spce_triclinic": "spce_triclinic_nvt",
+                   "co2_gcmc": "co2_gcmc", "framework_gcmc": "framework_gcmc"}[a.workload]
     tmp = tempfile.mkdtemp()
     common = dict(nb_block=2, nb_step=100, translation_proba=0.5, rotation_proba=0.5)
     cases = {
@@ -45,6 +53,14 @@ def main():
         "framework_nvt": (synth.framework_water_box(), dict(translation_step=0.5, rotation_step_angle=0.5,
                                                             masses=[12.0] * 7 + [15.9994, 1.008, 1e-4], fugacity_atm=[1.0, 1.0])),
     }
+    gcmc = dict(nb_block=2, nb_step=100, translation_proba=0.3, rotation_proba=0.3, insertion_deletion_proba=0.4)
+    gc_cases = {
+        "co2_gcmc": (synth.co2_box(), dict(translation_step=1.0, rotation_step_angle=0.6, masses=[12.011, 15.9994], atom_names=["C", "O"],
+                                           fugacity_atm=[30.0])),
+        "framework_gcmc": (synth.framework_water_box(), dict(translation_step=0.5, rotation_step_angle=0.5,
+                                                             masses=[12.0] * 7 + [15.9994, 1.008, 1e-4], fugacity_atm=[1.0, 0.05])),
+    }
+    cases.update(gc_cases)
     if "spce_triclinic_nvt" in a.cases.split(","):
         # bench.py's spce_triclinic: rows a = (lx, 0, 0), b = (xy, ly, 0), c = (xz, yz, lz), the centres sheared with the cell
         s = synth.spce_box(15)
@@ -56,14 +72,15 @@ def main():
     n = a.blocks * a.steps
     for name in a.cases.split(","):
         system, kw = cases[name]
-        files = io_maniac.write_input_files(system, os.path.join(tmp, name + "_in"), **common, **kw)
+        files = io_maniac.write_input_files(system, os.path.join(tmp, name + "_in"), **(gcmc if name in gc_cases else common), **kw)
         rates = {label: [] for label, _ in modes}
         base = None
         for rnd in range(a.rounds):
             for label, cr in modes:
                 out = os.path.join(tmp, f"{name}_{label.replace(' ', '_').replace('=', '')}_{rnd}") + "/"
                 res = run.run_simulation(*files, out, seed=5, nb_block=a.blocks, nb_step=a.steps, chain_run=cr,
-                                         chain_run_triclinic=cr is not None and system.is_triclinic())
+                                         chain_run_triclinic=cr is not None and system.is_triclinic(),
+                                         chain_run_gcmc=cr is not None and a.chain_run_gcmc)
                 if cr is not None and not res["chain_run"]["on"]:
                     raise SystemExit(f"{name}: the engine did not take the chain run (Engine.chain_run_capacity)")
                 rate = n / res["mc_seconds"]
@@ -77,9 +94,10 @@ def main():
                     r = res["chain_run"]
                     work = max(1, r["launches"] - r["void_launches"])
                     extra = (f"on {r['on']}, launches {r['launches']}, steps per working launch {r['steps'] / work:.2f}, "
-                             f"void {r['void_launches'] / max(1, r['launches']):.1%}, undecided {r['undecided']}")
+                             f"void {r['void_launches'] / max(1, r['launches']):.1%}, undecided {r['undecided']}, "
+                             f"fallback steps {r['fallback_steps']}")
                 print(f"{name:16s} round {rnd} {label:18s}: {rate:9.0f} steps/s (loop {res['mc_seconds']:.3f} s of {n} steps; {extra}; "
-                      f"acceptance {int(c[1] + c[3]) / n:.2f}; files as the first run's: {not diff}{' ' + str(diff) if diff else ''})", flush=True)
+                      f"acceptance {int(c[1] + c[3] + c[5] + c[7]) / n:.2f}; files as the first run's: {not diff}{' ' + str(diff) if diff else ''})", flush=True)
         print(f"\n{name}: steps/s of the loop alone, the rounds side by side")
         for label, _ in modes:
             v = rates[label]
