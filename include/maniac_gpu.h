@@ -580,7 +580,7 @@ int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long lo
  *               ApplyPBC's triclinic form (src/geometry_utils.f90:167-220: through fractional coordinates, modulo(f, 1)
  *               always) and sweep with ComputeDistance's image search (:397-411), as the farm windows of such a box do.
  *               MGPU_ERR_STATE, and the switch stays as it was: an orthorhombic box, mgpu_set_triclinic_moves not on, a run
- *               open.
+ *               open, and on = 0 while set_gc is on (grand-canonical runs of a triclinic box stand on this switch).
  *   open        replaces the block's set-up (src/monte_carlo.f90:40-48): cursor 0, the block's step sizes and temperature.
  *               The replica needs resident frames of every active type, lane 0 must be idle, one run per engine
  *               (MGPU_ERR_STATE otherwise).  Drains every lane.
@@ -592,8 +592,10 @@ int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long lo
  *               stream: launches queued BEFORE a push do not see it.
  *   set_gc      on = 1: the engine's runs are those of a grand-canonical block (off at creation): they take by-count records
  *               through push_gc and launch the GC instances of the kernel.  MGPU_ERR_STATE, and the switch stays as it was: a
- *               triclinic box, an engine that holds a reservoir (no such instance exists), a run open.  With the switch off
- *               every entry point, refusal and kernel instance is what it was.  The capacity does not depend on it.
+ *               triclinic box whose set_triclinic is off (on = 1; with it on the box is admitted, and its launches are the
+ *               instance with both the image search and by-count records), an engine that holds a reservoir (no such instance
+ *               exists), a run open.  With the switch off every entry point, refusal and kernel instance is what it was.  The
+ *               capacity does not depend on it.
  *   push_gc     (switch on; MGPU_ERR_STATE otherwise) n BY-COUNT records: t, move (0-4: 3 creation, 4 deletion), u5, accept_u as
  *               push takes them, sel_u[n] the draw of PickRandomMoleculeIndex in [0, 1), phi_v[n] > 0 (moves 3 / 4).  The launch
  *               that takes a record completes it from the molecule count it FINDS: slot = min(int(sel_u N), N - 1), prefactor

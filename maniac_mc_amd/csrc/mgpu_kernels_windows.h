@@ -968,10 +968,12 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI 
 // switched both device-built moves and triclinic runs on (mgpu_chain_run_set_triclinic).  TRI changes what it changes in
 // farm_window_kernel and nothing else: every role and the commit build the candidate with the triclinic form of trial_frame
 // (trial_com_triclinic's centre, wrapped always), and the pair role runs the register-site sweep with ComputeDistance's
-// image search; no flat form, no fast fold.  No WIDE or RSV instance exists (capacity 0).
-// GC (mgpu_chain_run_set_gc, orthorhombic boxes without reservoirs: <FLAT, FASTW, false, true>): the run of a grand-canonical
-// block.  Which molecule a step picks and its prefactor depend on the molecule count, i.e. on the outcome of the steps before
-// it, so the driver pushes BY-COUNT records (RunRec::pad; the draw of PickRandomMoleculeIndex and phi V travel in a second
+// image search; no flat form, no fast fold.  No WIDE or RSV instance exists (capacity 0).  The instances in all: four
+// <FLAT, FASTW>, <false, false, true>, and the grand-canonical form of each of the five (GC = true, below): ten.
+// GC (mgpu_chain_run_set_gc, boxes without reservoirs: <FLAT, FASTW, false, true> for an orthorhombic box, <false, false, true,
+// true> for a triclinic one whose engine has triclinic runs on): the run of a grand-canonical block.  Which molecule a step
+// picks and its prefactor depend on the molecule count, i.e. on the outcome of the steps before it, so the driver pushes
+// BY-COUNT records (RunRec::pad; the draw of PickRandomMoleculeIndex and phi V travel in a second
 // ring, ChainRunArgs::gc_ring, which these instances alone read) and every workgroup completes the launch's records from the
 // count the launch finds, with farm_window_kernel's integer arithmetic and prefactors: slot = min(int(u N), N - 1),
 // phi V / (N + 1) for an insertion, N / (phi V) for a deletion, and a move or deletion of an empty type or an insertion into a
@@ -981,6 +983,12 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI 
 // role has no old entry for an insertion (which excludes nothing) and no new entry for a deletion, and the resolver reads
 // the absent entries as zero -- they are never written.  Totals with self and intra terms, the prefactor in the rule and the
 // commit (append at slot N; swap with the last molecule) are farm_resolve's.
+// TRI with GC is the two together and nothing of its own, call for call farm_window_kernel<false, false, false, false, true> with
+// by-count records: trial_frame<false, true> builds the insertion's centre (lo + box%matrix u, never wrapped)
+// in the k role, the pair role and the commit wave; the k role's RecipItem carries the same {m = -1 for an insertion, kind}; the
+// intra term is intra_energy's, which takes the image search from bx.triclinic by itself (a molecule that straddles a cell face
+// is stored whole, centre + offset, so the search finds the direct distance), and a deletion's resident entry runs the image
+// search from the resident sites as a move's old entry does.  The instance has the NVT triclinic one's register budget.
 // ------------------------------------------------------------------------------------------
 struct RunState { int cursor, pushed, stalled, pad; };
 struct RunRec {
@@ -1022,7 +1030,6 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
     double2 *__restrict__ A_base, const ChainRunArgs g) {
     static_assert(!TRI || (!FLAT && !FASTW), "the image search has no flat form and no fast fold (farm_window_kernel's triclinic family)");
-    static_assert(!(TRI && GC), "no grand-canonical run of a triclinic box (mgpu_chain_run_set_gc refuses it)");
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];      // Coulomb table | phase tables | partials staging
     __shared__ double2 s_pair[kMaxTypes * kMaxTypes];
     __shared__ int4 s_grp[kMaxGrp];

@@ -143,7 +143,7 @@ void window_types_build(mgpu_engine *e) {
 //   farm windows and chain runs: a triclinic box whose engine has not switched device-built moves on;
 //   chain runs (no such instance of chain_run_kernel exists): reservoirs, and a triclinic box unless triclinic runs are on.
 //     (Grand-canonical runs, mgpu_chain_run_set_gc, are admitted exactly where runs are: the switch is refused for a triclinic box
-//     and for an engine with a reservoir, and the GC instances' dynamic LDS is window_lds_bytes(kPathRun, ...) -- their k role, pair
+//     whose triclinic runs are off and for an engine with a reservoir, and the GC instances' dynamic LDS is window_lds_bytes(kPathRun, ...) -- their k role, pair
 //     role and resolver stage what the NVT instances stage; what they add is 16 double2 of static LDS.)
 // rides[t]: a record of type t may travel (a single-chain window takes any row of <= kMaxFusedSitesWide sites; a run any active type).
 struct WindowAdmission {
@@ -714,12 +714,14 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     ln.forget_trial();
     alt_forget(e, rn.replica);
     // The run kernel's families: with the image search (no flat form, no fast fold: farm_window_kernel's triclinic family), the
-    // orthorhombic one, whose flags are free, and the grand-canonical one (orthorhombic; the run was opened with the switch on).
+    // orthorhombic one, whose flags are free, and the grand-canonical forms of both (the run was opened with the switch on).
     auto tri_family = [](auto &&f) { f(chain_run_kernel<false, false, true>); };
     auto ortho_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); };
     auto gc_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, true>); };
+    auto tri_gc_family = [](auto &&f) { f(chain_run_kernel<false, false, true, true>); };
     auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
-    if (e->bx.triclinic) tri_family(launch);
+    if (e->bx.triclinic && rn.gc) tri_gc_family(launch);
+    else if (e->bx.triclinic) tri_family(launch);
     else if (rn.gc) with_bools([&](auto... flags) { gc_family(launch, flags...); }, e->pair_flat, ff);
     else with_bools([&](auto... flags) { ortho_family(launch, flags...); }, e->pair_flat, ff);
     HIP_TRY(hipGetLastError());
@@ -741,6 +743,8 @@ int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on) {
     if (!e->bx.triclinic) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: the box is orthorhombic");
     if (!e->tri_moves) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: device-built triclinic moves are off (mgpu_set_triclinic_moves)");
     if (e->run.open) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: a run is open");
+    // (grand-canonical runs of a triclinic box stand on this switch: mgpu_chain_run_set_gc)
+    if (!on && e->run.gc) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: grand-canonical runs are on (mgpu_chain_run_set_gc)");
     e->run.triclinic = on != 0;
     return MGPU_OK;
 }
@@ -748,7 +752,8 @@ int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on) {
 int mgpu_chain_run_set_gc(mgpu_engine *e, int on) {
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
     // every refusal leaves the switch as it was
-    if (e->bx.triclinic) return set_error(MGPU_ERR_STATE, "chain_run_set_gc: the box is triclinic (no such instance of the run kernel)");
+    if (on && e->bx.triclinic && !e->run.triclinic)
+        return set_error(MGPU_ERR_STATE, "chain_run_set_gc: the box is triclinic and triclinic runs are off (mgpu_chain_run_set_triclinic)");
     if (e->rsv_any) return set_error(MGPU_ERR_STATE, "chain_run_set_gc: the engine holds a reservoir (no such instance of the run kernel)");
     if (e->run.open) return set_error(MGPU_ERR_STATE, "chain_run_set_gc: a run is open");
     e->run.gc = on != 0;

@@ -293,7 +293,8 @@ class Engine:
 
     def chain_run_set_triclinic(self, on=True):
         """mgpu_chain_run_set_triclinic: a triclinic box takes chain runs (off by default).  Refused (MgpuError, the switch
-        unchanged) for an orthorhombic box, without set_triclinic_moves, and while a run is open."""
+        unchanged) for an orthorhombic box, without set_triclinic_moves, while a run is open, and -- switching it off -- while
+        chain_run_set_gc is on."""
         check(self.L.mgpu_chain_run_set_triclinic(self.h, C.c_int(1 if on else 0)))
 
     def chain_run_open(self, replica, k, translation_step, rotation_step, temperature):
@@ -310,8 +311,8 @@ class Engine:
 
     def chain_run_set_gc(self, on=True):
         """mgpu_chain_run_set_gc: the engine's runs are those of a grand-canonical block (off by default): by-count records
-        through chain_run_push_gc.  Refused (MgpuError, the switch unchanged) for a triclinic box, with a reservoir, and while
-        a run is open."""
+        through chain_run_push_gc.  Refused (MgpuError, the switch unchanged) for a triclinic box unless
+        chain_run_set_triclinic is on, with a reservoir, and while a run is open."""
         check(self.L.mgpu_chain_run_set_gc(self.h, C.c_int(1 if on else 0)))
 
     def chain_run_push_gc(self, t, move, u, accept_u, sel_u, phi_v):

@@ -328,7 +328,7 @@ module maniac_gpu
             integer(c_int), intent(out) :: max_k, max_in_flight, ring_steps
             integer(c_int) :: rc
         end function
-        ! a triclinic box takes runs (off by default; needs mgpu_set_triclinic_moves)
+        ! a triclinic box takes runs (off by default; needs mgpu_set_triclinic_moves; not switched off while set_gc is on)
         function mgpu_chain_run_set_triclinic(e, on) bind(C, name="mgpu_chain_run_set_triclinic") result(rc)
             import :: c_ptr, c_int
             type(c_ptr), value :: e
@@ -350,6 +350,7 @@ module maniac_gpu
             real(c_double), intent(in) :: u5(*), accept_u(*)
             integer(c_int) :: rc
         end function
+        ! grand-canonical runs (off by default; refused with a reservoir, and for a triclinic box unless set_triclinic is on)
         function mgpu_chain_run_set_gc(e, on) bind(C, name="mgpu_chain_run_set_gc") result(rc)
             import :: c_ptr, c_int
             type(c_ptr), value :: e

@@ -95,6 +95,8 @@ module mc_chain
     ! Grand-canonical chain runs (mchain_set_chain_run_gcmc; mgpu_chain_run_set_gc, mgpu_chain_run_push_gc): a block with exchange
     ! moves runs as a chain run of by-count records (run_block_gc).  run_gc_want: the host asked; run_gc: it applies to this run;
     ! run_fallback: steps of the last mchain_run taken through the windows because the ahead-of-outcome rule failed.
+    ! Orthorhombic boxes, and triclinic ones whose engine has triclinic runs on (mgpu_chain_run_set_triclinic); never with a
+    ! reservoir or as_written.
     logical, save :: run_gc_want = .false., run_gc = .false.
     integer, save :: run_fallback = 0
     integer(c_int), save :: run_ring = 0
@@ -1752,7 +1754,10 @@ contains
         ! block is then driven exactly as an orthorhombic one: the engine wraps the centres, refresh_frames reads them back);
         ! elsewhere the windows above
         ! A block WITH insertions / deletions: only where the host has asked for it (mchain_set_chain_run_gcmc), the run is not
-        ! --as-written and the engine takes the switch (orthorhombic box, no reservoir): run_block_gc.
+        ! --as-written and the engine takes the switch (no reservoir; a triclinic box only with triclinic runs on, which the
+        ! capacity above has already said): run_block_gc, for either kind of box -- the engine builds the insertion's centre
+        ! (lo + box%matrix u) and wraps the translations, refresh_frames reads them back, and the fallback's windows are the
+        ! ones such a box takes without runs: host-built rows through the loop's own ApplyPBC, after drop_frames.
         run_on = .false.
         run_gc = .false.
         run_fallback = 0
@@ -1761,7 +1766,7 @@ contains
             stat = mgpu_chain_run_capacity(S%engine, run_kmax, run_dmax, run_ring)
             call note(stat)
             if (stat == 0 .and. run_kmax > 0 .and. want_gc) then
-                ! (a refusal -- a triclinic box -- is not an error of the run: it keeps its windows)
+                ! (a refusal is not an error of the run: it keeps its windows)
                 if (mgpu_chain_run_set_gc(S%engine, 1_c_int) /= MGPU_OK) run_kmax = 0
             end if
             if (stat == 0 .and. run_kmax > 0) then

@@ -642,6 +642,16 @@ def _data_block(name, dat, inp, is_primary, masses_n):
     for key in ("bonds", "angles", "dihedrals", "impropers"):
         if dat["bonded_counts"][key] == 0:
             out.append(f"INFO: No {key} expected in data file: {name}")
+    # TransformCoordinate, then CheckMolecule (data_parser.f90:1465-1478, check_utils.f90:23-33): a centre is compared with
+    # xlo..zhi per axis AFTER ApplyPBC, and in a triclinic cell the wrapped centre lo + box%matrix f leaves that brick by up to
+    # the tilt -- one warning per molecule and axis from each of the two, residue types in order, molecules in the file's
+    lo, hi = np.asarray(dat["lo"], dtype=np.float64), np.asarray(dat["hi"], dtype=np.float64)
+    for text in ("Molecule COM outside simulation box", "Error: Molecule COM outside simulation box!"):
+        for i in range(len(inp.residues)):
+            for com in np.asarray(dat["com"][i], dtype=np.float64).reshape(-1, 3)[:int(dat["n_mol"][i])]:
+                for d in range(3):
+                    if com[d] < lo[d] or com[d] > hi[d]:
+                        out += _warn(text)
     out += ["", "====== Import data file ======", f"Reading file {name}", "",
             f"Number of atoms: {dat['n_atoms']}", f"Number of type of residues: {len(inp.residues)}",
             f"Number of type of atoms: {dat['n_atom_types']}"]

@@ -160,7 +160,8 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     (Engine.chain_run_set_gc / chain_run_push_gc): the launch that takes a record picks the molecule and forms the prefactor
     from the count it finds.  The loop draws a record ahead of the outcomes before it only while no count can reach 0 or the
     capacity; where that rule fails it takes steps through its windows (``chain_run['fallback_steps']``).  Same files as the
-    windows.  Runs with ``as_written`` or a reservoir, and triclinic boxes, keep their windows (``on`` False); False
+    windows.  Runs with ``as_written`` or a reservoir keep their windows (``on`` False), and so does a TRICLINIC grand-canonical
+    input unless ``chain_run_triclinic`` is given as well: it takes both switches, and either alone leaves it its windows.  False
     (default): a grand-canonical input keeps its windows whatever ``chain_run`` says.  ValueError without ``chain_run``.
     ``chain_run`` in the result gains ``gcmc`` and ``fallback_steps``.
     """
@@ -264,9 +265,11 @@ def main(argv=None):
     ap.add_argument("--chain-run", dest="chain_run", default=None, metavar="K[,DEPTH]",
                     help="NVT inputs: run each block as a chain run of K steps per launch, DEPTH (default 3) launches in flight")
     ap.add_argument("--chain-run-triclinic", dest="chain_run_triclinic", action="store_true",
-                    help="with --chain-run: a triclinic input's blocks are chain runs too (off by default: such an input keeps its windows)")
+                    help="with --chain-run: a triclinic input's blocks are chain runs too (off by default: such an input keeps its windows; "
+                         "a triclinic grand-canonical input needs --chain-run-gcmc as well)")
     ap.add_argument("--chain-run-gcmc", dest="chain_run_gcmc", action="store_true",
-                    help="with --chain-run: a grand-canonical input's blocks are chain runs too (off by default: such an input keeps its windows)")
+                    help="with --chain-run: a grand-canonical input's blocks are chain runs too (off by default: such an input keeps its windows; "
+                         "a triclinic grand-canonical input needs --chain-run-triclinic as well)")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
     ap.add_argument("--replicas", type=int, default=None,

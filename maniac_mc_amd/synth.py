@@ -205,12 +205,15 @@ def _spread_points(rng, n, L, min_sep):
     return pts
 
 
-def framework_water_box(n_water=40, seed=11, L=34.0, rc=12.0, tol=1e-5, temperature=300.0, n_frame=2208):
+def framework_water_box(n_water=40, seed=11, L=34.0, rc=12.0, tol=1e-5, temperature=300.0, n_frame=2208, tilt=None):
     """Synthetic stand-in for the README's ZIF-8 + water case (BASELINE.json configs[3]).
 
     One inactive residue of ``n_frame`` atoms (7 atom types, net-neutral charges, jittered
     simple-cubic lattice so that the minimum separation stays >= 1.5 A) plus a 4-site
     TIP4P-like water as the active species.  Entirely synthetic.
+    ``tilt`` = (xy, xz, yz): the same box sheared into a triclinic cell (rows a = (L, 0, 0), b = (xy, L, 0), c = (xz, yz, L)):
+    the framework atoms and the waters' centres keep their fractions f (position lo + box%matrix f), the waters their
+    orientations.
     """
     rng = np.random.default_rng(seed)
     side = int(np.ceil(n_frame ** (1 / 3)))
@@ -256,6 +259,15 @@ def framework_water_box(n_water=40, seed=11, L=34.0, rc=12.0, tol=1e-5, temperat
     charges[1, :4] = [0.0, 0.52, 0.52, -1.04]
     topo = Topology(atoms_in_res=[n_frame, 4], atom_types=atom_types, charges=charges, is_active=[0, 1],
                     epsilon=eps, sigma=sig, names=["FRAME", "H2O"])
+    if tilt is not None:
+        mat = np.array([[L, 0.0, 0.0], [tilt[0], L, 0.0], [tilt[1], tilt[2], L]])
+        lo = np.full(3, -L / 2)
+        # (lo + box%matrix f, the reference's own map from fractions to positions: create_molecule.f90:181-182)
+        fpos = lo[None, :] + ((fpos - lo[None, :]) / L) @ mat.T
+        wcom = lo[None, :] + ((wcom - lo[None, :]) / L) @ mat.T
+        fcom = fpos.mean(0)
+        return System(topo, mat, lo, rc, tol, temperature, [fcom[None, :], wcom], [(fpos - fcom)[None, :, :], woff],
+                      label=f"framework{n_frame}_water{n_water}_tilted")
     return System(topo, np.diag([L, L, L]), np.full(3, -L / 2), rc, tol, temperature,
                   [fcom[None, :], wcom], [(fpos - fcom)[None, :, :], woff],
                   label=f"framework{n_frame}_water{n_water}")

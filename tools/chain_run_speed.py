@@ -6,13 +6,17 @@ continue from the step cursor on the device).
     python tools/chain_run_speed.py [--blocks 2] [--steps 2000] [--ks 1,2,4,8] [--depths 2,3,4] [--cases spce_10125_nvt,framework_nvt]
     python tools/chain_run_speed.py --workload spce_triclinic
     python tools/chain_run_speed.py --workload co2_gcmc --chain-run-gcmc --ks 4,8 --depths 3
+    python tools/chain_run_speed.py --workload co2_gcmc_triclinic --chain-run-triclinic --chain-run-gcmc --ks 4,8 --depths 3
 
 Boxes: bench.py's 10 125-atom SPC/E box and its framework box (2208 framework atoms + 40 four-site waters), NVT, 50 %
 translations / 50 % rotations.  --workload spce_triclinic: bench.py's sheared 10 125-atom box (tilt 3.0 / -2.0 / 1.5 A) instead,
 its chain runs with chain_run_triclinic=True (the default mode is the windows such a box runs through without the switch).
 --workload co2_gcmc / framework_gcmc (with --chain-run-gcmc: their chain runs are those of by-count records, chain_run_gcmc=True): a
 CO2 box (64 three-site molecules in 50 A) and the framework box with its waters, grand-canonical -- 30 % translations, 30 %
-rotations, 40 % insertions / deletions; per run also the steps the run took through the windows (fallback).  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
+rotations, 40 % insertions / deletions; per run also the steps the run took through the windows (fallback).
+--workload co2_gcmc_triclinic / framework_gcmc_triclinic (with --chain-run-triclinic AND --chain-run-gcmc, as on run.py's command
+line: either alone leaves such a box its windows and the tool stops): the same two boxes sheared by spce_triclinic's tilt scaled to
+their edge, the framework atoms and the centres keeping their fractions.  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
 build on one box in one session; per run: steps/s of the loop alone, mean steps per launch that did something, the share of
 void launches, undecided steps.  The output files of every mode must be those of the default mode (checked here).  A
 difference between two modes that is smaller than the spread between the two runs of one mode is no difference.
@@ -36,15 +40,19 @@ def main():
     ap.add_argument("--ks", default="1,2,4,8")
     ap.add_argument("--depths", default="2,3,4")
     ap.add_argument("--cases", default="spce_10125_nvt,framework_nvt")
-    ap.add_argument("--workload", default=None, choices=("spce", "framework", "spce_triclinic", "co2_gcmc", "framework_gcmc"),
+    ap.add_argument("--workload", default=None, choices=("spce", "framework", "spce_triclinic", "co2_gcmc", "framework_gcmc", "co2_gcmc_triclinic",
+                                                     "framework_gcmc_triclinic"),
                     help="one box instead of --cases")
     ap.add_argument("--chain-run-gcmc", dest="chain_run_gcmc", action="store_true",
                     help="the grand-canonical boxes' chain runs (chain_run_gcmc=True); without it such a box keeps its windows and the tool stops")
+    ap.add_argument("--chain-run-triclinic", dest="chain_run_triclinic", action="store_true",
+                    help="the sheared grand-canonical boxes' chain runs (chain_run_triclinic=True, with --chain-run-gcmc); the sheared NVT "
+                         "box's chain runs take the switch by themselves, as they always did")
     ap.add_argument("--rounds", type=int, default=2)
     a = ap.parse_args()
     if a.workload is not None:
         a.cases = {"spce": "spce_10125_nvt", "framework": "framework_nvt", "spce_triclinic": "spce_triclinic_nvt",
-                   "co2_gcmc": "co2_gcmc", "framework_gcmc": "framework_gcmc"}[a.workload]
+                   "co2_gcmc": "co2_gcmc", "framework_gcmc": "framework_gcmc"}.get(a.workload, a.workload)
     tmp = tempfile.mkdtemp()
     common = dict(nb_block=2, nb_step=100, translation_proba=0.5, rotation_proba=0.5)
     cases = {
@@ -60,6 +68,17 @@ def main():
         "framework_gcmc": (synth.framework_water_box(), dict(translation_step=0.5, rotation_step_angle=0.5,
                                                              masses=[12.0] * 7 + [15.9994, 1.008, 1e-4], fugacity_atm=[1.0, 0.05])),
     }
+    # the grand-canonical boxes sheared: spce_triclinic's tilt (3.0 / -2.0 / 1.5 A on its 46.56 A edge) scaled to the box's edge
+    tilt_of = lambda L: tuple(x * L / 46.56 for x in (3.0, -2.0, 1.5))
+    if "co2_gcmc_triclinic" in a.cases.split(","):
+        s = synth.co2_box()
+        L = float(s.box_matrix[0, 0])
+        xy, xz, yz = tilt_of(L)
+        s.box_matrix = np.array([[L, 0.0, 0.0], [xy, L, 0.0], [xz, yz, L]])
+        s.com[0] = s.bounds_lo[None, :] + ((s.com[0] - s.bounds_lo[None, :]) / L) @ s.box_matrix.T
+        gc_cases["co2_gcmc_triclinic"] = (s, gc_cases["co2_gcmc"][1])
+    if "framework_gcmc_triclinic" in a.cases.split(","):
+        gc_cases["framework_gcmc_triclinic"] = (synth.framework_water_box(tilt=tilt_of(34.0)), gc_cases["framework_gcmc"][1])
     cases.update(gc_cases)
     if "spce_triclinic_nvt" in a.cases.split(","):
         # bench.py's spce_triclinic: rows a = (lx, 0, 0), b = (xy, ly, 0), c = (xz, yz, lz), the centres sheared with the cell
@@ -79,7 +98,8 @@ def main():
             for label, cr in modes:
                 out = os.path.join(tmp, f"{name}_{label.replace(' ', '_').replace('=', '')}_{rnd}") + "/"
                 res = run.run_simulation(*files, out, seed=5, nb_block=a.blocks, nb_step=a.steps, chain_run=cr,
-                                         chain_run_triclinic=cr is not None and system.is_triclinic(),
+                                         chain_run_triclinic=cr is not None and system.is_triclinic() and
+                                         (a.chain_run_triclinic or name not in gc_cases),
                                          chain_run_gcmc=cr is not None and a.chain_run_gcmc)
                 if cr is not None and not res["chain_run"]["on"]:
                     raise SystemExit(f"{name}: the engine did not take the chain run (Engine.chain_run_capacity)")
