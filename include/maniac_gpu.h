@@ -623,6 +623,15 @@ int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long lo
  *   get_stats   since the engine was created: launches seen, steps they consumed, void launches, launches that ended at an
  *               undecided step.  get_launches: (first step, steps consumed) of the launches seen since open, oldest first
  *               (the last 1024).
+ *   set_wide    on: runs also take rigid molecules of 6 to 63 sites (off when the engine is created: capacity reports 0 for an
+ *               engine with such an active type, as it always has).  Such a step is evaluated as the batched path evaluates
+ *               it (ComputePairInteractionEnergy_singlemol, src/energy_utils.f90:381-446, through the LDS-staged sweep with the
+ *               engine's nsplit; ComputeRecipEnergySingleMol, src/ewald_energy.f90:219-275, in the form of the row's own type:
+ *               row form, vector wide form or untiled matrix-unit wide form; ComputeIntraResidueRealCoulombEnergySingleMol,
+ *               src/ewald_energy.f90, for an insertion / deletion), bit for bit; smaller molecules in the same run are taken as
+ *               before.  Admitted where the farm windows admit the type (plane-major types whose k form is one of the three and
+ *               whose LDS fits); works with set_gc / push_gc.  MGPU_ERR_STATE, the switch unchanged: while a run is open; on = 1
+ *               for a triclinic box (no WIDE sweep has the image search) and for an engine with a reservoir (no such instance).
  * An open run does not lock the engine: every synchronous entry point DRAINS it first -- it waits for the launches queued so
  * far and sees the state they committed; their results stay collectable -- and a submit on lane 0 is ordered behind them by
  * the stream.  Single-driver: one host thread at a time opens, pushes, launches, collects, forces and closes a run. */
@@ -631,6 +640,7 @@ int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on);
 int mgpu_chain_run_open(mgpu_engine *e, int replica, int k, double t_step, double r_step, double temperature);
 int mgpu_chain_run_push(mgpu_engine *e, int n, const int *t, const int *m, const int *move, const double *u5, const double *accept_u);
 int mgpu_chain_run_set_gc(mgpu_engine *e, int on);
+int mgpu_chain_run_set_wide(mgpu_engine *e, int on);
 int mgpu_chain_run_push_gc(mgpu_engine *e, int n, const int *t, const int *move, const double *u5, const double *accept_u,
                            const double *sel_u, const double *phi_v);
 int mgpu_chain_run_launch(mgpu_engine *e, int n_launches);

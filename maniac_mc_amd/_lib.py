@@ -39,7 +39,7 @@ EXPORTS = [
     "mgpu_chain_get_stats", "mgpu_chain_set_timing", "mgpu_chain_get_timing", "mgpu_farm_window_capacity", "mgpu_farm_window_submit",
     "mgpu_farm_window_wait", "mgpu_farm_window_flush", "mgpu_farm_window_get_stats",
     "mgpu_chain_run_capacity", "mgpu_chain_run_open", "mgpu_chain_run_push", "mgpu_chain_run_launch", "mgpu_chain_run_collect",
-    "mgpu_chain_run_force", "mgpu_chain_run_close", "mgpu_chain_run_get_stats", "mgpu_chain_run_get_launches", "mgpu_chain_run_set_triclinic", "mgpu_chain_run_set_gc", "mgpu_chain_run_push_gc", "mgpu_comm_unique_id", "mgpu_comm_create",
+    "mgpu_chain_run_force", "mgpu_chain_run_close", "mgpu_chain_run_get_stats", "mgpu_chain_run_get_launches", "mgpu_chain_run_set_triclinic", "mgpu_chain_run_set_gc", "mgpu_chain_run_push_gc", "mgpu_chain_run_set_wide", "mgpu_comm_unique_id", "mgpu_comm_create",
     "mgpu_comm_destroy", "mgpu_comm_rank", "mgpu_allgather_block_stats", "mgpu_append_atom_records", "mgpu_format_fixed", "mgpu_phase_factors", "mgpu_synchronize", "mgpu_profile_enable", "mgpu_profile_reset",
     "mgpu_profile_get",
 ]

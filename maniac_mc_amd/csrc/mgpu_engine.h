@@ -383,6 +383,7 @@ struct mgpu_engine {
     struct Run {
         bool open = false;
         bool triclinic = false;                      // a triclinic box takes runs (mgpu_chain_run_set_triclinic; needs tri_moves)
+        bool wide = false;                           // runs take types of 6..63 sites (mgpu_chain_run_set_wide: the WIDE instances)
         int replica = -1, k = 0;
         double t_step = 0.0, r_step = 0.0, temperature = 0.0;
         bool fast = false;                           // every record so far admits the fast fold

@@ -101,6 +101,78 @@ static_assert(sizeof(BoxDev) + sizeof(ChainArgs) + 160 <= 4096, "a window must f
 // TRI: triclinic box -- the pair role runs the register-site sweeps with ComputeDistance's image search (the batched path's
 // kernels for such boxes: the same sums); everything else of a window is the same (the phase tables take the box's reciprocal
 // matrix either way).
+// ---- what the WIDE instances of the three kernels share for a row of a molecule of more than kMaxFusedSitesWide sites: where a
+// pair wave's row and slabs lie, and the k role behind the candidate row.  The callers differ in where the row comes from (the
+// window's block, or the resident frames and the record's numbers) and in where A + delta goes.
+// dynamic LDS of the pair role behind the Coulomb table (wide_at): per wave a candidate row, a site slab and a type slab
+struct WidePairLds { double *cand, *w_site; int *w_sty; };
+__device__ __forceinline__ WidePairLds wide_pair_lds(char *s_dyn, int wide_at, int wave) {
+    double *slab = reinterpret_cast<double *>(s_dyn + wide_at);
+    return {slab + (size_t)wave * kFarmWideSites * 3, slab + (size_t)kPairWaves * kFarmWideSites * 3 + (size_t)wave * kSiteChunk * 4,
+            reinterpret_cast<int *>(slab + (size_t)kPairWaves * (kFarmWideSites * 3 + kSiteChunk * 4)) + wave * kSiteChunk};
+}
+// The k role behind the row (every thread of the workgroup; the row's writers have not synchronised yet): the sweep of the
+// type's form -- row form, vector wide form or untiled matrix-unit wide form -- reading A and storing A + delta into A_other
+// (STORE: recip_rows_pass's store mode), the intra term of an insertion / deletion (`intra`: pit's molecule) on the spare waves
+// meanwhile -- one thread up to kIntraThreadMax sites, one wave above: launch_intra's rule -- and the energies into *res.
+// Dynamic LDS: kFarmKFront bytes of row and intra tiles, the form's tables behind them.
+template <int STORE>
+__device__ __forceinline__ void wide_k_sweep(const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q, const int *trj,
+                                             const double2 *tw, int n_tasks, const RecipRow *rows, int n_rows, const int *row_first,
+                                             int form, int rpt, int nss, double2 *A, double2 *A_other, const RecipItem &it, bool intra,
+                                             const PairItem &pit, ChainResult *res, char *s_dyn, double *s_red, int tid) {
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n1 = tp.n1[it.t];
+    double *cand = reinterpret_cast<double *>(s_dyn);
+    double4 *intra_a = reinterpret_cast<double4 *>(s_dyn + (size_t)kFarmWideSites * 3 * sizeof(double)), *intra_b = intra_a + kFarmWideSites;
+    double2 *tabs = reinterpret_cast<double2 *>(s_dyn + kFarmKFront);
+    __syncthreads();
+    const bool active = tid < kBlock;
+    // ComputeIntraResidueRealCoulombEnergySingleMol of the inserted (candidate row) / deleted (resident) molecule
+    auto spare = [&] {
+        if (!intra) return;
+        if (n1 <= kIntraThreadMax) {
+            if (tid == kBlock)
+                __hip_atomic_store(&res->intra, intra_energy(tp, bx, pos, res_q, pit, cand, kFarmWideSites), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        } else if (wave == kWavesPerBlock) {
+            const double u = intra_energy_wave<kFarmWideSites>(tp, bx, pos, res_q, pit, cand, kFarmWideSites, lane, intra_a, intra_b, [] {
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            });
+            if (lane == 0) __hip_atomic_store(&res->intra, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    };
+    double acc = 0.0, acc0 = 0.0;
+    if (form == kFarmFormRows) {
+        const RecipLds v = recip_lds_view(tp, bx, it, n_rows, tabs);
+        RecipInFlight<kRecipTaskChunk> inflight;
+        recip_rows_tables(tp, bx, pos, res_q, rows, n_rows, it, cand, v, tid, active,
+                          [&] { recip_rows_prefetch<false>(inflight, trj, tw, n_tasks, A, tid); });
+        if (active) recip_rows_pass<false, true, kRecipTaskChunk, STORE>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0, A_other);
+        else spare();
+    } else if (form == kFarmFormWideMfma) {
+        recip_wide_sweep<false, true, true, false, STORE>(tp, bx, pos, res_q, trj, tw, rows, row_first, n_rows, 0, nss, A, it, cand, nullptr,
+                                                          n_tasks, tabs, tid, active, acc, acc0, A_other, spare);
+    } else {
+        recip_wide_sweep<false, true, false, false, STORE>(tp, bx, pos, res_q, trj, tw, rows, row_first, n_rows, rpt, nss, A, it, cand, nullptr,
+                                                           n_tasks, tabs, tid, active, acc, acc0, A_other, spare);
+    }
+    if (active) {
+        acc = wave_sum(acc);
+        acc0 = wave_sum(acc0);
+        if (lane == 0) { s_red[2 * wave] = acc; s_red[2 * wave + 1] = acc0; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double u = 0.0, u0 = 0.0;
+        for (int wv = 0; wv < kWavesPerBlock; ++wv) { u += s_red[2 * wv]; u0 += s_red[2 * wv + 1]; }
+        __hip_atomic_store(&res->u_new, u * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ewald_energy.f90:272
+        __hip_atomic_store(&res->u_old, u0 * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
 // ---- the WIDE instances' pieces for a row of a molecule of more than kMaxFusedSitesWide sites (farm_wide_pair_unit and
 // farm_wide_k_role are their models; here the row comes from the window's block and A + delta goes to the row's own buffer)
 // One pair work unit (entry, split) by ONE WAVE: the candidate row copied into the wave's row in dynamic LDS, then
@@ -108,10 +180,9 @@ static_assert(sizeof(BoxDev) + sizeof(ChainArgs) + 160 <= 4096, "a window must f
 __device__ __forceinline__ void chain_wide_pair_unit(const Topo &tp, const BoxDev &bx, const double *pos, const int *nmol, const double *res_q,
                                                      const int *res_atype, const double2 *pair_tab, const ChainArgs &g, int c, bool is_new,
                                                      int split, char *s_dyn, const double2 *s_pair, int wave, int lane, int w) {
-    double *slab = reinterpret_cast<double *>(s_dyn + g.wide_at);
-    double *cand = slab + (size_t)wave * kFarmWideSites * 3;
-    double *w_site = slab + (size_t)kPairWaves * kFarmWideSites * 3 + (size_t)wave * kSiteChunk * 4;
-    int *w_sty = reinterpret_cast<int *>(slab + (size_t)kPairWaves * (kFarmWideSites * 3 + kSiteChunk * 4)) + wave * kSiteChunk;
+    const WidePairLds l = wide_pair_lds(s_dyn, g.wide_at, wave);
+    double *cand = l.cand, *w_site = l.w_site;
+    int *w_sty = l.w_sty;
     const int t = g.t[c], kind = g.kind[c];
     if (is_new) {
         if (lane < tp.n1[t]) {
@@ -135,65 +206,16 @@ __device__ __forceinline__ void chain_wide_pair_unit(const Topo &tp, const BoxDe
 __device__ __forceinline__ void chain_wide_k_role(const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q, const int *trj,
                                                   const double2 *tw, int n_tasks, const RecipRow *rows, int n_rows, double2 *A,
                                                   const ChainArgs &g, int c, char *s_dyn, double *s_red, int tid) {
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int t = g.t[c], kind = g.kind[c], link = g.link[c];
-    const int n1 = tp.n1[t];
     double *cand = reinterpret_cast<double *>(s_dyn);
-    double4 *intra_a = reinterpret_cast<double4 *>(s_dyn + (size_t)kFarmWideSites * 3 * sizeof(double)), *intra_b = intra_a + kFarmWideSites;
-    double2 *tabs = reinterpret_cast<double2 *>(s_dyn + kFarmKFront);
-    if (kind != 2 && tid < n1) {
+    if (kind != 2 && tid < tp.n1[t]) {
         const double *row = g.wide_sites + ((size_t)c * kFarmWideSites + tid) * 3;
         for (int d = 0; d < 3; ++d) cand[tid * 3 + d] = row[d];
     }
-    __syncthreads();
-    double2 *A_other = g.alt + (size_t)c * bx.n_slots;
     const RecipItem it{g.replica, t, g.m[c], kind, 0, 0, 0};
-    const bool active = tid < kBlock;
-    // ComputeIntraResidueRealCoulombEnergySingleMol of the inserted (candidate row) / deleted (resident) molecule
-    auto spare = [&] {
-        if (link == -2 || kind == 0) return;
-        const PairItem pit{g.replica, t, g.m[c], kind == 1 ? 0 : -1, 0};
-        if (n1 <= kIntraThreadMax) {
-            if (tid == kBlock)
-                __hip_atomic_store(&g.res[c].intra, intra_energy(tp, bx, pos, res_q, pit, cand, kFarmWideSites), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        } else if (wave == kWavesPerBlock) {
-            const double u = intra_energy_wave<kFarmWideSites>(tp, bx, pos, res_q, pit, cand, kFarmWideSites, lane, intra_a, intra_b, [] {
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            });
-            if (lane == 0) __hip_atomic_store(&g.res[c].intra, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    };
-    double acc = 0.0, acc0 = 0.0;
-    const int form = g.kform[t];
-    if (form == kFarmFormRows) {
-        const RecipLds v = recip_lds_view(tp, bx, it, n_rows, tabs);
-        RecipInFlight<kRecipTaskChunk> inflight;
-        recip_rows_tables(tp, bx, pos, res_q, rows, n_rows, it, cand, v, tid, active,
-                          [&] { recip_rows_prefetch<false>(inflight, trj, tw, n_tasks, A, tid); });
-        if (active) recip_rows_pass<false, true, kRecipTaskChunk, 2>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0, A_other);
-        else spare();
-    } else if (form == kFarmFormWideMfma) {
-        recip_wide_sweep<false, true, true, false, 2>(tp, bx, pos, res_q, trj, tw, rows, g.row_first, n_rows, 0, g.wide_nss[t], A, it, cand,
-                                                      nullptr, n_tasks, tabs, tid, active, acc, acc0, A_other, spare);
-    } else {
-        recip_wide_sweep<false, true, false, false, 2>(tp, bx, pos, res_q, trj, tw, rows, g.row_first, n_rows, g.wide_rpt[t], g.wide_nss[t], A,
-                                                       it, cand, nullptr, n_tasks, tabs, tid, active, acc, acc0, A_other, spare);
-    }
-    if (active) {
-        acc = wave_sum(acc);
-        acc0 = wave_sum(acc0);
-        if (lane == 0) { s_red[2 * wave] = acc; s_red[2 * wave + 1] = acc0; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double u = 0.0, u0 = 0.0;
-        for (int wv = 0; wv < kWavesPerBlock; ++wv) { u += s_red[2 * wv]; u0 += s_red[2 * wv + 1]; }
-        __hip_atomic_store(&g.res[c].u_new, u * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ewald_energy.f90:272
-        __hip_atomic_store(&g.res[c].u_old, u0 * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const PairItem pit{g.replica, t, g.m[c], kind == 1 ? 0 : -1, 0};
+    wide_k_sweep<2>(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, g.row_first, g.kform[t], g.wide_rpt[t], g.wide_nss[t], A,
+                    g.alt + (size_t)c * bx.n_slots, it, link != -2 && kind != 0, pit, g.res + c, s_dyn, s_red, tid);
 }
 
 // WIDE: a window that carries a row of a molecule of 6..63 sites (orthorhombic boxes).  Such a row's pair
@@ -635,10 +657,9 @@ __device__ __forceinline__ void farm_wide_pair_unit(const Topo &tp, const BoxDev
                                                     const int *res_atype, const double2 *pair_tab, const FarmArgs &g, const FarmRec &rec,
                                                     int kind, int ent, int split, int ns, char *s_dyn, const double2 *s_pair, int wave, int lane,
                                                     int wg) {
-    double *slab = reinterpret_cast<double *>(s_dyn + g.wide_at);
-    double *cand = slab + (size_t)wave * kFarmWideSites * 3;
-    double *w_site = slab + (size_t)kPairWaves * kFarmWideSites * 3 + (size_t)wave * kSiteChunk * 4;
-    int *w_sty = reinterpret_cast<int *>(slab + (size_t)kPairWaves * (kFarmWideSites * 3 + kSiteChunk * 4)) + wave * kSiteChunk;
+    const WidePairLds l = wide_pair_lds(s_dyn, g.wide_at, wave);
+    double *cand = l.cand, *w_site = l.w_site;
+    int *w_sty = l.w_sty;
     if (ent == 1) {
         const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
         if (lane < tp.n1[rec.t]) {
@@ -662,70 +683,20 @@ template <bool RSV>
 __device__ __forceinline__ void farm_wide_k_role(const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q, const int *trj,
                                                  const double2 *tw, int n_tasks, const RecipRow *rows, int n_rows, double2 *A_base,
                                                  const FarmArgs &g, const FarmRec &rec, int c, int acur, char *s_dyn, double *s_red, int tid) {
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
-    const int n1 = tp.n1[rec.t];
     double *cand = reinterpret_cast<double *>(s_dyn);
-    double4 *intra_a = reinterpret_cast<double4 *>(s_dyn + (size_t)kFarmWideSites * 3 * sizeof(double)), *intra_b = intra_a + kFarmWideSites;
-    double2 *tabs = reinterpret_cast<double2 *>(s_dyn + kFarmKFront);
-    if (kind != 2 && tid < n1) {
+    if (kind != 2 && tid < tp.n1[rec.t]) {
         const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
         double off[3];
         trial_offset<RSV>(tp, f, rec.replica, rec.t, tid, off);
         for (int d = 0; d < 3; ++d) cand[tid * 3 + d] = f.com[d] + off[d];
     }
-    __syncthreads();
     double2 *A = (acur ? g.A_alt : A_base) + (size_t)rec.replica * bx.n_slots;
     double2 *A_other = (acur ? A_base : g.A_alt) + (size_t)rec.replica * bx.n_slots;
     const RecipItem it{rec.replica, rec.t, kind == 1 ? -1 : rec.m, kind, 0, 0, 0};
-    const bool active = tid < kBlock;
-    // ComputeIntraResidueRealCoulombEnergySingleMol of the inserted (candidate row) / deleted (resident) molecule, in the form
-    // launch_intra gives its size: one thread up to kIntraThreadMax sites, one wave above
-    auto spare = [&] {
-        if (kind == 0) return;
-        const PairItem pit{rec.replica, rec.t, rec.m, kind == 1 ? 0 : -1, 0};
-        if (n1 <= kIntraThreadMax) {
-            if (tid == kBlock)
-                __hip_atomic_store(&g.res[c].intra, intra_energy(tp, bx, pos, res_q, pit, cand, kFarmWideSites), __ATOMIC_RELAXED,
-                                   __HIP_MEMORY_SCOPE_AGENT);
-        } else if (wave == kWavesPerBlock) {
-            const double u = intra_energy_wave<kFarmWideSites>(tp, bx, pos, res_q, pit, cand, kFarmWideSites, lane, intra_a, intra_b, [] {
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-            });
-            if (lane == 0) __hip_atomic_store(&g.res[c].intra, u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    };
-    double acc = 0.0, acc0 = 0.0;
-    const int form = g.kform[rec.t];
-    if (form == kFarmFormRows) {
-        const RecipLds v = recip_lds_view(tp, bx, it, n_rows, tabs);
-        RecipInFlight<kRecipTaskChunk> inflight;
-        recip_rows_tables(tp, bx, pos, res_q, rows, n_rows, it, cand, v, tid, active,
-                          [&] { recip_rows_prefetch<false>(inflight, trj, tw, n_tasks, A, tid); });
-        if (active) recip_rows_pass<false, true, kRecipTaskChunk, 1>(v, trj, tw, n_tasks, A, tid, inflight, acc, acc0, A_other);
-        else spare();
-    } else if (form == kFarmFormWideMfma) {
-        recip_wide_sweep<false, true, true, false, 1>(tp, bx, pos, res_q, trj, tw, rows, g.row_first, n_rows, 0, g.wide_nss[rec.t], A, it, cand,
-                                                      nullptr, n_tasks, tabs, tid, active, acc, acc0, A_other, spare);
-    } else {
-        recip_wide_sweep<false, true, false, false, 1>(tp, bx, pos, res_q, trj, tw, rows, g.row_first, n_rows, g.wide_rpt[rec.t],
-                                                       g.wide_nss[rec.t], A, it, cand, nullptr, n_tasks, tabs, tid, active, acc, acc0, A_other,
-                                                       spare);
-    }
-    if (active) {
-        acc = wave_sum(acc);
-        acc0 = wave_sum(acc0);
-        if (lane == 0) { s_red[2 * wave] = acc; s_red[2 * wave + 1] = acc0; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double u = 0.0, u0 = 0.0;
-        for (int wv = 0; wv < kWavesPerBlock; ++wv) { u += s_red[2 * wv]; u0 += s_red[2 * wv + 1]; }
-        __hip_atomic_store(&g.res[c].u_new, u * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ewald_energy.f90:272
-        __hip_atomic_store(&g.res[c].u_old, u0 * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const PairItem pit{rec.replica, rec.t, rec.m, kind == 1 ? 0 : -1, 0};
+    wide_k_sweep<1>(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, g.row_first, g.kform[rec.t], g.wide_rpt[rec.t], g.wide_nss[rec.t],
+                    A, A_other, it, kind != 0, pit, g.res + c, s_dyn, s_red, tid);
 }
 
 // (launch bounds: four waves per SIMD = two of these 8-wave workgroups per CU, i.e. at most 128 VGPRs.  Left to itself
@@ -968,8 +939,9 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI 
 // switched both device-built moves and triclinic runs on (mgpu_chain_run_set_triclinic).  TRI changes what it changes in
 // farm_window_kernel and nothing else: every role and the commit build the candidate with the triclinic form of trial_frame
 // (trial_com_triclinic's centre, wrapped always), and the pair role runs the register-site sweep with ComputeDistance's
-// image search; no flat form, no fast fold.  No WIDE or RSV instance exists (capacity 0).  The instances in all: four
-// <FLAT, FASTW>, <false, false, true>, and the grand-canonical form of each of the five (GC = true, below): ten.
+// image search; no flat form, no fast fold.  No RSV instance exists (capacity 0).  The instances in all: four
+// <FLAT, FASTW>, <false, false, true>, the grand-canonical form of each of the five (GC = true, below): ten; and the WIDE form
+// of the eight orthorhombic ones (molecules of 6 to 63 sites: above the kernel): eighteen.
 // GC (mgpu_chain_run_set_gc, boxes without reservoirs: <FLAT, FASTW, false, true> for an orthorhombic box, <false, false, true,
 // true> for a triclinic one whose engine has triclinic runs on): the run of a grand-canonical block.  Which molecule a step
 // picks and its prefactor depend on the molecule count, i.e. on the outcome of the steps before it, so the driver pushes
@@ -1020,16 +992,35 @@ struct ChainRunArgs {
     // parallel to `ring`, and ewald_self per residue type
     const double2 *gc_ring;                      // device [ring_steps]
     double self_of_type[kMaxRes];
+    // the WIDE instances only (behind everything the others read; ChainArgs has the same): the rows' first tasks, where the pair
+    // role's slabs start in dynamic LDS, per residue type the k role's form and its tile
+    const int *row_first;
+    int wide_at;                                 // bytes: the Coulomb table's, rounded up to 16
+    signed char kform[kMaxRes];                  // kFarmForm*
+    int wide_rpt[kMaxRes];                       // vector form: rows per tile
+    int wide_nss[kMaxRes];                       // site-states per tile (the layout of the form's tables)
 };
 static_assert(sizeof(BoxDev) + sizeof(ChainRunArgs) + 160 <= 4096, "a chain-run launch must fit the kernel-argument segment");
 
-template <bool FLAT, bool FASTW, bool TRI = false, bool GC = false>
+// WIDE (mgpu_chain_run_set_wide, orthorhombic boxes without reservoirs: <FLAT, FASTW, false, GC, true>): the instances a run
+// launches when an active type of the engine has 6..63 sites -- the choice is the run's, not the launch's: which records a launch
+// consumes is known on the device alone.  A step of such a type takes farm_window_kernel<..., WIDE>'s front end and
+// chain_window_kernel<..., WIDE>'s k role: its pair units rebuild the candidate row from the frames into the wave's row in dynamic
+// LDS behind the Coulomb table and run the LDS-staged NS = 0 sweep with the engine's nsplit (farm_wide_pair_unit's calls); its k
+// workgroup rebuilds the row into the kFarmKFront bytes in front of the tables and runs the form of the row's own type
+// (wide_k_sweep<2>: A + delta into g.alt + c n_slots with `sc1` stores, which the commit copies), with the intra term of an
+// insertion / deletion (GC) on the spare waves.  Steps of <= kMaxFusedSitesWide sites in the same launch take the narrow
+// instance's code.  Cursor, records, by-count completion, ticket, hand-offs, resolver, stall and force, and the commit wave (lane <
+// n1: one wave up to 63 sites) are the same code; what differs is the row's stride and where it lies.  No WIDE sweep has the image
+// search: no TRI form.
+template <bool FLAT, bool FASTW, bool TRI = false, bool GC = false, bool WIDE = false>
 __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
     double2 *__restrict__ A_base, const ChainRunArgs g) {
     static_assert(!TRI || (!FLAT && !FASTW), "the image search has no flat form and no fast fold (farm_window_kernel's triclinic family)");
+    static_assert(!(WIDE && TRI), "no WIDE sweep has the image search");
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];      // Coulomb table | phase tables | partials staging
     __shared__ double2 s_pair[kMaxTypes * kMaxTypes];
     __shared__ int4 s_grp[kMaxGrp];
@@ -1115,6 +1106,20 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             if constexpr (GC) kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
             bool build = tid < n1;
             if constexpr (GC) build = build && kind != 2;
+            if (WIDE && n1 > kMaxFusedSitesWide) {
+                // (farm_wide_k_role's front, chain_wide_k_role's back: the row from the frames, A + delta into the step's buffer)
+                if (build) {
+                    const auto f = trial_frame<false>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                    double off[3];
+                    trial_offset<false>(tp, f, g.replica, rec.t, tid, off);
+                    for (int d = 0; d < 3; ++d) reinterpret_cast<double *>(s_dyn)[tid * 3 + d] = f.com[d] + off[d];
+                }
+                const RecipItem it{g.replica, rec.t, kind == 1 ? -1 : rec.m, kind, 0, 0, 0};
+                const PairItem pit{g.replica, rec.t, rec.m, kind == 1 ? 0 : -1, 0};
+                wide_k_sweep<2>(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, g.row_first, g.kform[rec.t], g.wide_rpt[rec.t],
+                                g.wide_nss[rec.t], A_base + (size_t)g.replica * bx.n_slots, g.alt + (size_t)c * bx.n_slots, it, kind != 0,
+                                pit, g.res + c, s_dyn, s_red, tid);
+            } else {
             if (build) {
                 const auto f = trial_frame<false, TRI>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                 double off[3];
@@ -1152,6 +1157,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
                 __hip_atomic_store(&g.res[c].u_new, u * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ewald_energy.f90:272
                 __hip_atomic_store(&g.res[c].u_old, u0 * kEps0InvEvA / kKbEvK * kTwoPi / bx.volume, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
+            }
         }
     } else {
         // ---------------- pair role: one wave per (step, entry, split); entry 0 = the resident molecule, 1 = the candidate
@@ -1168,7 +1174,10 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             const RunRec &rec = s_rec[c];
             const int ent = j / ns, split = j - ent * ns;
             const int n1 = tp.n1[rec.t];
-            double *cand = &s_cand[wave][0];
+            const bool wide_row = WIDE && n1 > kMaxFusedSitesWide;
+            WidePairLds wl{nullptr, nullptr, nullptr};
+            if constexpr (WIDE) wl = wide_pair_lds(s_dyn, g.wide_at, wave);
+            double *cand = wide_row ? wl.cand : &s_cand[wave][0];
             if (ent == 1) {
                 const auto f = trial_frame<false, TRI>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                 if (lane < n1) {
@@ -1182,6 +1191,11 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             // old state: the resident molecule; new state: the candidate row; an insertion excludes nothing
             PairItem it{g.replica, rec.t, rec.m, ent == 1 ? 0 : -1, 0};
             if constexpr (GC) { if (kind_w == 1) it.m = -1; }
+            if (wide_row) {
+                // (farm_wide_pair_unit's sweep: the batched path's NS = 0 kernel of the unit, the wave's slabs)
+                pair_sweep_item<0, false, false, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, wl.w_site,
+                                                                     wl.w_sty, it, cand, kFarmWideSites, split, ns, lane, g.partials, wg);
+            } else {
 #define MGPU_RUN_PAIR(NS)                                                                                                \
             do {                                                                                                         \
                 if constexpr (FLAT)                                                                                      \
@@ -1199,6 +1213,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
                 default: MGPU_RUN_PAIR(5); break;
             }
 #undef MGPU_RUN_PAIR
+            }
         }
     }
 

@@ -141,7 +141,9 @@ void window_types_build(mgpu_engine *e) {
 //     kMaxFusedSitesWide sites unless the path has WIDE instances, they are on and windows take the type), a Coulomb table or a
 //     resolver beyond 64 KiB, WIDE LDS beyond its budget;
 //   farm windows and chain runs: a triclinic box whose engine has not switched device-built moves on;
-//   chain runs (no such instance of chain_run_kernel exists): reservoirs, and a triclinic box unless triclinic runs are on.
+//   chain runs (no such instance of chain_run_kernel exists): reservoirs, and a triclinic box unless triclinic runs are on; a type
+//     of more than kMaxFusedSitesWide sites unless WIDE runs are on (mgpu_chain_run_set_wide: refused for a triclinic box and for
+//     an engine with a reservoir, so the WIDE instances meet neither).
 //     (Grand-canonical runs, mgpu_chain_run_set_gc, are admitted exactly where runs are: the switch is refused for a triclinic box
 //     whose triclinic runs are off and for an engine with a reservoir, and the GC instances' dynamic LDS is window_lds_bytes(kPathRun, ...) -- their k role, pair
 //     role and resolver stage what the NVT instances stage; what they add is 16 double2 of static LDS.)
@@ -152,7 +154,7 @@ struct WindowAdmission {
 };
 static WindowAdmission window_admission(const mgpu_engine *e, WindowPath path) {
     const mgpu_engine::WindowTypes &w = e->win;
-    const bool wide_on = path == kPathFarm || (path == kPathChain && e->chain.wide);
+    const bool wide_on = path == kPathFarm || (path == kPathChain && e->chain.wide) || (path == kPathRun && e->run.wide);
     WindowAdmission a;
     bool ok = true, wide = false;
     for (int t = 0; t < e->tp.n_res; ++t) {
@@ -195,7 +197,7 @@ static void wide_args(const mgpu_engine *e, const int **row_first, int *wide_at,
 // Beyond 64 KiB of dynamic LDS a kernel opts in (gfx950: up to 160 KiB per workgroup); only the WIDE instances get here.  The
 // limit belongs to the kernel function, not to an engine: the most each family has asked for on each device is kept for the
 // whole process, and only a larger size sets the attribute again.  each(f) calls f(kernel) for every instance of the family.
-enum LdsFamily { kLdsChainWide, kLdsFarmWide, kLdsFamilies };
+enum LdsFamily { kLdsChainWide, kLdsFarmWide, kLdsRunWide, kLdsFamilies };
 static std::mutex g_lds_opt_mu;
 static std::map<int, size_t> g_lds_opted[kLdsFamilies];       // [family][device]
 template <class Each>
@@ -692,8 +694,19 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     size_t k_rows = 0;
     for (int t = 0; t < e->tp.n_res; ++t)
         if (e->is_active[t]) k_rows = std::max(k_rows, e->win.k_lds[t]);
-    const size_t lds = window_lds(e, kPathRun, false, k_rows, rn.k);
-    if (!window_lds_fits(false, lds)) return set_error(MGPU_ERR_CAPACITY, "chain_run_launch: the launch does not fit the LDS budget");
+    // the WIDE instances when any active type has more than kMaxFusedSitesWide sites: the run's choice, not the launch's (which
+    // records a launch consumes is known on the device alone)
+    bool wide = false;
+    for (int t = 0; t < e->tp.n_res; ++t) wide = wide || (e->is_active[t] && e->win.take[t] == kWindowWide);
+    const size_t lds = window_lds(e, kPathRun, wide, k_rows, rn.k);
+    if (!window_lds_fits(wide, lds)) return set_error(MGPU_ERR_CAPACITY, "chain_run_launch: the launch does not fit the LDS budget");
+    auto wide_family = [](auto &&f, auto FLAT, auto FASTW, auto GC) {
+        f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, decltype(GC)::value, true>);
+    };
+    if (wide && (rc = lds_opt_in(e->device, kLdsRunWide, lds, [&](auto &&f) {
+             for_all_bools([&](auto... flags) { wide_family(f, flags...); }, std::integral_constant<int, 3>{});
+         })))
+        return rc;
     ChainRunArgs g{};
     rn.seq += 1;
     g.state = rn.d_state; g.ring = rn.d_ring; g.partials = rn.d_part; g.res = rn.d_res; g.ticket = rn.d_ticket; g.alt = rn.d_alt;
@@ -708,13 +721,15 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
         g.gc_ring = rn.d_gc;
         for (int tt = 0; tt < e->tp.n_res; ++tt) g.self_of_type[tt] = e->self_of_type[tt];
     }
+    if (wide) wide_args(e, &g.row_first, &g.wide_at, g.kform, g.wide_rpt, g.wide_nss);
     const int grid = (rn.k * 2 * nsplit + kPairWaves - 1) / kPairWaves + rn.k;
     const bool ff = rn.fast && e->pair_fast_fold;
     ln.dirty = true;
     ln.forget_trial();
     alt_forget(e, rn.replica);
     // The run kernel's families: with the image search (no flat form, no fast fold: farm_window_kernel's triclinic family), the
-    // orthorhombic one, whose flags are free, and the grand-canonical forms of both (the run was opened with the switch on).
+    // orthorhombic one, whose flags are free, and the grand-canonical forms of both (the run was opened with the switch on); the
+    // WIDE family above (orthorhombic, NVT and grand-canonical) for an engine with an active type of 6..63 sites.
     auto tri_family = [](auto &&f) { f(chain_run_kernel<false, false, true>); };
     auto ortho_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); };
     auto gc_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, true>); };
@@ -722,6 +737,7 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
     if (e->bx.triclinic && rn.gc) tri_gc_family(launch);
     else if (e->bx.triclinic) tri_family(launch);
+    else if (wide) with_bools([&](auto... flags) { wide_family(launch, flags...); }, e->pair_flat, ff, rn.gc);
     else if (rn.gc) with_bools([&](auto... flags) { gc_family(launch, flags...); }, e->pair_flat, ff);
     else with_bools([&](auto... flags) { ortho_family(launch, flags...); }, e->pair_flat, ff);
     HIP_TRY(hipGetLastError());
@@ -746,6 +762,17 @@ int mgpu_chain_run_set_triclinic(mgpu_engine *e, int on) {
     // (grand-canonical runs of a triclinic box stand on this switch: mgpu_chain_run_set_gc)
     if (!on && e->run.gc) return set_error(MGPU_ERR_STATE, "chain_run_set_triclinic: grand-canonical runs are on (mgpu_chain_run_set_gc)");
     e->run.triclinic = on != 0;
+    return MGPU_OK;
+}
+
+int mgpu_chain_run_set_wide(mgpu_engine *e, int on) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    // every refusal leaves the switch as it was
+    if (e->run.open) return set_error(MGPU_ERR_STATE, "chain_run_set_wide: a run is open");
+    if (on && e->bx.triclinic)
+        return set_error(MGPU_ERR_STATE, "chain_run_set_wide: the box is triclinic (no WIDE sweep has the image search)");
+    if (on && e->rsv_any) return set_error(MGPU_ERR_STATE, "chain_run_set_wide: the engine holds a reservoir (no RSV instance of the run kernel)");
+    e->run.wide = on != 0;
     return MGPU_OK;
 }
 

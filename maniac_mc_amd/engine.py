@@ -309,6 +309,12 @@ class Engine:
         check(self.L.mgpu_chain_run_push(self.h, C.c_int(n), _i(t), _i(m), _i(move), _d(u), _d(au)))
         return n
 
+    def chain_run_set_wide(self, on=True):
+        """mgpu_chain_run_set_wide: the engine's runs also take rigid molecules of 6 to 63 sites (off by default: such an
+        engine reports capacity 0).  Refused (MgpuError, the switch unchanged) while a run is open, and switching it on for a
+        triclinic box or an engine with a reservoir.  Works with chain_run_set_gc / chain_run_push_gc."""
+        check(self.L.mgpu_chain_run_set_wide(self.h, C.c_int(1 if on else 0)))
+
     def chain_run_set_gc(self, on=True):
         """mgpu_chain_run_set_gc: the engine's runs are those of a grand-canonical block (off by default): by-count records
         through chain_run_push_gc.  Refused (MgpuError, the switch unchanged) for a triclinic box unless

@@ -357,6 +357,13 @@ module maniac_gpu
             integer(c_int), value :: on
             integer(c_int) :: rc
         end function
+        ! runs of rigid molecules of 6 to 63 sites (off by default; refused for a triclinic box, with a reservoir, while a run is open)
+        function mgpu_chain_run_set_wide(e, on) bind(C, name="mgpu_chain_run_set_wide") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: on
+            integer(c_int) :: rc
+        end function
         function mgpu_chain_run_push_gc(e, n, t, move, u5, accept_u, sel_u, phi_v) bind(C, name="mgpu_chain_run_push_gc") result(rc)
             import :: c_ptr, c_int, c_double
             type(c_ptr), value :: e

@@ -1291,7 +1291,8 @@ contains
     ! How many numbers a step draws depends on the molecule count at its edges (pick_molecule_index draws nothing for an empty type,
     ! the moves and the deletion return early for one, CheckMoleculeIndex aborts a creation into a full one), so a record is drawn
     ! AHEAD OF THE OUTCOMES before it only while no count can reach an edge: with count_t from the verdicts collected so far and
-    ! I_t / D_t the insertion / deletion records pushed and not yet collected, count_t - D_t >= 1 and
+    ! I_t / D_t the insertion / deletion records pushed and not yet collected, count_t - D_t >= 1 (>= 2 for a type of more than one
+    ! site: ahead_ok) and
     ! count_t + I_t <= min(cap_t, NB_MAX_MOLECULE) - 1 for EVERY active type.  Where the rule fails with records outstanding they are
     ! collected first; where it fails with none, the run is closed, the mirror refreshed, steps go through the window path until it
     ! holds again (at least one; counted in run_fallback), the frames are uploaded and the run reopened.
@@ -1406,6 +1407,10 @@ contains
             do tt = 1, S%n_res
                 if (S%res(tt)%active /= 1) cycle
                 if (S%res(tt)%count - n_del(tt) < 1) ok = .false.
+                ! a type of more than one site keeps its LAST molecule for the window path: an insertion copies the geometry the
+                ! mirror holds in slot 1 (propose_step), which for an emptied type is the deleted molecule's as it was last moved --
+                ! the window path's mirror has it, refresh_frames cannot ask the engine for the frame of an empty type
+                if (S%res(tt)%n1 /= 1 .and. S%res(tt)%count - n_del(tt) < 2) ok = .false.
                 if (S%res(tt)%count + n_ins(tt) > min(S%res(tt)%cap, NB_MAX_MOLECULE) - 1) ok = .false.
             end do
         end function ahead_ok

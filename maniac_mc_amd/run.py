@@ -122,7 +122,7 @@ WIDE_CHAIN_WINDOWS_DEFAULT = False
 def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoir_path=None, device=0,
                    mol_capacity=None, nb_block=None, nb_step=None, seams=False, as_written=False, speculate=4,
                    chain_windows=True, chain_margin=None, wide_chain_windows=WIDE_CHAIN_WINDOWS_DEFAULT, chain_run=None,
-                   chain_run_triclinic=False, chain_run_gcmc=False):
+                   chain_run_triclinic=False, chain_run_gcmc=False, chain_run_wide=False):
     """Run the chain; returns a dict with the final energies (K), counters, molecule counts, step sizes.
 
     ``seed``: None -> the input file's ``seed`` if present, else the generator is left unseeded
@@ -164,6 +164,10 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     input unless ``chain_run_triclinic`` is given as well: it takes both switches, and either alone leaves it its windows.  False
     (default): a grand-canonical input keeps its windows whatever ``chain_run`` says.  ValueError without ``chain_run``.
     ``chain_run`` in the result gains ``gcmc`` and ``fallback_steps``.
+    ``chain_run_wide``: True (with ``chain_run``) -> an input with rigid molecules of 6 to 63 sites runs its blocks as chain runs
+    too (Engine.chain_run_set_wide), NVT or -- with ``chain_run_gcmc`` -- grand-canonical.  Same files as the windows.  Runs with
+    ``as_written`` or a reservoir and triclinic inputs keep their windows (``on`` False).  False (default): such an input keeps
+    its windows whatever ``chain_run`` says.  ValueError without ``chain_run``.
     """
     system, inp, dat = io_maniac.load_system(maniac_path, data_path, inc_path, with_data=True)
     rdat = io_maniac.read_lammps_data(reservoir_path, inp) if reservoir_path else None
@@ -175,10 +179,14 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
         raise ValueError("chain_run_triclinic needs chain_run=(k, depth)")
     if chain_run_gcmc and chain_run is None:
         raise ValueError("chain_run_gcmc needs chain_run=(k, depth)")
+    if chain_run_wide and chain_run is None:
+        raise ValueError("chain_run_wide needs chain_run=(k, depth)")
     run_tri = bool(chain_run_triclinic) and not seams and system.is_triclinic()
     eng = Engine.from_system(system, n_replicas=1, device=device, mol_capacity=mol_capacity, triclinic_moves=run_tri)
     if run_tri:
         eng.chain_run_set_triclinic(True)
+    if chain_run_wide and not seams and not as_written and rdat is None and not system.is_triclinic():
+        eng.chain_run_set_wide(True)
     if chain_margin is not None:
         eng.chain_set_margin(float(chain_margin))
     H = fortran_host.lib()
@@ -270,6 +278,9 @@ def main(argv=None):
     ap.add_argument("--chain-run-gcmc", dest="chain_run_gcmc", action="store_true",
                     help="with --chain-run: a grand-canonical input's blocks are chain runs too (off by default: such an input keeps its windows; "
                          "a triclinic grand-canonical input needs --chain-run-triclinic as well)")
+    ap.add_argument("--chain-run-wide", dest="chain_run_wide", action="store_true",
+                    help="with --chain-run: an input with rigid molecules of 6 to 63 sites runs its blocks as chain runs too (off by "
+                         "default: such an input keeps its windows; not for triclinic inputs, reservoirs or --as-written)")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
     ap.add_argument("--replicas", type=int, default=None,
@@ -289,6 +300,8 @@ def main(argv=None):
         ap.error("--chain-run-triclinic needs --chain-run K[,DEPTH]")
     if a.chain_run_gcmc and chain_run is None:
         ap.error("--chain-run-gcmc needs --chain-run K[,DEPTH]")
+    if a.chain_run_wide and chain_run is None:
+        ap.error("--chain-run-wide needs --chain-run K[,DEPTH]")
     if chain_run is not None and a.replicas is not None:
         ap.error("--chain-run is the single chain's mode: it cannot be combined with --replicas")
     if a.replicas is None:
@@ -322,7 +335,8 @@ def main(argv=None):
     res = run_simulation(a.maniac, a.data, a.inc, a.out, seed=a.seed, reservoir_path=a.reservoir, device=a.device,
                          as_written=a.as_written, speculate=a.speculate, chain_windows=not a.no_chain_windows,
                          wide_chain_windows=a.wide_chain_windows, chain_run=chain_run,
-                         chain_run_triclinic=a.chain_run_triclinic, chain_run_gcmc=a.chain_run_gcmc)
+                         chain_run_triclinic=a.chain_run_triclinic, chain_run_gcmc=a.chain_run_gcmc,
+                         chain_run_wide=a.chain_run_wide)
     e = res["energy"]
     print(f"final energy (K): total {e['total']:.6f}  non_coulomb {e['non_coulomb']:.6f}  coulomb {e['coulomb']:.6f}  "
           f"recip {e['recip_coulomb']:.6f};  molecules {res['n_mol'].tolist()};  output in {os.path.join(a.out, '')}")
