@@ -474,10 +474,21 @@ int mgpu_replica_set_num_molecules(mgpu_engine *e, int replica, int t, int n_mol
  * update (mgpu_recip_form: "rows", "wide-vector", "wide-mfma"), and mgpu_chain_window accepts their rows at the caller's
  * site_stride; a window with such a row reads its rows from pinned host memory (they do not fit the kernel's arguments).
  * Still 0 / MGPU_ERR_INVALID_ARG: molecules of 64 sites or more, the per-k and the tiled matrix-unit form, a triclinic box
- * with such an active type, a Coulomb table beyond 64 KiB.  Energies, decisions and committed state are those of the
- * batched path (mgpu_gcmc_trial_submit / wait, mgpu_commit_*), bit for bit, with the switch on or off. */
+ * with such an active type (unless mgpu_chain_set_wide_triclinic is on, below), a Coulomb table beyond 64 KiB.  Energies,
+ * decisions and committed state are those of the batched path (mgpu_gcmc_trial_submit / wait, mgpu_commit_*), bit for bit,
+ * with the switch on or off.
+ * mgpu_chain_set_wide_triclinic(e, 1): the single-chain one-launch paths -- these windows and the chain runs below, never the
+ * farm windows -- take rigid molecules of 6 to 63 sites in a TRICLINIC box (off at creation: every capacity, refusal and
+ * refusal text is then what it was).  With it on, mgpu_chain_set_wide(e, 1) gives such a box a capacity > 0 by the orthorhombic
+ * rule (plane-major, <= 63 sites, row form or an untiled wide form for the type alone), and mgpu_chain_run_set_wide(e, 1) is
+ * admitted for it.  Such a row's pair energy is ComputePairInteractionEnergy_singlemol (src/energy_utils.f90:381-446) through
+ * the LDS-staged sweep with ComputeDistance's image search (src/geometry_utils.f90:397-411), as the batched path sweeps it;
+ * a run's candidate is built with ApplyPBC's triclinic form (:167-220).  Site-major types, per-k and tiled forms, reservoirs
+ * (runs) and Coulomb tables over 64 KiB keep capacity 0.  MGPU_ERR_STATE, the switch unchanged: an orthorhombic box; a run
+ * open; on = 0 while mgpu_chain_run_set_wide is on (WIDE runs of a triclinic box stand on this switch).  Drains every lane. */
 int mgpu_chain_window_capacity(const mgpu_engine *e, int *max_candidates);
 int mgpu_chain_set_wide(mgpu_engine *e, int on);
+int mgpu_chain_set_wide_triclinic(mgpu_engine *e, int on);
 int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const int *m, const int *kind, const int *link,
                       const double *sites, int site_stride, const double *accept_u, const double *accept_pref,
                       double temperature, double recip_energy, double *old_energy, double *new_energy,
@@ -631,7 +642,9 @@ int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long lo
  *               src/ewald_energy.f90, for an insertion / deletion), bit for bit; smaller molecules in the same run are taken as
  *               before.  Admitted where the farm windows admit the type (plane-major types whose k form is one of the three and
  *               whose LDS fits); works with set_gc / push_gc.  MGPU_ERR_STATE, the switch unchanged: while a run is open; on = 1
- *               for a triclinic box (no WIDE sweep has the image search) and for an engine with a reservoir (no such instance).
+ *               for a triclinic box whose mgpu_chain_set_wide_triclinic is off (with it on the box is admitted -- its launches
+ *               are the instances with both the image search and the LDS-staged sweep -- and still needs set_triclinic for a
+ *               capacity > 0) and for an engine with a reservoir (no such instance).
  * An open run does not lock the engine: every synchronous entry point DRAINS it first -- it waits for the launches queued so
  * far and sees the state they committed; their results stay collectable -- and a submit on lane 0 is ordered behind them by
  * the stream.  Single-driver: one host thread at a time opens, pushes, launches, collects, forces and closes a run. */

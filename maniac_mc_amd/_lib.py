@@ -35,7 +35,7 @@ EXPORTS = [
     "mgpu_recip_energy_candidates", "mgpu_recip_form", "mgpu_pair_layout", "mgpu_self_energy", "mgpu_intra_energy_candidates",
     "mgpu_trial_energy_candidates", "mgpu_commit_candidates", "mgpu_trial_submit", "mgpu_trial_wait",
     "mgpu_commit_submit", "mgpu_lane_site_buffer", "mgpu_set_host_team", "mgpu_set_triclinic_moves", "mgpu_replica_set_frames", "mgpu_replica_get_frames", "mgpu_replica_set_reservoir", "mgpu_replica_get_reservoir", "mgpu_farm_snapshot_submit", "mgpu_farm_snapshot_wait", "mgpu_move_trial_submit", "mgpu_move_trial_decide_submit", "mgpu_gcmc_trial_decide_submit", "mgpu_trial_decide_wait", "mgpu_gcmc_trial_submit", "mgpu_gcmc_trial_wait", "mgpu_replica_replace_molecule",
-    "mgpu_replica_set_num_molecules", "mgpu_chain_window_capacity", "mgpu_chain_window", "mgpu_chain_set_margin", "mgpu_chain_set_wide",
+    "mgpu_replica_set_num_molecules", "mgpu_chain_window_capacity", "mgpu_chain_window", "mgpu_chain_set_margin", "mgpu_chain_set_wide", "mgpu_chain_set_wide_triclinic",
     "mgpu_chain_get_stats", "mgpu_chain_set_timing", "mgpu_chain_get_timing", "mgpu_farm_window_capacity", "mgpu_farm_window_submit",
     "mgpu_farm_window_wait", "mgpu_farm_window_flush", "mgpu_farm_window_get_stats",
     "mgpu_chain_run_capacity", "mgpu_chain_run_open", "mgpu_chain_run_push", "mgpu_chain_run_launch", "mgpu_chain_run_collect",

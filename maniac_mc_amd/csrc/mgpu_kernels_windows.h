@@ -36,8 +36,8 @@ namespace mgpu {
 // reciprocal energy is the creation-kind energy of row `link` (the molecule RemoveMolecule swaps into the slot) and an
 // accepted step adds THAT molecule's terms to A(k) while the coordinates lose slot m; row `link` itself is energy-only
 // (link = -2).  Row-form k sweep and molecules of <= kMaxFusedSitesWide sites (orthorhombic boxes, and triclinic ones through
-// the TRI instance); the WIDE instances (orthorhombic boxes) also take rows of molecules of up to kFarmWideSites - 1 = 63
-// sites, in the k form of the row's own type (see the kernel).
+// the TRI instance); the WIDE instances (orthorhombic boxes, and triclinic ones through the TRI x WIDE instance) also take rows
+// of molecules of up to kFarmWideSites - 1 = 63 sites, in the k form of the row's own type (see the kernel).
 // ------------------------------------------------------------------------------------------
 constexpr int kChainMaxCand = 16;
 #ifndef MGPU_FARM_WIDE_MINWAVES
@@ -176,7 +176,9 @@ __device__ __forceinline__ void wide_k_sweep(const Topo &tp, const BoxDev &bx, c
 // ---- the WIDE instances' pieces for a row of a molecule of more than kMaxFusedSitesWide sites (farm_wide_pair_unit and
 // farm_wide_k_role are their models; here the row comes from the window's block and A + delta goes to the row's own buffer)
 // One pair work unit (entry, split) by ONE WAVE: the candidate row copied into the wave's row in dynamic LDS, then
-// pair_sweep_item<0, ...> with the wave's slabs: the batched path's NS = 0 sweep of the unit, the engine's nsplit.
+// pair_sweep_item<0, ...> with the wave's slabs: the batched path's NS = 0 sweep of the unit, the engine's nsplit.  TRI: the
+// sweep with ComputeDistance's image search (pair_sweep_kernel<0, false, true>'s for such boxes).
+template <bool TRI>
 __device__ __forceinline__ void chain_wide_pair_unit(const Topo &tp, const BoxDev &bx, const double *pos, const int *nmol, const double *res_q,
                                                      const int *res_atype, const double2 *pair_tab, const ChainArgs &g, int c, bool is_new,
                                                      int split, char *s_dyn, const double2 *s_pair, int wave, int lane, int w) {
@@ -194,8 +196,8 @@ __device__ __forceinline__ void chain_wide_pair_unit(const Topo &tp, const BoxDe
     }
     // old state: the resident molecule; new state: the candidate row; an insertion excludes nothing
     const PairItem it{g.replica, t, kind == 1 ? -1 : g.m[c], is_new ? 0 : -1, 0};
-    pair_sweep_item<0, false, false, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, w_site, w_sty, it, cand,
-                                                         kFarmWideSites, split, g.nsplit, lane, g.partials, w);
+    pair_sweep_item<0, false, TRI, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, w_site, w_sty, it, cand,
+                                                       kFarmWideSites, split, g.nsplit, lane, g.partials, w);
 }
 
 // The k role of such a row c (every thread of the workgroup): the row into LDS, the sweep of the type's form -- row form,
@@ -218,7 +220,8 @@ __device__ __forceinline__ void chain_wide_k_role(const Topo &tp, const BoxDev &
                     g.alt + (size_t)c * bx.n_slots, it, link != -2 && kind != 0, pit, g.res + c, s_dyn, s_red, tid);
 }
 
-// WIDE: a window that carries a row of a molecule of 6..63 sites (orthorhombic boxes).  Such a row's pair
+// WIDE: a window that carries a row of a molecule of 6..63 sites (with TRI, mgpu_chain_set_wide_triclinic:
+// the NS = 0 sweep with the image search, everything else the same text -- the k forms take the box from bx).  Such a row's pair
 // units run the LDS-staged NS = 0 sweep (the batched path's kernel for the size, the engine's nsplit: the resolver's split-order
 // sum is the batched path's) with its candidate row and slabs in dynamic LDS behind the Coulomb table; its k role takes the
 // form of its own type, storing A + delta into the row's own buffer; its intra term runs on the k workgroup's spare waves.
@@ -313,7 +316,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_window_kernel(
             const PairItem it{g.replica, t, kind == 1 ? -1 : g.m[c], g.ent_new[ent] ? c : -1, 0};
             const int n1 = tp.n1[t];
             if (WIDE && n1 > kMaxFusedSitesWide) {
-                chain_wide_pair_unit(tp, bx, pos, nmol, res_q, res_atype, pair_tab, g, c, g.ent_new[ent] != 0, split, s_dyn, s_pair, wave, lane, w);
+                chain_wide_pair_unit<TRI>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, g, c, g.ent_new[ent] != 0, split, s_dyn, s_pair, wave, lane, w);
             } else {
 #define MGPU_CHAIN_PAIR(NS)                                                                                              \
             do {                                                                                                         \
@@ -1002,7 +1005,8 @@ struct ChainRunArgs {
 };
 static_assert(sizeof(BoxDev) + sizeof(ChainRunArgs) + 160 <= 4096, "a chain-run launch must fit the kernel-argument segment");
 
-// WIDE (mgpu_chain_run_set_wide, orthorhombic boxes without reservoirs: <FLAT, FASTW, false, GC, true>): the instances a run
+// WIDE (mgpu_chain_run_set_wide, boxes without reservoirs: <FLAT, FASTW, false, GC, true>, and for a triclinic box under
+// mgpu_chain_set_wide_triclinic <false, false, true, GC, true>): the instances a run
 // launches when an active type of the engine has 6..63 sites -- the choice is the run's, not the launch's: which records a launch
 // consumes is known on the device alone.  A step of such a type takes farm_window_kernel<..., WIDE>'s front end and
 // chain_window_kernel<..., WIDE>'s k role: its pair units rebuild the candidate row from the frames into the wave's row in dynamic
@@ -1011,8 +1015,9 @@ static_assert(sizeof(BoxDev) + sizeof(ChainRunArgs) + 160 <= 4096, "a chain-run 
 // (wide_k_sweep<2>: A + delta into g.alt + c n_slots with `sc1` stores, which the commit copies), with the intra term of an
 // insertion / deletion (GC) on the spare waves.  Steps of <= kMaxFusedSitesWide sites in the same launch take the narrow
 // instance's code.  Cursor, records, by-count completion, ticket, hand-offs, resolver, stall and force, and the commit wave (lane <
-// n1: one wave up to 63 sites) are the same code; what differs is the row's stride and where it lies.  No WIDE sweep has the image
-// search: no TRI form.
+// n1: one wave up to 63 sites) are the same code; what differs is the row's stride and where it lies.  TRI x WIDE is the combination
+// of the two and nothing of its own: the row from trial_frame<false, true> in the three places that rebuild it, the NS = 0 sweep
+// with the image search.
 template <bool FLAT, bool FASTW, bool TRI = false, bool GC = false, bool WIDE = false>
 __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
@@ -1020,7 +1025,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
     double2 *__restrict__ A_base, const ChainRunArgs g) {
     static_assert(!TRI || (!FLAT && !FASTW), "the image search has no flat form and no fast fold (farm_window_kernel's triclinic family)");
-    static_assert(!(WIDE && TRI), "no WIDE sweep has the image search");
+    static_assert(!(WIDE && TRI) || (!FLAT && !FASTW), "the WIDE sweep with the image search has no flat form and no fast fold");
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];      // Coulomb table | phase tables | partials staging
     __shared__ double2 s_pair[kMaxTypes * kMaxTypes];
     __shared__ int4 s_grp[kMaxGrp];
@@ -1109,7 +1114,7 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             if (WIDE && n1 > kMaxFusedSitesWide) {
                 // (farm_wide_k_role's front, chain_wide_k_role's back: the row from the frames, A + delta into the step's buffer)
                 if (build) {
-                    const auto f = trial_frame<false>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+                    const auto f = trial_frame<false, TRI>(tp, bx, g.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
                     double off[3];
                     trial_offset<false>(tp, f, g.replica, rec.t, tid, off);
                     for (int d = 0; d < 3; ++d) reinterpret_cast<double *>(s_dyn)[tid * 3 + d] = f.com[d] + off[d];
@@ -1193,8 +1198,8 @@ __global__ __launch_bounds__(kChainBlock, 1) void chain_run_kernel(
             if constexpr (GC) { if (kind_w == 1) it.m = -1; }
             if (wide_row) {
                 // (farm_wide_pair_unit's sweep: the batched path's NS = 0 kernel of the unit, the wave's slabs)
-                pair_sweep_item<0, false, false, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, wl.w_site,
-                                                                     wl.w_sty, it, cand, kFarmWideSites, split, ns, lane, g.partials, wg);
+                pair_sweep_item<0, false, TRI, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, wl.w_site,
+                                                                   wl.w_sty, it, cand, kFarmWideSites, split, ns, lane, g.partials, wg);
             } else {
 #define MGPU_RUN_PAIR(NS)                                                                                                \
             do {                                                                                                         \

@@ -106,8 +106,9 @@ int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int
 // type t -- the form recip_plan picks for the type alone, as the batched path's per-type launches do (recip_groups) -- and the
 // dynamic LDS that role needs.  kWindowNone: windows do not take the type (site-major types, i.e. molecules of kFarmWideSites
 // sites or more, frozen ones among them; a molecule of <= kMaxFusedSitesWide sites whose type does not take the row form; a larger
-// one in a triclinic box -- there is no WIDE instance with the image search -- or whose type takes the per-k or the tiled
-// matrix-unit form).  Everything read here is fixed when the engine is created.
+// one in a triclinic box -- farm windows have no WIDE instance with the image search; what the single-chain paths' instances
+// would take of such a type goes to take_tri, read under mgpu_chain_set_wide_triclinic -- or whose type takes the per-k or the
+// tiled matrix-unit form).  Everything read here is fixed when the engine is created.
 void window_types_build(mgpu_engine *e) {
     mgpu_engine::WindowTypes &w = e->win;
     w = mgpu_engine::WindowTypes{};
@@ -117,7 +118,8 @@ void window_types_build(mgpu_engine *e) {
         const int n1 = e->tp.n1[t];
         const bool wide = n1 > kMaxFusedSitesWide;
         if (!wide) w.k_lds[t] = window_k_lds_bytes(false, recip_rows_lds_bytes(e, n1));   // (a narrow row's k role is the row form's)
-        if (e->tp.site_major[t] || n1 >= kFarmWideSites || (wide && e->bx.triclinic)) continue;
+        if (e->tp.site_major[t] || n1 >= kFarmWideSites) continue;
+        const bool tri_wide = wide && e->bx.triclinic;
         const RecipPlan p = recip_plan(e, n1, true);
         if (p.form == MGPU_RECIP_FORM_ROWS) {
             w.k_lds[t] = window_k_lds_bytes(wide, recip_rows_lds_bytes(e, n1));
@@ -129,6 +131,8 @@ void window_types_build(mgpu_engine *e) {
         } else {
             continue;
         }
+        w.k_lds_max_tri = std::max(w.k_lds_max_tri, w.k_lds[t]);
+        if (tri_wide) { w.take_tri[t] = kWindowWide; continue; }
         w.take[t] = wide ? kWindowWide : kWindowNarrow;
         w.k_lds_max = std::max(w.k_lds_max, w.k_lds[t]);         // (every type a row may carry)
     }
@@ -142,8 +146,10 @@ void window_types_build(mgpu_engine *e) {
 //     resolver beyond 64 KiB, WIDE LDS beyond its budget;
 //   farm windows and chain runs: a triclinic box whose engine has not switched device-built moves on;
 //   chain runs (no such instance of chain_run_kernel exists): reservoirs, and a triclinic box unless triclinic runs are on; a type
-//     of more than kMaxFusedSitesWide sites unless WIDE runs are on (mgpu_chain_run_set_wide: refused for a triclinic box and for
-//     an engine with a reservoir, so the WIDE instances meet neither).
+//     of more than kMaxFusedSitesWide sites unless WIDE runs are on (mgpu_chain_run_set_wide: refused for an engine with a
+//     reservoir, and for a triclinic box unless mgpu_chain_set_wide_triclinic is on);
+//   single-chain windows and chain runs under mgpu_chain_set_wide_triclinic: a type of 6..63 sites of a triclinic box is taken as
+//     take_tri says (the TRI x WIDE instances); farm windows never read it.
 //     (Grand-canonical runs, mgpu_chain_run_set_gc, are admitted exactly where runs are: the switch is refused for a triclinic box
 //     whose triclinic runs are off and for an engine with a reservoir, and the GC instances' dynamic LDS is window_lds_bytes(kPathRun, ...) -- their k role, pair
 //     role and resolver stage what the NVT instances stage; what they add is 16 double2 of static LDS.)
@@ -152,24 +158,31 @@ struct WindowAdmission {
     int capacity = 0;
     bool rides[kMaxRes] = {};
 };
+// the image-search WIDE instances serve this path of this engine (mgpu_chain_set_wide_triclinic; never a farm window), and
+// whether the path's WIDE instances, once on, take type t
+static bool window_tri_wide(const mgpu_engine *e, WindowPath path) { return path != kPathFarm && e->bx.triclinic && e->wide_tri; }
+static bool window_takes_wide(const mgpu_engine *e, WindowPath path, int t) {
+    return e->win.take[t] == kWindowWide || (window_tri_wide(e, path) && e->win.take_tri[t] == kWindowWide);
+}
 static WindowAdmission window_admission(const mgpu_engine *e, WindowPath path) {
     const mgpu_engine::WindowTypes &w = e->win;
     const bool wide_on = path == kPathFarm || (path == kPathChain && e->chain.wide) || (path == kPathRun && e->run.wide);
+    const bool tri_wide_on = window_tri_wide(e, path);
     WindowAdmission a;
     bool ok = true, wide = false;
     for (int t = 0; t < e->tp.n_res; ++t) {
-        const bool takes = w.take[t] == kWindowNarrow || (w.take[t] == kWindowWide && wide_on);
+        const bool takes = w.take[t] == kWindowNarrow || (window_takes_wide(e, path, t) && wide_on);
         a.rides[t] = path == kPathRun ? e->is_active[t] != 0 : (takes || (path == kPathChain && e->tp.n1[t] <= kMaxFusedSitesWide));
         if (!e->is_active[t]) continue;
         ok = ok && takes;
-        wide = wide || w.take[t] == kWindowWide;
+        wide = wide || window_takes_wide(e, path, t);
     }
     if (path != kPathChain && e->bx.triclinic && !e->tri_moves) ok = false;
     if (path == kPathRun && (e->rsv_any || (e->bx.triclinic && !e->run.triclinic))) ok = false;
     if (path == kPathChain && !w.rows_one) ok = false;
     const int nsplit = e->pair_nsplit;
     if (!window_lds_fits(false, window_lds_bytes(path, false, e->coul_bytes, 0, 0, nsplit))) ok = false;
-    if (wide && !window_lds_fits(true, window_lds_bytes(path, true, e->coul_bytes, w.k_lds_max, 0, nsplit))) ok = false;
+    if (wide && !window_lds_fits(true, window_lds_bytes(path, true, e->coul_bytes, tri_wide_on ? w.k_lds_max_tri : w.k_lds_max, 0, nsplit))) ok = false;
     if (!ok) return a;
     // (single-chain windows, runs: the resolving workgroup stages every split partial in LDS, 2 entries per step at most)
     a.capacity = path == kPathFarm ? std::min(kFarmMaxChains, e->n_replicas)
@@ -180,7 +193,7 @@ static WindowAdmission window_admission(const mgpu_engine *e, WindowPath path) {
 // a launch's dynamic LDS (mgpu_internal.h): `k_rows` = the largest k role among the narrow rows it carries; a WIDE launch takes
 // the largest over every type a row may carry
 static size_t window_lds(const mgpu_engine *e, WindowPath path, bool wide, size_t k_rows, int count) {
-    const size_t k_bytes = wide ? e->win.k_lds_max : std::max(e->win.k_lds_one, k_rows);
+    const size_t k_bytes = wide ? (window_tri_wide(e, path) ? e->win.k_lds_max_tri : e->win.k_lds_max) : std::max(e->win.k_lds_one, k_rows);
     return window_lds_bytes(path, wide, e->coul_bytes, k_bytes, count, e->pair_nsplit);
 }
 
@@ -249,6 +262,20 @@ extern "C" {
 int mgpu_chain_set_wide(mgpu_engine *e, int on) {
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
     e->chain.wide = on != 0;
+    return MGPU_OK;
+}
+
+int mgpu_chain_set_wide_triclinic(mgpu_engine *e, int on) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    // every refusal leaves the switch as it was
+    if (!e->bx.triclinic) return set_error(MGPU_ERR_STATE, "chain_set_wide_triclinic: the box is orthorhombic");
+    if (e->run.open) return set_error(MGPU_ERR_STATE, "chain_set_wide_triclinic: a run is open");
+    // (WIDE runs of a triclinic box stand on this switch: mgpu_chain_run_set_wide)
+    if (!on && e->run.wide) return set_error(MGPU_ERR_STATE, "chain_set_wide_triclinic: WIDE runs are on (mgpu_chain_run_set_wide)");
+    int rc = use_device(e);
+    if (rc) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;      // (no trial or window in flight sees the switch move)
+    e->wide_tri = on != 0;
     return MGPU_OK;
 }
 
@@ -388,8 +415,10 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     const size_t lds = window_lds(e, kPathChain, wide, k_rows, n_ent);
     if (!window_lds_fits(wide, lds)) return set_error(MGPU_ERR_CAPACITY, "chain_window: the window does not fit the LDS budget");
     auto wide_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, true>); };
+    auto tri_wide_family = [](auto &&f) { f(chain_window_kernel<false, false, true, true>); };
     if ((rc = lds_opt_in(e->device, kLdsChainWide, lds, [&](auto &&f) {
              for_all_bools([&](auto... flags) { wide_family(f, flags...); }, std::integral_constant<int, 2>{});
+             tri_wide_family(f);
          })))
         return rc;
     ch.seq += 1;
@@ -408,8 +437,9 @@ int mgpu_chain_window(mgpu_engine *e, int replica, int n, const int *t, const in
     ln.dirty = true;
     ln.forget_trial();
     auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
-    // (the image search has no flat and no fast-fold form)
-    if (e->bx.triclinic) launch(chain_window_kernel<false, false, true>);
+    // (the image search has no flat and no fast-fold form; a WIDE row of a triclinic box got here under mgpu_chain_set_wide_triclinic)
+    if (e->bx.triclinic && wide) tri_wide_family(launch);
+    else if (e->bx.triclinic) launch(chain_window_kernel<false, false, true>);
     else if (wide) with_bools([&](auto... flags) { wide_family(launch, flags...); }, e->pair_flat, ff);
     else with_bools([&](auto FLAT, auto FASTW) { launch(chain_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); }, e->pair_flat, ff);
     HIP_TRY(hipGetLastError());
@@ -697,14 +727,16 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     // the WIDE instances when any active type has more than kMaxFusedSitesWide sites: the run's choice, not the launch's (which
     // records a launch consumes is known on the device alone)
     bool wide = false;
-    for (int t = 0; t < e->tp.n_res; ++t) wide = wide || (e->is_active[t] && e->win.take[t] == kWindowWide);
+    for (int t = 0; t < e->tp.n_res; ++t) wide = wide || (e->is_active[t] && window_takes_wide(e, kPathRun, t));
     const size_t lds = window_lds(e, kPathRun, wide, k_rows, rn.k);
     if (!window_lds_fits(wide, lds)) return set_error(MGPU_ERR_CAPACITY, "chain_run_launch: the launch does not fit the LDS budget");
     auto wide_family = [](auto &&f, auto FLAT, auto FASTW, auto GC) {
         f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, decltype(GC)::value, true>);
     };
+    auto tri_wide_family = [](auto &&f, auto GC) { f(chain_run_kernel<false, false, true, decltype(GC)::value, true>); };
     if (wide && (rc = lds_opt_in(e->device, kLdsRunWide, lds, [&](auto &&f) {
              for_all_bools([&](auto... flags) { wide_family(f, flags...); }, std::integral_constant<int, 3>{});
+             for_all_bools([&](auto... flags) { tri_wide_family(f, flags...); }, std::integral_constant<int, 1>{});
          })))
         return rc;
     ChainRunArgs g{};
@@ -729,13 +761,15 @@ static int run_launch_one(mgpu_engine *e, int force_step, int force_verdict) {
     alt_forget(e, rn.replica);
     // The run kernel's families: with the image search (no flat form, no fast fold: farm_window_kernel's triclinic family), the
     // orthorhombic one, whose flags are free, and the grand-canonical forms of both (the run was opened with the switch on); the
-    // WIDE family above (orthorhombic, NVT and grand-canonical) for an engine with an active type of 6..63 sites.
+    // WIDE families above (orthorhombic, and with the image search under mgpu_chain_set_wide_triclinic; NVT and grand-canonical)
+    // for an engine with an active type of 6..63 sites.
     auto tri_family = [](auto &&f) { f(chain_run_kernel<false, false, true>); };
     auto ortho_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value>); };
     auto gc_family = [](auto &&f, auto FLAT, auto FASTW) { f(chain_run_kernel<decltype(FLAT)::value, decltype(FASTW)::value, false, true>); };
     auto tri_gc_family = [](auto &&f) { f(chain_run_kernel<false, false, true, true>); };
     auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
-    if (e->bx.triclinic && rn.gc) tri_gc_family(launch);
+    if (e->bx.triclinic && wide) with_bools([&](auto... flags) { tri_wide_family(launch, flags...); }, rn.gc);
+    else if (e->bx.triclinic && rn.gc) tri_gc_family(launch);
     else if (e->bx.triclinic) tri_family(launch);
     else if (wide) with_bools([&](auto... flags) { wide_family(launch, flags...); }, e->pair_flat, ff, rn.gc);
     else if (rn.gc) with_bools([&](auto... flags) { gc_family(launch, flags...); }, e->pair_flat, ff);
@@ -769,8 +803,9 @@ int mgpu_chain_run_set_wide(mgpu_engine *e, int on) {
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
     // every refusal leaves the switch as it was
     if (e->run.open) return set_error(MGPU_ERR_STATE, "chain_run_set_wide: a run is open");
-    if (on && e->bx.triclinic)
-        return set_error(MGPU_ERR_STATE, "chain_run_set_wide: the box is triclinic (no WIDE sweep has the image search)");
+    if (on && e->bx.triclinic && !e->wide_tri)
+        return set_error(MGPU_ERR_STATE, "chain_run_set_wide: the box is triclinic (no WIDE sweep has the image search unless "
+                                         "mgpu_chain_set_wide_triclinic is on)");
     if (on && e->rsv_any) return set_error(MGPU_ERR_STATE, "chain_run_set_wide: the engine holds a reservoir (no RSV instance of the run kernel)");
     e->run.wide = on != 0;
     return MGPU_OK;

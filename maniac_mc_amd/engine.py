@@ -535,6 +535,13 @@ class Engine:
         """mgpu_chain_set_wide: single-chain windows also take rigid molecules of 6 to 63 sites (off by default)."""
         check(self.L.mgpu_chain_set_wide(self.h, C.c_int(1 if on else 0)))
 
+    def chain_set_wide_triclinic(self, on=True):
+        """mgpu_chain_set_wide_triclinic: the single-chain one-launch paths (windows under chain_set_wide, runs under
+        chain_run_set_wide) take rigid molecules of 6 to 63 sites in a triclinic box (off by default; farm windows never).
+        Refused (MgpuError, the switch unchanged) for an orthorhombic box, while a run is open, and switched off while
+        chain_run_set_wide is on."""
+        check(self.L.mgpu_chain_set_wide_triclinic(self.h, C.c_int(1 if on else 0)))
+
     def chain_set_timing(self, on=True):
         check(self.L.mgpu_chain_set_timing(self.h, C.c_int(1 if on else 0)))
 

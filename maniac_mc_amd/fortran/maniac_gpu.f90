@@ -459,6 +459,14 @@ module maniac_gpu
             integer(c_int), value :: on
             integer(c_int) :: rc
         end function
+        ! the single-chain one-launch paths (windows, chain runs) take rigid molecules of 6 to 63 sites in a triclinic box (off by
+        ! default; refused for an orthorhombic box, while a run is open, and switched off while mgpu_chain_run_set_wide is on)
+        function mgpu_chain_set_wide_triclinic(e, on) bind(C, name="mgpu_chain_set_wide_triclinic") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: on
+            integer(c_int) :: rc
+        end function
         function mgpu_chain_window(e, replica, n, t, m, kind, link, sites, site_stride, accept_u, accept_pref, temperature, &
                                    recip_energy, old_energy, new_energy, first_accepted, undecided) &
                 bind(C, name="mgpu_chain_window") result(rc)

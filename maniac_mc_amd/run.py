@@ -122,7 +122,7 @@ WIDE_CHAIN_WINDOWS_DEFAULT = False
 def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoir_path=None, device=0,
                    mol_capacity=None, nb_block=None, nb_step=None, seams=False, as_written=False, speculate=4,
                    chain_windows=True, chain_margin=None, wide_chain_windows=WIDE_CHAIN_WINDOWS_DEFAULT, chain_run=None,
-                   chain_run_triclinic=False, chain_run_gcmc=False, chain_run_wide=False):
+                   chain_run_triclinic=False, chain_run_gcmc=False, chain_run_wide=False, wide_triclinic=False):
     """Run the chain; returns a dict with the final energies (K), counters, molecule counts, step sizes.
 
     ``seed``: None -> the input file's ``seed`` if present, else the generator is left unseeded
@@ -166,8 +166,12 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     ``chain_run`` in the result gains ``gcmc`` and ``fallback_steps``.
     ``chain_run_wide``: True (with ``chain_run``) -> an input with rigid molecules of 6 to 63 sites runs its blocks as chain runs
     too (Engine.chain_run_set_wide), NVT or -- with ``chain_run_gcmc`` -- grand-canonical.  Same files as the windows.  Runs with
-    ``as_written`` or a reservoir and triclinic inputs keep their windows (``on`` False).  False (default): such an input keeps
-    its windows whatever ``chain_run`` says.  ValueError without ``chain_run``.
+    ``as_written`` or a reservoir and triclinic inputs (unless ``wide_triclinic``) keep their windows (``on`` False).  False
+    (default): such an input keeps its windows whatever ``chain_run`` says.  ValueError without ``chain_run``.
+    ``wide_triclinic``: True -> a TRICLINIC input with rigid molecules of 6 to 63 sites is taken by the single-chain one-launch
+    paths (Engine.chain_set_wide_triclinic): ``wide_chain_windows`` and ``chain_run_wide`` then apply to it as they do to an
+    orthorhombic input (runs still need ``chain_run_triclinic``, which creates the engine with device-built moves).  Same files.
+    False (default): such an input does what it always did -- batched windows, no runs.  Other inputs do not look at it.
     """
     system, inp, dat = io_maniac.load_system(maniac_path, data_path, inc_path, with_data=True)
     rdat = io_maniac.read_lammps_data(reservoir_path, inp) if reservoir_path else None
@@ -185,7 +189,10 @@ def run_simulation(maniac_path, data_path, inc_path, outdir, seed=None, reservoi
     eng = Engine.from_system(system, n_replicas=1, device=device, mol_capacity=mol_capacity, triclinic_moves=run_tri)
     if run_tri:
         eng.chain_run_set_triclinic(True)
-    if chain_run_wide and not seams and not as_written and rdat is None and not system.is_triclinic():
+    tri_wide = bool(wide_triclinic) and not seams and system.is_triclinic()
+    if tri_wide:
+        eng.chain_set_wide_triclinic(True)
+    if chain_run_wide and not seams and not as_written and rdat is None and (not system.is_triclinic() or tri_wide):
         eng.chain_run_set_wide(True)
     if chain_margin is not None:
         eng.chain_set_margin(float(chain_margin))
@@ -280,7 +287,11 @@ def main(argv=None):
                          "a triclinic grand-canonical input needs --chain-run-triclinic as well)")
     ap.add_argument("--chain-run-wide", dest="chain_run_wide", action="store_true",
                     help="with --chain-run: an input with rigid molecules of 6 to 63 sites runs its blocks as chain runs too (off by "
-                         "default: such an input keeps its windows; not for triclinic inputs, reservoirs or --as-written)")
+                         "default: such an input keeps its windows; not for reservoirs or --as-written, and for triclinic inputs "
+                         "only with --wide-triclinic)")
+    ap.add_argument("--wide-triclinic", dest="wide_triclinic", action="store_true",
+                    help="a triclinic input with rigid molecules of 6 to 63 sites: --wide-chain-windows and --chain-run-wide apply to it "
+                         "(off by default: such an input keeps its batched windows)")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
     ap.add_argument("--replicas", type=int, default=None,
@@ -336,7 +347,7 @@ def main(argv=None):
                          as_written=a.as_written, speculate=a.speculate, chain_windows=not a.no_chain_windows,
                          wide_chain_windows=a.wide_chain_windows, chain_run=chain_run,
                          chain_run_triclinic=a.chain_run_triclinic, chain_run_gcmc=a.chain_run_gcmc,
-                         chain_run_wide=a.chain_run_wide)
+                         chain_run_wide=a.chain_run_wide, wide_triclinic=a.wide_triclinic)
     e = res["energy"]
     print(f"final energy (K): total {e['total']:.6f}  non_coulomb {e['non_coulomb']:.6f}  coulomb {e['coulomb']:.6f}  "
           f"recip {e['recip_coulomb']:.6f};  molecules {res['n_mol'].tolist()};  output in {os.path.join(a.out, '')}")

@@ -9,6 +9,8 @@ continue from the step cursor on the device).
     python tools/chain_run_speed.py --workload co2_gcmc_triclinic --chain-run-triclinic --chain-run-gcmc --ks 4,8 --depths 3
     python tools/chain_run_speed.py --workload adsorbate24 --chain-run-wide --wide-chain-windows --ks 4,8 --depths 3
     python tools/chain_run_speed.py --workload adsorbate24_gcmc --chain-run-wide --chain-run-gcmc --wide-chain-windows --ks 4,8 --depths 3
+    python tools/chain_run_speed.py --workload adsorbate24_triclinic --chain-run-triclinic --chain-run-wide --wide-chain-windows --ks 4,8 --depths 3
+    python tools/chain_run_speed.py --workload adsorbate24_gcmc_triclinic --chain-run-triclinic --chain-run-wide --chain-run-gcmc --wide-chain-windows --ks 4,8 --depths 3
 
 Boxes: bench.py's 10 125-atom SPC/E box and its framework box (2208 framework atoms + 40 four-site waters), NVT, 50 %
 translations / 50 % rotations.  --workload spce_triclinic: bench.py's sheared 10 125-atom box (tilt 3.0 / -2.0 / 1.5 A) instead,
@@ -22,7 +24,11 @@ their edge, the framework atoms and the centres keeping their fractions.
 --workload adsorbate24 / adsorbate24_gcmc (with --chain-run-wide: chain_run_wide=True; the second with --chain-run-gcmc as well):
 bench.py's 64 rigid 24-site adsorbates in a 60 A box, NVT and grand-canonical.  Without the switch such a box keeps its windows and
 the tool stops.  --wide-chain-windows adds a second yardstick beside the default mode (whose windows of such molecules are made of
-batched calls): the same box through the WIDE one-launch windows, wide_chain_windows=True.  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
+batched calls): the same box through the WIDE one-launch windows, wide_chain_windows=True.
+--workload adsorbate24_triclinic / adsorbate24_gcmc_triclinic (with --chain-run-triclinic and --chain-run-wide, the second with
+--chain-run-gcmc as well): the same 60 A box sheared by spce_triclinic's tilt scaled to its edge, the centres keeping their
+fractions.  The default mode is the batched windows such a box runs through without wide_triclinic; every other mode (the WIDE
+windows, the runs) sets wide_triclinic=True.  Every mode runs twice, the modes alternating (default, runs ..., default, runs ...), from one
 build on one box in one session; per run: steps/s of the loop alone, mean steps per launch that did something, the share of
 void launches, undecided steps.  The output files of every mode must be those of the default mode (checked here).  A
 difference between two modes that is smaller than the spread between the two runs of one mode is no difference.
@@ -47,7 +53,8 @@ def main():
     ap.add_argument("--depths", default="2,3,4")
     ap.add_argument("--cases", default="spce_10125_nvt,framework_nvt")
     ap.add_argument("--workload", default=None, choices=("spce", "framework", "spce_triclinic", "co2_gcmc", "framework_gcmc", "co2_gcmc_triclinic",
-                                                     "framework_gcmc_triclinic", "adsorbate24", "adsorbate24_gcmc"),
+                                                     "framework_gcmc_triclinic", "adsorbate24", "adsorbate24_gcmc", "adsorbate24_triclinic",
+                                                     "adsorbate24_gcmc_triclinic"),
                     help="one box instead of --cases")
     ap.add_argument("--chain-run-gcmc", dest="chain_run_gcmc", action="store_true",
                     help="the grand-canonical boxes' chain runs (chain_run_gcmc=True); without it such a box keeps its windows and the tool stops")
@@ -62,7 +69,8 @@ def main():
     a = ap.parse_args()
     if a.workload is not None:
         a.cases = {"spce": "spce_10125_nvt", "framework": "framework_nvt", "spce_triclinic": "spce_triclinic_nvt",
-                   "co2_gcmc": "co2_gcmc", "framework_gcmc": "framework_gcmc", "adsorbate24": "adsorbate24_nvt"}.get(a.workload, a.workload)
+                   "co2_gcmc": "co2_gcmc", "framework_gcmc": "framework_gcmc", "adsorbate24": "adsorbate24_nvt",
+                   "adsorbate24_triclinic": "adsorbate24_triclinic_nvt"}.get(a.workload, a.workload)
     tmp = tempfile.mkdtemp()
     common = dict(nb_block=2, nb_step=100, translation_proba=0.5, rotation_proba=0.5)
     cases = {
@@ -93,6 +101,16 @@ def main():
         s.box_matrix = np.array([[L, 0.0, 0.0], [xy, L, 0.0], [xz, yz, L]])
         s.com[0] = s.bounds_lo[None, :] + ((s.com[0] - s.bounds_lo[None, :]) / L) @ s.box_matrix.T
         gc_cases["co2_gcmc_triclinic"] = (s, gc_cases["co2_gcmc"][1])
+    def sheared_adsorbates():
+        s = synth.rigid_adsorbate_box(n_mol=64, L=60.0, seed=17)
+        xy, xz, yz = tilt_of(60.0)
+        s.box_matrix = np.array([[60.0, 0.0, 0.0], [xy, 60.0, 0.0], [xz, yz, 60.0]])
+        s.com[0] = s.bounds_lo[None, :] + ((s.com[0] - s.bounds_lo[None, :]) / 60.0) @ s.box_matrix.T
+        return s
+    if "adsorbate24_triclinic_nvt" in a.cases.split(","):
+        cases["adsorbate24_triclinic_nvt"] = (sheared_adsorbates(), ads)
+    if "adsorbate24_gcmc_triclinic" in a.cases.split(","):
+        gc_cases["adsorbate24_gcmc_triclinic"] = (sheared_adsorbates(), dict(ads, fugacity_atm=[5.0]))
     if "framework_gcmc_triclinic" in a.cases.split(","):
         gc_cases["framework_gcmc_triclinic"] = (synth.framework_water_box(tilt=tilt_of(34.0)), gc_cases["framework_gcmc"][1])
     cases.update(gc_cases)
@@ -120,7 +138,8 @@ def main():
                                          chain_run_wide=cr is not None and a.chain_run_wide, **(dict(wide_chain_windows=True) if ww else {}),
                                          chain_run_triclinic=cr is not None and system.is_triclinic() and
                                          (a.chain_run_triclinic or name not in gc_cases),
-                                         chain_run_gcmc=cr is not None and a.chain_run_gcmc)
+                                         chain_run_gcmc=cr is not None and a.chain_run_gcmc,
+                                         wide_triclinic=(ww or cr is not None) and name.startswith("adsorbate24") and system.is_triclinic())
                 if cr is not None and not res["chain_run"]["on"]:
                     raise SystemExit(f"{name}: the engine did not take the chain run (Engine.chain_run_capacity)")
                 rate = n / res["mc_seconds"]
