@@ -557,9 +557,21 @@ int mgpu_chain_get_timing(mgpu_engine *e, double us[15]);
  * every active residue type is a molecule of <= 5 sites whose type takes the row form, or a plane-major molecule of <= 63
  * sites whose type takes (mgpu_recip_form, for the type alone) the row form, the vector wide form or the untiled
  * matrix-unit wide form.  0 where the path does not apply: a triclinic box without mgpu_set_triclinic_moves, or one with an
- * active type of more than 5 sites; a site-major type (64 sites or more), the per-k
+ * active type of more than 5 sites (unless mgpu_farm_set_wide_triclinic is on, below); a site-major type (64 sites or more), the per-k
  * form, the tiled matrix-unit form, a Coulomb table over 64 KiB, or the windows' LDS beyond its budget.  Lanes may be
- * driven by different host threads (one thread per lane at a time), as the other per-lane entry points. */
+ * driven by different host threads (one thread per lane at a time), as the other per-lane entry points.
+ * mgpu_farm_set_wide_triclinic(e, 1): farm windows -- these, never the single-chain windows or the chain runs, which have
+ * mgpu_chain_set_wide_triclinic -- take rigid molecules of 6 to 63 sites in a TRICLINIC box (off at creation: every capacity,
+ * refusal and refusal text is then what it was).  With it on, and mgpu_set_triclinic_moves on as for every farm window of such a
+ * box, the capacity is min(4096, replicas) by the orthorhombic rule: plane-major, <= 63 sites, the row form, the vector wide form
+ * or the untiled matrix-unit wide form for the type alone, the windows' LDS within its budget.  A chain of such a type builds its
+ * candidate with ApplyPBC's triclinic form (src/geometry_utils.f90:167-220) and its pair energy is
+ * ComputePairInteractionEnergy_singlemol (src/energy_utils.f90:374-442) through the LDS-staged sweep with ComputeDistance's image
+ * search (src/geometry_utils.f90:359-415), as the batched path sweeps it: energies, verdicts and committed state are the batched
+ * path's, bit for bit.  Site-major types, the per-k and the tiled forms and Coulomb tables over 64 KiB keep capacity 0.
+ * MGPU_ERR_STATE, the switch unchanged: an orthorhombic box; on = 0 while a farm window of any lane is uncollected.  Drains
+ * every lane. */
+int mgpu_farm_set_wide_triclinic(mgpu_engine *e, int on);
 int mgpu_farm_window_capacity(const mgpu_engine *e, int *max_chains, int *max_in_flight);
 int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica, const int *t, const int *m, const int *move,
                             const int *forced, const double *u5, const double *accept_u, const double *accept_pref,

@@ -307,6 +307,7 @@ struct mgpu_engine {
     int *d_rsv_nc = nullptr;
     bool tri_moves = false;          // mgpu_set_triclinic_moves: a triclinic engine builds moves on the device and takes farm windows
     bool wide_tri = false;           // mgpu_chain_set_wide_triclinic: the single-chain one-launch paths take types of 6..63 sites in this triclinic box
+    bool farm_wide_tri = false;      // mgpu_farm_set_wide_triclinic: farm windows take types of 6..63 sites in this triclinic box
     bool rsv_any = false;            // some reservoir was set: device-built rows carry the pick (reservoir_row_pick)
     // Register-site sweeps of this engine go through pair_flat_kernel (one software-pipelined loop over all units of
     // a work unit) instead of the plane-by-plane pair_sweep_kernel: chosen at creation for topologies with short planes
@@ -380,7 +381,8 @@ struct mgpu_engine {
         // a triclinic box: what a type of 6..63 sites would take with the image-search WIDE instances (chain_window_kernel<false,
         // false, true, true>, chain_run_kernel<false, false, true, GC, true>) -- kWindowWide or kWindowNone, by the orthorhombic
         // rule; kform, wide_rpt, wide_nss and k_lds of such a type are recorded either way.  Read by kPathChain and kPathRun
-        // under mgpu_chain_set_wide_triclinic, never by kPathFarm; k_lds_max_tri = k_lds_max with these types counted.
+        // under mgpu_chain_set_wide_triclinic and by kPathFarm (farm_window_kernel<false, false, true, RSV, true>) under
+        // mgpu_farm_set_wide_triclinic; k_lds_max_tri = k_lds_max with these types counted.
         signed char take_tri[kMaxRes];
         size_t k_lds_max_tri;
         bool rows_one;                               // a one-site molecule takes the row form (single-chain windows without a narrow active type)

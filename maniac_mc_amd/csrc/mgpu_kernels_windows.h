@@ -654,8 +654,9 @@ __device__ __forceinline__ void farm_resolve(const Topo &tp, const BoxDev &bx, d
 
 // ---- the WIDE instances' pieces for a chain of more than kMaxFusedSitesWide sites
 // One pair work unit (entry, split) by ONE WAVE: the candidate row rebuilt into the wave's row in dynamic LDS, then
-// pair_sweep_item<0, ...> with the wave's slabs, exactly the batched path's NS = 0 sweep of the unit.
-template <bool RSV>
+// pair_sweep_item<0, ...> with the wave's slabs, exactly the batched path's NS = 0 sweep of the unit.  TRI: the row from the
+// triclinic form of trial_frame, the sweep with ComputeDistance's image search (chain_wide_pair_unit<true>'s).
+template <bool RSV, bool TRI = false>
 __device__ __forceinline__ void farm_wide_pair_unit(const Topo &tp, const BoxDev &bx, const double *pos, const int *nmol, const double *res_q,
                                                     const int *res_atype, const double2 *pair_tab, const FarmArgs &g, const FarmRec &rec,
                                                     int kind, int ent, int split, int ns, char *s_dyn, const double2 *s_pair, int wave, int lane,
@@ -664,7 +665,7 @@ __device__ __forceinline__ void farm_wide_pair_unit(const Topo &tp, const BoxDev
     double *cand = l.cand, *w_site = l.w_site;
     int *w_sty = l.w_sty;
     if (ent == 1) {
-        const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+        const auto f = trial_frame<RSV, TRI>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
         if (lane < tp.n1[rec.t]) {
             double off[3];
             trial_offset<RSV>(tp, f, rec.replica, rec.t, lane, off);
@@ -675,21 +676,22 @@ __device__ __forceinline__ void farm_wide_pair_unit(const Topo &tp, const BoxDev
     }
     // old state: the resident molecule; new state: the candidate row; an insertion excludes nothing
     const PairItem it{rec.replica, rec.t, kind == 1 ? -1 : rec.m, ent == 1 ? 0 : -1, 0};
-    pair_sweep_item<0, false, false, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, w_site, w_sty, it, cand,
-                                                         kFarmWideSites, split, ns, lane, g.partials, wg);
+    pair_sweep_item</* NS */ 0, false, TRI, false, false, true>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, s_dyn, s_pair, w_site, w_sty, it,
+                                                                cand, kFarmWideSites, split, ns, lane, g.partials, wg);
 }
 
 // The k role of chain c (every thread of the workgroup; s_skip is clear): candidate row, the sweep of the type's form with A +
 // delta into the replica's other A(k) buffer, the intra term of an insertion / deletion on the spare waves meanwhile, and the
-// energies into g.res[c].  Dynamic LDS: kFarmKFront bytes of row and intra tiles, the form's tables behind them.
-template <bool RSV>
+// energies into g.res[c].  Dynamic LDS: kFarmKFront bytes of row and intra tiles, the form's tables behind them.  TRI: the row
+// from the triclinic form of trial_frame; the k forms and the intra term take the box from bx.
+template <bool RSV, bool TRI = false>
 __device__ __forceinline__ void farm_wide_k_role(const Topo &tp, const BoxDev &bx, const double *pos, const double *res_q, const int *trj,
                                                  const double2 *tw, int n_tasks, const RecipRow *rows, int n_rows, double2 *A_base,
                                                  const FarmArgs &g, const FarmRec &rec, int c, int acur, char *s_dyn, double *s_red, int tid) {
     const int kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
     double *cand = reinterpret_cast<double *>(s_dyn);
     if (kind != 2 && tid < tp.n1[rec.t]) {
-        const auto f = trial_frame<RSV>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
+        const auto f = trial_frame<RSV, TRI>(tp, bx, rec.replica, rec.t, rec.m, rec.move, rec.u, g.t_step, g.r_step);
         double off[3];
         trial_offset<RSV>(tp, f, rec.replica, rec.t, tid, off);
         for (int d = 0; d < 3; ++d) cand[tid * 3 + d] = f.com[d] + off[d];
@@ -715,15 +717,20 @@ __device__ __forceinline__ void farm_wide_k_role(const Topo &tp, const BoxDev &b
 // TRI: a triclinic box whose engine has device-built moves switched on (mgpu_set_triclinic_moves).  The roles build their
 // candidates with the triclinic form of trial_frame, and the pair role runs the register-site sweep with ComputeDistance's
 // image search, pair_sweep_item<NS, false, true, ...> with the engine's nsplit: the batched path's kernel for such a box and
-// chain_window_kernel<false, false, true>'s.  No FLAT, no FASTW and no WIDE form exists for such a box (launch_pair has none
-// either; a triclinic box with an active type of 6..63 sites keeps capacity 0).  The k role, the tickets, the resolver, the
-// hand-offs and RSV are the narrow instance's, unchanged.
+// chain_window_kernel<false, false, true>'s.  No FLAT and no FASTW form exists for such a box (launch_pair has none either).
+// The k role, the tickets, the resolver, the hand-offs and RSV are the narrow instance's, unchanged.
+// TRI x WIDE (mgpu_farm_set_wide_triclinic; without it a triclinic box with an active type of 6..63 sites keeps capacity 0) is
+// the combination of the two and nothing of its own: a chain of such a type builds its row with the triclinic form of
+// trial_frame in the pair role, the k role and the commit, and its pair units run the LDS-staged NS = 0 sweep with the image
+// search (pair_sweep_kernel<0, false, true>'s, as chain_wide_pair_unit<true> does); the k forms and the intra term read the box
+// from bx.  Chains of <= kMaxFusedSitesWide sites in such a launch run the narrow TRI text.
 template <bool FLAT, bool FASTW, bool WIDE = false, bool RSV = false, bool TRI = false>
 __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI ? MGPU_FARM_TRI_MINWAVES : 4)) void farm_window_kernel(
     const Topo *__restrict__ tpp, BoxDev bx, double *__restrict__ pos, int *__restrict__ nmol, const double *__restrict__ res_q,
     const int *__restrict__ res_atype, const double2 *__restrict__ pair_tab, const char *__restrict__ coul_tab_g,
     const int *__restrict__ trj, const double2 *__restrict__ tw, int n_tasks, const RecipRow *__restrict__ rows, int n_rows,
     double2 *__restrict__ A_base, const FarmArgs g) {
+    static_assert(!TRI || (!FLAT && !FASTW), "the image search has no flat form and no fast fold, with WIDE or without");
     extern __shared__ __attribute__((aligned(16))) char s_dyn[];      // Coulomb table | phase tables; then the resolving waves' scratch
     __shared__ double2 s_pair[kMaxTypes * kMaxTypes];
     __shared__ int4 s_grp[kMaxGrp];
@@ -798,7 +805,7 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI 
         const int c = c_lo;
         const FarmRec &rec = s_rec[0];
         if (WIDE && !s_skip[0] && tp.n1[rec.t] > kMaxFusedSitesWide) {
-            farm_wide_k_role<RSV>(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, A_base, g, rec, c, s_acur, s_dyn, s_red, tid);
+            farm_wide_k_role<RSV, TRI>(tp, bx, pos, res_q, trj, tw, n_tasks, rows, n_rows, A_base, g, rec, c, s_acur, s_dyn, s_red, tid);
         } else if (!s_skip[0]) {
             const int kind = rec.move <= 2 ? 0 : (rec.move == 3 ? 1 : 2);
             const int n1 = tp.n1[rec.t];
@@ -852,7 +859,7 @@ __global__ __launch_bounds__(kChainBlock, WIDE ? MGPU_FARM_WIDE_MINWAVES : (TRI 
             const int ent = j / ns, split = j - ent * ns;
             const int n1 = tp.n1[rec.t];
             if (WIDE && n1 > kMaxFusedSitesWide && (ent == 0 ? kind != 1 : kind != 2)) {
-                farm_wide_pair_unit<RSV>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, g, rec, kind, ent, split, ns, s_dyn, s_pair, wave, lane, wg);
+                farm_wide_pair_unit<RSV, TRI>(tp, bx, pos, nmol, res_q, res_atype, pair_tab, g, rec, kind, ent, split, ns, s_dyn, s_pair, wave, lane, wg);
             } else if (ent == 0 ? kind != 1 : kind != 2) {
                 double *cand = &s_cand[wave][0];
                 if (ent == 1) {

@@ -106,9 +106,9 @@ int wait_for_tag(hipStream_t stream, const volatile unsigned long long *tag, int
 // type t -- the form recip_plan picks for the type alone, as the batched path's per-type launches do (recip_groups) -- and the
 // dynamic LDS that role needs.  kWindowNone: windows do not take the type (site-major types, i.e. molecules of kFarmWideSites
 // sites or more, frozen ones among them; a molecule of <= kMaxFusedSitesWide sites whose type does not take the row form; a larger
-// one in a triclinic box -- farm windows have no WIDE instance with the image search; what the single-chain paths' instances
-// would take of such a type goes to take_tri, read under mgpu_chain_set_wide_triclinic -- or whose type takes the per-k or the
-// tiled matrix-unit form).  Everything read here is fixed when the engine is created.
+// one in a triclinic box -- what the image-search WIDE instances would take of such a type goes to take_tri, read by the
+// single-chain paths under mgpu_chain_set_wide_triclinic and by farm windows under mgpu_farm_set_wide_triclinic -- or whose type
+// takes the per-k or the tiled matrix-unit form).  Everything read here is fixed when the engine is created.
 void window_types_build(mgpu_engine *e) {
     mgpu_engine::WindowTypes &w = e->win;
     w = mgpu_engine::WindowTypes{};
@@ -149,7 +149,8 @@ void window_types_build(mgpu_engine *e) {
 //     of more than kMaxFusedSitesWide sites unless WIDE runs are on (mgpu_chain_run_set_wide: refused for an engine with a
 //     reservoir, and for a triclinic box unless mgpu_chain_set_wide_triclinic is on);
 //   single-chain windows and chain runs under mgpu_chain_set_wide_triclinic: a type of 6..63 sites of a triclinic box is taken as
-//     take_tri says (the TRI x WIDE instances); farm windows never read it.
+//     take_tri says (the TRI x WIDE instances); farm windows read it under a switch of their own, mgpu_farm_set_wide_triclinic,
+//     and neither switch gives the other's paths anything.
 //     (Grand-canonical runs, mgpu_chain_run_set_gc, are admitted exactly where runs are: the switch is refused for a triclinic box
 //     whose triclinic runs are off and for an engine with a reservoir, and the GC instances' dynamic LDS is window_lds_bytes(kPathRun, ...) -- their k role, pair
 //     role and resolver stage what the NVT instances stage; what they add is 16 double2 of static LDS.)
@@ -158,9 +159,11 @@ struct WindowAdmission {
     int capacity = 0;
     bool rides[kMaxRes] = {};
 };
-// the image-search WIDE instances serve this path of this engine (mgpu_chain_set_wide_triclinic; never a farm window), and
-// whether the path's WIDE instances, once on, take type t
-static bool window_tri_wide(const mgpu_engine *e, WindowPath path) { return path != kPathFarm && e->bx.triclinic && e->wide_tri; }
+// the image-search WIDE instances serve this path of this engine (farm windows: mgpu_farm_set_wide_triclinic; the single-chain
+// paths: mgpu_chain_set_wide_triclinic), and whether the path's WIDE instances, once on, take type t
+static bool window_tri_wide(const mgpu_engine *e, WindowPath path) {
+    return e->bx.triclinic && (path != kPathFarm ? e->wide_tri : e->farm_wide_tri);
+}
 static bool window_takes_wide(const mgpu_engine *e, WindowPath path, int t) {
     return e->win.take[t] == kWindowWide || (window_tri_wide(e, path) && e->win.take_tri[t] == kWindowWide);
 }
@@ -471,6 +474,22 @@ int mgpu_farm_window_capacity(const mgpu_engine *e, int *max_chains, int *max_in
     return MGPU_OK;
 }
 
+int mgpu_farm_set_wide_triclinic(mgpu_engine *e, int on) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    // every refusal leaves the switch as it was
+    if (!e->bx.triclinic) return set_error(MGPU_ERR_STATE, "farm_set_wide_triclinic: the box is orthorhombic");
+    int rc = use_device(e);
+    if (rc) return rc;
+    // (a window in flight was admitted, and its LDS sized, under the switch as it stands: it is collected first)
+    if (!on)
+        for (int l = 0; l < kLanes; ++l)
+            if (!e->lanes[l].farm.pending.empty())
+                return set_error(MGPU_ERR_STATE, "farm_set_wide_triclinic: a farm window is in flight (mgpu_farm_window_wait)");
+    if ((rc = sync_all_lanes(e))) return rc;      // (no trial or window in flight sees the switch move)
+    e->farm_wide_tri = on != 0;
+    return MGPU_OK;
+}
+
 int mgpu_farm_window_get_stats(const mgpu_engine *e, long long *windows, long long *undecided) {
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
     if (windows) *windows = e->farm.windows;
@@ -582,7 +601,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
         }
         fast = fast && replica_in_range(e, replica[c]);
         if ((rc = admit_built(e, idx, k, mv, kAdmitInsertion | kAdmitRange, "farm_window_submit", "chain", c, why, pd.ok[c], fast))) { set_error(rc, why); break; }
-        wide = wide || e->win.take[t[c]] == kWindowWide;
+        wide = wide || window_takes_wide(e, kPathFarm, t[c]);
         k_rows = std::max(k_rows, e->win.k_lds[t[c]]);
         pd.kind[c] = k;
         // windows still in flight behind this one must not take the fast fold if this step is accepted: the range flag is
@@ -604,9 +623,12 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     // a chain of more than kMaxFusedSitesWide sites: the WIDE instance, else the narrow one
     const size_t lds = window_lds(e, kPathFarm, wide, k_rows, n);
     if (!window_lds_fits(wide, lds)) return set_error(MGPU_ERR_CAPACITY, "farm_window_submit: the window does not fit the LDS budget");
-    // The window kernel's families: with the image search (no flat form, no fast fold, no wide chains: window_types_build), WIDE,
-    // narrow; within each the flags are free.  (An engine without reservoirs runs the instances without their code.)
-    auto tri_family = [](auto &&f, auto RSV) { f(farm_window_kernel<false, false, false, decltype(RSV)::value, true>); };
+    // The window kernel's families: with the image search (no flat form, no fast fold; a WIDE chain of such a box got here under
+    // mgpu_farm_set_wide_triclinic), WIDE, narrow; within each the flags are free.  (An engine without reservoirs runs the
+    // instances without their code.)
+    auto tri_family = [](auto &&f, auto WIDE, auto RSV) {
+        f(farm_window_kernel<false, false, decltype(WIDE)::value, decltype(RSV)::value, true>);
+    };
     auto wide_family = [](auto &&f, auto FLAT, auto FASTW, auto RSV) {
         f(farm_window_kernel<decltype(FLAT)::value, decltype(FASTW)::value, true, decltype(RSV)::value>);
     };
@@ -615,6 +637,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     };
     if ((rc = lds_opt_in(e->device, kLdsFarmWide, lds, [&](auto &&f) {
              for_all_bools([&](auto... flags) { wide_family(f, flags...); }, std::integral_constant<int, 3>{});
+             for_all_bools([&](auto RSV) { tri_family(f, std::true_type{}, RSV); }, std::integral_constant<int, 1>{});
          })))
         return rc;
     fw.seq += 1;
@@ -638,7 +661,7 @@ int mgpu_farm_window_submit(mgpu_engine *e, int lane, int n, const int *replica,
     for (int c = 0; c < n; ++c) alt_forget(e, replica[c]);     // (the window's k role overwrites their other buffers)
     e->a_switched = true;
     auto launch = [&](auto kernel) { window_launch(kernel, e, d_topo, grid, lds, ln.stream, g); };
-    if (e->bx.triclinic) with_bools([&](auto... flags) { tri_family(launch, flags...); }, e->rsv_any);
+    if (e->bx.triclinic) with_bools([&](auto... flags) { tri_family(launch, flags...); }, wide, e->rsv_any);
     else if (wide) with_bools([&](auto... flags) { wide_family(launch, flags...); }, e->pair_flat, ff, e->rsv_any);
     else with_bools([&](auto... flags) { narrow_family(launch, flags...); }, e->pair_flat, ff, e->rsv_any);
     HIP_TRY(hipGetLastError());

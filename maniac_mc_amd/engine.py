@@ -255,6 +255,12 @@ class Engine:
         check(self.L.mgpu_farm_window_capacity(self.h, C.byref(n), C.byref(d)))
         return n.value, d.value
 
+    def farm_set_wide_triclinic(self, on=True):
+        """mgpu_farm_set_wide_triclinic: farm windows take rigid molecules of 6 to 63 sites in a triclinic box (off by default;
+        the single-chain paths have chain_set_wide_triclinic).  Needs set_triclinic_moves as every farm window of such a box.
+        Refused (MgpuError, the switch unchanged) for an orthorhombic box, and switched off while a farm window is uncollected."""
+        check(self.L.mgpu_farm_set_wide_triclinic(self.h, C.c_int(1 if on else 0)))
+
     def farm_window_submit(self, replica, t, m, move, u, translation_step, rotation_step, accept_u, accept_pref, temperature,
                            forced=None, lane=0, slot_u=None):
         """mgpu_farm_window_submit: one launch evaluates, decides and commits one step of every chain given."""

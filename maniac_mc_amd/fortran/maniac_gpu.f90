@@ -301,6 +301,14 @@ module maniac_gpu
             integer(c_int), intent(out) :: max_chains, max_in_flight
             integer(c_int) :: rc
         end function
+        ! farm windows take rigid molecules of 6 to 63 sites in a triclinic box (off by default; refused for an orthorhombic box,
+        ! and switched off while a farm window is uncollected; needs mgpu_set_triclinic_moves as every farm window of such a box)
+        function mgpu_farm_set_wide_triclinic(e, on) bind(C, name="mgpu_farm_set_wide_triclinic") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: on
+            integer(c_int) :: rc
+        end function
         function mgpu_farm_window_submit(e, lane, n, replica, t, m, move, forced, u5, accept_u, accept_pref, slot_u, &
                                          translation_step, rotation_step, temperature) &
                 bind(C, name="mgpu_farm_window_submit") result(rc)

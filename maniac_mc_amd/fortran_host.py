@@ -101,6 +101,8 @@ class FortranFarm:
     ``reservoir={t: off (n, n1, 3)}`` gives every chain a reservoir of residue type t (MANIAC's ``-r reservoir.data``;
     ``io_maniac.reservoir_offsets`` reads one): insertions of t copy a reservoir molecule unrotated and take it out of the
     reservoir, deletions put the box's last molecule of t into it, and an insertion from an empty reservoir is skipped.
+    ``wide_triclinic=True`` (with ``triclinic_moves``): window mode also applies to a triclinic box with rigid molecules of 6
+    to 63 sites (``Engine.farm_set_wide_triclinic``); off by default, and such a farm then keeps the batched path.
     """
 
     _live = None          # the farm created last that is still open (tests close leftovers through it)
@@ -111,7 +113,8 @@ class FortranFarm:
                  translation_step: float = 0.3, rotation_step: float = 0.3, p_translation: float = 0.5,
                  rng_kind: int = 1, n_threads: int = 8, mol_capacity=None, gcmc=None,
                  n_lanes: int = 2, n_drivers: int = 1, device_build: bool = False, device_accept: bool = False,
-                 window: bool = False, window_depth: int = 2, reservoir=None, triclinic_moves: bool = False):
+                 window: bool = False, window_depth: int = 2, reservoir=None, triclinic_moves: bool = False,
+                 wide_triclinic: bool = False):
         self.H = lib()
         # mc_farm.f90 keeps up to MAX_FARMS farms; every call below selects this farm's slot first
         free = [k for k in range(FortranFarm.MAX_FARMS) if k not in FortranFarm._slots]
@@ -127,6 +130,11 @@ class FortranFarm:
         self.eng = Engine(topo, system.box_matrix, system.bounds_lo, system.real_space_cutoff,
                           system.ewald_tolerance, self.R, device, self.mol_capacity,
                           triclinic_moves=bool(triclinic_moves) and system.is_triclinic())
+        # wide_triclinic (with triclinic_moves): farm windows take rigid molecules of 6 to 63 sites in this triclinic box
+        # (Engine.farm_set_wide_triclinic) -- set before mc_farm.f90 asks for the windows' capacity
+        self.wide_triclinic = bool(wide_triclinic) and bool(triclinic_moves) and system.is_triclinic()
+        if self.wide_triclinic:
+            self.eng.farm_set_wide_triclinic(True)
         self.eng.load_system(system, 0)
         # device_build: the engine keeps the molecules' frames (com, offsets) and builds the trial moves itself; the
         # Fortran driver then holds no mirror of the coordinates (orthorhombic boxes; triclinic ones with triclinic_moves,

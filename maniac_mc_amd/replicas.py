@@ -71,7 +71,7 @@ def _stats(x):
 
 def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=None, fugacities=None, frames=(0,),
                  mode="auto", device=0, nb_block=None, nb_step=None, mol_capacity=None, n_lanes=2, n_threads=8,
-                 chunk=None):
+                 chunk=None, wide_triclinic=False):
     """Run `replicas` independent chains of the input; returns a dict with the final energies (R, 5) in K (non-Coulomb,
     Coulomb, reciprocal, self, intramolecular), counts (R, n_active), chain counters (R, 8), the farm's counters, the
     mode that ran and the block timings.
@@ -83,6 +83,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     boxes) host-built ones; "windows" | "device" | "device_accept" | "host" force one.  A triclinic input runs an explicit
     "windows", "device" or "device_accept" with the engine's triclinic moves switched on (Engine.set_triclinic_moves);
     "auto" keeps choosing "host" there.
+    ``wide_triclinic``: True -> mode "windows" also takes a triclinic input with rigid molecules of 6 to 63 sites
+    (Engine.farm_set_wide_triclinic); off by default: "windows" then raises for such an input, as it always did.  "auto" is
+    not changed by it.
     ``chunk``: replicas per snapshot launch (default: about SNAPSHOT_BYTES at the types' capacities).
     """
     import time
@@ -127,7 +130,7 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
                        rotation_step=inp.rotation_step_angle, p_translation=inp.translation_proba, n_threads=n_threads,
                        mol_capacity=mol_capacity, gcmc=gcmc_arg, n_lanes=n_lanes, device_build=device_build,
                        device_accept=mode == "device_accept", window=mode in ("auto", "windows"), reservoir=reservoir,
-                       triclinic_moves=triclinic_moves)
+                       triclinic_moves=triclinic_moves, wide_triclinic=bool(wide_triclinic) and triclinic_moves)
     try:
         ran = "host" if not farm.device_build else ("windows" if farm.window else
                                                      ("device_accept" if farm.device_accept else "device"))

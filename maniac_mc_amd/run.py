@@ -291,7 +291,8 @@ def main(argv=None):
                          "only with --wide-triclinic)")
     ap.add_argument("--wide-triclinic", dest="wide_triclinic", action="store_true",
                     help="a triclinic input with rigid molecules of 6 to 63 sites: --wide-chain-windows and --chain-run-wide apply to it "
-                         "(off by default: such an input keeps its batched windows)")
+                         "(off by default: such an input keeps its batched windows); with --replicas: --farm-mode windows applies to it "
+                         "(off by default: that mode then stops for such an input)")
     ap.add_argument("--as-written", action="store_true",
                     help="the reference's deletion update exactly as written (SURVEY F3) instead of the intended physics")
     ap.add_argument("--replicas", type=int, default=None,
@@ -336,7 +337,8 @@ def main(argv=None):
     if a.replicas is not None:
         try:
             res = farm_run.run_replicas(a.maniac, a.data, a.inc, a.out, a.replicas, seed=a.seed, reservoir_path=a.reservoir,
-                                        fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device)
+                                        fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device,
+                                        wide_triclinic=a.wide_triclinic)
         except ValueError as err:
             print(f"error: {err}", file=sys.stderr)
             return 2
