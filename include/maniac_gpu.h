@@ -323,8 +323,15 @@ int mgpu_replica_get_frames(mgpu_engine *e, int replica, int t, int *n_mol, doub
  *           = 4  DeleteMolecule   the resident molecule m as it is
  * In a triclinic cell (box_type 3) ApplyPBC is the reference's round trip through fractional coordinates, applied always
  * (src/geometry_utils.f90:167-220): f = modulo(reciprocal (pos - lo), 1), com <- lo + matrix f; CreateMolecule places
- * com <- lo + matrix u[c][0..2] (src/create_molecule.f90:180-184).  Both in the reference's doubles: no product is fused
- * into the addition behind it.
+ * com <- lo + matrix u[c][0..2] (src/create_molecule.f90:180-184).
+ * The centres are the reference's doubles in every cell, orthorhombic or triclinic: no product is fused into the addition
+ * behind it -- the displacement (u - 1/2) translation_step is rounded before it is added to com (src/translation.f90:104-107
+ * stores it), L u and matrix u are rounded before lo is added -- and ApplyPBC is lo + modulo(pos - lo, L) (x == L comes back
+ * as lo; a hair below lo comes back as lo + L, as the reference returns it).  A translation returns the offsets unchanged, and
+ * a rotation by a zero angle (u[c][3] = 1/2; an insertion's u[c][3] = 0) every bit of them.  A rotated offset is the
+ * reference's within 2 * 2^-52 * (|x| + |y|) of the two components the rotation mixes (the third is untouched): cos and sin
+ * are the device's sincos, the reference's are libm's, and the two-term sums are formed in the compiler's order
+ * (tests/test_gpu_ortho_moves.py, tests/test_gpu_triclinic_moves.py).
  * u = n x 5 uniform numbers in [0, 1) drawn by the host (the random stream stays on the host, as the acceptance does).
  * Energies come back through mgpu_gcmc_trial_wait; mgpu_commit_submit(sites = NULL) on the same lane applies the accepted
  * candidates from the rows the device built, sites and frames. */

@@ -1169,9 +1169,31 @@ __device__ __forceinline__ void trial_com_triclinic(const BoxDev &bx, int mv, co
         com[i] = bx.lo[i] + ((a + b) + c);
     }
 }
+// The centre of a candidate in an orthorhombic cell, the reference's doubles: as above, every product is rounded before it is
+// added (under HIP's default contraction each of the two lines was one v_fmac_f64, and the last bit of most insertions and of
+// one translation in nine at a 6 A step was not the reference's).
+//   translation (translation.f90:104-110 stores (u - 1/2) step, then adds it; geometry_utils.f90:190): lo + modulo(pos - lo, L)
+//   insertion (create_molecule.f90:180-184): com = lo + L u
+__device__ __forceinline__ void trial_com_orthorhombic(const BoxDev &bx, int mv, const double *u, double t_step, double com[3]) {
+#pragma clang fp contract(off)
+    for (int d = 0; d < 3; ++d) {
+        if (mv == 1) {
+            const double s = (u[d] - 0.5) * t_step;
+            double x = (com[d] + s) - bx.lo[d];
+            if (x < 0.0 || x >= bx.L[d]) {
+                x = fmod(x, bx.L[d]);
+                if (x < 0.0) x += bx.L[d];
+            }
+            com[d] = bx.lo[d] + x;
+        } else {
+            const double s = bx.L[d] * u[d];
+            com[d] = bx.lo[d] + s;
+        }
+    }
+}
 // RSV = false: the code of an engine that holds no reservoir (the farm windows' instances without one)
 // TRI: the triclinic form of the centre (trial_com_triclinic) -- a template parameter, not a branch on bx.triclinic: the
-// orthorhombic instances are the code they were
+// orthorhombic instances hold trial_com_orthorhombic alone
 template <bool RSV = true, bool TRI = false, class TopoT>
 __device__ __forceinline__ TrialFrameR<RSV> trial_frame(const TopoT &tp, const BoxDev &bx, int replica, int t, int m, int mv, const double *u,
                                                   double t_step, double r_step) {
@@ -1185,15 +1207,7 @@ __device__ __forceinline__ TrialFrameR<RSV> trial_frame(const TopoT &tp, const B
     f.rot = false;
     if (TRI && (mv == 1 || mv == 3)) trial_com_triclinic(bx, mv, u, t_step, f.com);
     if (!TRI && mv == 1) {
-        for (int d = 0; d < 3; ++d) {
-            // translation.f90:104-110, geometry_utils.f90:190: lo + modulo(pos - lo, L)
-            double x = (f.com[d] + (u[d] - 0.5) * t_step) - bx.lo[d];
-            if (x < 0.0 || x >= bx.L[d]) {
-                x = fmod(x, bx.L[d]);
-                if (x < 0.0) x += bx.L[d];
-            }
-            f.com[d] = bx.lo[d] + x;
-        }
+        trial_com_orthorhombic(bx, 1, u, t_step, f.com);
     } else if (mv == 2 || (mv == 3 && n1 > 1)) {
         const int axis = (int)(u[4] * 3.0) + 1;                              // monte_carlo_utils.f90:54-64
         const double theta = mv == 2 ? (u[3] - 0.5) * r_step : u[3] * kTwoPi;
@@ -1202,8 +1216,7 @@ __device__ __forceinline__ TrialFrameR<RSV> trial_frame(const TopoT &tp, const B
         f.q = (axis + 1) % 3;
         f.rot = true;
     }
-    if (!TRI && mv == 3)
-        for (int d = 0; d < 3; ++d) f.com[d] = bx.lo[d] + bx.L[d] * u[d];     // create_molecule.f90:180-184
+    if (!TRI && mv == 3) trial_com_orthorhombic(bx, 3, u, t_step, f.com);
     if constexpr (RSV) {
     f.rsv = nullptr;
     if (mv == 3 && tp.rsv) {
