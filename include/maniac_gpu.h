@@ -205,6 +205,21 @@ int mgpu_system_energy(mgpu_engine *e, int replica, double out[6]);
  * factor S(k) = sum_j q_j exp(i k.r_j) (ComputeRecipAmplitude, ewald_energy.f90:40-77);
  * mode 0 zeroes it (for as-written comparisons). */
 int mgpu_init_structure_factor(mgpu_engine *e, int replica, int mode);
+
+/* The two calls above for MANY replicas at once.  replicas[n]: any order, any subset, each replica at most once (a replica
+ * listed twice, an index out of range, n < 0 or a null buffer: MGPU_ERR_INVALID_ARG with nothing done; n = 0: MGPU_OK).
+ * Both are synchronous and treat work in flight exactly as their per-replica twins do.
+ *
+ * mgpu_system_energy_replicas: out[i][6] = what mgpu_system_energy(e, replicas[i], ...) returns, bit for bit.
+ * a_deviation (or NULL): a_deviation[i] = max over the k-vectors of max(|Re(A - S)|, |Im(A - S)|), A = the replica's A(k),
+ * S = the S(k) this call computed for the energy; A(k) is not changed.  chunk = replicas per device pass (<= 0: the
+ * engine's choice from a byte budget of scratch; a chunk that would not fit the budget is made smaller, never below one
+ * replica); results do not depend on it.
+ *
+ * mgpu_init_structure_factor_replicas: afterwards A(k) of every listed replica is what
+ * mgpu_init_structure_factor(e, replica, mode) leaves, bit for bit. */
+int mgpu_system_energy_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, double *out, double *a_deviation);
+int mgpu_init_structure_factor_replicas(mgpu_engine *e, int n, const int *replicas, int mode);
 /* a[n_kvectors][2] = (re, im) of ewald%recip_amplitude */
 int mgpu_get_structure_factor(mgpu_engine *e, int replica, double *a);
 int mgpu_set_structure_factor(mgpu_engine *e, int replica, const double *a);

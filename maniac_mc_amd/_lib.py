@@ -12,8 +12,9 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmaniac_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["mgpu_engine.hip", "mgpu_launch.hip", "mgpu_lanes.hip", "mgpu_windows.hip", "mgpu_host_setup.cpp", "mgpu_comm.cpp"]
-HEADERS = ["mgpu_kernels.h", "mgpu_kernels_common.h", "mgpu_kernels_pair.h", "mgpu_kernels_recip.h", "mgpu_kernels_windows.h",
+SOURCES = ["mgpu_engine.hip", "mgpu_launch.hip", "mgpu_lanes.hip", "mgpu_windows.hip", "mgpu_replicas.hip", "mgpu_host_setup.cpp",
+           "mgpu_comm.cpp"]
+HEADERS = ["mgpu_kernels.h", "mgpu_kernels_replicas.h", "mgpu_kernels_common.h", "mgpu_kernels_pair.h", "mgpu_kernels_recip.h", "mgpu_kernels_windows.h",
            "mgpu_internal.h", "mgpu_engine.h"]
 
 MGPU_OK = 0
@@ -41,7 +42,7 @@ EXPORTS = [
     "mgpu_chain_run_capacity", "mgpu_chain_run_open", "mgpu_chain_run_push", "mgpu_chain_run_launch", "mgpu_chain_run_collect",
     "mgpu_chain_run_force", "mgpu_chain_run_close", "mgpu_chain_run_get_stats", "mgpu_chain_run_get_launches", "mgpu_chain_run_set_triclinic", "mgpu_chain_run_set_gc", "mgpu_chain_run_push_gc", "mgpu_chain_run_set_wide", "mgpu_comm_unique_id", "mgpu_comm_create",
     "mgpu_comm_destroy", "mgpu_comm_rank", "mgpu_allgather_block_stats", "mgpu_append_atom_records", "mgpu_format_fixed", "mgpu_phase_factors", "mgpu_synchronize", "mgpu_profile_enable", "mgpu_profile_reset",
-    "mgpu_profile_get",
+    "mgpu_profile_get", "mgpu_system_energy_replicas", "mgpu_init_structure_factor_replicas",
 ]
 
 

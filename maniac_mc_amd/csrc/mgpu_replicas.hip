@@ -1,0 +1,210 @@
+// Whole-system energies and S(k) for many replicas per call: mgpu_system_energy_replicas and
+// mgpu_init_structure_factor_replicas, the batched twins of mgpu_system_energy and mgpu_init_structure_factor
+// (mgpu_engine.hip).  A call is cut into passes of as many replicas as a byte budget of scratch allows; a pass is one
+// ordered pair launch, one intra launch, one phase-table + S(k) launch pair, one reciprocal-energy launch, one reduction
+// (and one deviation launch) for all its replicas.  Nothing is waited for between the passes; one copy brings the results back.
+#include "mgpu_engine.h"
+#include "mgpu_kernels_replicas.h"
+
+namespace mgpu {
+
+// scratch a pass may take (items, partials, phase tables, S): what bounds the engine's own choice of `chunk`
+constexpr size_t kReplicasPassBytes = (size_t)256 << 20;
+constexpr int kReplicasPassMax = 32768;                    // replicas per pass (the grids' y extent)
+constexpr long long kReplicasPassItems = (long long)1 << 28;   // pair work units (items x splits) per pass
+
+static int check_replica_list(const mgpu_engine *e, int n, const int *replicas, const char *who) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    if (n < 0 || (n > 0 && !replicas)) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": bad replica list");
+    std::vector<char> seen((size_t)e->n_replicas, 0);
+    for (int i = 0; i < n; ++i) {
+        const int r = replicas[i];
+        if (r < 0 || r >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": replica out of range");
+        if (seen[r]) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": replica " + std::to_string(r) + " listed twice");
+        seen[r] = 1;
+    }
+    return MGPU_OK;
+}
+
+static size_t phase_tab_entries(const mgpu_engine *e) { return (size_t)recip_ktot(e) * e->tp.n_cap_atoms; }
+
+// the phase tables of the replicas d_reps[0 .. c) into d_tab, then their S(k): into block i of S_all (to_replica = false) or
+// into block d_reps[i] (true: S_all = the replicas' A(k))
+static int launch_sfactor_replicas(mgpu_engine *e, const int *d_reps, int c, double2 *d_tab, bool to_replica, double2 *S_all) {
+    const int ncap = e->tp.n_cap_atoms;
+    const size_t stride = phase_tab_entries(e);
+    hipEvent_t a = nullptr, b = nullptr;
+    int rc = prof_begin(e, e->lanes[0], MGPU_KERNEL_SFACTOR, &a, &b);
+    if (rc) return rc;
+    hipLaunchKernelGGL(phase_table_replicas_kernel, dim3((ncap + 255) / 256, c), dim3(256), 0, e->stream, e->tp, e->bx, e->d_pos,
+                       e->d_nmol, e->d_atom_res, e->d_atom_mol, d_reps, stride, d_tab);
+    hipExtLaunchKernelGGL(sfactor_replicas_kernel, dim3(e->nk, c), dim3(kBlock), 0, e->stream, a, b, 0, e->tp, e->bx, e->d_nmol,
+                          e->d_atom_res, e->d_atom_mol, e->d_atom_q, e->d_kpack, e->d_kslot, d_reps, stride,
+                          (const double2 *)d_tab, to_replica ? 1 : 0, S_all);
+    rc = prof_end(e, e->lanes[0], MGPU_KERNEL_SFACTOR, a, b);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return MGPU_OK;
+}
+
+struct Pass { int first, c; long long n_pair, n_in; };
+
+}  // namespace mgpu
+
+extern "C" {
+
+int mgpu_system_energy_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, double *out, double *a_deviation) {
+    int rc = check_replica_list(e, n, replicas, "system_energy_replicas");
+    if (rc) return rc;
+    if (n > 0 && !out) return set_error(MGPU_ERR_INVALID_ARG, "system_energy_replicas: null out");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const Topo &tp = e->tp;
+    const int nsplit = e->pair_nsplit;
+    const size_t tab_n = phase_tab_entries(e);
+    unsigned active_mask = 0;
+    SelfTerms self{};
+    for (int t = 0; t < tp.n_res; ++t) {
+        if (e->is_active[t] == 1) active_mask |= 1u << t;
+        self.v[t] = self_energy_host(e, t);
+    }
+    auto counts = [&](int r, long long &n_pair, long long &n_in) {
+        n_pair = 0; n_in = 0;
+        for (int t = 0; t < tp.n_res; ++t) {
+            const int nm = e->h_nmol[r * tp.n_res + t];
+            n_pair += nm;
+            if (e->is_active[t] == 1) n_in += nm;
+        }
+    };
+    // what a replica adds to a pass: its phase tables and S(k), its items, their split partials and results, its records
+    auto bytes_of = [&](long long n_pair, long long n_in) {
+        return (tab_n + e->n_slots) * sizeof(double2) + (size_t)(n_pair + n_in) * sizeof(PairItem) +
+               (size_t)n_pair * nsplit * sizeof(double2) + (size_t)(2 * n_pair + n_in + 1) * sizeof(double) + sizeof(RecipItem) +
+               sizeof(EnergyRep) + sizeof(int);
+    };
+    // the passes: replicas in the caller's order, as many as `chunk` and the budget allow, never fewer than one
+    const int most = chunk > 0 ? std::min(chunk, kReplicasPassMax) : kReplicasPassMax;
+    std::vector<Pass> passes;
+    size_t max_tab = 0, max_items = 0, max_rec = 0, max_res = 0;
+    for (int i = 0; i < n;) {
+        Pass p{i, 0, 0, 0};
+        size_t bytes = 0;
+        while (i < n && p.c < most) {
+            long long np, ni;
+            counts(replicas[i], np, ni);
+            const size_t b = bytes_of(np, ni);
+            if (p.c > 0 && (bytes + b > kReplicasPassBytes || (p.n_pair + np) * nsplit > kReplicasPassItems)) break;
+            bytes += b; p.n_pair += np; p.n_in += ni; p.c += 1; ++i;
+        }
+        if (p.n_pair * nsplit >= ((long long)1 << 31) - kPairWaves)
+            return set_error(MGPU_ERR_CAPACITY, "system_energy_replicas: one replica's pair sweep exceeds 2^31 work units");
+        passes.push_back(p);
+        max_tab = std::max(max_tab, (size_t)p.c * (tab_n + e->n_slots) * sizeof(double2));
+        max_items = std::max(max_items, (size_t)(p.n_pair + p.n_in) * sizeof(PairItem));
+        max_rec = std::max(max_rec, (size_t)p.c * (sizeof(RecipItem) + sizeof(EnergyRep) + sizeof(int)));
+        max_res = std::max(max_res, (size_t)(2 * p.n_pair + p.n_in + p.c) * sizeof(double));
+    }
+    // every block is reserved once, before the first pass: nothing is freed under a pass still in flight
+    const size_t head = (size_t)n * (a_deviation ? 7 : 6) * sizeof(double);
+    if ((rc = e->d_out.reserve(head + max_res))) return rc;
+    if ((rc = e->d_items.reserve(std::max<size_t>(max_items, 8)))) return rc;
+    if ((rc = e->d_items2.reserve(max_rec))) return rc;
+    if ((rc = e->lanes[0].d_scratch.reserve(max_tab))) return rc;
+    double *d_out6 = (double *)e->d_out.p, *d_dev = d_out6 + (size_t)n * 6, *d_res = (double *)((char *)e->d_out.p + head);
+    // the host images of the passes' uploads live until the stream has been waited for
+    std::deque<std::vector<PairItem>> h_items;
+    std::deque<std::vector<char>> h_recs;
+    for (const Pass &p : passes) {
+        const int c = p.c, n_pair = (int)p.n_pair, n_in = (int)p.n_in;
+        // ComputePairwiseEnergy (energy_utils.f90:83-115): one ordered item per molecule; behind them the intra items of the
+        // ACTIVE types (energy_utils.f90:67-69), both replica by replica in (type, molecule) order
+        h_items.emplace_back();
+        std::vector<PairItem> &items = h_items.back();
+        items.reserve((size_t)n_pair + n_in);
+        h_recs.emplace_back((size_t)c * (sizeof(RecipItem) + sizeof(EnergyRep) + sizeof(int)));
+        char *blob = h_recs.back().data();
+        RecipItem *rits = (RecipItem *)blob;
+        EnergyRep *reps = (EnergyRep *)(blob + (size_t)c * sizeof(RecipItem));
+        int *idx = (int *)(blob + (size_t)c * (sizeof(RecipItem) + sizeof(EnergyRep)));
+        int in_at = 0;
+        for (int i = 0; i < c; ++i) {
+            const int r = replicas[p.first + i];
+            EnergyRep &er = reps[i];
+            er = EnergyRep{};
+            er.replica = r;
+            er.pair_first = (int)items.size();
+            er.intra_first = in_at;
+            for (int t = 0; t < tp.n_res; ++t) {
+                er.n[t] = e->h_nmol[r * tp.n_res + t];
+                for (int m = 0; m < er.n[t]; ++m) items.push_back(PairItem{r, t, m, -1, 1});
+                if (e->is_active[t] == 1) in_at += er.n[t];
+            }
+            rits[i] = RecipItem{i, 0, -1, MGPU_NONE, -1, 0};       // block i of the pass's S(k): the energy of A as it is
+            idx[i] = r;
+        }
+        for (int i = 0; i < c; ++i)
+            for (int t = 0; t < tp.n_res; ++t) {
+                if (e->is_active[t] != 1) continue;
+                for (int m = 0; m < reps[i].n[t]; ++m) items.push_back(PairItem{reps[i].replica, t, m, -1, 0});
+            }
+        HIP_TRY(hipMemcpyAsync(e->d_items2.p, blob, h_recs.back().size(), hipMemcpyHostToDevice, e->stream));
+        const RecipItem *d_rits = (const RecipItem *)e->d_items2.p;
+        const EnergyRep *d_reps = (const EnergyRep *)((const char *)e->d_items2.p + (size_t)c * sizeof(RecipItem));
+        const int *d_idx = (const int *)((const char *)e->d_items2.p + (size_t)c * (sizeof(RecipItem) + sizeof(EnergyRep)));
+        double *d_lj = d_res, *d_c = d_lj + n_pair, *d_in = d_c + n_pair, *d_u = d_in + n_in;
+        if (n_pair > 0) {
+            HIP_TRY(hipMemcpyAsync(e->d_items.p, items.data(), items.size() * sizeof(PairItem), hipMemcpyHostToDevice, e->stream));
+            if ((rc = launch_pair(e, e->lanes[0], (const PairItem *)e->d_items.p, n_pair, 0, 1, nsplit, d_lj, d_c, true))) return rc;
+            if (n_in > 0 && (rc = launch_intra(e, e->lanes[0], (const PairItem *)e->d_items.p + n_pair, n_in, nullptr, 1, d_in))) return rc;
+        }
+        // ComputeEwaldRecip (energy_utils.f90:270-286): S(k) of every replica of the pass into scratch (the slots no k owns
+        // stay zero, as the engine's one-replica scratch keeps them), then sum ff W |S|^2, one item per replica
+        double2 *d_tab = (double2 *)e->lanes[0].d_scratch.p, *d_S = d_tab + (size_t)c * tab_n;
+        HIP_TRY(hipMemsetAsync(d_S, 0, (size_t)c * e->n_slots * sizeof(double2), e->stream));
+        if ((rc = launch_sfactor_replicas(e, d_idx, c, d_tab, false, d_S))) return rc;
+        if ((rc = launch_recip(e, e->lanes[0], d_rits, c, 1, 1, false, d_S, d_u))) return rc;
+        hipLaunchKernelGGL(energy_reduce_replicas_kernel, dim3((c + 63) / 64), dim3(64), 0, e->stream, tp.n_res, d_reps, c, active_mask,
+                           self, (const double *)d_lj, (const double *)d_c, (const double *)d_in, (const double *)d_u,
+                           d_out6 + (size_t)p.first * 6);
+        if (a_deviation)
+            hipLaunchKernelGGL(a_deviation_replicas_kernel, dim3(c), dim3(kBlock), 0, e->stream, e->bx, e->d_kslot, d_idx,
+                               (const double2 *)e->d_A, (const double2 *)d_S, d_dev + p.first);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(out, d_out6, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    if (a_deviation) HIP_TRY(hipMemcpyAsync(a_deviation, d_dev, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+    return sync_stream(e);
+}
+
+int mgpu_init_structure_factor_replicas(mgpu_engine *e, int n, const int *replicas, int mode) {
+    int rc = check_replica_list(e, n, replicas, "init_structure_factor_replicas");
+    if (rc) return rc;
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    if (mode == 0) {
+        // runs of consecutive replicas are zeroed together
+        std::vector<int> sorted(replicas, replicas + n);
+        std::sort(sorted.begin(), sorted.end());
+        for (int i = 0; i < n;) {
+            int j = i + 1;
+            while (j < n && sorted[j] == sorted[j - 1] + 1) ++j;
+            HIP_TRY(hipMemsetAsync(e->d_A + (size_t)sorted[i] * e->n_slots, 0, (size_t)(j - i) * e->n_slots * sizeof(double2), e->stream));
+            i = j;
+        }
+        return sync_stream(e);
+    }
+    const size_t tab_n = phase_tab_entries(e);
+    const int per_pass = (int)std::max<size_t>(1, std::min<size_t>(kReplicasPassMax, kReplicasPassBytes / (tab_n * sizeof(double2))));
+    if ((rc = e->d_items2.reserve((size_t)n * sizeof(int)))) return rc;
+    if ((rc = e->lanes[0].d_scratch.reserve((size_t)std::min(n, per_pass) * tab_n * sizeof(double2)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_items2.p, replicas, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    for (int first = 0; first < n; first += per_pass)
+        if ((rc = launch_sfactor_replicas(e, (const int *)e->d_items2.p + first, std::min(per_pass, n - first),
+                                          (double2 *)e->lanes[0].d_scratch.p, true, e->d_A)))
+            return rc;
+    return sync_stream(e);
+}
+
+}  // extern "C"

@@ -418,6 +418,28 @@ class Engine:
     def init_structure_factor(self, replica=0, full=True):
         check(self.L.mgpu_init_structure_factor(self.h, C.c_int(replica), C.c_int(1 if full else 0)))
 
+    def _replica_list(self, replicas):
+        if replicas is None:
+            return np.arange(self.n_replicas, dtype=np.int32)
+        return np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
+
+    def system_energy_replicas(self, replicas=None, chunk=None, a_deviation=False):
+        """ComputeSystemEnergy of many replicas in one call: an (n, 6) array whose row i is system_energy(replicas[i]) bit for
+        bit (non_coulomb, coulomb, recip_coulomb, ewald_self, intra_coulomb, total); with a_deviation also the (n,) array
+        max |A(k) - S(k)| per replica.  replicas = None: all of them; chunk = replicas per device pass (None: the engine's)."""
+        r = self._replica_list(replicas)
+        n = r.shape[0]
+        out = np.zeros((n, 6))
+        dev = np.zeros(n) if a_deviation else None
+        check(self.L.mgpu_system_energy_replicas(self.h, C.c_int(n), _i(r), C.c_int(0 if chunk is None else int(chunk)),
+                                                 _d(out), _d(dev)))
+        return (out, dev) if a_deviation else out
+
+    def init_structure_factor_replicas(self, replicas=None, full=True):
+        """init_structure_factor for many replicas in one call (None: all of them)."""
+        r = self._replica_list(replicas)
+        check(self.L.mgpu_init_structure_factor_replicas(self.h, C.c_int(r.shape[0]), _i(r), C.c_int(1 if full else 0)))
+
     def structure_factor(self, replica=0):
         a = np.zeros((self.nk, 2))
         check(self.L.mgpu_get_structure_factor(self.h, C.c_int(replica), _d(a)))

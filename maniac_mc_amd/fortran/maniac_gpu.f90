@@ -134,6 +134,25 @@ module maniac_gpu
             integer(c_int), value :: replica, mode
             integer(c_int) :: rc
         end function
+        ! the two calls above for many replicas at once (a_deviation: an array of n, or c_null_ptr)
+        function mgpu_system_energy_replicas(e, n, replicas, chunk, out, a_deviation) &
+                bind(C, name="mgpu_system_energy_replicas") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: n, chunk
+            integer(c_int), intent(in) :: replicas(*)
+            real(c_double), intent(out) :: out(6, *)
+            type(c_ptr), value :: a_deviation
+            integer(c_int) :: rc
+        end function
+        function mgpu_init_structure_factor_replicas(e, n, replicas, mode) &
+                bind(C, name="mgpu_init_structure_factor_replicas") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n, mode
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_int) :: rc
+        end function
         function mgpu_pair_energy_candidates(e, n, replica, t, m, use_resident, sites, site_stride, e_nc, e_c) &
                 bind(C, name="mgpu_pair_energy_candidates") result(rc)
             import :: c_ptr, c_int, c_double

@@ -127,6 +127,7 @@ module mc_farm
         integer(int64) :: skipped = 0                      ! no-op selections (empty type, full type)
         type(lane_buffers) :: lane(0:MGPU_LANES - 1)
         logical :: ready = .false.
+        logical :: started = .false.                       ! mfarm_run was called: the chains' states are the driver's own
         integer(int64) :: ticks(7) = 0                     ! generate, submit, wait, resolve, commit, rng, gather
         integer :: rng_kind = 1, n_threads = 1, n_lanes = 2
         integer :: team = 1                                ! OpenMP threads of one lane's loops
@@ -369,8 +370,57 @@ contains
             F%lane(g)%nc = 0
             call alloc_lane(F%lane(g), max(1, F%lane(g)%n), int(max_n1), g)
         end do
+        F%started = .false.
         F%ready = .true.
     end function mfarm_create
+
+    !---------------------------------------------------------------------------
+    ! One replica's own start (after mfarm_create, before the first mfarm_run): replica r (0-based) holds n_mol(ia)
+    ! molecules of every active type, com / off as mfarm_create takes them, and the running energies `energy`.  The
+    ! engine's replica must already hold that configuration with A(k) initialised.  The mirror rows are set only where
+    ! the farm is host-built.  Non-zero code, nothing changed: no farm (5), after the first mfarm_run or with a
+    ! reservoir set (6: the conservation bound was taken from the counts), r out of range or a count above the type's
+    ! capacity (3).
+    !---------------------------------------------------------------------------
+    function mfarm_set_replica(r, n_mol, com, off, energy) bind(C, name="mfarm_set_replica") result(rc)
+        integer(c_int), value :: r
+        integer(c_int), intent(in) :: n_mol(*)
+        real(c_double), intent(in) :: com(3, *), off(3, F%max_n1, *), energy(5)
+        integer(c_int) :: rc
+        integer :: ia, k, src
+        rc = MGPU_OK
+        if (.not. F%ready) then
+            rc = 5
+            return
+        end if
+        if (F%started .or. F%has_rsv) then
+            rc = 6
+            return
+        end if
+        if (r < 0 .or. r >= F%n_replicas) then
+            rc = 3
+            return
+        end if
+        do ia = 1, F%n_active
+            if (n_mol(ia) < 0 .or. n_mol(ia) > F%cap(ia)) then
+                rc = 3
+                return
+            end if
+        end do
+        if (.not. F%device_build) F%mol(:, :, r + 1) = 0.0_real64
+        src = 0
+        do ia = 1, F%n_active
+            if (.not. F%device_build) then
+                do k = 1, n_mol(ia)
+                    F%mol(1:3, F%first(ia) + k, r + 1) = com(:, src + k)
+                    F%mol(4:, F%first(ia) + k, r + 1) = reshape(off(:, :, src + k), [3 * F%max_n1])
+                end do
+            end if
+            F%cnt(ia, r + 1) = n_mol(ia)
+            src = src + n_mol(ia)
+        end do
+        F%energy(:, r + 1) = energy
+    end function mfarm_set_replica
 
     !---------------------------------------------------------------------------
     ! Triclinic box (after mfarm_create): box%matrix and box%reciprocal as the Fortran arrays, and the cell
@@ -1309,6 +1359,7 @@ contains
             rc = 5
             return
         end if
+        F%started = .true.
         ! diagnostic: MFARM_STEPLOG=<file> appends the host timers (microseconds) after every step
         call get_environment_variable("MFARM_STEPLOG", logpath, nlen, ios)
         if (ios == 0 .and. nlen > 0 .and. n_steps > 0) allocate(slog(7, 0:n_steps))

@@ -57,6 +57,7 @@ def lib():
         L.mfarm_create.restype = C.c_int
         L.mfarm_run.restype = C.c_int
         L.mfarm_set_gcmc.restype = C.c_int
+        L.mfarm_set_replica.restype = C.c_int
         L.mfarm_set_reservoir.restype = C.c_int
         L.mfarm_get_reservoir.restype = C.c_int
         L.mfarm_write_block.restype = C.c_int
@@ -103,6 +104,9 @@ class FortranFarm:
     reservoir, deletions put the box's last molecule of t into it, and an insertion from an empty reservoir is skipped.
     ``wide_triclinic=True`` (with ``triclinic_moves``): window mode also applies to a triclinic box with rigid molecules of 6
     to 63 sites (``Engine.farm_set_wide_triclinic``); off by default, and such a farm then keeps the batched path.
+    ``initial=[R Systems]``: every chain starts from its own configuration (the topology and box of ``system``, counts within
+    ``mol_capacity``; anything else raises ValueError before a farm slot is taken): one batched S(k) initialisation and one
+    batched whole-system energy over all replicas, then ``mfarm_set_replica`` per chain.  Default: R copies of ``system``.
     """
 
     _live = None          # the farm created last that is still open (tests close leftovers through it)
@@ -114,7 +118,7 @@ class FortranFarm:
                  rng_kind: int = 1, n_threads: int = 8, mol_capacity=None, gcmc=None,
                  n_lanes: int = 2, n_drivers: int = 1, device_build: bool = False, device_accept: bool = False,
                  window: bool = False, window_depth: int = 2, reservoir=None, triclinic_moves: bool = False,
-                 wide_triclinic: bool = False):
+                 wide_triclinic: bool = False, initial=None):
         self.H = lib()
         # mc_farm.f90 keeps up to MAX_FARMS farms; every call below selects this farm's slot first
         free = [k for k in range(FortranFarm.MAX_FARMS) if k not in FortranFarm._slots]
@@ -127,6 +131,9 @@ class FortranFarm:
         if mol_capacity is None:
             mol_capacity = [max(1, int(n)) for n in system.n_mol]
         self.mol_capacity = [int(c) for c in mol_capacity]
+        if initial is not None:
+            initial = list(initial)
+            self._check_initial(system, initial)
         self.eng = Engine(topo, system.box_matrix, system.bounds_lo, system.real_space_cutoff,
                           system.ewald_tolerance, self.R, device, self.mol_capacity,
                           triclinic_moves=bool(triclinic_moves) and system.is_triclinic())
@@ -135,20 +142,35 @@ class FortranFarm:
         self.wide_triclinic = bool(wide_triclinic) and bool(triclinic_moves) and system.is_triclinic()
         if self.wide_triclinic:
             self.eng.farm_set_wide_triclinic(True)
-        self.eng.load_system(system, 0)
+        if initial is None:
+            self.eng.load_system(system, 0)
         # device_build: the engine keeps the molecules' frames (com, offsets) and builds the trial moves itself; the
         # Fortran driver then holds no mirror of the coordinates (orthorhombic boxes; triclinic ones with triclinic_moves,
         # Engine.set_triclinic_moves -- without it a triclinic system's moves are built on the host, as they always were)
         self.triclinic_moves = bool(triclinic_moves) and system.is_triclinic()
         self.device_build = bool(device_build) and (not system.is_triclinic() or self.triclinic_moves)
-        if self.device_build:
-            for tt in range(topo.n_res):
-                if topo.is_active[tt]:
-                    self.eng.set_frames(0, tt, system.com[tt], system.offsets[tt])
-        self.eng.init_structure_factor(0, True)
-        for r in range(1, self.R):
-            self.eng.replica_copy(r, 0)
-        e0 = self.eng.system_energy(0)
+        if initial is not None:
+            # every replica its own configuration: one S(k) and one whole-system energy pass over all of them; the driver
+            # is created with replica 0's state and told every replica's own below (mfarm_set_replica)
+            for r, s_r in enumerate(initial):
+                self.eng.load_system(s_r, r)
+                if self.device_build:
+                    for tt in range(topo.n_res):
+                        if topo.is_active[tt]:
+                            self.eng.set_frames(r, tt, s_r.com[tt], s_r.offsets[tt])
+            self.eng.init_structure_factor_replicas()
+            e_all = self.eng.system_energy_replicas()
+            system = initial[0]
+            e0 = dict(zip(("non_coulomb", "coulomb", "recip_coulomb", "ewald_self", "intra_coulomb"), e_all[0, :5]))
+        else:
+            if self.device_build:
+                for tt in range(topo.n_res):
+                    if topo.is_active[tt]:
+                        self.eng.set_frames(0, tt, system.com[tt], system.offsets[tt])
+            self.eng.init_structure_factor(0, True)
+            for r in range(1, self.R):
+                self.eng.replica_copy(r, 0)
+            e0 = self.eng.system_energy(0)
         active = [t for t in range(topo.n_res) if topo.is_active[t]]
         self.active = np.array(active, dtype=np.int32)
         n1 = np.array([topo.atoms_in_res[t] for t in active], dtype=np.int32)
@@ -185,6 +207,22 @@ class FortranFarm:
                                  C.c_double(rotation_step), C.c_double(p_translation), C.c_int(seed),
                                  C.c_int(rng_kind), C.c_int(n_threads), C.c_int(n_lanes))
         _lib.check(rc)
+        if initial is not None:
+            for r, s_r in enumerate(initial):
+                nm_r = np.array([s_r.n_mol[t] for t in active], dtype=np.int32)
+                tot_r = max(1, int(nm_r.sum()))
+                com_r = np.zeros((tot_r, 3))
+                off_r = np.zeros((tot_r, max_n1, 3))
+                pos = 0
+                for k, t in enumerate(active):
+                    com_r[pos:pos + nm_r[k]] = s_r.com[t]
+                    off_r[pos:pos + nm_r[k], :n1[k]] = s_r.offsets[t]
+                    pos += nm_r[k]
+                e_r = np.ascontiguousarray(e_all[r, :5])
+                rc = self.H.mfarm_set_replica(C.c_int(r), nm_r.ctypes.data_as(_ip), com_r.ctypes.data_as(_dp),
+                                              off_r.ctypes.data_as(_dp), e_r.ctypes.data_as(_dp))
+                if rc:
+                    raise RuntimeError(f"mfarm_set_replica({r}): code {rc}")
         if system.is_triclinic():
             from .engine import box_prepare
             _, volume, reciprocal, _ = box_prepare(system.box_matrix)
@@ -220,8 +258,39 @@ class FortranFarm:
             off = np.ascontiguousarray(np.asarray(off, dtype=np.float64).reshape(-1, n1, 3))
             _lib.check(self.H.mfarm_set_reservoir(C.c_int(int(t)), C.c_int(off.shape[0]), off.ctypes.data_as(_dp)))
 
+    def _check_initial(self, system, initial):
+        """`initial`: R Systems with the topology and the box of `system`, every count within mol_capacity."""
+        if len(initial) != self.R:
+            raise ValueError(f"initial: {len(initial)} systems for {self.R} replicas")
+        topo = system.topo
+        for r, s_r in enumerate(initial):
+            tr = s_r.topo
+            same = tr is topo or (tr.n_res == topo.n_res and all(
+                np.array_equal(np.asarray(getattr(tr, a)), np.asarray(getattr(topo, a)))
+                for a in ("atoms_in_res", "atom_types", "charges", "is_active", "epsilon", "sigma")))
+            if not same:
+                raise ValueError(f"initial[{r}]: another topology than the farm's system")
+            if not (np.array_equal(np.asarray(s_r.box_matrix), np.asarray(system.box_matrix))
+                    and np.array_equal(np.asarray(s_r.bounds_lo), np.asarray(system.bounds_lo))):
+                raise ValueError(f"initial[{r}]: another box than the farm's system")
+            for t in range(topo.n_res):
+                if int(s_r.n_mol[t]) > self.mol_capacity[t]:
+                    raise ValueError(f"initial[{r}]: {int(s_r.n_mol[t])} molecules of type {t} exceed the capacity "
+                                     f"{self.mol_capacity[t]}")
+
     def _select(self):
         self.H.mfarm_select(C.c_int(self.slot))
+
+    def audit(self, replicas=None):
+        """Every listed chain's energy from scratch against its running energy, in K, from ONE system_energy_replicas call:
+        recomputed (n, 6), running (n, 5), energy_deviation (n,) = the largest |running - recomputed| over the five components,
+        a_deviation (n,) = max |A(k) - S(k)|.  replicas = None: all of them."""
+        reps = np.arange(self.R, dtype=np.int32) if replicas is None else np.ascontiguousarray(replicas, dtype=np.int32).reshape(-1)
+        recomputed, a_dev = self.eng.system_energy_replicas(reps, a_deviation=True)
+        running = np.array([self.energy(int(r)) for r in reps]).reshape(-1, 5)
+        return dict(recomputed=recomputed, running=running,
+                    energy_deviation=np.max(np.abs(running - recomputed[:, :5]), axis=1) if len(reps) else np.zeros(0),
+                    a_deviation=a_dev)
 
     def run(self, n_steps: int) -> int:
         """Advance every chain by n_steps move selections; returns the moves accepted during this call."""

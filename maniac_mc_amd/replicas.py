@@ -71,7 +71,7 @@ def _stats(x):
 
 def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=None, fugacities=None, frames=(0,),
                  mode="auto", device=0, nb_block=None, nb_step=None, mol_capacity=None, n_lanes=2, n_threads=8,
-                 chunk=None, wide_triclinic=False):
+                 chunk=None, wide_triclinic=False, restart_from=None, audit=False):
     """Run `replicas` independent chains of the input; returns a dict with the final energies (R, 5) in K (non-Coulomb,
     Coulomb, reciprocal, self, intramolecular), counts (R, n_active), chain counters (R, 8), the farm's counters, the
     mode that ran and the block timings.
@@ -87,6 +87,14 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     (Engine.farm_set_wide_triclinic); off by default: "windows" then raises for such an input, as it always did.  "auto" is
     not changed by it.
     ``chunk``: replicas per snapshot launch (default: about SNAPSHOT_BYTES at the types' capacities).
+    ``restart_from``: a directory an earlier run_replicas wrote: replica r starts from
+    <restart_from>/replica_NNNN/topology.data (read with the same input and parameter files; `data` still supplies the
+    topology).  A NEW run from those configurations -- blocks count from 0, streams are seeded from `seed` and r as always --
+    not a bit-continuation: topology.data holds positions to seven decimals.  Not with a reservoir, whose contents
+    topology.data does not hold.
+    ``audit``: True -> after the last block every replica's energy and S(k) are recomputed from scratch (FortranFarm.audit,
+    one batched call) and written to <outdir>/audit.dat, one line per replica in kcal/mol: replica, running total, recomputed
+    total, largest component difference, max |A(k) - S(k)|; the result gains ``recomputed_energy`` (R, 6) in K and ``audit``.
     """
     import time
     if mode not in MODES:
@@ -94,6 +102,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     R = int(replicas)
     if R < 1:
         raise ValueError("replicas must be at least 1")
+    if restart_from is not None and reservoir_path:
+        raise ValueError("restart_from cannot be combined with a reservoir: topology.data does not hold a reservoir's contents")
     system, inp, dat = io_maniac.load_system(maniac, data, inc, with_data=True)
     rdat = io_maniac.read_lammps_data(reservoir_path, inp) if reservoir_path else None
     topo = system.topo
@@ -125,12 +135,25 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         fug_grid = np.tile(np.array([inp.fugacity_per_A3()[t] for t in active])[None, :], (R, 1)) if gcmc else None
     gcmc_arg = dict(p_translation=inp.translation_proba, p_rotation=inp.rotation_proba, fugacity=fug_grid) if gcmc else None
     reservoir = io_maniac.reservoir_offsets(reservoir_path, inp) if reservoir_path else None
+    initial = None
+    if restart_from is not None:
+        initial = []
+        for r in range(R):
+            path = os.path.join(restart_from, f"replica_{r:04d}", "topology.data")
+            if not os.path.isfile(path):
+                raise ValueError(f"restart_from: {path} is missing")
+            s_r, _ = io_maniac.load_system(maniac, path, inc)
+            for t in range(n_res):
+                if int(s_r.n_mol[t]) > int(mol_capacity[t]):
+                    raise ValueError(f"restart_from: {path} holds {int(s_r.n_mol[t])} molecules of residue type {t}, "
+                                     f"above the capacity {int(mol_capacity[t])}")
+            initial.append(s_r)
     device_build = (not triclinic or triclinic_moves) and mode != "host"
     farm = FortranFarm(system, R, device=device, seed=int(seed), translation_step=inp.translation_step,
                        rotation_step=inp.rotation_step_angle, p_translation=inp.translation_proba, n_threads=n_threads,
                        mol_capacity=mol_capacity, gcmc=gcmc_arg, n_lanes=n_lanes, device_build=device_build,
                        device_accept=mode == "device_accept", window=mode in ("auto", "windows"), reservoir=reservoir,
-                       triclinic_moves=triclinic_moves, wide_triclinic=bool(wide_triclinic) and triclinic_moves)
+                       triclinic_moves=triclinic_moves, wide_triclinic=bool(wide_triclinic) and triclinic_moves, initial=initial)
     try:
         ran = "host" if not farm.device_build else ("windows" if farm.window else
                                                      ("device_accept" if farm.device_accept else "device"))
@@ -211,7 +234,21 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         write(nb_block, True)
         _lib.check(0)
         energies = np.array([farm.energy(r) for r in range(R)])
-        return dict(energy=energies, counts=farm.counts(), chain_counters=farm.chain_counters(), counters=farm.counters(),
-                    accepted=farm.accepted, mode=ran, seconds=times, group=group)
+        res = dict(energy=energies, counts=farm.counts(), chain_counters=farm.chain_counters(), counters=farm.counters(),
+                   accepted=farm.accepted, mode=ran, seconds=times, group=group)
+        if audit:
+            a = farm.audit()
+            run_k, rec_k = a["running"], a["recomputed"]
+            with open(os.path.join(root, "audit.dat"), "w") as f:
+                f.write("#  replica    running_total  recomputed_total   max_component_diff        max_|A-S|\n")
+                for r in range(R):
+                    # (the totals as energy.dat forms its own: the five components added in K, then kcal/mol)
+                    tot_run = (run_k[r, 0] + run_k[r, 1] + run_k[r, 2] + run_k[r, 3] + run_k[r, 4]) * KB_KCALMOL
+                    tot_rec = (rec_k[r, 0] + rec_k[r, 1] + rec_k[r, 2] + rec_k[r, 3] + rec_k[r, 4]) * KB_KCALMOL
+                    f.write(f"{r:10d} {tot_run:16.6f} {tot_rec:17.6f} {a['energy_deviation'][r] * KB_KCALMOL:20.6e} "
+                            f"{a['a_deviation'][r]:16.6e}\n")
+            res["recomputed_energy"] = a["recomputed"]
+            res["audit"] = a
+        return res
     finally:
         farm.close()

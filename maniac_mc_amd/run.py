@@ -303,6 +303,12 @@ def main(argv=None):
                     help="with --replicas: replicas writing trajectory / topology every block: 0,3,7 | all | none (default 0)")
     ap.add_argument("--farm-mode", default="auto", choices=("auto", "windows", "device", "device_accept", "host"),
                     help="with --replicas: how the farm builds and decides its steps (default auto)")
+    ap.add_argument("--restart-from", dest="restart_from", default=None, metavar="DIR",
+                    help="with --replicas: replica r starts from DIR/replica_NNNN/topology.data (a new run from those "
+                         "configurations; -d still supplies the topology)")
+    ap.add_argument("--audit", action="store_true",
+                    help="with --replicas: after the last block recompute every replica's energy and S(k) from scratch and "
+                         "write <out>/audit.dat")
     a = ap.parse_args(argv)
     try:
         chain_run = parse_chain_run(a.chain_run) if a.chain_run is not None else None
@@ -319,6 +325,8 @@ def main(argv=None):
     if a.replicas is None:
         if a.fugacities is not None or a.frames != "0" or a.farm_mode != "auto":
             ap.error("--fugacities, --frames and --farm-mode need --replicas")
+        if a.restart_from is not None or a.audit:
+            ap.error("--restart-from and --audit need --replicas")
     else:
         from . import replicas as farm_run
         if a.as_written:
@@ -338,7 +346,7 @@ def main(argv=None):
         try:
             res = farm_run.run_replicas(a.maniac, a.data, a.inc, a.out, a.replicas, seed=a.seed, reservoir_path=a.reservoir,
                                         fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device,
-                                        wide_triclinic=a.wide_triclinic)
+                                        wide_triclinic=a.wide_triclinic, restart_from=a.restart_from, audit=a.audit)
         except ValueError as err:
             print(f"error: {err}", file=sys.stderr)
             return 2

@@ -19,7 +19,7 @@ import tempfile
 from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-UNITS = ("mgpu_engine.hip", "mgpu_launch.hip", "mgpu_lanes.hip", "mgpu_windows.hip")
+UNITS = ("mgpu_engine.hip", "mgpu_launch.hip", "mgpu_lanes.hip", "mgpu_windows.hip", "mgpu_replicas.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fopenmp", "-Rpass-analysis=kernel-resource-usage"]
 KEYS = [("vgpr", r"VGPRs"), ("agpr", r"AGPRs"), ("sgpr", r"SGPRs"), ("spillV", r"VGPRs? Spill"), ("spillS", r"SGPRs? Spill"),
         ("scratch", r"ScratchSize \[bytes/lane\]"), ("occ", r"Occupancy \[waves/SIMD\]"), ("lds", r"LDS Size \[bytes/block\]")]
@@ -87,6 +87,7 @@ def main():
         root = os.path.abspath(args[i + 1])
         del args[i:i + 2]
     srcs = [os.path.join(root, "maniac_mc_amd", "csrc", f) for f in UNITS]
+    srcs = [s for s in srcs if os.path.exists(s)]          # (--root of a checkout from before a unit was added)
     with tempfile.TemporaryDirectory() as d, ThreadPoolExecutor(max_workers=len(srcs)) as pool:
         built = list(pool.map(lambda s: compile_unit(s, d, args, digest), srcs))
     rows = []            # (mangled symbol, resource columns), in the units' order
