@@ -397,6 +397,29 @@ int mgpu_replica_get_reservoir(mgpu_engine *e, int replica, int t, int *n, doubl
  * One snapshot at a time per engine. */
 int mgpu_farm_snapshot_submit(mgpu_engine *e, int n, const int *replicas, long long *bytes);
 int mgpu_farm_snapshot_wait(mgpu_engine *e, const void **data, long long *bytes);
+/* State block: the WHOLE resident state of the replicas replicas[0..n-1] (any order, any subset, each once) out of an engine,
+ * and into another one, in ONE launch each way.  Export is ordered as a farm snapshot is (the lanes drained, A(k) back in its
+ * primary buffer) and gathers, per listed replica: A(k) as the engine holds it (2 n_slots doubles, the engine's slot order),
+ * and per residue type the occupied position planes, the frames com / off where the engine holds them, and the reservoir --
+ * {count, capacity} and the whole block.  Values are copied bit for bit; nothing is wrapped, rebuilt or recomputed.  The block
+ * is copied into a pinned host buffer the engine owns; mgpu_state_export_wait waits for it and returns the buffer (valid until
+ * the next export or the engine's destruction) and its size.  One export at a time per engine.
+ * Layout (8-byte words from the start; csrc/mgpu_internal.h holds it as integer functions): a head {magic, n, n_res, n_slots,
+ * frames held, total words, 0, 0}; the box (matrix and lower bounds, 12 doubles); per type {sites, mol_capacity}; per listed
+ * replica {its index, first word of its A(k)}; per (listed replica, type) a record {n, nf, reservoir capacity, flags, first
+ * word of pos, com, off, reservoir (-1: none)}; then the data, every segment and plane 16-byte aligned.  nf = molecules of
+ * frames carried: n, or 1 for an empty type whose slot 0 still holds the offsets a by-count insertion copies.  flags = the
+ * host-side marks a later launch reads: 1 in_range, 2 frames_ok, 4 frames_tight, 8 frames_held, 16 rsv_tight.
+ * mgpu_state_import checks the block against the engine first -- the list's length, residue types, sites per type, capacities,
+ * n_slots, the box, and the layout the engine itself gives those counts must all agree; MGPU_ERR_INVALID_ARG or
+ * MGPU_ERR_CAPACITY otherwise, and nothing is written -- then scatters it into the listed replicas (which need not be the
+ * ones it was taken from), allocating frames and reservoirs as the block needs, restores the host-side marks and clears what
+ * every reload clears (stall marks, the other A(k) buffer's ownership, the buffer switch).  Refused (MGPU_ERR_STATE) while farm
+ * windows or a chain run of a listed replica are in flight.  A block of 2^31 words or more is refused either way: the caller
+ * cuts large farms by the replica list.  A block continues a run bit for bit on the same library build and GPU model. */
+int mgpu_state_export_submit(mgpu_engine *e, int n, const int *replicas, long long *bytes);
+int mgpu_state_export_wait(mgpu_engine *e, const void **data, long long *bytes);
+int mgpu_state_import(mgpu_engine *e, int n, const int *replicas, const void *data, long long bytes);
 /* The same trials with the ACCEPTANCE TEST ON THE DEVICE.  The k sweep is the last kernel of a trial, one workgroup per
  * candidate; once it has summed the candidate's reciprocal energies its first thread holds everything
  * mc_acceptance_probability (src/monte_carlo_utils.f90:184-226) needs, so it applies the rule itself,

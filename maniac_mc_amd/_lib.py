@@ -43,6 +43,7 @@ EXPORTS = [
     "mgpu_chain_run_force", "mgpu_chain_run_close", "mgpu_chain_run_get_stats", "mgpu_chain_run_get_launches", "mgpu_chain_run_set_triclinic", "mgpu_chain_run_set_gc", "mgpu_chain_run_push_gc", "mgpu_chain_run_set_wide", "mgpu_comm_unique_id", "mgpu_comm_create",
     "mgpu_comm_destroy", "mgpu_comm_rank", "mgpu_allgather_block_stats", "mgpu_append_atom_records", "mgpu_format_fixed", "mgpu_phase_factors", "mgpu_synchronize", "mgpu_profile_enable", "mgpu_profile_reset",
     "mgpu_profile_get", "mgpu_system_energy_replicas", "mgpu_init_structure_factor_replicas",
+    "mgpu_state_export_submit", "mgpu_state_export_wait", "mgpu_state_import",
 ]
 
 

@@ -331,6 +331,12 @@ struct mgpu_engine {
     HostBuf h_snap, h_snap_items;
     size_t snap_bytes = 0;
     bool snap_pending = false;
+    // state blocks (mgpu_state_export_submit / _wait, mgpu_state_import): the item table, the block on the device and the
+    // pinned host copy of an export, which the caller reads after the wait
+    DevBuf d_state, d_state_items;
+    HostBuf h_state, h_state_items;
+    size_t state_bytes = 0;
+    bool state_pending = false;
     // single-chain windows (mgpu_chain_window): pinned, host-coherent blocks the kernel reads its candidates from and
     // writes its results to (no copies, no stream synchronisation: the host polls the tag), and device scratch
     struct Chain {

@@ -302,6 +302,143 @@ __global__ __launch_bounds__(kBlock) void farm_snapshot_kernel(const SnapItem *_
     }
 }
 
+// ---- state blocks (mgpu_state_export_submit / mgpu_state_import): one run-strided segment of one replica per item ----
+struct StateItem {
+    unsigned long long *base;     // the engine's array the segment lives in (pos, com, off, A(k), a reservoir block, the {count, capacity} table)
+    long long src, stride;        // first word of the segment in `base`, words from one run to the next
+    long long dst;                // first word in the block: the runs follow each other there
+    int len, nrun;                // words per run, runs
+    int vec;                      // state_item_vec: 16-byte accesses
+    int nmol_at, nmol;            // import: the molecule count to store at d_nmol[nmol_at] (-1: none)
+};
+
+// Moves the items' segments between the engine's arrays and the block (mgpu_internal.h: the state block), IMPORT = false out
+// of the engine, true into it: the same item table and the same loops either way.  Copies of 8-byte words, bit for bit; pairs of
+// words where state_item_vec allows.  gridDim.y workgroups share a large item.  Ordered by the stream alone.
+template <bool IMPORT>
+__global__ __launch_bounds__(kBlock) void state_block_kernel(const StateItem *__restrict__ items, unsigned long long *__restrict__ block,
+                                                             int *__restrict__ nmol) {
+    const StateItem &it = items[blockIdx.x];
+    const unsigned stride = gridDim.y * blockDim.x, q0 = blockIdx.y * blockDim.x + threadIdx.x;
+    if (IMPORT && it.nmol_at >= 0 && q0 == 0) nmol[it.nmol_at] = it.nmol;
+    if (it.vec) {
+        const unsigned half = (unsigned)it.len >> 1, nq = half * (unsigned)it.nrun;
+        for (unsigned q = q0; q < nq; q += stride) {
+            const unsigned r = q / half, k = q - r * half;
+            ulonglong2 *eng = reinterpret_cast<ulonglong2 *>(it.base + it.src + (long long)r * it.stride) + k;
+            ulonglong2 *blk = reinterpret_cast<ulonglong2 *>(block + it.dst + (long long)r * it.len) + k;
+            if (IMPORT) *eng = *blk; else *blk = *eng;
+        }
+    } else {
+        const unsigned len = (unsigned)it.len, nq = len * (unsigned)it.nrun;
+        for (unsigned q = q0; q < nq; q += stride) {
+            const unsigned r = q / len, k = q - r * len;
+            unsigned long long *eng = it.base + it.src + (long long)r * it.stride + k;
+            unsigned long long *blk = block + it.dst + (long long)r * it.len + k;
+            if (IMPORT) *eng = *blk; else *blk = *eng;
+        }
+    }
+}
+
+// what a block holds of (listed replica, type): the record's first four words
+struct StateCount { int n, nf, rsv_cap; long long flags; };
+
+// The block of the replicas replicas[0 .. n) with the counts c[i * n_res + t]: its header into `head` (state_data_at words)
+// and, where `items` is given, the item table with the engine's pointers as they are now.  total = the block's words, most =
+// the largest item's.  Export and import both plan with this.
+static void state_plan(const mgpu_engine *e, int n, const int *replicas, const StateCount *c, bool frames, std::vector<long long> &head,
+                       std::vector<StateItem> *items, size_t &total, size_t &most) {
+    const Topo &tp = e->tp;
+    const int n_res = tp.n_res;
+    head.assign(state_data_at(n, n_res), 0);
+    head[0] = kStateMagic; head[1] = n; head[2] = n_res; head[3] = e->n_slots; head[4] = frames ? 1 : 0;
+    std::memcpy(&head[kStateHeadWords], e->box_matrix, 9 * sizeof(double));
+    std::memcpy(&head[kStateHeadWords + 9], e->bounds_lo, 3 * sizeof(double));
+    for (int t = 0; t < n_res; ++t) {
+        head[state_types_at() + (size_t)kStateTypeWords * t] = tp.n1[t];
+        head[state_types_at() + (size_t)kStateTypeWords * t + 1] = tp.cap[t];
+    }
+    if (items) items->clear();
+    most = 0;
+    auto add = [&](void *base, long long src, long long stride, long long dst, long long len, long long nrun) {
+        most = std::max(most, (size_t)(len * nrun));
+        if (!items || len * nrun == 0) return;
+        items->push_back(StateItem{(unsigned long long *)base, src, stride, dst, (int)len, (int)nrun,
+                                   state_item_vec(src, dst, len, nrun > 1 ? stride : 0) ? 1 : 0, -1, 0});
+    };
+    // the planes x, y, z of the first `nm` molecules of (r, t) in an array laid out as pos is
+    auto planes = [&](double *base, int r, int t, int nm, long long dst) {
+        const long long n1 = tp.n1[t], pw = (long long)state_plane_words(nm, tp.n1[t]);
+        for (int d = 0; d < 3; ++d) {
+            const long long src = ((long long)r * 3 + d) * tp.n_cap_atoms + tp.seg_off[t];
+            if (tp.site_major[t]) add(base, src, 0, dst + d * pw, nm * n1, 1);
+            else add(base, src, tp.cap[t], dst + d * pw, nm, n1);
+        }
+    };
+    size_t at = state_data_at(n, n_res);
+    for (int i = 0; i < n; ++i) {
+        const int r = replicas[i];
+        head[state_reps_at(n_res) + (size_t)kStateRepWords * i] = r;
+        head[state_reps_at(n_res) + (size_t)kStateRepWords * i + 1] = (long long)at;
+        add(e->d_A, (long long)r * e->n_slots * 2, 0, (long long)at, (long long)state_A_words(e->n_slots), 1);
+        at += state_A_words(e->n_slots);
+        for (int t = 0; t < n_res; ++t) {
+            const size_t idx = (size_t)r * n_res + t;
+            const StateCount &k = c[(size_t)i * n_res + t];
+            const StateSegs sg = state_type_segments(at, k.n, k.nf, tp.n1[t], k.rsv_cap, frames && !e->frozen[t]);
+            long long *rec = &head[state_rec_at(n, n_res, i, t)];
+            rec[kStateRecN] = k.n; rec[kStateRecNf] = k.nf; rec[kStateRecRsvCap] = k.rsv_cap; rec[kStateRecFlags] = k.flags;
+            rec[kStateRecPos] = sg.pos; rec[kStateRecCom] = sg.com; rec[kStateRecOff] = sg.off; rec[kStateRecRsv] = sg.rsv;
+            if (items) items->push_back(StateItem{nullptr, 0, 0, 0, 0, 0, 0, (int)idx, k.n});      // the count (import)
+            planes(e->d_pos, r, t, k.n, sg.pos);
+            if (sg.com >= 0) {
+                const long long pw = (long long)state_plane_words(k.nf, 1);
+                for (int d = 0; d < 3; ++d)
+                    add(e->d_com, ((long long)r * 3 + d) * tp.n_mol_slots + tp.mol_off[t], 0, sg.com + d * pw, k.nf, 1);
+                planes(e->d_off, r, t, k.nf, sg.off);
+            }
+            if (sg.rsv >= 0) {
+                add(e->d_rsv_nc, (long long)idx, 0, sg.rsv, 1, 1);
+                add(e->rsv_ptr.empty() ? nullptr : e->rsv_ptr[idx], 0, 0, sg.rsv + 2, 3ll * k.rsv_cap * tp.n1[t], 1);
+            }
+            at = sg.end;
+        }
+    }
+    total = at;
+    head[5] = (long long)total;
+}
+
+// uploads the item table and launches state_block_kernel<IMPORT> over it on lane 0's stream
+template <bool IMPORT>
+static int state_launch(mgpu_engine *e, const std::vector<StateItem> &items, size_t most) {
+    if (items.empty()) return MGPU_OK;
+    int rc;
+    const size_t bytes = items.size() * sizeof(StateItem);
+    if ((rc = e->h_state_items.reserve(bytes))) return rc;
+    if ((rc = e->d_state_items.reserve(bytes))) return rc;
+    std::memcpy(e->h_state_items.p, items.data(), bytes);
+    hipStream_t s = e->lanes[0].stream;
+    HIP_TRY(hipMemcpyAsync(e->d_state_items.p, e->h_state_items.p, bytes, hipMemcpyHostToDevice, s));
+    const unsigned split = (unsigned)std::min<size_t>(64, std::max<size_t>(1, (most + 8 * kBlock - 1) / (8 * kBlock)));
+    hipLaunchKernelGGL(state_block_kernel<IMPORT>, dim3((unsigned)items.size(), split), dim3(kBlock), 0, s,
+                       (const StateItem *)e->d_state_items.p, (unsigned long long *)e->d_state.p, e->d_nmol);
+    HIP_TRY(hipGetLastError());
+    return MGPU_OK;
+}
+
+static int state_check_list(const mgpu_engine *e, int n, const int *replicas, const char *who) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    if (n < 0 || (n > 0 && !replicas)) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": bad replica list");
+    std::vector<char> seen((size_t)e->n_replicas, 0);
+    for (int i = 0; i < n; ++i) {
+        const int r = replicas[i];
+        if (r < 0 || r >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": replica out of range");
+        if (seen[r]) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": replica " + std::to_string(r) + " listed twice");
+        seen[r] = 1;
+    }
+    return MGPU_OK;
+}
+
 }  // namespace mgpu
 
 extern "C" {
@@ -683,6 +820,10 @@ int mgpu_engine_destroy(mgpu_engine *e) {
     e->h_snap_items.release();
     e->d_snap.release();
     e->d_snap_items.release();
+    e->h_state.release();
+    e->h_state_items.release();
+    e->d_state.release();
+    e->d_state_items.release();
     for (void *p : {(void *)e->chain.h_out, (void *)e->chain.h_tag, (void *)e->chain.h_rows})
         if (p) (void)hipHostFree(p);
     for (void *p : {(void *)e->chain.d_res, (void *)e->chain.d_part, (void *)e->chain.d_ticket, (void *)e->chain.d_topo, (void *)e->chain.d_alt,
@@ -805,6 +946,21 @@ int mgpu_replica_get_molecules(mgpu_engine *e, int replica, int t, int *n_mol, d
     return MGPU_OK;
 }
 
+// the frames' buffers (Topo::com / off), allocated and zeroed on first use
+static int frames_reserve(mgpu_engine *e) {
+    if (e->d_com) return MGPU_OK;
+    const Topo &tp = e->tp;
+    const size_t R = e->n_replicas;
+    HIP_TRY(hipMalloc(&e->d_com, R * 3 * tp.n_mol_slots * sizeof(double)));
+    HIP_TRY(hipMemset(e->d_com, 0, R * 3 * tp.n_mol_slots * sizeof(double)));
+    HIP_TRY(hipMalloc(&e->d_off, R * 3 * tp.n_cap_atoms * sizeof(double)));
+    HIP_TRY(hipMemset(e->d_off, 0, R * 3 * tp.n_cap_atoms * sizeof(double)));
+    e->tp.com = e->d_com;
+    e->tp.off = e->d_off;
+    e->chain.topo_stale = true;
+    return MGPU_OK;
+}
+
 // Molecule frames of one residue type as the reference keeps them: com[n_mol][3] = primary%mol_com, off[n_mol][n1][3] =
 // primary%site_offset (simulation_state.f90:115-116).  The sites com + off are formed here exactly as the reference forms
 // them before every use (geometry_utils.f90:379-382) and uploaded as mgpu_replica_set_molecules does.
@@ -837,16 +993,7 @@ int mgpu_replica_set_frames(mgpu_engine *e, int replica, int t, int n_mol, const
         }
     }
     if ((rc = mgpu_replica_set_molecules(e, replica, t, n_mol, sites.data()))) return rc;
-    if (!e->d_com) {
-        const size_t R = e->n_replicas;
-        HIP_TRY(hipMalloc(&e->d_com, R * 3 * tp.n_mol_slots * sizeof(double)));
-        HIP_TRY(hipMemset(e->d_com, 0, R * 3 * tp.n_mol_slots * sizeof(double)));
-        HIP_TRY(hipMalloc(&e->d_off, R * 3 * tp.n_cap_atoms * sizeof(double)));
-        HIP_TRY(hipMemset(e->d_off, 0, R * 3 * tp.n_cap_atoms * sizeof(double)));
-        e->tp.com = e->d_com;
-        e->tp.off = e->d_off;
-        e->chain.topo_stale = true;
-    }
+    if ((rc = frames_reserve(e))) return rc;
     const size_t seg = (size_t)n1 * cap;
     if ((rc = e->h_stage.reserve(3 * (seg + cap) * sizeof(double)))) return rc;
     double *st = (double *)e->h_stage.p, *sc = st + 3 * seg;
@@ -1109,6 +1256,199 @@ int mgpu_farm_snapshot_wait(mgpu_engine *e, const void **data, long long *bytes)
     HIP_TRY(hipStreamSynchronize(e->lanes[0].stream));
     if (data) *data = e->h_snap.p;
     if (bytes) *bytes = (long long)e->snap_bytes;
+    return MGPU_OK;
+}
+
+int mgpu_state_export_submit(mgpu_engine *e, int n, const int *replicas, long long *bytes) {
+    int rc = state_check_list(e, n, replicas, "state_export");
+    if (rc) return rc;
+    if (e->state_pending) return set_error(MGPU_ERR_STATE, "state_export: the last export was not waited for");
+    if ((rc = use_device(e))) return rc;
+    // after the last commit of every lane, A(k) back in its primary buffer: the state the per-replica getters read
+    if ((rc = sync_all_lanes(e))) return rc;
+    const Topo &tp = e->tp;
+    std::vector<StateCount> counts((size_t)n * tp.n_res);
+    for (int i = 0; i < n; ++i)
+        for (int t = 0; t < tp.n_res; ++t) {
+            const size_t idx = (size_t)replicas[i] * tp.n_res + t;
+            StateCount &k = counts[(size_t)i * tp.n_res + t];
+            const bool frames = e->d_com && !e->frozen[t];
+            k.n = e->h_nmol[idx];
+            k.nf = frames ? state_frames_held(k.n, e->frames_held[idx]) : 0;
+            k.rsv_cap = has_reservoir(e, idx) ? e->rsv_cap[idx] : 0;
+            k.flags = (e->in_range[idx] ? kStateInRange : 0) | (e->frames_ok[idx] ? kStateFramesOk : 0) |
+                      (e->frames_tight[idx] ? kStateFramesTight : 0) | (e->frames_held[idx] ? kStateFramesHeld : 0) |
+                      (k.rsv_cap > 0 && e->rsv_tight[idx] ? kStateRsvTight : 0);     // (an entry without a reservoir: the mark's default)
+        }
+    std::vector<long long> head;
+    std::vector<StateItem> items;
+    size_t total = 0, most = 0;
+    state_plan(e, n, replicas, counts.data(), e->d_com != nullptr, head, &items, total, most);
+    if (total >= (size_t)1 << 31) return set_error(MGPU_ERR_CAPACITY, "state_export: the block exceeds 2^31 values (cut the replica list)");
+    const size_t nbytes = total * sizeof(long long);
+    if ((rc = e->d_state.reserve(nbytes))) return rc;
+    if ((rc = e->h_state.reserve(nbytes))) return rc;
+    hipStream_t s = e->lanes[0].stream;
+    // the header goes out through the device block with the rest: one copy brings everything back (the padding words are zero)
+    HIP_TRY(hipMemsetAsync(e->d_state.p, 0, nbytes, s));
+    std::memcpy(e->h_state.p, head.data(), head.size() * sizeof(long long));
+    HIP_TRY(hipMemcpyAsync(e->d_state.p, e->h_state.p, head.size() * sizeof(long long), hipMemcpyHostToDevice, s));
+    if ((rc = state_launch<false>(e, items, most))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->h_state.p, e->d_state.p, nbytes, hipMemcpyDeviceToHost, s));
+    e->state_bytes = nbytes;
+    e->state_pending = true;
+    if (bytes) *bytes = (long long)nbytes;
+    return MGPU_OK;
+}
+
+int mgpu_state_export_wait(mgpu_engine *e, const void **data, long long *bytes) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    if (!e->state_pending) return set_error(MGPU_ERR_STATE, "state_export_wait: no export submitted");
+    int rc;
+    if ((rc = use_device(e))) return rc;
+    e->state_pending = false;
+    HIP_TRY(hipStreamSynchronize(e->lanes[0].stream));
+    if (data) *data = e->h_state.p;
+    if (bytes) *bytes = (long long)e->state_bytes;
+    return MGPU_OK;
+}
+
+int mgpu_state_import(mgpu_engine *e, int n, const int *replicas, const void *data, long long bytes) {
+    int rc = state_check_list(e, n, replicas, "state_import");
+    if (rc) return rc;
+    if (e->state_pending) return set_error(MGPU_ERR_STATE, "state_import: an export was not waited for");
+    const Topo &tp = e->tp;
+    const int n_res = tp.n_res;
+    const long long *blk = (const long long *)data;
+    // ---- the block against the engine: nothing is written before all of it has passed
+    if (!data || bytes < (long long)(state_types_at() * sizeof(long long)) || bytes % (long long)sizeof(long long))
+        return set_error(MGPU_ERR_INVALID_ARG, "state_import: not a state block");
+    if (blk[0] != kStateMagic) return set_error(MGPU_ERR_INVALID_ARG, "state_import: not a state block (magic)");
+    if (blk[1] != n) return set_error(MGPU_ERR_INVALID_ARG, "state_import: the block holds " + std::to_string(blk[1]) + " replicas, the list " + std::to_string(n));
+    if (blk[2] != n_res) return set_error(MGPU_ERR_INVALID_ARG, "state_import: the block's number of residue types is not the engine's");
+    if (blk[3] != e->n_slots) return set_error(MGPU_ERR_INVALID_ARG, "state_import: the block's A(k) length (n_slots) is not the engine's");
+    if (std::memcmp(blk + kStateHeadWords, e->box_matrix, 9 * sizeof(double)) || std::memcmp(blk + kStateHeadWords + 9, e->bounds_lo, 3 * sizeof(double)))
+        return set_error(MGPU_ERR_INVALID_ARG, "state_import: the block's box is not the engine's");
+    const size_t head_words = state_data_at(n, n_res);
+    if ((size_t)bytes < head_words * sizeof(long long)) return set_error(MGPU_ERR_INVALID_ARG, "state_import: the block is shorter than its header");
+    for (int t = 0; t < n_res; ++t) {
+        if (blk[state_types_at() + (size_t)kStateTypeWords * t] != tp.n1[t])
+            return set_error(MGPU_ERR_INVALID_ARG, "state_import: sites of residue type " + std::to_string(t) + " differ from the engine's");
+        if (blk[state_types_at() + (size_t)kStateTypeWords * t + 1] != tp.cap[t])
+            return set_error(MGPU_ERR_CAPACITY, "state_import: mol_capacity of residue type " + std::to_string(t) + " differs from the engine's");
+    }
+    const bool frames = blk[4] != 0;
+    std::vector<StateCount> counts((size_t)n * n_res);
+    for (int i = 0; i < n; ++i)
+        for (int t = 0; t < n_res; ++t) {
+            const long long *rec = blk + state_rec_at(n, n_res, i, t);
+            StateCount &k = counts[(size_t)i * n_res + t];
+            const long long cap = tp.cap[t], rsv_most = (((long long)1 << 31) - 1) / (3ll * tp.n1[t]);
+            if (rec[kStateRecN] < 0 || rec[kStateRecN] > cap || rec[kStateRecNf] < 0 || rec[kStateRecNf] > cap)
+                return set_error(MGPU_ERR_CAPACITY, "state_import: a molecule count exceeds the residue type's mol_capacity");
+            if (rec[kStateRecRsvCap] < 0 || rec[kStateRecRsvCap] > rsv_most || (rec[kStateRecFlags] & ~31ll))
+                return set_error(MGPU_ERR_INVALID_ARG, "state_import: bad record");
+            k.n = (int)rec[kStateRecN]; k.nf = (int)rec[kStateRecNf]; k.rsv_cap = (int)rec[kStateRecRsvCap]; k.flags = rec[kStateRecFlags];
+            if (k.nf != ((frames && !e->frozen[t]) ? state_frames_held(k.n, (k.flags & kStateFramesHeld) != 0) : 0))
+                return set_error(MGPU_ERR_INVALID_ARG, "state_import: bad record (frames)");
+        }
+    std::vector<long long> head;
+    std::vector<StateItem> items;
+    size_t total = 0, most = 0;
+    state_plan(e, n, replicas, counts.data(), frames, head, nullptr, total, most);
+    for (int i = 0; i < n; ++i) head[state_reps_at(n_res) + (size_t)kStateRepWords * i] = blk[state_reps_at(n_res) + (size_t)kStateRepWords * i];
+    if (total >= (size_t)1 << 31 || (long long)(total * sizeof(long long)) != bytes || std::memcmp(head.data(), blk, head_words * sizeof(long long)))
+        return set_error(MGPU_ERR_INVALID_ARG, "state_import: the block's layout is not what this engine gives its counts");
+    for (int i = 0; i < n; ++i)
+        for (int t = 0; t < n_res; ++t) {
+            const long long at = blk[state_rec_at(n, n_res, i, t) + kStateRecRsv];
+            if (at < 0) continue;
+            int nc[2];
+            std::memcpy(nc, blk + at, sizeof(nc));
+            if (nc[1] != counts[(size_t)i * n_res + t].rsv_cap || nc[0] < 0 || nc[0] > nc[1])
+                return set_error(MGPU_ERR_INVALID_ARG, "state_import: bad reservoir count");
+        }
+    // ---- nothing of a listed replica may be in flight
+    std::vector<char> listed((size_t)e->n_replicas, 0);
+    for (int i = 0; i < n; ++i) listed[replicas[i]] = 1;
+    for (const Lane &ln : e->lanes)
+        for (const auto &pd : ln.farm.pending)
+            for (int r : pd.rep)
+                if (listed[r]) return set_error(MGPU_ERR_STATE, "state_import: farm windows of replica " + std::to_string(r) + " are in flight (wait for them first)");
+    if (e->run.open && listed[e->run.replica])
+        return set_error(MGPU_ERR_STATE, "state_import: a chain run of replica " + std::to_string(e->run.replica) + " is open (close it first)");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    // ---- what the block needs that this engine has not allocated yet: the frames' buffers, the reservoirs at the block's capacities
+    if (frames && (rc = frames_reserve(e))) return rc;
+    bool any_rsv = false;
+    for (const StateCount &k : counts) any_rsv = any_rsv || k.rsv_cap > 0;
+    if (any_rsv && (rc = reservoir_tables(e))) return rc;
+    if (e->d_rsv)
+        for (int i = 0; i < n; ++i)
+            for (int t = 0; t < n_res; ++t) {
+                const size_t idx = (size_t)replicas[i] * n_res + t;
+                if (e->rsv_cap[idx] != counts[(size_t)i * n_res + t].rsv_cap && (rc = reservoir_block(e, idx, counts[(size_t)i * n_res + t].rsv_cap))) return rc;
+            }
+    // ---- the block to device scratch, scattered by the export's item table and kernel body
+    state_plan(e, n, replicas, counts.data(), frames, head, &items, total, most);
+    if ((rc = e->d_state.reserve((size_t)bytes))) return rc;
+    hipStream_t s = e->lanes[0].stream;
+    HIP_TRY(hipMemcpyAsync(e->d_state.p, data, (size_t)bytes, hipMemcpyHostToDevice, s));
+    if ((rc = state_launch<true>(e, items, most))) return rc;
+    if ((rc = sync_stream(e))) return rc;
+    // ---- the host's flags, and what every reload clears: stall marks (runs of consecutive replicas together), alt_owner, acur
+    for (int i = 0; i < n; ++i)
+        for (int t = 0; t < n_res; ++t) {
+            const size_t idx = (size_t)replicas[i] * n_res + t;
+            const StateCount &k = counts[(size_t)i * n_res + t];
+            e->h_nmol[idx] = k.n;
+            e->in_range[idx] = (k.flags & kStateInRange) ? 1 : 0;
+            e->frames_ok[idx] = (k.flags & kStateFramesOk) ? 1 : 0;
+            e->frames_tight[idx] = (k.flags & kStateFramesTight) ? 1 : 0;
+            e->frames_held[idx] = (k.flags & kStateFramesHeld) ? 1 : 0;
+            if (!e->rsv_tight.empty()) e->rsv_tight[idx] = (k.rsv_cap == 0 || (k.flags & kStateRsvTight)) ? 1 : 0;
+        }
+    // a frozen framework: does the replica still hold replica 0's copy?  (mgpu_replica_set_molecules' rule; replica 0 first)
+    for (int pass = 0; pass < 2; ++pass)
+        for (int i = 0; i < n; ++i) {
+            if ((replicas[i] == 0) != (pass == 0)) continue;
+            for (int t = 0; t < n_res; ++t) {
+                if (!e->frozen[t]) continue;
+                const int r = replicas[i], nm = counts[(size_t)i * n_res + t].n;
+                const size_t seg = (size_t)tp.n1[t] * tp.cap[t], live = (size_t)nm * tp.n1[t], pw = state_plane_words(nm, tp.n1[t]);
+                const long long *pos = blk + blk[state_rec_at(n, n_res, i, t) + kStateRecPos];
+                auto set_same = [&](int rr, char v) {
+                    char &f = e->frozen_same[(size_t)rr * n_res + t];
+                    e->frozen_diff[t] += (f ? 1 : 0) - (v ? 1 : 0);
+                    f = v;
+                };
+                if (r == 0) {
+                    e->frozen_ref[t].assign(3 * seg, 0.0);
+                    for (int d = 0; d < 3; ++d) std::memcpy(e->frozen_ref[t].data() + d * seg, pos + d * pw, live * sizeof(double));
+                    for (int rr = 1; rr < e->n_replicas; ++rr) set_same(rr, 0);
+                    set_same(0, 1);
+                } else {
+                    bool same = e->frozen_ref[t].size() == 3 * seg && nm == e->h_nmol[t];
+                    for (int d = 0; d < 3 && same; ++d) {
+                        same = std::memcmp(e->frozen_ref[t].data() + d * seg, pos + d * pw, live * sizeof(double)) == 0;
+                        for (size_t j = live; j < seg && same; ++j) same = e->frozen_ref[t][d * seg + j] == 0.0;
+                    }
+                    set_same(r, same ? 1 : 0);
+                }
+            }
+        }
+    std::vector<int> sorted(replicas, replicas + n);
+    std::sort(sorted.begin(), sorted.end());
+    for (int i = 0; i < n;) {
+        int j = i + 1;
+        while (j < n && sorted[j] == sorted[j - 1] + 1) ++j;
+        if (e->farm.d_stalled) HIP_TRY(hipMemset(e->farm.d_stalled + sorted[i], 0, (size_t)(j - i) * sizeof(int)));
+        if (e->d_acur) HIP_TRY(hipMemset(e->d_acur + sorted[i], 0, (size_t)(j - i) * sizeof(int)));
+        i = j;
+    }
+    for (int i = 0; i < n; ++i) alt_forget(e, replicas[i]);
     return MGPU_OK;
 }
 

@@ -189,6 +189,57 @@ inline TrialResult trial_result(int n, int n_partials, int n_pair, bool frozen_e
     return r;
 }
 
+// ---- The state block of mgpu_state_export_* / mgpu_state_import (mgpu_engine.hip): the whole resident state of n listed
+// replicas, the one home of its layout, plain integers as above.  Everything is counted in 8-byte WORDS from the start of the
+// block; the values (doubles, and the reservoirs' {count, capacity} int pairs) are copied as words, bit for bit.
+//   [head: kStateHeadWords | box: kStateBoxWords | per type {n1, mol_capacity} | per listed replica {replica, A_at} |
+//    per (listed replica i, type t) a record of kStateRecWords | data]
+// data, replica by replica in the list's order: A(k) (2 n_slots words), then per type
+//   pos  3 planes x, y, z of the type's n occupied molecules, each plane in the engine's slot order with the empty slots left
+//        out -- plane-major types [site][molecule], site-major ones [molecule][site] -- and padded to an even word count;
+//   com  3 planes of nf molecule centres, off 3 planes of nf molecules' offsets (as pos): only where the engine holds frames
+//        for the type; nf = n, or 1 where n = 0 and slot 0 still holds the offsets a by-count insertion copies (frames_held);
+//   rsv  {count, capacity} (one word), one word of padding, the whole block [capacity][n1][3]: only where there is a reservoir.
+// Every segment (A, pos, com, off, rsv) and every plane starts on an even word: 16-byte aligned in the block.
+constexpr long long kStateMagic = 0x3141545355504d4dll;      // "MMPUSTA1", little-endian
+constexpr int kStateHeadWords = 8;      // magic, n, n_res, n_slots, the engine holds frames (0 / 1), total words, 0, 0
+constexpr int kStateBoxWords = 12;      // box matrix (9) and lower bounds (3): the doubles' bit patterns
+constexpr int kStateTypeWords = 2, kStateRepWords = 2;
+constexpr int kStateRecWords = 8;       // n, nf, reservoir capacity, flags, pos_at, com_at, off_at, rsv_at (-1: none)
+enum { kStateRecN, kStateRecNf, kStateRecRsvCap, kStateRecFlags, kStateRecPos, kStateRecCom, kStateRecOff, kStateRecRsv };
+// the host-side flags of (replica, type) a later launch reads
+enum { kStateInRange = 1, kStateFramesOk = 2, kStateFramesTight = 4, kStateFramesHeld = 8, kStateRsvTight = 16 };
+inline size_t state_up2(size_t w) { return (w + 1) & ~(size_t)1; }
+inline size_t state_types_at() { return (size_t)kStateHeadWords + kStateBoxWords; }
+inline size_t state_reps_at(int n_res) { return state_types_at() + (size_t)kStateTypeWords * n_res; }
+inline size_t state_recs_at(int n, int n_res) { return state_reps_at(n_res) + (size_t)kStateRepWords * n; }
+inline size_t state_rec_at(int n, int n_res, int i, int t) { return state_recs_at(n, n_res) + (size_t)kStateRecWords * ((size_t)i * n_res + t); }
+inline size_t state_data_at(int n, int n_res) { return state_up2(state_rec_at(n, n_res, n, 0)); }
+inline size_t state_A_words(int n_slots) { return 2 * (size_t)n_slots; }
+inline size_t state_plane_words(int n, int n1) { return state_up2((size_t)n * n1); }      // one plane of n molecules of n1 sites
+inline size_t state_rsv_words(int rsv_cap, int n1) { return rsv_cap > 0 ? 2 + state_up2((size_t)3 * rsv_cap * n1) : 0; }
+inline int state_frames_held(int n, bool frames_held) { return n > 0 ? n : (frames_held ? 1 : 0); }   // nf
+// the segments of one (replica, type) laid out from word `at` on (even); -1: the type has none
+struct StateSegs { long long pos, com, off, rsv; size_t end; };
+inline StateSegs state_type_segments(size_t at, int n, int nf, int n1, int rsv_cap, bool frames) {
+    StateSegs s{-1, -1, -1, -1, at};
+    s.pos = (long long)s.end;
+    s.end += 3 * state_plane_words(n, n1);
+    if (frames) {
+        s.com = (long long)s.end;
+        s.end += 3 * state_plane_words(nf, 1);
+        s.off = (long long)s.end;
+        s.end += 3 * state_plane_words(nf, n1);
+    }
+    if (rsv_cap > 0) {
+        s.rsv = (long long)s.end;
+        s.end += state_rsv_words(rsv_cap, n1);
+    }
+    return s;
+}
+// 16-byte accesses for a run-strided item: block offset, engine offset, run length and run stride all even
+inline bool state_item_vec(long long src, long long dst, long long len, long long stride) { return ((src | dst | len | stride) & 1) == 0; }
+
 }  // namespace mgpu
 
 #endif

@@ -72,6 +72,49 @@ def ewald_kvectors(reciprocal, alpha, kmax, nk):
     return dict(kx=kx, ky=ky, kz=kz, k2mag=k2, form_factor=ff, weights=w)
 
 
+STATE_FLAGS = dict(in_range=1, frames_ok=2, frames_tight=4, frames_held=8, rsv_tight=16)
+
+
+def state_unpack(block):
+    """The pieces of a state block (Engine.state_export; layout: include/maniac_gpu.h).  Returns a list with one dict per listed
+    replica: replica, A (n_slots, 2) in the engine's slot order, and per residue type the lists n, flags, pos (n, n1, 3) in the
+    engine's site order, com (n, 3) / off (n, n1, 3) over the nf molecules of frames carried (None without frames), rsv
+    (count, n1, 3) and rsv_cap (None / 0 without a reservoir).  Copies, bit for bit."""
+    w = np.frombuffer(block, dtype=np.int64)
+    f = np.frombuffer(block, dtype=np.float64)
+    n, n_res, n_slots = int(w[1]), int(w[2]), int(w[3])
+    types_at = 8 + 12
+    reps_at = types_at + 2 * n_res
+    recs_at = reps_at + 2 * n
+    n1s = [int(w[types_at + 2 * t]) for t in range(n_res)]
+
+    def planes(at, nm, n1):
+        pw = (nm * n1 + 1) & ~1
+        p = np.stack([f[at + d * pw: at + d * pw + nm * n1] for d in range(3)], axis=-1)
+        return (p.reshape(nm, n1, 3) if n1 >= 64 else p.reshape(n1, nm, 3).transpose(1, 0, 2)).copy()
+
+    out = []
+    for i in range(n):
+        a_at = int(w[reps_at + 2 * i + 1])
+        rep = dict(replica=int(w[reps_at + 2 * i]), A=f[a_at: a_at + 2 * n_slots].reshape(n_slots, 2).copy(),
+                   n=[], flags=[], pos=[], com=[], off=[], rsv=[], rsv_cap=[])
+        for t in range(n_res):
+            nm, nf, rcap, flags, pos_at, com_at, off_at, rsv_at = (int(v) for v in w[recs_at + 8 * (i * n_res + t):][:8])
+            rep["n"].append(nm)
+            rep["flags"].append(flags)
+            rep["pos"].append(planes(pos_at, nm, n1s[t]))
+            rep["com"].append(planes(com_at, nf, 1)[:, 0, :] if com_at >= 0 else None)
+            rep["off"].append(planes(off_at, nf, n1s[t]) if off_at >= 0 else None)
+            rep["rsv_cap"].append(rcap)
+            if rsv_at >= 0:
+                count = int(np.frombuffer(block, dtype=np.int32)[2 * rsv_at])
+                rep["rsv"].append(f[rsv_at + 2: rsv_at + 2 + 3 * count * n1s[t]].reshape(count, n1s[t], 3).copy())
+            else:
+                rep["rsv"].append(None)
+        out.append(rep)
+    return out
+
+
 class Engine:
     """One HIP device, R replicas of one (box, force field, k table)."""
 
@@ -220,6 +263,26 @@ class Engine:
                     ri.append(block[rat: rat + 3 * nr * n1s[t]].reshape(nr, n1s[t], 3).copy() if rat >= 0 else None)
                 com.append(ci); off.append(oi); rsv.append(ri)
         return counts, com, off, rsv
+
+    def state_export(self, replicas, copy=True):
+        """mgpu_state_export_submit + _wait: the whole resident state of the listed replicas (any order, any subset, each once) as
+        one block -- a uint8 array, a copy of the engine's pinned buffer (copy=False: a view of it, valid until the next export
+        or the engine's close); include/maniac_gpu.h has the layout, state_unpack reads it."""
+        reps = _ints(replicas) if len(np.atleast_1d(replicas)) else np.zeros(0, np.int32)
+        nbytes = C.c_longlong()
+        check(self.L.mgpu_state_export_submit(self.h, C.c_int(reps.shape[0]), _i(reps), C.byref(nbytes)))
+        ptr = C.c_void_p()
+        check(self.L.mgpu_state_export_wait(self.h, C.byref(ptr), C.byref(nbytes)))
+        block = np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(nbytes.value,))
+        return block.copy() if copy else block
+
+    def state_import(self, replicas, block):
+        """mgpu_state_import: the block of a state_export into the listed replicas of this engine (as many as the block holds).
+        The engine checks the block against itself first and writes nothing where it does not fit."""
+        reps = _ints(replicas) if len(np.atleast_1d(replicas)) else np.zeros(0, np.int32)
+        buf = np.ascontiguousarray(np.frombuffer(block, dtype=np.uint8))
+        check(self.L.mgpu_state_import(self.h, C.c_int(reps.shape[0]), _i(reps), buf.ctypes.data_as(C.c_void_p),
+                                       C.c_longlong(buf.shape[0])))
 
     def move_trial(self, replica, t, m, move, u, translation_step, rotation_step, lane=0):
         """Device-built trials (mgpu_move_trial_submit + wait): (old[n,5], new[n,5])."""

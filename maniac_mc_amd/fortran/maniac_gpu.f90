@@ -283,6 +283,30 @@ module maniac_gpu
             integer(c_long_long), intent(out) :: bytes
             integer(c_int) :: rc
         end function
+        ! state block: the whole resident state of a list of replicas out of an engine and into one (layout: include/maniac_gpu.h)
+        function mgpu_state_export_submit(e, n, replicas, bytes) bind(C, name="mgpu_state_export_submit") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_long_long), intent(out) :: bytes
+            integer(c_int) :: rc
+        end function
+        function mgpu_state_export_wait(e, data, bytes) bind(C, name="mgpu_state_export_wait") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            type(c_ptr), intent(out) :: data
+            integer(c_long_long), intent(out) :: bytes
+            integer(c_int) :: rc
+        end function
+        function mgpu_state_import(e, n, replicas, data, bytes) bind(C, name="mgpu_state_import") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e, data
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_long_long), value :: bytes
+            integer(c_int) :: rc
+        end function
         function mgpu_move_trial_submit(e, lane, n, replica, t, m, move, u, translation_step, rotation_step) &
                 bind(C, name="mgpu_move_trial_submit") result(rc)
             import :: c_ptr, c_int, c_double

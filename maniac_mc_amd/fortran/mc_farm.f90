@@ -52,6 +52,7 @@ module mc_farm
     public :: mfarm_rng_sample, mfarm_set_drivers, mfarm_configure, mfarm_select, mfarm_exchange_block
     public :: mfarm_window_mode, mfarm_set_window_depth, mfarm_set_reservoir, mfarm_get_reservoir
     public :: mfarm_get_chain_counters, mfarm_set_output_template, mfarm_set_log_header, mfarm_write_block
+    public :: mfarm_state_bytes, mfarm_state_export, mfarm_state_import
 
     real(real64), parameter :: PI = 3.14159265358979323846_real64
     real(real64), parameter :: TWOPI = 2.0_real64 * PI
@@ -65,6 +66,9 @@ module mc_farm
     integer, parameter :: RNG_BLOCK = 256                 ! chains per mgpu_rng_fill call
     ! internal move codes; engine kinds are MGPU_MOVE / MGPU_CREATION / MGPU_DELETION
     integer, parameter :: MV_TRANSLATION = 1, MV_ROTATION = 2, MV_CREATION = 3, MV_DELETION = 4
+    ! the driver's state block (mfarm_state_export): words of its head, and where `started` and the total sit in it
+    integer, parameter :: STATE_HEAD = 16, STATE_STARTED = 13, STATE_TOTAL = 14
+    integer(int64), parameter :: STATE_MAGIC = 3554557597459760717_int64       ! "MFARMST1", little-endian
 
     type :: lane_buffers
         integer :: first = 0, n = 0                        ! replicas [first, first + n)
@@ -1831,6 +1835,237 @@ contains
         F%rsv_on(ia) = .true.
         F%has_rsv = .true.
     end function mfarm_set_reservoir
+
+    !---------------------------------------------------------------------------
+    ! The driver's own state as one block of 8-byte words: everything the next mfarm_run reads that the engine does not hold
+    ! (the engine's side is mgpu_state_export_submit's block).  Valid only BETWEEN mfarm_run calls: nothing is then issued,
+    ! pending or in flight in any lane, and the lanes' accumulators have been folded into the farm's.
+    !   head (STATE_HEAD words): magic, R, n_active, max_n1, cap_total, device_build, device_accept, window, rng_kind,
+    !         has_rsv, words of the intrinsic generator's state (rng_kind 0, else 0), slots of the host-built reservoirs,
+    !         started, total words, 0, 0;  per active type: engine residue type, n1, capacity
+    !   body: cxs(4, R) | the intrinsic generator's state | cnt | energy(5, R) | fugacity | translation_step, rotation_step |
+    !         trials, accepted, skipped, undecided | counters(8) | chain_counters(8, R) | rsv_on, rsv_total (has_rsv) |
+    !         host-built farms: per chain and type the mirror's records 1 .. max(count, 1) (record 1 of an empty type is what
+    !         an insertion copies), then rsv_n and per chain and type the reservoir's records 1 .. rsv_n
+    ! Reals travel as their bit patterns.  state_walk is the one description: mode 0 counts the words (with the farm's own
+    ! counts), 1 writes the block, 2 reads one -- whose head and counts mfarm_state_import has checked first.
+    !---------------------------------------------------------------------------
+    subroutine state_walk(mode, buf, at)
+        integer, intent(in) :: mode
+        integer(c_long_long), intent(inout) :: buf(*)
+        integer(int64), intent(out) :: at
+        integer :: r, ia, k, n_seed, nrec, nm
+        integer, allocatable :: sd(:)
+        logical :: was_started
+        n_seed = 0
+        if (F%rng_kind == 0) then
+            call random_seed(size=n_seed)
+            allocate(sd(n_seed))
+            if (mode == 1) call random_seed(get=sd)
+        end if
+        nrec = 3 + 3 * F%max_n1
+        was_started = F%started
+        at = 0
+        call word(STATE_MAGIC)
+        call word(int(F%n_replicas, int64)); call word(int(F%n_active, int64)); call word(int(F%max_n1, int64))
+        call word(int(F%cap_total, int64))
+        call word(merge(1_int64, 0_int64, F%device_build)); call word(merge(1_int64, 0_int64, F%device_accept))
+        call word(merge(1_int64, 0_int64, F%window)); call word(int(F%rng_kind, int64))
+        call word(merge(1_int64, 0_int64, F%has_rsv)); call word(int(n_seed, int64))
+        if (allocated(F%rsv)) then
+            call word(int(size(F%rsv, 2), int64))
+        else
+            call word(0_int64)
+        end if
+        at = at + 1
+        if (mode == 1) buf(at) = merge(1_int64, 0_int64, F%started)
+        if (mode == 2) was_started = buf(at) /= 0
+        at = at + 3                                       ! the total (filled in by the caller) and two spare words
+        if (mode == 1) buf(at - 2:at) = 0
+        do ia = 1, F%n_active
+            call word(int(F%res_type(ia), int64)); call word(int(F%n1(ia), int64)); call word(int(F%cap(ia), int64))
+        end do
+        do r = 1, F%n_replicas
+            do k = 1, 4
+                call i8(F%cxs(k, r))
+            end do
+        end do
+        do k = 1, n_seed
+            call i4(sd(k))
+        end do
+        if (mode == 2 .and. n_seed > 0) call random_seed(put=sd)
+        do r = 1, F%n_replicas
+            do ia = 1, F%n_active
+                call i4(F%cnt(ia, r))
+            end do
+        end do
+        do r = 1, F%n_replicas
+            do k = 1, 5
+                call r8(F%energy(k, r))
+            end do
+        end do
+        do r = 1, F%n_replicas
+            do ia = 1, F%n_active
+                call r8(F%fugacity(ia, r))
+            end do
+        end do
+        call r8(F%translation_step); call r8(F%rotation_step)
+        call i8(F%trials); call i8(F%accepted); call i8(F%skipped); call i8(F%undecided)
+        do k = 1, 8
+            call i8(F%counters(k))
+        end do
+        do r = 1, F%n_replicas
+            do k = 1, 8
+                call i8(F%chain_counters(k, r))
+            end do
+        end do
+        if (F%has_rsv) then
+            do ia = 1, F%n_active
+                k = merge(1, 0, F%rsv_on(ia))
+                call i4(k)
+            end do
+            do r = 1, F%n_replicas
+                do ia = 1, F%n_active
+                    call i4(F%rsv_total(ia, r))
+                end do
+            end do
+        end if
+        if (.not. F%device_build) then
+            do r = 1, F%n_replicas
+                do ia = 1, F%n_active
+                    nm = max(F%cnt(ia, r), 1)
+                    do k = F%first(ia) + 1, F%first(ia) + nm
+                        if (mode == 1) buf(at + 1:at + nrec) = transfer(F%mol(:, k, r), 1_c_long_long, nrec)
+                        if (mode == 2) F%mol(:, k, r) = transfer(buf(at + 1:at + nrec), 1.0_real64, nrec)
+                        at = at + nrec
+                    end do
+                end do
+            end do
+            if (F%has_rsv .and. allocated(F%rsv_n)) then
+                do r = 1, F%n_replicas
+                    do ia = 1, F%n_active
+                        call i4(F%rsv_n(ia, r))
+                    end do
+                end do
+                nrec = 3 * F%max_n1
+                do r = 1, F%n_replicas
+                    do ia = 1, F%n_active
+                        do k = 1, F%rsv_n(ia, r)
+                            if (mode == 1) buf(at + 1:at + nrec) = transfer(F%rsv(:, k, ia, r), 1_c_long_long, nrec)
+                            if (mode == 2) F%rsv(:, k, ia, r) = transfer(buf(at + 1:at + nrec), 1.0_real64, nrec)
+                            at = at + nrec
+                        end do
+                    end do
+                end do
+            end if
+        end if
+        if (mode == 2) F%started = was_started
+    contains
+        subroutine word(v)                                ! a word of the head: written, never read back into the farm
+            integer(int64), intent(in) :: v
+            at = at + 1
+            if (mode == 1) buf(at) = v
+        end subroutine word
+        subroutine i8(v)
+            integer(int64), intent(inout) :: v
+            at = at + 1
+            if (mode == 1) buf(at) = v
+            if (mode == 2) v = buf(at)
+        end subroutine i8
+        subroutine i4(v)
+            integer, intent(inout) :: v
+            at = at + 1
+            if (mode == 1) buf(at) = int(v, int64)
+            if (mode == 2) v = int(buf(at))
+        end subroutine i4
+        subroutine r8(v)
+            real(real64), intent(inout) :: v
+            at = at + 1
+            if (mode == 1) buf(at) = transfer(v, 1_c_long_long)
+            if (mode == 2) v = transfer(buf(at), 1.0_real64)
+        end subroutine r8
+    end subroutine state_walk
+
+    ! bytes of the selected farm's state block as it stands now (0: no farm)
+    function mfarm_state_bytes() bind(C, name="mfarm_state_bytes") result(nbytes)
+        integer(c_long_long) :: nbytes
+        integer(c_long_long) :: none(1)
+        integer(int64) :: n
+        nbytes = 0
+        if (.not. F%ready) return
+        call state_walk(0, none, n)
+        nbytes = 8 * n
+    end function mfarm_state_bytes
+
+    ! the block into buf (nbytes = mfarm_state_bytes()); 5: no farm, 3: another size
+    function mfarm_state_export(buf, nbytes) bind(C, name="mfarm_state_export") result(rc)
+        integer(c_long_long), intent(inout) :: buf(*)
+        integer(c_long_long), value :: nbytes
+        integer(c_int) :: rc
+        integer(int64) :: n
+        rc = 5
+        if (.not. F%ready) return
+        rc = 3
+        if (nbytes /= mfarm_state_bytes()) return
+        call state_walk(1, buf, n)
+        buf(STATE_TOTAL) = n
+        rc = MGPU_OK
+    end function mfarm_state_export
+
+    ! A block into the selected farm, which must have been created as the block's farm was: the head (R, the active types with
+    ! their sites and capacities, the mode flags, rng_kind, the reservoirs) is compared word for word, the counts are held to
+    ! the capacities and the size to what they give.  Non-zero code, nothing changed: 5 no farm, 1 not a block or another
+    ! farm's, 3 a count beyond its capacity or another size.
+    function mfarm_state_import(buf, nbytes) bind(C, name="mfarm_state_import") result(rc)
+        integer(c_long_long), intent(inout) :: buf(*)
+        integer(c_long_long), value :: nbytes
+        integer(c_int) :: rc
+        integer(c_long_long), allocatable :: mine(:)
+        integer(int64) :: n, at, want
+        integer :: r, ia, n_head, n_seed, nrec
+        rc = 5
+        if (.not. F%ready) return
+        rc = 1
+        n_head = STATE_HEAD + 3 * F%n_active
+        if (nbytes < 8 * int(n_head, int64) .or. mod(nbytes, 8_c_long_long) /= 0) return
+        call state_walk(0, buf, n)
+        allocate(mine(max(n, int(n_head, int64))))
+        call state_walk(1, mine, n)
+        mine(STATE_STARTED) = buf(STATE_STARTED)
+        mine(STATE_TOTAL) = buf(STATE_TOTAL)
+        if (any(mine(1:n_head) /= buf(1:n_head))) return
+        rc = 3
+        if (buf(STATE_TOTAL) * 8 /= nbytes) return
+        ! the counts (behind the generators' states) against the capacities, and the size they give
+        n_seed = int(buf(11))
+        at = n_head + 4 * int(F%n_replicas, int64) + n_seed
+        want = at + int(F%n_active, int64) * F%n_replicas * 2 + 5 * int(F%n_replicas, int64) + 2 + 4 + 8 + 8 * int(F%n_replicas, int64)
+        if (F%has_rsv) want = want + F%n_active + int(F%n_active, int64) * F%n_replicas
+        if (want > buf(STATE_TOTAL)) return
+        nrec = 3 + 3 * F%max_n1
+        do r = 1, F%n_replicas
+            do ia = 1, F%n_active
+                at = at + 1
+                if (buf(at) < 0 .or. buf(at) > F%cap(ia)) return
+                if (.not. F%device_build) want = want + int(nrec, int64) * max(buf(at), 1_int64)
+            end do
+        end do
+        if (.not. F%device_build .and. F%has_rsv .and. allocated(F%rsv_n)) then
+            if (want + int(F%n_active, int64) * F%n_replicas > buf(STATE_TOTAL)) return
+            at = want
+            want = want + int(F%n_active, int64) * F%n_replicas
+            do r = 1, F%n_replicas
+                do ia = 1, F%n_active
+                    at = at + 1
+                    if (buf(at) < 0 .or. buf(at) > size(F%rsv, 2)) return
+                    want = want + 3 * int(F%max_n1, int64) * buf(at)
+                end do
+            end do
+        end if
+        if (want /= buf(STATE_TOTAL)) return
+        call state_walk(2, buf, n)
+        rc = MGPU_OK
+    end function mfarm_state_import
 
     ! chain `replica` (0-based)'s reservoir of active type ia (0-based): its count, and off(3, n1, n) where room allows (cap)
     function mfarm_get_reservoir(replica, ia, cap, n, off) bind(C, name="mfarm_get_reservoir") result(rc)

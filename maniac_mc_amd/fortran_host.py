@@ -61,6 +61,9 @@ def lib():
         L.mfarm_set_reservoir.restype = C.c_int
         L.mfarm_get_reservoir.restype = C.c_int
         L.mfarm_write_block.restype = C.c_int
+        L.mfarm_state_bytes.restype = C.c_longlong
+        L.mfarm_state_export.restype = C.c_int
+        L.mfarm_state_import.restype = C.c_int
         _host = L
     return _host
 
@@ -381,6 +384,51 @@ class FortranFarm:
         if n.value > cap:
             raise RuntimeError("reservoir larger than the buffer")
         return off[: n.value].copy()
+
+    STATE_CHUNK_BYTES = 1 << 30       # an engine block's size at the types' capacities: larger farms are cut by the replica list
+
+    def _state_chunks(self):
+        """the replica lists of the engine blocks of a checkpoint: all R replicas in order, cut so that a block stays well
+        below the engine's limit of 2^31 words"""
+        topo = self.sys.topo
+        per = 16 * (self.eng.nk + 1) * 2 + sum(8 * 3 * (2 * int(topo.atoms_in_res[t]) + 1) * int(self.mol_capacity[t]) * 2
+                                               for t in range(topo.n_res))
+        step = max(1, FortranFarm.STATE_CHUNK_BYTES // max(1, per))
+        return [list(range(c0, min(self.R, c0 + step))) for c0 in range(0, self.R, step)]
+
+    def checkpoint_state(self):
+        """Everything the next run() reads, between two run() calls: dict(driver=the Fortran driver's block (mfarm_state_export:
+        generator states, counts, running energies, step sizes, counters, and a host-built farm's mirror and reservoirs),
+        engine=[the engine's blocks (Engine.state_export) of all R replicas, in order]), uint8 arrays.  restore_state puts them
+        into a farm created the same way; the run then continues bit for bit on the same library build and GPU model."""
+        self._select()
+        n = int(self.H.mfarm_state_bytes())
+        drv = np.zeros(n, dtype=np.uint8)
+        rc = self.H.mfarm_state_export(drv.ctypes.data_as(C.c_void_p), C.c_longlong(n))
+        if rc:
+            raise RuntimeError(f"mfarm_state_export: code {rc}")
+        return dict(driver=drv, engine=[self.eng.state_export(reps) for reps in self._state_chunks()])
+
+    def restore_state(self, state):
+        """The inverse of checkpoint_state, into a farm created with the same system, replicas, capacities, mode, generator
+        and reservoirs; ValueError otherwise -- from the driver before anything has changed, from the engine (which checks each
+        block against itself and writes nothing of a block it refuses) after the driver has taken its own."""
+        chunks = self._state_chunks()
+        blocks = list(state["engine"])
+        if len(blocks) != len(chunks):
+            raise ValueError(f"restore_state: {len(blocks)} engine blocks for {len(chunks)} replica lists")
+        drv = np.ascontiguousarray(np.frombuffer(state["driver"], dtype=np.uint8)).copy()
+        self._select()
+        rc = self.H.mfarm_state_import(drv.ctypes.data_as(C.c_void_p), C.c_longlong(drv.shape[0]))
+        if rc:
+            raise ValueError(f"restore_state: the driver's block does not belong to a farm created like this one (code {rc})")
+        for reps, block in zip(chunks, blocks):
+            try:
+                self.eng.state_import(reps, block)
+            except _lib.MgpuError as err:
+                raise ValueError(f"restore_state: the engine refuses its block: {err}") from None
+        self._select()
+        _lib.check(self.H.mfarm_run(C.c_int(0), self.stats.ctypes.data_as(_dp)))     # (no steps: the carried totals)
 
     @property
     def trials(self):

@@ -21,7 +21,7 @@ import os
 
 import numpy as np
 
-from . import _lib, fortran_host, io_maniac
+from . import _lib, checkpoint, fortran_host, io_maniac
 from .fortran_host import FortranFarm
 from .run import header_text, set_chain_state
 from .system import KB_KCALMOL, NB_MAX_MOLECULE
@@ -71,7 +71,8 @@ def _stats(x):
 
 def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=None, fugacities=None, frames=(0,),
                  mode="auto", device=0, nb_block=None, nb_step=None, mol_capacity=None, n_lanes=2, n_threads=8,
-                 chunk=None, wide_triclinic=False, restart_from=None, audit=False):
+                 chunk=None, wide_triclinic=False, restart_from=None, audit=False, checkpoint_every=0, resume=False,
+                 recalibrate_moves=None):
     """Run `replicas` independent chains of the input; returns a dict with the final energies (R, 5) in K (non-Coulomb,
     Coulomb, reciprocal, self, intramolecular), counts (R, n_active), chain counters (R, 8), the farm's counters, the
     mode that ran and the block timings.
@@ -95,6 +96,17 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     ``audit``: True -> after the last block every replica's energy and S(k) are recomputed from scratch (FortranFarm.audit,
     one batched call) and written to <outdir>/audit.dat, one line per replica in kcal/mol: replica, running total, recomputed
     total, largest component difference, max |A(k) - S(k)|; the result gains ``recomputed_energy`` (R, 6) in K and ``audit``.
+    ``checkpoint_every``: N > 0 -> after every N-th block's files are written, and after the last block's, the farm's whole
+    state goes to <outdir>/checkpoint/farm.ckpt (maniac_mc_amd.checkpoint): the engine's state blocks, the Fortran driver's,
+    the run's identity and the size of every output file.  0 (default): no checkpoint/ directory.
+    ``resume``: True -> continue the run whose checkpoint lies in `outdir`: the same inputs, replicas, seed, mode, fugacities,
+    frames and nb_step (ValueError naming what differs), nb_block at least the blocks done (a larger one extends the run: the
+    block count the trajectory frames already written state, as the reference prints it in every frame, is restated).  The
+    output files are cut back to their recorded sizes, engine and farm are created as for a fresh run and take the carried
+    state -- generator states, unrounded coordinates, A(k), reservoirs, running energies, step sizes, counters -- and the blocks
+    go on from the recorded index, appending: the files are those of the uninterrupted run, byte for byte, on the same
+    library build and GPU model.  Works with a reservoir; not together with ``restart_from``.
+    ``recalibrate_moves``: None -> the input's choice; True / False override it.
     """
     import time
     if mode not in MODES:
@@ -104,6 +116,10 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         raise ValueError("replicas must be at least 1")
     if restart_from is not None and reservoir_path:
         raise ValueError("restart_from cannot be combined with a reservoir: topology.data does not hold a reservoir's contents")
+    if resume and restart_from is not None:
+        raise ValueError("resume cannot be combined with restart_from: a resumed run continues its own checkpoint")
+    if int(checkpoint_every) < 0:
+        raise ValueError("checkpoint_every must be 0 (off) or a positive number of blocks")
     system, inp, dat = io_maniac.load_system(maniac, data, inc, with_data=True)
     rdat = io_maniac.read_lammps_data(reservoir_path, inp) if reservoir_path else None
     topo = system.topo
@@ -135,6 +151,14 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         fug_grid = np.tile(np.array([inp.fugacity_per_A3()[t] for t in active])[None, :], (R, 1)) if gcmc else None
     gcmc_arg = dict(p_translation=inp.translation_proba, p_rotation=inp.rotation_proba, fugacity=fug_grid) if gcmc else None
     reservoir = io_maniac.reservoir_offsets(reservoir_path, inp) if reservoir_path else None
+    recalibrate = bool(inp.recalibrate_moves) if recalibrate_moves is None else bool(recalibrate_moves)
+    ident = ck = None
+    if checkpoint_every or resume:
+        ident = checkpoint.identity(_lib.ABI_VERSION, nb_step, seed, mode, R, fugacities, frames, maniac, data, inc, reservoir_path)
+        ident["recalibrate"] = int(recalibrate)
+    if resume:
+        ck = checkpoint.load(outdir)
+        checkpoint.check(ck, ident, nb_block)
     initial = None
     if restart_from is not None:
         initial = []
@@ -159,6 +183,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
                                                      ("device_accept" if farm.device_accept else "device"))
         if mode == "windows" and ran != "windows":
             raise ValueError("mode 'windows': the engine's one-launch farm window does not apply to this system")
+        if ck is not None and str(ck["mode_ran"]) != ran:
+            raise ValueError(f"resume: the farm mode taken ({ran}) differs from the checkpoint's ({str(ck['mode_ran'])})")
         H = fortran_host.lib()
         farm._select()
         hold = set_chain_state(H, farm.eng.h, system, inp, dat, mol_capacity, rdat)
@@ -223,14 +249,31 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
                     f.write(line + "\n")
             times["write"] += time.perf_counter() - t0
 
-        write(0, False)
-        for block in range(1, nb_block + 1):
+        def save_checkpoint(next_block):
+            t0 = time.perf_counter()
+            state = farm.checkpoint_state()
+            checkpoint.save(outdir, ident, next_block, nb_block, ran, state["engine"], state["driver"],
+                            checkpoint.output_sizes(outdir, R))
+            times["checkpoint"] = times.get("checkpoint", 0.0) + time.perf_counter() - t0
+
+        first = 1
+        if ck is not None:
+            # the files back to where the checkpoint left them, the carried state into the fresh engine and farm: no block 0
+            checkpoint.truncate_outputs(outdir, ck["sizes"])
+            checkpoint.restate_block_count(outdir, ck["sizes"], int(ck["nb_block"]), nb_block)
+            farm.restore_state(dict(engine=ck["engine"], driver=ck["driver"]))
+            first = int(ck["next_block"])
+        else:
+            write(0, False)
+        for block in range(first, nb_block + 1):
             t0 = time.perf_counter()
             farm.run(nb_step)
-            if inp.recalibrate_moves:
+            if recalibrate:
                 farm.recalibrate()
             times["run"] += time.perf_counter() - t0
             write(block, False)
+            if checkpoint_every and (block % int(checkpoint_every) == 0 or block == nb_block):
+                save_checkpoint(block + 1)
         write(nb_block, True)
         _lib.check(0)
         energies = np.array([farm.energy(r) for r in range(R)])

@@ -309,6 +309,12 @@ def main(argv=None):
     ap.add_argument("--audit", action="store_true",
                     help="with --replicas: after the last block recompute every replica's energy and S(k) from scratch and "
                          "write <out>/audit.dat")
+    ap.add_argument("--checkpoint-every", dest="checkpoint_every", type=int, default=0, metavar="N",
+                    help="with --replicas: after every N-th block (and the last) write <out>/checkpoint/farm.ckpt, the farm's "
+                         "whole state (default 0: none)")
+    ap.add_argument("--resume", action="store_true",
+                    help="with --replicas: continue the run whose checkpoint lies in <out>, bit for bit (same inputs, replicas, "
+                         "seed, mode and nb_step; a larger nb_block extends it)")
     a = ap.parse_args(argv)
     try:
         chain_run = parse_chain_run(a.chain_run) if a.chain_run is not None else None
@@ -327,12 +333,18 @@ def main(argv=None):
             ap.error("--fugacities, --frames and --farm-mode need --replicas")
         if a.restart_from is not None or a.audit:
             ap.error("--restart-from and --audit need --replicas")
+        if a.checkpoint_every or a.resume:
+            ap.error("--checkpoint-every and --resume need --replicas")
     else:
         from . import replicas as farm_run
         if a.as_written:
             ap.error("--as-written cannot be combined with --replicas: the replica farm implements the intended physics only")
         if a.replicas < 1:
             ap.error("--replicas must be at least 1")
+        if a.checkpoint_every < 0:
+            ap.error("--checkpoint-every must be a positive number of blocks")
+        if a.resume and a.restart_from is not None:
+            ap.error("--resume cannot be combined with --restart-from: a resumed run continues its own checkpoint")
         try:
             frames = farm_run.parse_frames(a.frames, a.replicas)
             fugacities = farm_run.parse_fugacities(a.fugacities) if a.fugacities is not None else None
@@ -346,7 +358,8 @@ def main(argv=None):
         try:
             res = farm_run.run_replicas(a.maniac, a.data, a.inc, a.out, a.replicas, seed=a.seed, reservoir_path=a.reservoir,
                                         fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device,
-                                        wide_triclinic=a.wide_triclinic, restart_from=a.restart_from, audit=a.audit)
+                                        wide_triclinic=a.wide_triclinic, restart_from=a.restart_from, audit=a.audit,
+                                        checkpoint_every=a.checkpoint_every, resume=a.resume)
         except ValueError as err:
             print(f"error: {err}", file=sys.stderr)
             return 2
