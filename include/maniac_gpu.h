@@ -220,6 +220,38 @@ int mgpu_init_structure_factor(mgpu_engine *e, int replica, int mode);
  * mgpu_init_structure_factor(e, replica, mode) leaves, bit for bit. */
 int mgpu_system_energy_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, double *out, double *a_deviation);
 int mgpu_init_structure_factor_replicas(mgpu_engine *e, int n, const int *replicas, int mode);
+
+/* Radial distribution functions of many replicas, histogrammed on the device from the resident coordinates.
+ *
+ * Configuration is per engine: n_bins in [1, 1024]; r_max > 0 and at most half the smallest perpendicular width of the cell
+ * (orthorhombic: min L / 2; triclinic: V / |a_i x a_j| / 2 from box%matrix) -- beyond it MGPU_ERR_INVALID_ARG with a text that
+ * names the limit; n_pairs in [1, 8] selected unordered pairs (type_a[p], type_b[p]) of 0-based atom types (a == b allowed; a
+ * duplicate, or a type outside the topology's, is refused); include_intra 0 or 1.
+ *
+ * ONE SAMPLE of one replica takes every unordered pair of occupied atom slots (i < j in slot order) whose atom types form
+ * selected pair p and which -- unless include_intra -- do not belong to the same molecule (residue type, molecule).  Such a
+ * pair adds 1 to eligible[replica][p]; if its minimum-image r^2 (the engine's image_r2: ComputeDistance's double, triclinic
+ * cells included) satisfies r^2 < r_max * r_max it also adds 1 to hist[replica][p][b], b = (int)(sqrt(r^2) * inv_dr) with
+ * inv_dr = n_bins / r_max formed once on the host (b == n_bins, which only rounding at the top edge can give, is dropped);
+ * samples[replica] grows by 1.  All accumulators are unsigned long long.  The counts are integers: they do not depend on the
+ * order of the replicas, on chunk, or on what shares a launch.  Normalisation to g(r) is the caller's (maniac_mc_amd/rdf.py):
+ * g_p(r_b) = V sum H_p(b) / (sum E_p V_shell(b)), V_shell(b) = 4 pi / 3 (r_{b+1}^3 - r_b^3).
+ *
+ *   configure    allocates and zeroes hist [R][n_pairs][n_bins], eligible [R][n_pairs], samples [R] on the device; again with
+ *                another shape: reallocates and zeroes; n_pairs = 0 frees them (the other arguments are then ignored).
+ *   accumulate   one sample of each listed replica (the list as mgpu_system_energy_replicas takes it), in passes of `chunk`
+ *                replicas (<= 0: the engine's choice); synchronous; work in flight is treated as that call treats it.
+ *   read         hist[n][n_pairs][n_bins], eligible[n][n_pairs], samples[n] of the listed replicas.
+ *   load         overwrites the listed replicas' accumulators with such arrays (a resumed run).
+ *   reset        zeroes the listed replicas' accumulators.
+ * accumulate, read, load and reset return MGPU_ERR_STATE while nothing is configured.  Nothing else touches the accumulators:
+ * they are not part of a state block, and mgpu_replica_copy and the setters leave them alone. */
+int mgpu_rdf_configure(mgpu_engine *e, int n_bins, double r_max, int n_pairs, const int *type_a, const int *type_b, int include_intra);
+int mgpu_rdf_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int chunk);
+int mgpu_rdf_read(mgpu_engine *e, int n, const int *replicas, unsigned long long *hist, unsigned long long *eligible, unsigned long long *samples);
+int mgpu_rdf_load(mgpu_engine *e, int n, const int *replicas, const unsigned long long *hist, const unsigned long long *eligible, const unsigned long long *samples);
+int mgpu_rdf_reset(mgpu_engine *e, int n, const int *replicas);
+
 /* a[n_kvectors][2] = (re, im) of ewald%recip_amplitude */
 int mgpu_get_structure_factor(mgpu_engine *e, int replica, double *a);
 int mgpu_set_structure_factor(mgpu_engine *e, int replica, const double *a);

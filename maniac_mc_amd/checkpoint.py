@@ -65,8 +65,10 @@ def identity(abi_version, nb_step, seed, mode, n_replicas, fugacities, frames, m
                 digest_reservoir=digest(reservoir_path))
 
 
-def save(outdir, ident, next_block, nb_block, mode_ran, engine_blocks, driver_block, sizes):
-    """Write <outdir>/checkpoint/farm.ckpt atomically (temporary name, flush, fsync, rename, fsync of the directory)."""
+def save(outdir, ident, next_block, nb_block, mode_ran, engine_blocks, driver_block, sizes, extra=None):
+    """Write <outdir>/checkpoint/farm.ckpt atomically (temporary name, flush, fsync, rename, fsync of the directory).
+    ``extra``: {name: array} of further arrays a run carries (the histograms of --rdf), stored as x_<name> in the same archive;
+    None or empty: the archive has exactly the keys it always had."""
     d = os.path.join(outdir, DIR_NAME)
     os.makedirs(d, exist_ok=True)
     names = sorted(sizes)
@@ -78,6 +80,8 @@ def save(outdir, ident, next_block, nb_block, mode_ran, engine_blocks, driver_bl
         arrays["id_" + k] = np.asarray(v)
     for i, b in enumerate(engine_blocks):
         arrays[f"engine_{i}"] = np.ascontiguousarray(np.frombuffer(b, dtype=np.uint8))
+    for k, v in (extra or {}).items():
+        arrays["x_" + str(k)] = np.ascontiguousarray(v)
     tmp, final = os.path.join(d, TMP_NAME), os.path.join(d, FILE_NAME)
     with open(tmp, "wb") as f:
         np.savez(f, **arrays)
@@ -94,7 +98,7 @@ def save(outdir, ident, next_block, nb_block, mode_ran, engine_blocks, driver_bl
 
 def load(outdir):
     """The checkpoint of outdir as a dict (a leftover temporary file beside it is ignored); ValueError where there is none or
-    it is of another format."""
+    it is of another format.  ck["extra"] = {name: array} of the arrays saved as ``extra`` (empty without any)."""
     p = path_of(outdir)
     if not os.path.isfile(p):
         raise ValueError(f"resume: no checkpoint at {p}")
@@ -107,18 +111,23 @@ def load(outdir):
         raise ValueError(f"resume: checkpoint format {int(ck['format']) if 'format' in ck else '?'}, this version reads format {FORMAT_VERSION}")
     ck["engine"] = [ck.pop(f"engine_{i}") for i in range(int(ck["n_engine"]))]
     ck["sizes"] = {str(n): int(b) for n, b in zip(ck.pop("size_names"), ck.pop("size_bytes"))}
+    ck["extra"] = {k[2:]: ck.pop(k) for k in [k for k in ck if k.startswith("x_")]}
     return ck
 
 
 _NAMES = dict(abi_version="ABI version", nb_step="nb_step", seed="seed", mode="mode", replicas="R (replicas)",
               fugacities="fugacities", frames="frames", digest_maniac="the input file's digest", digest_data="the data file's digest",
               digest_inc="the parameter file's digest", digest_reservoir="the reservoir (file's digest)",
-              recalibrate="recalibrate_moves")
+              recalibrate="recalibrate_moves", rdf="rdf (--rdf, --rdf-pairs, --rdf-intra)")
 
 
 def check(ck, ident, nb_block):
     """ValueError naming the first thing in which the run asked for differs from the run that wrote the checkpoint.  A larger
     nb_block than recorded extends the run; one below the blocks already done is refused."""
+    if "id_rdf" in ck and "rdf" not in ident:
+        # (an entry only a run with --rdf has: the checkpointed run had it switched on and this one has not)
+        raise ValueError(f"resume: {_NAMES['rdf']} differs from the checkpoint's (checkpoint "
+                         f"{np.asarray(ck['id_rdf']).tolist()!r}, this run without it)")
     for k, want in ident.items():
         got = ck.get("id_" + k)
         same = got is not None and np.asarray(got).shape == np.asarray(want).shape and np.array_equal(np.asarray(got), np.asarray(want))

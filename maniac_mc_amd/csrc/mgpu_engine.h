@@ -421,6 +421,15 @@ struct mgpu_engine {
         long long launches = 0, steps = 0, void_launches = 0, undecided = 0;
         std::deque<std::pair<int, int>> log;         // (first, consumed) of the last launches seen since open
     } run;
+    // radial distribution functions (mgpu_rdf_*, mgpu_replicas.hip): the selection, and the accumulators of every replica --
+    // d_acc = hist [R][n_pairs][n_bins] | eligible [R][n_pairs] | samples [R], unsigned long long; d_tab = the RdfTable.
+    // Nothing but the mgpu_rdf_* calls touches them.
+    struct Rdf {
+        int n_bins = 0, n_pairs = 0, include_intra = 0;       // n_pairs = 0: not configured
+        double r_max = 0.0, r_max2 = 0.0, inv_dr = 0.0;
+        int type_a[8]{}, type_b[8]{};
+        DevBuf d_acc, d_tab;
+    } rdf;
     // profiling
     bool profiling = false;
 };

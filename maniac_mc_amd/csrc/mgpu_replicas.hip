@@ -3,8 +3,11 @@
 // (mgpu_engine.hip).  A call is cut into passes of as many replicas as a byte budget of scratch allows; a pass is one
 // ordered pair launch, one intra launch, one phase-table + S(k) launch pair, one reciprocal-energy launch, one reduction
 // (and one deviation launch) for all its replicas.  Nothing is waited for between the passes; one copy brings the results back.
+// Beside them the radial distribution functions of many replicas per call (mgpu_rdf_*): integer histograms of the resident
+// coordinates, one rdf_hist_kernel launch per pass.
 #include "mgpu_engine.h"
 #include "mgpu_kernels_replicas.h"
+#include "mgpu_kernels_rdf.h"
 
 namespace mgpu {
 
@@ -48,6 +51,60 @@ static int launch_sfactor_replicas(mgpu_engine *e, const int *d_reps, int c, dou
 }
 
 struct Pass { int first, c; long long n_pair, n_in; };
+
+// ---- radial distribution functions
+constexpr int kRdfPassMax = 32768;                         // replicas per pass (the grid's y extent)
+
+// half the smallest perpendicular width of the cell: the largest r_max a histogram may have.  Orthorhombic: min L / 2;
+// triclinic: width i = V / |a_j x a_k| from box%matrix (its columns are the cell vectors).  Plain rounded operations in a
+// fixed order (maniac_mc_amd/rdf.py half_width forms the same double).
+static double rdf_half_width(const mgpu_engine *e) {
+#pragma clang fp contract(off)
+    const double *m = e->box_matrix;
+    if (!e->bx.triclinic) return 0.5 * std::min(m[0], std::min(m[4], m[8]));
+    double v[3][3];
+    for (int k = 0; k < 3; ++k) { v[k][0] = m[k]; v[k][1] = m[3 + k]; v[k][2] = m[6 + k]; }
+    auto cross = [](const double *a, const double *b, double *c) {
+        c[0] = a[1] * b[2] - a[2] * b[1];
+        c[1] = a[2] * b[0] - a[0] * b[2];
+        c[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    double bc[3];
+    cross(v[1], v[2], bc);
+    const double vol = std::fabs(v[0][0] * bc[0] + v[0][1] * bc[1] + v[0][2] * bc[2]);
+    double least = 0.0;
+    for (int i = 0; i < 3; ++i) {
+        double c[3];
+        cross(v[(i + 1) % 3], v[(i + 2) % 3], c);
+        const double w = vol / std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+        if (i == 0 || w < least) least = w;
+    }
+    return 0.5 * least;
+}
+
+static std::string rdf_number(double v) {
+    char buf[40];
+    std::snprintf(buf, sizeof buf, "%.17g", v);
+    return buf;
+}
+
+// the three accumulator arrays inside d_acc
+struct RdfBlocks { unsigned long long *hist, *eligible, *samples; size_t per_hist, bytes; };
+static RdfBlocks rdf_blocks(const mgpu_engine *e) {
+    const size_t R = (size_t)e->n_replicas, per = (size_t)e->rdf.n_pairs * e->rdf.n_bins;
+    RdfBlocks b;
+    b.hist = (unsigned long long *)e->rdf.d_acc.p;
+    b.eligible = b.hist + R * per;
+    b.samples = b.eligible + R * e->rdf.n_pairs;
+    b.per_hist = per;
+    b.bytes = (R * per + R * e->rdf.n_pairs + R) * sizeof(unsigned long long);
+    return b;
+}
+
+static int rdf_ready(const mgpu_engine *e, const char *who) {
+    if (e->rdf.n_pairs == 0) return set_error(MGPU_ERR_STATE, std::string(who) + ": no histogram is configured (mgpu_rdf_configure)");
+    return MGPU_OK;
+}
 
 }  // namespace mgpu
 
@@ -205,6 +262,155 @@ int mgpu_init_structure_factor_replicas(mgpu_engine *e, int n, const int *replic
                                           (double2 *)e->lanes[0].d_scratch.p, true, e->d_A)))
             return rc;
     return sync_stream(e);
+}
+
+int mgpu_rdf_configure(mgpu_engine *e, int n_bins, double r_max, int n_pairs, const int *type_a, const int *type_b, int include_intra) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc;
+    if (n_pairs == 0) {
+        if ((rc = use_device(e))) return rc;
+        if ((rc = sync_all_lanes(e))) return rc;
+        e->rdf.d_acc.release();
+        e->rdf.d_tab.release();
+        e->rdf.n_pairs = 0; e->rdf.n_bins = 0;
+        return MGPU_OK;
+    }
+    if (n_bins < 1 || n_bins > kRdfMaxBins)
+        return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: n_bins " + std::to_string(n_bins) + " is outside [1, " + std::to_string(kRdfMaxBins) + "]");
+    if (n_pairs < 1 || n_pairs > kRdfMaxPairs)
+        return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: n_pairs " + std::to_string(n_pairs) + " is outside [1, " + std::to_string(kRdfMaxPairs) + "]");
+    if (!type_a || !type_b) return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: null pair list");
+    if (include_intra != 0 && include_intra != 1) return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: include_intra must be 0 or 1");
+    if (!(r_max > 0.0) || !std::isfinite(r_max)) return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: r_max must be greater than 0");
+    const double limit = rdf_half_width(e);
+    if (r_max > limit)
+        return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: r_max " + rdf_number(r_max) +
+                         " exceeds half the smallest perpendicular width of the cell, " + rdf_number(limit));
+    const int nt = e->tp.n_types;
+    RdfTable tab;
+    for (int a = 0; a < kMaxTypes; ++a) { tab.row[a] = ~0ull; tab.partner[a] = 0; }
+    for (int p = 0; p < n_pairs; ++p) {
+        const int a = type_a[p], b = type_b[p];
+        if (a < 0 || a >= nt || b < 0 || b >= nt || a >= kMaxTypes || b >= kMaxTypes)
+            return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: pair " + std::to_string(p) + ": atom type out of range [0, " +
+                             std::to_string(nt - 1) + "]");
+        if (((tab.row[a] >> (4 * b)) & kRdfNone) != (unsigned)kRdfNone)
+            return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: pair " + std::to_string(p) + " (" + std::to_string(a) + ", " +
+                             std::to_string(b) + ") is a duplicate");
+        tab.row[a] = (tab.row[a] & ~((unsigned long long)kRdfNone << (4 * b))) | ((unsigned long long)p << (4 * b));
+        tab.row[b] = (tab.row[b] & ~((unsigned long long)kRdfNone << (4 * a))) | ((unsigned long long)p << (4 * a));
+        tab.partner[a] |= 1u << b;
+        tab.partner[b] |= 1u << a;
+    }
+    // a workgroup's 32-bit LDS bins take at most 256 x (atom slots) counts, its molecule keys (type << 28) | molecule
+    if (e->tp.n_cap_atoms >= (1 << 24))
+        return set_error(MGPU_ERR_CAPACITY, "rdf_configure: more than 2^24 atom slots per replica");
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    e->rdf.d_acc.release();
+    e->rdf.n_pairs = 0;
+    const size_t R = (size_t)e->n_replicas;
+    const size_t bytes = (R * n_pairs * n_bins + R * n_pairs + R) * sizeof(unsigned long long);
+    if ((rc = e->rdf.d_acc.reserve(bytes))) return rc;
+    if ((rc = e->rdf.d_tab.reserve(sizeof(RdfTable)))) return rc;
+    HIP_TRY(hipMemset(e->rdf.d_acc.p, 0, bytes));
+    HIP_TRY(hipMemcpy(e->rdf.d_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice));
+    e->rdf.n_bins = n_bins; e->rdf.n_pairs = n_pairs; e->rdf.include_intra = include_intra;
+    e->rdf.r_max = r_max; e->rdf.r_max2 = r_max * r_max; e->rdf.inv_dr = (double)n_bins / r_max;
+    for (int p = 0; p < n_pairs; ++p) { e->rdf.type_a[p] = type_a[p]; e->rdf.type_b[p] = type_b[p]; }
+    return MGPU_OK;
+}
+
+int mgpu_rdf_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int chunk) {
+    int rc = check_replica_list(e, n, replicas, "rdf_accumulate_replicas");
+    if (rc) return rc;
+    if ((rc = rdf_ready(e, "rdf_accumulate_replicas"))) return rc;
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const RdfBlocks acc = rdf_blocks(e);
+    if ((rc = e->d_items2.reserve((size_t)n * sizeof(int)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_items2.p, replicas, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    const int most = chunk > 0 ? std::min(chunk, kRdfPassMax) : kRdfPassMax;
+    const int n_iblk = (e->tp.n_cap_atoms + kRdfBlock - 1) / kRdfBlock;
+    const size_t lds = acc.per_hist * sizeof(unsigned);
+    for (int first = 0; first < n; first += most) {
+        const int c = std::min(most, n - first);
+        // j chunks per i block: few replicas -> many chunks, to give every CU some workgroups; many replicas -> one
+        RdfArgs ra{e->rdf.n_bins, e->rdf.n_pairs, e->rdf.include_intra, 1, e->rdf.r_max2, e->rdf.inv_dr};
+        const long long tiles = (long long)c * n_iblk;
+        ra.n_chunk = (int)std::max<long long>(1, std::min<long long>(n_iblk, (4LL * e->n_cu + tiles - 1) / tiles));
+        const dim3 grid((unsigned)(n_iblk * ra.n_chunk), (unsigned)c);
+        const int *d_reps = (const int *)e->d_items2.p + first;
+        with_bools([&](auto tri) {
+            hipLaunchKernelGGL((rdf_hist_kernel<decltype(tri)::value>), grid, dim3(kRdfBlock), lds, e->stream, e->tp, e->bx, ra,
+                               (const double *)e->d_pos, (const int *)e->d_nmol, (const int *)e->d_atom_res,
+                               (const int *)e->d_atom_mol, d_reps, (const RdfTable *)e->rdf.d_tab.p, acc.hist, acc.eligible, acc.samples);
+        }, e->bx.triclinic != 0);
+        HIP_TRY(hipGetLastError());
+    }
+    return sync_stream(e);
+}
+
+int mgpu_rdf_read(mgpu_engine *e, int n, const int *replicas, unsigned long long *hist, unsigned long long *eligible,
+                  unsigned long long *samples) {
+    int rc = check_replica_list(e, n, replicas, "rdf_read");
+    if (rc) return rc;
+    if ((rc = rdf_ready(e, "rdf_read"))) return rc;
+    if (n > 0 && (!hist || !eligible || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "rdf_read: null output");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const RdfBlocks acc = rdf_blocks(e);
+    std::vector<unsigned long long> all(acc.bytes / sizeof(unsigned long long));
+    HIP_TRY(hipMemcpy(all.data(), e->rdf.d_acc.p, acc.bytes, hipMemcpyDeviceToHost));
+    const size_t R = (size_t)e->n_replicas, np = (size_t)e->rdf.n_pairs;
+    const unsigned long long *h = all.data(), *el = h + R * acc.per_hist, *sm = el + R * np;
+    for (int i = 0; i < n; ++i) {
+        const size_t r = (size_t)replicas[i];
+        std::memcpy(hist + (size_t)i * acc.per_hist, h + r * acc.per_hist, acc.per_hist * sizeof(unsigned long long));
+        std::memcpy(eligible + (size_t)i * np, el + r * np, np * sizeof(unsigned long long));
+        samples[i] = sm[r];
+    }
+    return MGPU_OK;
+}
+
+int mgpu_rdf_load(mgpu_engine *e, int n, const int *replicas, const unsigned long long *hist, const unsigned long long *eligible,
+                  const unsigned long long *samples) {
+    int rc = check_replica_list(e, n, replicas, "rdf_load");
+    if (rc) return rc;
+    if ((rc = rdf_ready(e, "rdf_load"))) return rc;
+    if (n > 0 && (!hist || !eligible || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "rdf_load: null input");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const RdfBlocks acc = rdf_blocks(e);
+    const size_t np = (size_t)e->rdf.n_pairs;
+    for (int i = 0; i < n; ++i) {
+        const size_t r = (size_t)replicas[i];
+        HIP_TRY(hipMemcpy(acc.hist + r * acc.per_hist, hist + (size_t)i * acc.per_hist, acc.per_hist * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(acc.eligible + r * np, eligible + (size_t)i * np, np * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(acc.samples + r, samples + i, sizeof(unsigned long long), hipMemcpyHostToDevice));
+    }
+    return MGPU_OK;
+}
+
+int mgpu_rdf_reset(mgpu_engine *e, int n, const int *replicas) {
+    int rc = check_replica_list(e, n, replicas, "rdf_reset");
+    if (rc) return rc;
+    if ((rc = rdf_ready(e, "rdf_reset"))) return rc;
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const RdfBlocks acc = rdf_blocks(e);
+    const size_t np = (size_t)e->rdf.n_pairs;
+    for (int i = 0; i < n; ++i) {
+        const size_t r = (size_t)replicas[i];
+        HIP_TRY(hipMemset(acc.hist + r * acc.per_hist, 0, acc.per_hist * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(acc.eligible + r * np, 0, np * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(acc.samples + r, 0, sizeof(unsigned long long)));
+    }
+    return MGPU_OK;
 }
 
 }  // extern "C"

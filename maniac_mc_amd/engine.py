@@ -503,6 +503,59 @@ class Engine:
         r = self._replica_list(replicas)
         check(self.L.mgpu_init_structure_factor_replicas(self.h, C.c_int(r.shape[0]), _i(r), C.c_int(1 if full else 0)))
 
+    # ---- radial distribution functions ---------------------------------------------------
+    def rdf_configure(self, n_bins, r_max, pairs, include_intra=False):
+        """mgpu_rdf_configure: histograms of n_bins bins up to r_max for the unordered pairs [(a, b), ...] of 0-based atom types
+        (at most 8), zeroed, for every replica.  pairs = [] frees them."""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        ta = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int32)
+        tb = np.ascontiguousarray([p[1] for p in pairs], dtype=np.int32)
+        check(self.L.mgpu_rdf_configure(self.h, C.c_int(int(n_bins)), C.c_double(float(r_max)), C.c_int(len(pairs)),
+                                        _i(ta) if pairs else None, _i(tb) if pairs else None, C.c_int(1 if include_intra else 0)))
+        self.rdf_shape = (len(pairs), int(n_bins)) if pairs else None
+
+    def _rdf_shape(self):
+        shape = getattr(self, "rdf_shape", None)
+        if shape is None:
+            raise _lib.MgpuError(5, "no histogram is configured (Engine.rdf_configure)")
+        return shape
+
+    def rdf_accumulate(self, replicas=None, chunk=None):
+        """mgpu_rdf_accumulate_replicas: one sample of every listed replica (None: all) from the resident coordinates."""
+        r = self._replica_list(replicas)
+        check(self.L.mgpu_rdf_accumulate_replicas(self.h, C.c_int(r.shape[0]), _i(r), C.c_int(0 if chunk is None else int(chunk))))
+
+    def rdf_read(self, replicas=None):
+        """mgpu_rdf_read: (hist (n, n_pairs, n_bins), eligible (n, n_pairs), samples (n,)) of the listed replicas, uint64."""
+        r = self._replica_list(replicas)
+        np_, nb = self._rdf_shape()
+        n = r.shape[0]
+        hist = np.zeros((n, np_, nb), dtype=np.uint64)
+        elig = np.zeros((n, np_), dtype=np.uint64)
+        samples = np.zeros(n, dtype=np.uint64)
+        u = C.POINTER(C.c_ulonglong)
+        check(self.L.mgpu_rdf_read(self.h, C.c_int(n), _i(r), hist.ctypes.data_as(u), elig.ctypes.data_as(u), samples.ctypes.data_as(u)))
+        return hist, elig, samples
+
+    def rdf_load(self, hist, eligible, samples, replicas=None):
+        """mgpu_rdf_load: overwrite the listed replicas' accumulators with arrays shaped as rdf_read returns them."""
+        r = self._replica_list(replicas)
+        np_, nb = self._rdf_shape()
+        n = r.shape[0]
+        hist = np.ascontiguousarray(hist, dtype=np.uint64)
+        elig = np.ascontiguousarray(eligible, dtype=np.uint64)
+        samples = np.ascontiguousarray(samples, dtype=np.uint64)
+        if hist.shape != (n, np_, nb) or elig.shape != (n, np_) or samples.shape != (n,):
+            raise ValueError(f"rdf_load: arrays of shapes {hist.shape}, {elig.shape}, {samples.shape} for {n} replicas of "
+                             f"{np_} pairs and {nb} bins")
+        u = C.POINTER(C.c_ulonglong)
+        check(self.L.mgpu_rdf_load(self.h, C.c_int(n), _i(r), hist.ctypes.data_as(u), elig.ctypes.data_as(u), samples.ctypes.data_as(u)))
+
+    def rdf_reset(self, replicas=None):
+        """mgpu_rdf_reset: zero the listed replicas' accumulators (None: all)."""
+        r = self._replica_list(replicas)
+        check(self.L.mgpu_rdf_reset(self.h, C.c_int(r.shape[0]), _i(r)))
+
     def structure_factor(self, replica=0):
         a = np.zeros((self.nk, 2))
         check(self.L.mgpu_get_structure_factor(self.h, C.c_int(replica), _d(a)))

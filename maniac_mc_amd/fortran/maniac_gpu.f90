@@ -153,6 +153,47 @@ module maniac_gpu
             integer(c_int), intent(in) :: replicas(*)
             integer(c_int) :: rc
         end function
+        ! radial distribution functions of many replicas: integer histograms of the resident coordinates (0-based atom types)
+        function mgpu_rdf_configure(e, n_bins, r_max, n_pairs, type_a, type_b, include_intra) &
+                bind(C, name="mgpu_rdf_configure") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: n_bins, n_pairs, include_intra
+            real(c_double), value :: r_max
+            integer(c_int), intent(in) :: type_a(*), type_b(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_rdf_accumulate_replicas(e, n, replicas, chunk) &
+                bind(C, name="mgpu_rdf_accumulate_replicas") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n, chunk
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_rdf_read(e, n, replicas, hist, eligible, samples) bind(C, name="mgpu_rdf_read") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_long_long), intent(out) :: hist(*), eligible(*), samples(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_rdf_load(e, n, replicas, hist, eligible, samples) bind(C, name="mgpu_rdf_load") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_long_long), intent(in) :: hist(*), eligible(*), samples(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_rdf_reset(e, n, replicas) bind(C, name="mgpu_rdf_reset") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_int) :: rc
+        end function
         function mgpu_pair_energy_candidates(e, n, replica, t, m, use_resident, sites, site_stride, e_nc, e_c) &
                 bind(C, name="mgpu_pair_energy_candidates") result(rc)
             import :: c_ptr, c_int, c_double
@@ -744,5 +785,52 @@ contains
         rc = mgpu_commit_candidates(engine, 1_c_int, rep, t, m, kind, sites, int(natoms, c_int), acc)
         call GpuCheck(rc, 'GpuAcceptMove', stat)
     end subroutine GpuAcceptMove
+
+    !---------------------------------------------------------------------------
+    ! Radial distribution functions.  Atom types are 1-based here, as in the data file; replicas
+    ! are 0-based, as everywhere in this module.  The counts are integer(c_long_long): hist(n_bins,
+    ! n_pairs, n), eligible(n_pairs, n), samples(n).
+    !---------------------------------------------------------------------------
+    subroutine GpuRdfConfigure(engine, n_bins, r_max, n_pairs, type_a, type_b, include_intra, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n_bins, n_pairs, type_a(n_pairs), type_b(n_pairs)
+        real(real64), intent(in) :: r_max
+        logical, intent(in) :: include_intra
+        integer, intent(out), optional :: stat
+        integer(c_int) :: a(max(1, n_pairs)), b(max(1, n_pairs)), rc
+        a(1:n_pairs) = int(type_a - 1, c_int); b(1:n_pairs) = int(type_b - 1, c_int)
+        rc = mgpu_rdf_configure(engine, int(n_bins, c_int), r_max, int(n_pairs, c_int), a, b, merge(1_c_int, 0_c_int, include_intra))
+        call GpuCheck(rc, 'GpuRdfConfigure', stat)
+    end subroutine GpuRdfConfigure
+
+    subroutine GpuRdfAccumulate(engine, n, replicas, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, replicas(n)
+        integer, intent(out), optional :: stat
+        call GpuCheck(mgpu_rdf_accumulate_replicas(engine, int(n, c_int), int(replicas, c_int), 0_c_int), 'GpuRdfAccumulate', stat)
+    end subroutine GpuRdfAccumulate
+
+    subroutine GpuRdfRead(engine, n, replicas, hist, eligible, samples, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, replicas(n)
+        integer(c_long_long), intent(out) :: hist(*), eligible(*), samples(*)
+        integer, intent(out), optional :: stat
+        call GpuCheck(mgpu_rdf_read(engine, int(n, c_int), int(replicas, c_int), hist, eligible, samples), 'GpuRdfRead', stat)
+    end subroutine GpuRdfRead
+
+    subroutine GpuRdfLoad(engine, n, replicas, hist, eligible, samples, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, replicas(n)
+        integer(c_long_long), intent(in) :: hist(*), eligible(*), samples(*)
+        integer, intent(out), optional :: stat
+        call GpuCheck(mgpu_rdf_load(engine, int(n, c_int), int(replicas, c_int), hist, eligible, samples), 'GpuRdfLoad', stat)
+    end subroutine GpuRdfLoad
+
+    subroutine GpuRdfReset(engine, n, replicas, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, replicas(n)
+        integer, intent(out), optional :: stat
+        call GpuCheck(mgpu_rdf_reset(engine, int(n, c_int), int(replicas, c_int)), 'GpuRdfReset', stat)
+    end subroutine GpuRdfReset
 
 end module maniac_gpu

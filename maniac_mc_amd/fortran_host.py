@@ -295,6 +295,12 @@ class FortranFarm:
                     energy_deviation=np.max(np.abs(running - recomputed[:, :5]), axis=1) if len(reps) else np.zeros(0),
                     a_deviation=a_dev)
 
+    def rdf_sample(self, replicas=None, chunk=None):
+        """One sample of every listed chain (None: all) into the engine's histograms (Engine.rdf_configure first), from the
+        coordinates the engine holds -- which are current between two run() calls in every farm mode."""
+        self.eng.rdf_accumulate(replicas, chunk)
+        self._select()
+
     def run(self, n_steps: int) -> int:
         """Advance every chain by n_steps move selections; returns the moves accepted during this call."""
         self._select()

@@ -22,6 +22,7 @@ import os
 import numpy as np
 
 from . import _lib, checkpoint, fortran_host, io_maniac
+from . import rdf as rdf_mod
 from .fortran_host import FortranFarm
 from .run import header_text, set_chain_state
 from .system import KB_KCALMOL, NB_MAX_MOLECULE
@@ -72,7 +73,7 @@ def _stats(x):
 def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=None, fugacities=None, frames=(0,),
                  mode="auto", device=0, nb_block=None, nb_step=None, mol_capacity=None, n_lanes=2, n_threads=8,
                  chunk=None, wide_triclinic=False, restart_from=None, audit=False, checkpoint_every=0, resume=False,
-                 recalibrate_moves=None):
+                 recalibrate_moves=None, rdf=None):
     """Run `replicas` independent chains of the input; returns a dict with the final energies (R, 5) in K (non-Coulomb,
     Coulomb, reciprocal, self, intramolecular), counts (R, n_active), chain counters (R, 8), the farm's counters, the
     mode that ran and the block timings.
@@ -107,6 +108,13 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     go on from the recorded index, appending: the files are those of the uninterrupted run, byte for byte, on the same
     library build and GPU model.  Works with a reservoir; not together with ``restart_from``.
     ``recalibrate_moves``: None -> the input's choice; True / False override it.
+    ``rdf``: dict(r_max=..., n_bins=..., pairs=[(a, b), ...] (0-based atom types; default: every pair of the active types' atom
+    types, at most 8), every=1, include_intra=False) -> after every `every`-th block one sample of every replica goes into the
+    engine's histograms (Engine.rdf_accumulate; its time in seconds["rdf"]); after the last block <outdir>/rdf_counts.npz
+    (hist, eligible, samples per replica, the spec, every replica's group) and <outdir>/rdf.dat (per fugacity group and pair:
+    r_mid, g(r) pooled over the group's replicas and samples, its standard error over the replicas, the pooled raw count) are
+    written (maniac_mc_amd.rdf).  A checkpoint then carries the accumulators, and a resumed run must ask for the same rdf.
+    None (default): nothing of this, and every file is what it always was.
     """
     import time
     if mode not in MODES:
@@ -141,6 +149,24 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     nb_step = inp.nb_step if nb_step is None else int(nb_step)
     if seed is None:
         seed = inp.seed if inp.has_seed and inp.seed > 0 else 1
+    rdf_spec = None
+    if rdf is not None:
+        unknown = set(rdf) - {"r_max", "n_bins", "pairs", "every", "include_intra"}
+        if unknown or "r_max" not in rdf or "n_bins" not in rdf:
+            raise ValueError(f"rdf: needs r_max and n_bins, and takes pairs, every and include_intra besides ({sorted(unknown)} unknown)")
+        pairs = rdf.get("pairs")
+        pairs = rdf_mod.check_pairs(rdf_mod.default_pairs(topo) if pairs is None else pairs, topo.n_atom_types)
+        rdf_spec = dict(r_max=float(rdf["r_max"]), n_bins=int(rdf["n_bins"]), pairs=pairs, every=int(rdf.get("every", 1)),
+                        include_intra=bool(rdf.get("include_intra", False)))
+        if not rdf_spec["r_max"] > 0.0:
+            raise ValueError("rdf: r_max must be greater than 0")
+        if not 1 <= rdf_spec["n_bins"] <= rdf_mod.MAX_BINS:
+            raise ValueError(f"rdf: n_bins must lie in [1, {rdf_mod.MAX_BINS}]")
+        if rdf_spec["every"] < 1:
+            raise ValueError("rdf: every must be at least 1")
+        limit = rdf_mod.half_width(system.box_matrix)
+        if rdf_spec["r_max"] > limit:
+            raise ValueError(f"rdf: r_max {rdf_spec['r_max']!r} exceeds half the smallest perpendicular width of the cell, {limit!r}")
 
     group = np.zeros(R, dtype=np.int64)
     if fugacities is not None:
@@ -156,6 +182,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     if checkpoint_every or resume:
         ident = checkpoint.identity(_lib.ABI_VERSION, nb_step, seed, mode, R, fugacities, frames, maniac, data, inc, reservoir_path)
         ident["recalibrate"] = int(recalibrate)
+        if rdf_spec is not None:
+            ident["rdf"] = rdf_mod.identity_array(rdf_spec)
     if resume:
         ck = checkpoint.load(outdir)
         checkpoint.check(ck, ident, nb_block)
@@ -209,6 +237,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         names = [inp.residues[t].name for t in active]
         stats_path = os.path.join(root, "replicas.dat")
         times = dict(run=0.0, write=0.0, snapshot=0.0)
+        if rdf_spec is not None:
+            farm.eng.rdf_configure(rdf_spec["n_bins"], rdf_spec["r_max"], rdf_spec["pairs"], rdf_spec["include_intra"])
+            times["rdf"] = 0.0
 
         def write(block, final):
             t0 = time.perf_counter()
@@ -252,8 +283,11 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         def save_checkpoint(next_block):
             t0 = time.perf_counter()
             state = farm.checkpoint_state()
+            extra = None
+            if rdf_spec is not None:
+                extra = dict(zip(("rdf_hist", "rdf_eligible", "rdf_samples"), farm.eng.rdf_read()))
             checkpoint.save(outdir, ident, next_block, nb_block, ran, state["engine"], state["driver"],
-                            checkpoint.output_sizes(outdir, R))
+                            checkpoint.output_sizes(outdir, R), extra=extra)
             times["checkpoint"] = times.get("checkpoint", 0.0) + time.perf_counter() - t0
 
         first = 1
@@ -262,6 +296,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
             checkpoint.truncate_outputs(outdir, ck["sizes"])
             checkpoint.restate_block_count(outdir, ck["sizes"], int(ck["nb_block"]), nb_block)
             farm.restore_state(dict(engine=ck["engine"], driver=ck["driver"]))
+            if rdf_spec is not None:
+                x = ck["extra"]
+                farm.eng.rdf_load(x["rdf_hist"], x["rdf_eligible"], x["rdf_samples"])
             first = int(ck["next_block"])
         else:
             write(0, False)
@@ -271,10 +308,20 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
             if recalibrate:
                 farm.recalibrate()
             times["run"] += time.perf_counter() - t0
+            if rdf_spec is not None and block % rdf_spec["every"] == 0:
+                t0 = time.perf_counter()
+                farm.rdf_sample()
+                times["rdf"] += time.perf_counter() - t0
             write(block, False)
             if checkpoint_every and (block % int(checkpoint_every) == 0 or block == nb_block):
                 save_checkpoint(block + 1)
         write(nb_block, True)
+        if rdf_spec is not None:
+            hist, eligible, samples = farm.eng.rdf_read()
+            rdf_mod.write_counts(os.path.join(root, "rdf_counts.npz"), hist, eligible, samples, group, rdf_spec["pairs"],
+                                 rdf_spec["r_max"], rdf_spec["n_bins"], rdf_spec["every"], rdf_spec["include_intra"])
+            rdf_mod.write_dat(os.path.join(root, "rdf.dat"), hist, eligible, group, rdf_spec["pairs"],
+                              rdf_mod.volume(system.box_matrix), rdf_spec["r_max"])
         _lib.check(0)
         energies = np.array([farm.energy(r) for r in range(R)])
         res = dict(energy=energies, counts=farm.counts(), chain_counters=farm.chain_counters(), counters=farm.counters(),

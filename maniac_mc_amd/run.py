@@ -315,6 +315,15 @@ def main(argv=None):
     ap.add_argument("--resume", action="store_true",
                     help="with --replicas: continue the run whose checkpoint lies in <out>, bit for bit (same inputs, replicas, "
                          "seed, mode and nb_step; a larger nb_block extends it)")
+    ap.add_argument("--rdf", default=None, metavar="R_MAX,N_BINS[,EVERY]",
+                    help="with --replicas: pair distribution functions up to R_MAX (at most half the smallest cell width) in N_BINS "
+                         "bins, one sample of every replica after every EVERY-th block (default 1); writes <out>/rdf.dat and "
+                         "<out>/rdf_counts.npz")
+    ap.add_argument("--rdf-pairs", dest="rdf_pairs", default=None, metavar="A-B,A-B,...",
+                    help="with --rdf: the atom-type pairs, ids as in the data file (default: every pair of the active types' atom "
+                         "types; at most 8)")
+    ap.add_argument("--rdf-intra", dest="rdf_intra", action="store_true",
+                    help="with --rdf: count pairs inside one molecule too")
     a = ap.parse_args(argv)
     try:
         chain_run = parse_chain_run(a.chain_run) if a.chain_run is not None else None
@@ -335,6 +344,8 @@ def main(argv=None):
             ap.error("--restart-from and --audit need --replicas")
         if a.checkpoint_every or a.resume:
             ap.error("--checkpoint-every and --resume need --replicas")
+        if a.rdf is not None or a.rdf_pairs is not None or a.rdf_intra:
+            ap.error("--rdf, --rdf-pairs and --rdf-intra need --replicas: the single chain writes no distribution functions")
     else:
         from . import replicas as farm_run
         if a.as_written:
@@ -350,6 +361,17 @@ def main(argv=None):
             fugacities = farm_run.parse_fugacities(a.fugacities) if a.fugacities is not None else None
         except ValueError as err:
             ap.error(str(err))
+        rdf = None
+        if a.rdf is None and (a.rdf_pairs is not None or a.rdf_intra):
+            ap.error("--rdf-pairs and --rdf-intra need --rdf R_MAX,N_BINS[,EVERY]")
+        if a.rdf is not None:
+            from . import rdf as rdf_mod
+            try:
+                rdf = rdf_mod.parse_spec(a.rdf)
+                rdf["pairs"] = rdf_mod.parse_pairs(a.rdf_pairs) if a.rdf_pairs is not None else None
+                rdf["include_intra"] = bool(a.rdf_intra)
+            except ValueError as err:
+                ap.error(str(err))
     for path, what in ((a.maniac, "Input"), (a.data, "Data"), (a.inc, "Parameter"), (a.reservoir, "Reservoir")):
         if path is not None and not os.path.isfile(path):
             print(f"{what} file not found: {path}", file=sys.stderr)
@@ -359,7 +381,7 @@ def main(argv=None):
             res = farm_run.run_replicas(a.maniac, a.data, a.inc, a.out, a.replicas, seed=a.seed, reservoir_path=a.reservoir,
                                         fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device,
                                         wide_triclinic=a.wide_triclinic, restart_from=a.restart_from, audit=a.audit,
-                                        checkpoint_every=a.checkpoint_every, resume=a.resume)
+                                        checkpoint_every=a.checkpoint_every, resume=a.resume, rdf=rdf)
         except ValueError as err:
             print(f"error: {err}", file=sys.stderr)
             return 2
