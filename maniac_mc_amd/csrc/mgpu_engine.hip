@@ -738,10 +738,12 @@ int mgpu_engine_create(mgpu_engine **out, int device, int n_replicas, int n_res,
         const double sum_len = e->metrics[0] + e->metrics[1] + e->metrics[2];
         const double s_max = bx.triclinic ? sum_len * sum_len
                                           : 0.25 * (bx.L[0] * bx.L[0] + bx.L[1] * bx.L[1] + bx.L[2] * bx.L[2]) * 1.0001;
-        int idx_base = 0;
-        if (int rc2 = build_coulomb_table(e->alpha, std::max(s_max, 1.0), rows, &idx_base)) return fail(rc2);
+        int idx_base = 0, box_last_row = 0;
+        if (int rc2 = build_coulomb_table(e->alpha, std::max(s_max, 1.0), rows, &idx_base, &box_last_row)) return fail(rc2);
         e->bx.coul_idx_base = idx_base;
         e->bx.coul_last_row = (int)rows.size() - 1;
+        e->bx.coul_idx_far = idx_base + e->bx.coul_last_row;
+        e->bx.coul_idx_end = idx_base + box_last_row;
         e->coul_bytes = rows.size() * sizeof(CoulRow);
         if (e->coul_bytes + 16 * 1024 > 150 * 1024) return fail(set_error(MGPU_ERR_CAPACITY, "Coulomb table does not fit LDS"));
         HIP_TRY_E(hipMalloc(&e->d_coul_tab, e->coul_bytes));

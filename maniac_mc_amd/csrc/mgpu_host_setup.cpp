@@ -134,8 +134,11 @@ int ewald_kvectors(const double rcp[9], double alpha, const int kmax[3], int nk,
 // Coefficients: Chebyshev interpolation at 7 nodes in long double (64-bit mantissa, erfcl),
 // re-expanded in t, rounded once.  Indexing by the bits of s removes sqrt / rsqrt / erfc / exp and
 // every division from the per-pair arithmetic of energy_utils.f90:432.
+// rows.back() is the row every lookup index is clamped to: the shared far row (below), or the all-zero row behind the
+// octave of s_max.  *box_last_row (if asked for) = the index that all-zero row has or would have had: the first row
+// beyond every distance of the box.
 // ------------------------------------------------------------------------------------------
-int build_coulomb_table(double alpha, double s_max, std::vector<CoulRow> &rows, int *idx_base) {
+int build_coulomb_table(double alpha, double s_max, std::vector<CoulRow> &rows, int *idx_base, int *box_last_row) {
     if (!(alpha > 0.0) || !(s_max > 0.0) || !std::isfinite(s_max))
         return set_error(MGPU_ERR_INVALID_ARG, "build_coulomb_table: bad alpha / range");
     int emax = kCoulEmin;
@@ -194,6 +197,22 @@ int build_coulomb_table(double alpha, double s_max, std::vector<CoulRow> &rows, 
             row.c5 = (float)ldexpl(tc[5], sh * 5);
             row.c6 = (float)ldexpl(tc[6], sh * 6);
         }
+    if (box_last_row) *box_last_row = (int)rows.size() - 1;
+    // The shared far row: the first row at whose start s_far a term of unit charge product is worth no more than
+    // kCoulFarKelvin.  G falls with s, so every lookup from there on is G(s_far) to within G(s_far) itself.  A box that
+    // reaches beyond s_far gets that constant as its LAST row (c1 .. c6 = 0: the lookup's t, taken from the lane's own
+    // row start, multiplies zeros) and no row behind it; a box that does not keeps the table above as it is.
+    for (size_t i = 0; i + 1 < rows.size(); ++i) {
+        const long double a = ldexpl(1.0L, kCoulEmin + (int)(i / per_oct)) * (1.0L + (long double)(i % per_oct) / per_oct);
+        if (!(a < (long double)s_max)) break;
+        const long double r = sqrtl(a), g = erfcl(al * r) / r;
+        if ((long double)kCoulKelvin * g <= (long double)kCoulFarKelvin) {
+            rows.resize(i + 1);
+            rows[i] = CoulRow{};
+            rows[i].c[0] = (double)g;
+            break;
+        }
+    }
     return MGPU_OK;
 }
 
@@ -361,7 +380,7 @@ int mgpu_coulomb_table_eval(double alpha, double r2_max, int n, const double *r2
     if (n < 0 || (n > 0 && (!r2 || !out))) return mgpu::set_error(MGPU_ERR_INVALID_ARG, "mgpu_coulomb_table_eval: bad argument");
     std::vector<mgpu::CoulRow> rows;
     int idx_base = 0;
-    int rc = mgpu::build_coulomb_table(alpha, r2_max, rows, &idx_base);
+    int rc = mgpu::build_coulomb_table(alpha, r2_max, rows, &idx_base, nullptr);
     if (rc) return rc;
     for (int k = 0; k < n; ++k) out[k] = mgpu::coulomb_table_eval_host(rows, idx_base, alpha, r2[k]);
     return MGPU_OK;

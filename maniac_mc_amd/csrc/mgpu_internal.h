@@ -39,7 +39,11 @@ struct CoulRow {
 };
 static_assert(sizeof(CoulRow) == 48, "CoulRow must be three 16-byte LDS reads");
 constexpr int kCoulRowVec = sizeof(CoulRow) / 16;  // 16-byte LDS reads per row
-int build_coulomb_table(double alpha, double s_max, std::vector<CoulRow> &rows, int *idx_base);
+// the shared far row starts where kCoulKelvin * G(s) <= kCoulFarKelvin: a tenth of the 1e-11 K per unit charge product the
+// table is held to beyond alpha r = 1 (tests/test_coulomb_table.py)
+constexpr double kCoulKelvin = 167101.0;           // K A per unit charge product (the bound's scale, not the engine's constant)
+constexpr double kCoulFarKelvin = 1.0e-12;
+int build_coulomb_table(double alpha, double s_max, std::vector<CoulRow> &rows, int *idx_base, int *box_last_row = nullptr);
 double coulomb_table_eval_host(const std::vector<CoulRow> &rows, int idx_base, double alpha, double s);
 
 // ---- Dynamic LDS of the reciprocal kernels: the one home of this arithmetic (plain integers: the host tests compile it

@@ -101,7 +101,9 @@ struct BoxDev {
     double rc2;                   // real_space_cutoff^2
     double alpha;
     int coul_idx_base;            // Coulomb table: row = (hi32(r^2) >> 14) - coul_idx_base
-    int coul_last_row;            // index of the all-zero clamp row (= number of real rows)
+    int coul_last_row;            // last row of the staged table: the shared far row, or (a box that reaches none) the all-zero clamp row
+    int coul_idx_far;             // coul_idx_base + coul_last_row: every lookup's index is clamped to it (coul_lds)
+    int coul_idx_end;             // first index beyond the box's largest minimum-image distance (pair_term discards from here on)
     double volume;
     int kmax[3];
     int nk;
@@ -326,8 +328,12 @@ __device__ __forceinline__ double fast_rcp(double x) {
 // erfc, exp or division.
 // Index path, two instructions (round 4; it was four): sh = the high word of s shifted down to (exponent | 6 mantissa bits),
 // address = sh * 48 + tab_adj in ONE v_mad_u32_u24, where tab_adj = table - idx_base * 48 (coul_tab_adjusted) carries the
-// subtraction of the table's first index.  There is NO clamp: a minimum-image r^2 cannot lie beyond the table (it is built
-// up to the box's largest minimum-image distance), and an s BELOW the table (r < 0.5 A: sh < idx_base) makes the address
+// subtraction of the table's first index.
+// Far row (one v_min_u32 more): sh is clamped to idx_far, the table's last row.  Where the box reaches distances at which
+// 167101 K A * G <= 1e-12 K, that row holds the constant G(s_far) > 0 (c1 .. c6 = 0, so the lane's own t multiplies zeros)
+// and the table ends there: every far lane of a read gets ONE address, which LDS serves as a broadcast instead of as a
+// bank conflict per lane, at an error of at most G(s_far) per term.  Elsewhere the last row is the all-zero row no
+// minimum-image r^2 reaches.  An s BELOW the table (r < 0.5 A: sh < idx_base) is NOT clamped and makes the address
 // fall outside the table -- just below it into the workgroup's other LDS arrays, or wrapped far outside the allocation.
 // Such a read raises nothing (tools/probe_lds_oob.hip, measured on MI355X) but its VALUE IS UNDEFINED (stale LDS bytes
 // near the allocation, zeros far from it): every caller MUST look at `sh_out` and replace those lanes by the slow path --
@@ -336,10 +342,11 @@ __device__ __forceinline__ double fast_rcp(double x) {
 __device__ __forceinline__ const char *coul_tab_adjusted(const char *tab, int idx_base) {
     return tab - (size_t)idx_base * sizeof(CoulRow);
 }
-__device__ __forceinline__ double coul_lds(double s, const char *__restrict__ tab_adj, unsigned &sh_out) {
+__device__ __forceinline__ double coul_lds(double s, const char *__restrict__ tab_adj, unsigned idx_far, unsigned &sh_out) {
     const int hi = __double2hiint(s);
-    const unsigned sh = (unsigned)hi >> (20 - kCoulM);
-    sh_out = sh;
+    unsigned sh = (unsigned)hi >> (20 - kCoulM);
+    sh_out = sh;                                                         // unclamped: the callers' below-table test
+    sh = min(sh, idx_far);
     constexpr int kMant = (1 << (20 - kCoulM)) - 1;
     const double s0 = __hiloint2double(hi & ~kMant, 0);                  // the row's first s: low mantissa bits cleared
     const double t = s - s0;                                             // exact; rows are expanded in it
@@ -379,10 +386,10 @@ __device__ __forceinline__ void pair_term(double dx, double dy, double dz, const
     }
     if (do_c) {
         unsigned sh;
-        double g = coul_lds(r2, coul_tab_adjusted(coul_tab, bx.coul_idx_base), sh);
+        double g = coul_lds(r2, coul_tab_adjusted(coul_tab, bx.coul_idx_base), bx.coul_idx_far, sh);
         // (this generic path also serves triclinic boxes, where a site more than a cell outside the box can give an r^2
-        //  beyond the table: such a lookup is discarded -- the all-zero last row's value -- as the clamped index gave it)
-        if (sh >= (unsigned)(bx.coul_idx_base + bx.coul_last_row)) g = 0.0;
+        //  beyond the box's largest distance: such a lookup is discarded, whatever the last row holds)
+        if (sh >= (unsigned)bx.coul_idx_end) g = 0.0;
         if (sh < (unsigned)bx.coul_idx_base) g = coul_slow(r2, bx.alpha, GUARD_R0);
         ec += qq * g;
     }

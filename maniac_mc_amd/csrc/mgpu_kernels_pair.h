@@ -190,7 +190,7 @@ __device__ __forceinline__ void pair_sweep_item(
                             for (int s = 0; s < NREG; ++s) {
                                 if (!ALL_C && !c_on[s % NTY]) { g[s] = 0.0; continue; }
                                 unsigned sh;
-                                g[s] = coul_lds(r2[s], coul_adj, sh);
+                                g[s] = coul_lds(r2[s], coul_adj, bx.coul_idx_far, sh);
                                 sh_min = min(sh_min, sh);
                             }
                             if (sh_min < (unsigned)bx.coul_idx_base) {   // r < 0.5 A for this lane: rare slow path
@@ -548,7 +548,7 @@ __device__ __forceinline__ void pair_flat_item(
 #pragma unroll
                 for (int s = 0; s < NREG; ++s) {
                     unsigned sh;
-                    g[s] = coul_lds(r2[s], coul_adj, sh);
+                    g[s] = coul_lds(r2[s], coul_adj, bx.coul_idx_far, sh);
                     sh_min = min(sh_min, sh);
                 }
                 if (sh_min < (unsigned)bx.coul_idx_base) {   // r < 0.5 A for this lane: rare slow path
@@ -765,7 +765,7 @@ __global__ __launch_bounds__(kPairBlock, MGPU_PAIR_MINWAVES) void pair_frozen_ke
                     g[s] = 0.0;
                     if (q_on[s % NTY]) {
                         unsigned sh;
-                        g[s] = coul_lds(r2[s], coul_adj, sh);
+                        g[s] = coul_lds(r2[s], coul_adj, bx.coul_idx_far, sh);
                         sh_min = min(sh_min, sh);
                     }
                 }
@@ -826,7 +826,7 @@ __global__ __launch_bounds__(kPairBlock, MGPU_PAIR_MINWAVES) void pair_frozen_ke
                             g[s] = 0.0;
                             if (q_on[s % NTY]) {
                                 unsigned sh;
-                                g[s] = coul_lds(r2[s], coul_adj, sh);
+                                g[s] = coul_lds(r2[s], coul_adj, bx.coul_idx_far, sh);
                                 sh_min = min(sh_min, sh);
                             }
                         }

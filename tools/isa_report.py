@@ -3,7 +3,7 @@
 
     python tools/isa_report.py [--kernel SUBSTR] [-D...] > profiles/rNN/pair_sweep_isa.txt
 
-Compiles maniac_mc_amd/csrc/mgpu_engine.hip to gfx950 assembly (`hipcc -S --cuda-device-only`), cuts out the kernel whose
+Compiles maniac_mc_amd/csrc/mgpu_launch.hip to gfx950 assembly (`hipcc -S --cuda-device-only`), cuts out the kernel whose
 mangled name contains SUBSTR (default: pair_sweep_kernel<3, false, false, true, true>, the fused SPC/E sweep bench.py
 times), finds its hot basic block -- the ALL_C unit body: the block with the most fp64 VALU instructions -- prints it and
 counts its instructions by class, per unit (64 atoms x NREG site-states) and per site-atom term, beside the PMC figure of
@@ -16,7 +16,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "maniac_mc_amd", "csrc", "mgpu_engine.hip")
+SRC = os.path.join(ROOT, "maniac_mc_amd", "csrc", "mgpu_launch.hip")   # the unit that instantiates the pair sweeps
 
 def main():
     args = sys.argv[1:]
