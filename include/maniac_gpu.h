@@ -252,6 +252,29 @@ int mgpu_rdf_read(mgpu_engine *e, int n, const int *replicas, unsigned long long
 int mgpu_rdf_load(mgpu_engine *e, int n, const int *replicas, const unsigned long long *hist, const unsigned long long *eligible, const unsigned long long *samples);
 int mgpu_rdf_reset(mgpu_engine *e, int n, const int *replicas);
 
+/* Energies by residue-type pair of many replicas, from the resident coordinates; stateless and synchronous.
+ *
+ * The replica list and chunk are those of mgpu_system_energy_replicas.  The selection is n_sel in [1, 36] unordered pairs
+ * (res_a[p], res_b[p]) of 0-based residue types, either order inside a pair (normalised to a <= b), a == b allowed; a
+ * duplicate pair, a type outside [0, n_res), a null list or (n > 0) a null out: MGPU_ERR_INVALID_ARG with a text that names
+ * the pair, nothing done.
+ *
+ * out[i][p][0..4] = non_coulomb, coulomb, recip_coulomb, ewald_self, intra_coulomb in K of replica replicas[i] restricted to
+ * pair p (mgpu_system_energy's first five, in its order):
+ *   non_coulomb, coulomb   SingleMolPairwiseEnergy's Lennard-Jones and real-space Coulomb terms (energy_utils.f90:121-187) over
+ *                          every site pair with one site in a molecule of type a and one in a DIFFERENT molecule of type b,
+ *                          each molecule pair once, with its skips (cutoff, |q| < 1e-10, r < 1e-10);
+ *   recip_coulomb          ComputeReciprocalEnergy's prefactor times sum_k ff(k) W(k) F_ab(k), F_aa = |S_a|^2,
+ *                          F_ab = 2 Re(S_a conj S_b), S_t(k) the structure factor of the occupied atoms of type t, formed
+ *                          from the coordinates (A(k) is neither read nor written);
+ *   ewald_self, intra      a == b only (exactly 0 otherwise): the type's self term times its molecule count; the sum of the
+ *                          intra-molecular terms of its molecules (0 for an inactive type).
+ * Summed over all unordered pairs the first three give mgpu_system_energy_replicas' components (to rounding), the diagonal
+ * gives its self and intra terms.  A type without molecules gives exactly 0 everywhere, a type without a charged site exactly
+ * 0 in coulomb and recip_coulomb.  Every number is a function of the replica's configuration and of (a, b) alone: it does not
+ * change by a bit with the order of the replicas, chunk, the other pairs selected or their order, or a repeated call. */
+int mgpu_energy_pairs_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, int n_sel, const int *res_a, const int *res_b, double *out);
+
 /* a[n_kvectors][2] = (re, im) of ewald%recip_amplitude */
 int mgpu_get_structure_factor(mgpu_engine *e, int replica, double *a);
 int mgpu_set_structure_factor(mgpu_engine *e, int replica, const double *a);

@@ -4,10 +4,13 @@
 // ordered pair launch, one intra launch, one phase-table + S(k) launch pair, one reciprocal-energy launch, one reduction
 // (and one deviation launch) for all its replicas.  Nothing is waited for between the passes; one copy brings the results back.
 // Beside them the radial distribution functions of many replicas per call (mgpu_rdf_*): integer histograms of the resident
-// coordinates, one rdf_hist_kernel launch per pass.
+// coordinates, one rdf_hist_kernel launch per pass.  And the energies by residue-type pair (mgpu_energy_pairs_replicas): passes of
+// the same budget, per pass one sweep over (molecule, partner type) items, the partial structure factors of the selected types
+// and one ordered reduction per (replica, pair).
 #include "mgpu_engine.h"
 #include "mgpu_kernels_replicas.h"
 #include "mgpu_kernels_rdf.h"
+#include "mgpu_kernels_epairs.h"
 
 namespace mgpu {
 
@@ -261,6 +264,172 @@ int mgpu_init_structure_factor_replicas(mgpu_engine *e, int n, const int *replic
         if ((rc = launch_sfactor_replicas(e, (const int *)e->d_items2.p + first, std::min(per_pass, n - first),
                                           (double2 *)e->lanes[0].d_scratch.p, true, e->d_A)))
             return rc;
+    return sync_stream(e);
+}
+
+int mgpu_energy_pairs_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, int n_sel, const int *res_a, const int *res_b,
+                               double *out) {
+    const char *who = "energy_pairs_replicas";
+    int rc = check_replica_list(e, n, replicas, who);
+    if (rc) return rc;
+    const Topo &tp = e->tp;
+    const int n_res = tp.n_res;
+    if (n_sel < 1 || n_sel > kEpairsMaxSel)
+        return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": n_sel " + std::to_string(n_sel) + " pairs is outside [1, " +
+                         std::to_string(kEpairsMaxSel) + "]");
+    if (!res_a || !res_b) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": null pair list");
+    int sel_a[kEpairsMaxSel], sel_b[kEpairsMaxSel];
+    bool taken[kMaxRes][kMaxRes] = {};
+    for (int p = 0; p < n_sel; ++p) {
+        const int a = std::min(res_a[p], res_b[p]), b = std::max(res_a[p], res_b[p]);
+        const std::string name = ": pair " + std::to_string(p) + " (" + std::to_string(res_a[p]) + ", " + std::to_string(res_b[p]) + ")";
+        if (a < 0 || b >= n_res)
+            return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + name + ": residue type out of range [0, " + std::to_string(n_res - 1) + "]");
+        if (taken[a][b]) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + name + " is a duplicate");
+        taken[a][b] = true;
+        sel_a[p] = a; sel_b[p] = b;
+    }
+    if (n > 0 && !out) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": null out");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const int nsplit = e->pair_nsplit;
+    const int nk = e->nk;
+    const size_t tab_n = phase_tab_entries(e);
+    // the residue types whose S_t(k) a pass forms: those of the selection with a charged site (the others give exactly 0)
+    EpTypes types{};
+    int s_index[kMaxRes];
+    for (int t = 0; t < n_res; ++t) {
+        s_index[t] = -1;
+        bool wanted = false, charged = false;
+        for (int p = 0; p < n_sel; ++p) wanted = wanted || sel_a[p] == t || sel_b[p] == t;
+        for (int a = 0; a < tp.n1[t]; ++a) charged = charged || std::fabs(e->charges[(size_t)t * tp.max_atom + a]) >= kErrorTol;
+        if (wanted && charged) { s_index[t] = types.n; types.t[types.n++] = t; }
+    }
+    // the side of a pair whose molecules are the items: the type of fewer sites (a for equal counts): a guest's molecules
+    // against a framework, not the framework against every guest.  Fixed by (a, b) and the topology.
+    int item_t[kEpairsMaxSel], part_t[kEpairsMaxSel];
+    for (int p = 0; p < n_sel; ++p) {
+        const bool a_side = tp.n1[sel_a[p]] <= tp.n1[sel_b[p]];
+        item_t[p] = a_side ? sel_a[p] : sel_b[p];
+        part_t[p] = a_side ? sel_b[p] : sel_a[p];
+    }
+    auto counts = [&](int r, long long &n_it, long long &n_in) {
+        n_it = 0; n_in = 0;
+        for (int p = 0; p < n_sel; ++p) {
+            n_it += e->h_nmol[r * n_res + item_t[p]];
+            if (sel_a[p] == sel_b[p] && e->is_active[sel_a[p]] == 1) n_in += e->h_nmol[r * n_res + sel_a[p]];
+        }
+    };
+    const size_t s_n = types.n ? tab_n + (size_t)types.n * nk : 0;     // complex entries of a replica's tables and S_t(k)
+    auto bytes_of = [&](long long n_it, long long n_in) {
+        return s_n * sizeof(double2) + (size_t)n_it * sizeof(EpItem) + (size_t)n_in * sizeof(PairItem) +
+               (size_t)n_it * nsplit * sizeof(double2) + (size_t)(2 * n_it + n_in + n_sel) * sizeof(double) +
+               (size_t)n_sel * sizeof(EpRec) + sizeof(int);
+    };
+    // the passes: replicas in the caller's order, as many as `chunk` and the budget allow, never fewer than one
+    const int most = chunk > 0 ? std::min(chunk, kReplicasPassMax) : kReplicasPassMax;
+    std::vector<Pass> passes;
+    size_t max_tab = 0, max_items = 0, max_rec = 0, max_res = 0, max_part = 0;
+    for (int i = 0; i < n;) {
+        Pass p{i, 0, 0, 0};
+        size_t bytes = 0;
+        while (i < n && p.c < most) {
+            long long ni, nn;
+            counts(replicas[i], ni, nn);
+            const size_t b = bytes_of(ni, nn);
+            if (p.c > 0 && (bytes + b > kReplicasPassBytes || (p.n_pair + ni) * nsplit > kReplicasPassItems)) break;
+            bytes += b; p.n_pair += ni; p.n_in += nn; p.c += 1; ++i;
+        }
+        if (p.n_pair * nsplit >= ((long long)1 << 31) - kPairWaves)
+            return set_error(MGPU_ERR_CAPACITY, std::string(who) + ": one replica's sweep exceeds 2^31 work units");
+        passes.push_back(p);
+        max_tab = std::max(max_tab, (size_t)p.c * s_n * sizeof(double2));
+        max_items = std::max(max_items, (size_t)p.n_pair * sizeof(EpItem) + (size_t)p.n_in * sizeof(PairItem));
+        max_rec = std::max(max_rec, (size_t)p.c * ((size_t)n_sel * sizeof(EpRec) + sizeof(int)));
+        max_res = std::max(max_res, (size_t)(2 * p.n_pair + p.n_in + (long long)p.c * n_sel) * sizeof(double));
+        max_part = std::max(max_part, (size_t)p.n_pair * nsplit * sizeof(double2));
+    }
+    // every block is reserved once, before the first pass: nothing is freed under a pass still in flight
+    const size_t head = (size_t)n * n_sel * 5 * sizeof(double);
+    if ((rc = e->d_out.reserve(head + max_res))) return rc;
+    if ((rc = e->d_items.reserve(std::max<size_t>(max_items, 8)))) return rc;
+    if ((rc = e->d_items2.reserve(max_rec))) return rc;
+    if ((rc = e->d_partials.reserve(std::max<size_t>(max_part, 16)))) return rc;
+    if ((rc = e->lanes[0].d_scratch.reserve(std::max<size_t>(max_tab, 16)))) return rc;
+    double *d_out5 = (double *)e->d_out.p, *d_res = (double *)((char *)e->d_out.p + head);
+    // the host images of the passes' uploads live until the stream has been waited for
+    std::deque<std::vector<char>> h_items, h_recs;
+    for (const Pass &p : passes) {
+        const int c = p.c, n_it = (int)p.n_pair, n_in = (int)p.n_in, n_rec = c * n_sel;
+        h_items.emplace_back((size_t)n_it * sizeof(EpItem) + (size_t)n_in * sizeof(PairItem));
+        EpItem *items = (EpItem *)h_items.back().data();
+        PairItem *in_items = (PairItem *)(h_items.back().data() + (size_t)n_it * sizeof(EpItem));
+        h_recs.emplace_back((size_t)n_rec * sizeof(EpRec) + (size_t)c * sizeof(int));
+        EpRec *recs = (EpRec *)h_recs.back().data();
+        int *idx = (int *)(h_recs.back().data() + (size_t)n_rec * sizeof(EpRec));
+        int at = 0, in_at = 0;
+        for (int i = 0; i < c; ++i) {
+            const int r = replicas[p.first + i];
+            idx[i] = r;
+            for (int q = 0; q < n_sel; ++q) {
+                const int a = sel_a[q], b = sel_b[q];
+                EpRec &er = recs[i * n_sel + q];
+                er = EpRec{};
+                er.entry = i;
+                er.same = a == b ? 1 : 0;
+                er.sa = s_index[a]; er.sb = s_index[b];
+                er.item_first = at;
+                er.n_items = e->h_nmol[r * n_res + item_t[q]];
+                for (int m = 0; m < er.n_items; ++m) items[at++] = EpItem{r, item_t[q], m, part_t[q]};
+                er.intra_first = in_at;
+                if (a == b) {
+                    er.n_self = e->h_nmol[r * n_res + a];
+                    er.self_v = self_energy_host(e, a);
+                    if (e->is_active[a] == 1) {
+                        // ComputeTotalIntraResidueCoulombEnergy skips the inactive types
+                        er.n_intra = er.n_self;
+                        for (int m = 0; m < er.n_intra; ++m) in_items[in_at++] = PairItem{r, a, m, -1, 0};
+                    }
+                }
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(e->d_items2.p, h_recs.back().data(), h_recs.back().size(), hipMemcpyHostToDevice, e->stream));
+        const EpRec *d_recs = (const EpRec *)e->d_items2.p;
+        const int *d_idx = (const int *)((const char *)e->d_items2.p + (size_t)n_rec * sizeof(EpRec));
+        double *d_lj = d_res, *d_c = d_lj + n_it, *d_in = d_c + n_it, *d_u = d_in + n_in;
+        if (!h_items.back().empty())
+            HIP_TRY(hipMemcpyAsync(e->d_items.p, h_items.back().data(), h_items.back().size(), hipMemcpyHostToDevice, e->stream));
+        if (n_it > 0) {
+            const int n_work = n_it * nsplit;
+            const int grid = std::max(1, std::min((n_work + kPairWaves - 1) / kPairWaves, e->n_cu * e->pair_blocks_per_cu));
+            with_bools([&](auto tri) {
+                hipLaunchKernelGGL((epairs_sweep_kernel<decltype(tri)::value>), dim3(grid), dim3(kPairBlock), e->coul_bytes, e->stream, tp,
+                                   e->bx, (const double *)e->d_pos, (const int *)e->d_nmol, (const double *)e->d_res_q,
+                                   (const int *)e->d_res_atype, (const double2 *)e->d_pair_tab, (const char *)e->d_coul_tab,
+                                   (const EpItem *)e->d_items.p, nsplit, n_work, (double2 *)e->d_partials.p);
+            }, e->bx.triclinic != 0);
+            hipLaunchKernelGGL(pair_finalize_kernel, dim3((n_it + 255) / 256), dim3(256), 0, e->stream, (const double2 *)e->d_partials.p,
+                               n_it, nsplit, d_lj, d_c);
+        }
+        if (n_in > 0 && (rc = launch_intra(e, e->lanes[0], (const PairItem *)((const char *)e->d_items.p + (size_t)n_it * sizeof(EpItem)),
+                                           n_in, nullptr, 1, d_in)))
+            return rc;
+        double2 *d_tab = (double2 *)e->lanes[0].d_scratch.p, *d_S = d_tab + (size_t)c * tab_n;
+        if (types.n > 0) {
+            hipLaunchKernelGGL(phase_table_replicas_kernel, dim3((tp.n_cap_atoms + 255) / 256, c), dim3(256), 0, e->stream, tp, e->bx,
+                               e->d_pos, e->d_nmol, e->d_atom_res, e->d_atom_mol, d_idx, tab_n, d_tab);
+            hipLaunchKernelGGL(sfactor_types_replicas_kernel, dim3(nk, c), dim3(kBlock), 0, e->stream, tp, e->bx, (const int *)e->d_nmol,
+                               (const int *)e->d_atom_mol, (const double *)e->d_atom_q, (const int *)e->d_kpack, d_idx, tab_n,
+                               (const double2 *)d_tab, types, d_S);
+        }
+        hipLaunchKernelGGL(epairs_recip_kernel, dim3(n_rec), dim3(kBlock), 0, e->stream, e->bx, (const double *)e->d_kw, d_recs,
+                           types.n, (const double2 *)d_S, d_u);
+        hipLaunchKernelGGL(epairs_reduce_kernel, dim3((n_rec + 63) / 64), dim3(64), 0, e->stream, d_recs, n_rec, (const double *)d_lj,
+                           (const double *)d_c, (const double *)d_in, (const double *)d_u, d_out5 + (size_t)p.first * n_sel * 5);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(out, d_out5, head, hipMemcpyDeviceToHost, e->stream));
     return sync_stream(e);
 }
 

@@ -503,6 +503,21 @@ class Engine:
         r = self._replica_list(replicas)
         check(self.L.mgpu_init_structure_factor_replicas(self.h, C.c_int(r.shape[0]), _i(r), C.c_int(1 if full else 0)))
 
+    def energy_pairs_replicas(self, pairs, replicas=None, chunk=None):
+        """mgpu_energy_pairs_replicas: the energy by residue-type pair of many replicas in one call, an (n, n_sel, 5) array in K
+        (non_coulomb, coulomb, recip_coulomb, ewald_self, intra_coulomb) for the unordered pairs [(a, b), ...] of 0-based
+        residue types (at most 36, a == b allowed).  replicas = None: all of them; chunk as system_energy_replicas takes it."""
+        pairs = [(int(a), int(b)) for a, b in pairs]
+        ra = np.ascontiguousarray([p[0] for p in pairs], dtype=np.int32)
+        rb = np.ascontiguousarray([p[1] for p in pairs], dtype=np.int32)
+        r = self._replica_list(replicas)
+        n = r.shape[0]
+        out = np.zeros((n, len(pairs), 5))
+        check(self.L.mgpu_energy_pairs_replicas(self.h, C.c_int(n), _i(r), C.c_int(0 if chunk is None else int(chunk)),
+                                                C.c_int(len(pairs)), _i(ra) if pairs else None, _i(rb) if pairs else None,
+                                                _d(out) if out.size else None))
+        return out
+
     # ---- radial distribution functions ---------------------------------------------------
     def rdf_configure(self, n_bins, r_max, pairs, include_intra=False):
         """mgpu_rdf_configure: histograms of n_bins bins up to r_max for the unordered pairs [(a, b), ...] of 0-based atom types

@@ -194,6 +194,16 @@ module maniac_gpu
             integer(c_int), intent(in) :: replicas(*)
             integer(c_int) :: rc
         end function
+        ! energies by residue-type pair of many replicas (0-based residue types): out(5, n_sel, n) in K
+        function mgpu_energy_pairs_replicas(e, n, replicas, chunk, n_sel, res_a, res_b, out) &
+                bind(C, name="mgpu_energy_pairs_replicas") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: n, chunk, n_sel
+            integer(c_int), intent(in) :: replicas(*), res_a(*), res_b(*)
+            real(c_double), intent(out) :: out(*)
+            integer(c_int) :: rc
+        end function
         function mgpu_pair_energy_candidates(e, n, replica, t, m, use_resident, sites, site_stride, e_nc, e_c) &
                 bind(C, name="mgpu_pair_energy_candidates") result(rc)
             import :: c_ptr, c_int, c_double
@@ -832,5 +842,22 @@ contains
         integer, intent(out), optional :: stat
         call GpuCheck(mgpu_rdf_reset(engine, int(n, c_int), int(replicas, c_int)), 'GpuRdfReset', stat)
     end subroutine GpuRdfReset
+
+    !---------------------------------------------------------------------------
+    ! Energies by residue-type pair: out(5, n_sel, n) in K = non_coulomb, coulomb, recip_coulomb,
+    ! ewald_self, intra_coulomb of replica replicas(i) restricted to the unordered pair
+    ! (res_a(p), res_b(p)).  Residue types are 1-based here, as in the input file; replicas are
+    ! 0-based, as everywhere in this module.
+    !---------------------------------------------------------------------------
+    subroutine GpuEnergyPairs(engine, n, replicas, n_sel, res_a, res_b, out, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, replicas(n), n_sel, res_a(n_sel), res_b(n_sel)
+        real(real64), intent(out) :: out(*)
+        integer, intent(out), optional :: stat
+        integer(c_int) :: a(max(1, n_sel)), b(max(1, n_sel)), rc
+        a(1:n_sel) = int(res_a - 1, c_int); b(1:n_sel) = int(res_b - 1, c_int)
+        rc = mgpu_energy_pairs_replicas(engine, int(n, c_int), int(replicas, c_int), 0_c_int, int(n_sel, c_int), a, b, out)
+        call GpuCheck(rc, 'GpuEnergyPairs', stat)
+    end subroutine GpuEnergyPairs
 
 end module maniac_gpu

@@ -301,6 +301,13 @@ class FortranFarm:
         self.eng.rdf_accumulate(replicas, chunk)
         self._select()
 
+    def energy_pairs_sample(self, pairs, replicas=None, chunk=None):
+        """The energy by residue-type pair of every listed chain (None: all), (n, n_sel, 5) in K (Engine.energy_pairs_replicas),
+        from the coordinates the engine holds -- which are current between two run() calls in every farm mode."""
+        out = self.eng.energy_pairs_replicas(pairs, replicas, chunk)
+        self._select()
+        return out
+
     def run(self, n_steps: int) -> int:
         """Advance every chain by n_steps move selections; returns the moves accepted during this call."""
         self._select()

@@ -22,6 +22,7 @@ import os
 import numpy as np
 
 from . import _lib, checkpoint, fortran_host, io_maniac
+from . import energy_pairs as epairs_mod
 from . import rdf as rdf_mod
 from .fortran_host import FortranFarm
 from .run import header_text, set_chain_state
@@ -73,7 +74,7 @@ def _stats(x):
 def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=None, fugacities=None, frames=(0,),
                  mode="auto", device=0, nb_block=None, nb_step=None, mol_capacity=None, n_lanes=2, n_threads=8,
                  chunk=None, wide_triclinic=False, restart_from=None, audit=False, checkpoint_every=0, resume=False,
-                 recalibrate_moves=None, rdf=None):
+                 recalibrate_moves=None, rdf=None, energy_pairs=None):
     """Run `replicas` independent chains of the input; returns a dict with the final energies (R, 5) in K (non-Coulomb,
     Coulomb, reciprocal, self, intramolecular), counts (R, n_active), chain counters (R, 8), the farm's counters, the
     mode that ran and the block timings.
@@ -115,6 +116,13 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     r_mid, g(r) pooled over the group's replicas and samples, its standard error over the replicas, the pooled raw count) are
     written (maniac_mc_amd.rdf).  A checkpoint then carries the accumulators, and a resumed run must ask for the same rdf.
     None (default): nothing of this, and every file is what it always was.
+    ``energy_pairs``: dict(every=1, pairs=None) -> after every `every`-th block the energy by residue-type pair of every replica
+    (FortranFarm.energy_pairs_sample; its time in seconds["energy_pairs"]) adds one line to
+    <outdir>/replica_NNNN/energy_pairs.dat: the block, then per pair the five components and their sum in kcal/mol.  ``pairs``:
+    [(a, b), ...] of 0-based residue types (default: every pair with at least one active type, e.g. guest-framework and
+    guest-guest).  After the last block <outdir>/energy_pairs.dat holds, per fugacity group and pair, mean and standard error
+    over the replicas (maniac_mc_amd.energy_pairs).  The sampling keeps no state: a checkpoint only records the option, and a
+    resumed run must ask for the same.  None (default): nothing of this, and every file is what it always was.
     """
     import time
     if mode not in MODES:
@@ -168,6 +176,17 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         if rdf_spec["r_max"] > limit:
             raise ValueError(f"rdf: r_max {rdf_spec['r_max']!r} exceeds half the smallest perpendicular width of the cell, {limit!r}")
 
+    ep_spec = None
+    if energy_pairs is not None:
+        unknown = set(energy_pairs) - {"every", "pairs"}
+        if unknown:
+            raise ValueError(f"energy_pairs: takes every and pairs ({sorted(unknown)} unknown)")
+        pairs = energy_pairs.get("pairs")
+        ep_spec = dict(every=int(energy_pairs.get("every", 1)),
+                       pairs=epairs_mod.check_pairs(epairs_mod.default_pairs(topo) if pairs is None else pairs, n_res))
+        if ep_spec["every"] < 1:
+            raise ValueError("energy_pairs: every must be at least 1")
+
     group = np.zeros(R, dtype=np.int64)
     if fugacities is not None:
         fugacities = [float(f) for f in fugacities]
@@ -184,6 +203,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         ident["recalibrate"] = int(recalibrate)
         if rdf_spec is not None:
             ident["rdf"] = rdf_mod.identity_array(rdf_spec)
+        if ep_spec is not None:
+            ident["energy_pairs"] = epairs_mod.identity_array(ep_spec)
     if resume:
         ck = checkpoint.load(outdir)
         checkpoint.check(ck, ident, nb_block)
@@ -240,6 +261,13 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         if rdf_spec is not None:
             farm.eng.rdf_configure(rdf_spec["n_bins"], rdf_spec["r_max"], rdf_spec["pairs"], rdf_spec["include_intra"])
             times["rdf"] = 0.0
+        ep_paths = [os.path.join(root, f"replica_{r:04d}", epairs_mod.FILE_NAME) for r in range(R)]
+        if ep_spec is not None:
+            times["energy_pairs"] = 0.0
+            if ck is None:
+                labels = epairs_mod.pair_names(ep_spec["pairs"], [res.name for res in inp.residues])
+                for p in ep_paths:
+                    epairs_mod.start_replica_file(p, labels)
 
         def write(block, final):
             t0 = time.perf_counter()
@@ -312,6 +340,12 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
                 t0 = time.perf_counter()
                 farm.rdf_sample()
                 times["rdf"] += time.perf_counter() - t0
+            if ep_spec is not None and block % ep_spec["every"] == 0:
+                t0 = time.perf_counter()
+                values = farm.energy_pairs_sample(ep_spec["pairs"])
+                for r in range(R):
+                    epairs_mod.append_replica_file(ep_paths[r], block, values[r])
+                times["energy_pairs"] += time.perf_counter() - t0
             write(block, False)
             if checkpoint_every and (block % int(checkpoint_every) == 0 or block == nb_block):
                 save_checkpoint(block + 1)
@@ -322,6 +356,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
                                  rdf_spec["r_max"], rdf_spec["n_bins"], rdf_spec["every"], rdf_spec["include_intra"])
             rdf_mod.write_dat(os.path.join(root, "rdf.dat"), hist, eligible, group, rdf_spec["pairs"],
                               rdf_mod.volume(system.box_matrix), rdf_spec["r_max"])
+        if ep_spec is not None:
+            f_atm = fugacities if fugacities is not None else [inp.residues[active[0]].fugacity_atm if active else 0.0]
+            epairs_mod.write_pooled_file(os.path.join(root, epairs_mod.FILE_NAME), ep_paths, group, f_atm)
         _lib.check(0)
         energies = np.array([farm.energy(r) for r in range(R)])
         res = dict(energy=energies, counts=farm.counts(), chain_counters=farm.chain_counters(), counters=farm.counters(),

@@ -324,6 +324,12 @@ def main(argv=None):
                          "types; at most 8)")
     ap.add_argument("--rdf-intra", dest="rdf_intra", action="store_true",
                     help="with --rdf: count pairs inside one molecule too")
+    ap.add_argument("--energy-pairs", dest="energy_pairs", nargs="?", const="1", default=None, metavar="EVERY",
+                    help="with --replicas: the energy by residue-type pair (guest-framework, guest-guest, ...; van der Waals, "
+                         "Coulomb, reciprocal, self, intra) of every replica after every EVERY-th block (default 1); writes "
+                         "<out>/replica_NNNN/energy_pairs.dat and <out>/energy_pairs.dat")
+    ap.add_argument("--energy-pairs-select", dest="energy_pairs_select", default=None, metavar="NAME:NAME,...",
+                    help="with --energy-pairs: the pairs, by the input's residue names (default: every pair with an active type)")
     a = ap.parse_args(argv)
     try:
         chain_run = parse_chain_run(a.chain_run) if a.chain_run is not None else None
@@ -346,6 +352,8 @@ def main(argv=None):
             ap.error("--checkpoint-every and --resume need --replicas")
         if a.rdf is not None or a.rdf_pairs is not None or a.rdf_intra:
             ap.error("--rdf, --rdf-pairs and --rdf-intra need --replicas: the single chain writes no distribution functions")
+        if a.energy_pairs is not None or a.energy_pairs_select is not None:
+            ap.error("--energy-pairs and --energy-pairs-select need --replicas: the single chain writes no energy decomposition")
     else:
         from . import replicas as farm_run
         if a.as_written:
@@ -372,6 +380,20 @@ def main(argv=None):
                 rdf["include_intra"] = bool(a.rdf_intra)
             except ValueError as err:
                 ap.error(str(err))
+        energy_pairs = None
+        if a.energy_pairs is None and a.energy_pairs_select is not None:
+            ap.error("--energy-pairs-select needs --energy-pairs [EVERY]")
+        if a.energy_pairs is not None:
+            from . import energy_pairs as epairs_mod
+            try:
+                energy_pairs = epairs_mod.parse_spec(a.energy_pairs)
+                energy_pairs["pairs"] = None
+                if a.energy_pairs_select is not None and os.path.isfile(a.maniac):
+                    from . import io_maniac
+                    names = [r.name for r in io_maniac.read_maniac_input(a.maniac).residues]
+                    energy_pairs["pairs"] = epairs_mod.parse_select(a.energy_pairs_select, names)
+            except ValueError as err:
+                ap.error(str(err))
     for path, what in ((a.maniac, "Input"), (a.data, "Data"), (a.inc, "Parameter"), (a.reservoir, "Reservoir")):
         if path is not None and not os.path.isfile(path):
             print(f"{what} file not found: {path}", file=sys.stderr)
@@ -381,7 +403,8 @@ def main(argv=None):
             res = farm_run.run_replicas(a.maniac, a.data, a.inc, a.out, a.replicas, seed=a.seed, reservoir_path=a.reservoir,
                                         fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device,
                                         wide_triclinic=a.wide_triclinic, restart_from=a.restart_from, audit=a.audit,
-                                        checkpoint_every=a.checkpoint_every, resume=a.resume, rdf=rdf)
+                                        checkpoint_every=a.checkpoint_every, resume=a.resume, rdf=rdf,
+                                        energy_pairs=energy_pairs)
         except ValueError as err:
             print(f"error: {err}", file=sys.stderr)
             return 2
