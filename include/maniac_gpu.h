@@ -252,6 +252,42 @@ int mgpu_rdf_read(mgpu_engine *e, int n, const int *replicas, unsigned long long
 int mgpu_rdf_load(mgpu_engine *e, int n, const int *replicas, const unsigned long long *hist, const unsigned long long *eligible, const unsigned long long *samples);
 int mgpu_rdf_reset(mgpu_engine *e, int n, const int *replicas);
 
+/* Density maps of many replicas, binned on the device from the resident coordinates: the number of sites of selected atom types
+ * per voxel of a 3-D grid over the cell, pooled over samples and over the replicas of a group.
+ *
+ * Configuration is per engine: the grid n[3], voxels along the three cell vectors (the columns of box%matrix), each in
+ * [1, 1024], their product at most 2^24; n_channels in [1, 8] channels, each a 0-based atom type (a duplicate, or a type outside
+ * the topology's, is refused; a type without atoms is allowed and stays zero); n_groups in [1, R] and group_of[R] with entries
+ * in [0, n_groups), or -1: a replica that is never counted, even when listed.  All replicas of a group add into the same map;
+ * group_of[r] = r gives one map per replica.  The accumulators hist[n_groups][n_channels][n2][n1][n0] and samples[n_groups],
+ * unsigned long long, may take MGPU_DENSITY_MAX_BYTES together; a larger request is MGPU_ERR_INVALID_ARG with a text that names
+ * the limit and the size asked for.
+ *
+ * ONE SAMPLE of one replica takes every occupied atom slot whose atom type is channel c, forms the fractional coordinates of
+ * ApplyPBC, s = box%reciprocal (r - bounds_lo) (orthorhombic: s_d = (r_d - lo_d) / L_d as a product with the rounded 1 / L_d),
+ * then u_d = s_d n_d, i_d = floor(u_d), v_d = i_d mod n_d -- the Euclidean mod, so a site any number of cells away folds back
+ * and a coordinate a hair below bounds_lo lands in the last voxel -- and adds 1 to hist[g][c][v2][v1][v0], g = group_of[replica];
+ * samples[g] grows by 1 per counted replica.  The counts are integers: they do not depend on the order of the replicas, on
+ * chunk, or on what shares a launch or a map.  Normalisation is the caller's (maniac_mc_amd/density.py):
+ * rho_c(v) = H / (samples V / (n0 n1 n2)).
+ *
+ *   configure    allocates and zeroes the accumulators on the device; again with another shape: reallocates and zeroes;
+ *                n_channels = 0 frees them (the other arguments are then ignored).
+ *   accumulate   one sample of each listed replica (the list as mgpu_system_energy_replicas takes it), in passes of `chunk`
+ *                replicas (<= 0: the engine's choice); synchronous; work in flight is treated as that call treats it.
+ *   read         hist[n][n_channels][n2][n1][n0], samples[n] of the listed groups (each in [0, n_groups), none twice).
+ *   load         overwrites the listed groups' accumulators with such arrays (a resumed run).
+ *   reset        zeroes the listed groups' accumulators.
+ * accumulate, read, load and reset return MGPU_ERR_STATE while nothing is configured.  Nothing else touches the accumulators:
+ * they are not part of a state block, mgpu_replica_copy and the setters leave them alone, and they are independent of the
+ * mgpu_rdf_* accumulators. */
+#define MGPU_DENSITY_MAX_BYTES (2ull << 30)
+int mgpu_density_configure(mgpu_engine *e, const int *n, int n_channels, const int *types, int n_groups, const int *group_of);
+int mgpu_density_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int chunk);
+int mgpu_density_read(mgpu_engine *e, int n, const int *groups, unsigned long long *hist, unsigned long long *samples);
+int mgpu_density_load(mgpu_engine *e, int n, const int *groups, const unsigned long long *hist, const unsigned long long *samples);
+int mgpu_density_reset(mgpu_engine *e, int n, const int *groups);
+
 /* Energies by residue-type pair of many replicas, from the resident coordinates; stateless and synchronous.
  *
  * The replica list and chunk are those of mgpu_system_energy_replicas.  The selection is n_sel in [1, 36] unordered pairs

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libmaniac_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["mgpu_engine.hip", "mgpu_launch.hip", "mgpu_lanes.hip", "mgpu_windows.hip", "mgpu_replicas.hip", "mgpu_host_setup.cpp",
            "mgpu_comm.cpp"]
-HEADERS = ["mgpu_kernels.h", "mgpu_kernels_replicas.h", "mgpu_kernels_rdf.h", "mgpu_kernels_epairs.h", "mgpu_kernels_common.h", "mgpu_kernels_pair.h", "mgpu_kernels_recip.h", "mgpu_kernels_windows.h",
+HEADERS = ["mgpu_kernels.h", "mgpu_kernels_replicas.h", "mgpu_kernels_rdf.h", "mgpu_kernels_density.h", "mgpu_kernels_epairs.h", "mgpu_kernels_common.h", "mgpu_kernels_pair.h", "mgpu_kernels_recip.h", "mgpu_kernels_windows.h",
            "mgpu_internal.h", "mgpu_engine.h"]
 
 MGPU_OK = 0
@@ -46,6 +46,7 @@ EXPORTS = [
     "mgpu_state_export_submit", "mgpu_state_export_wait", "mgpu_state_import",
     "mgpu_rdf_configure", "mgpu_rdf_accumulate_replicas", "mgpu_rdf_read", "mgpu_rdf_load", "mgpu_rdf_reset",
     "mgpu_energy_pairs_replicas",
+    "mgpu_density_configure", "mgpu_density_accumulate_replicas", "mgpu_density_read", "mgpu_density_load", "mgpu_density_reset",
 ]
 
 

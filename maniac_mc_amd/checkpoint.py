@@ -119,7 +119,8 @@ _NAMES = dict(abi_version="ABI version", nb_step="nb_step", seed="seed", mode="m
               fugacities="fugacities", frames="frames", digest_maniac="the input file's digest", digest_data="the data file's digest",
               digest_inc="the parameter file's digest", digest_reservoir="the reservoir (file's digest)",
               recalibrate="recalibrate_moves", rdf="rdf (--rdf, --rdf-pairs, --rdf-intra)",
-              energy_pairs="energy_pairs (--energy-pairs, --energy-pairs-select)")
+              energy_pairs="energy_pairs (--energy-pairs, --energy-pairs-select)",
+              density="density (--density, --density-types, --density-per-replica)")
 
 
 def check(ck, ident, nb_block):
@@ -133,6 +134,10 @@ def check(ck, ident, nb_block):
         # (likewise: only a run with --energy-pairs writes the entry)
         raise ValueError(f"resume: {_NAMES['energy_pairs']} differs from the checkpoint's (checkpoint "
                          f"{np.asarray(ck['id_energy_pairs']).tolist()!r}, this run without it)")
+    if "id_density" in ck and "density" not in ident:
+        # (likewise: only a run with --density writes the entry)
+        raise ValueError(f"resume: {_NAMES['density']} differs from the checkpoint's (checkpoint "
+                         f"{np.asarray(ck['id_density']).tolist()!r}, this run without it)")
     for k, want in ident.items():
         got = ck.get("id_" + k)
         same = got is not None and np.asarray(got).shape == np.asarray(want).shape and np.array_equal(np.asarray(got), np.asarray(want))

@@ -430,6 +430,15 @@ struct mgpu_engine {
         int type_a[8]{}, type_b[8]{};
         DevBuf d_acc, d_tab;
     } rdf;
+    // density maps (mgpu_density_*, mgpu_replicas.hip): the grid, the channels' atom types, every replica's group, and the
+    // accumulators -- d_acc = hist [n_groups][n_channels][n2][n1][n0] | samples [n_groups], unsigned long long; d_group =
+    // group_of [R].  Nothing but the mgpu_density_* calls touches them.
+    struct Density {
+        int n[3]{}, n_channels = 0, n_groups = 0;             // n_channels = 0: not configured
+        int types[8]{};
+        unsigned long long table = ~0ull;                     // atom type -> channel, a nibble each (0xF: none)
+        DevBuf d_acc, d_group;
+    } density;
     // profiling
     bool profiling = false;
 };

@@ -6,10 +6,12 @@
 // Beside them the radial distribution functions of many replicas per call (mgpu_rdf_*): integer histograms of the resident
 // coordinates, one rdf_hist_kernel launch per pass.  And the energies by residue-type pair (mgpu_energy_pairs_replicas): passes of
 // the same budget, per pass one sweep over (molecule, partner type) items, the partial structure factors of the selected types
-// and one ordered reduction per (replica, pair).
+// and one ordered reduction per (replica, pair).  And the density maps (mgpu_density_*): integer counts per voxel of selected
+// atom types, pooled per group of replicas, one density_map_kernel launch per pass.
 #include "mgpu_engine.h"
 #include "mgpu_kernels_replicas.h"
 #include "mgpu_kernels_rdf.h"
+#include "mgpu_kernels_density.h"
 #include "mgpu_kernels_epairs.h"
 
 namespace mgpu {
@@ -106,6 +108,38 @@ static RdfBlocks rdf_blocks(const mgpu_engine *e) {
 
 static int rdf_ready(const mgpu_engine *e, const char *who) {
     if (e->rdf.n_pairs == 0) return set_error(MGPU_ERR_STATE, std::string(who) + ": no histogram is configured (mgpu_rdf_configure)");
+    return MGPU_OK;
+}
+
+// ---- density maps
+constexpr int kDensityPassMax = 32768;                     // replicas per pass (the grid's y extent)
+
+// the two accumulator arrays inside d_acc
+struct DensityBlocks { unsigned long long *hist, *samples; size_t per_group; };
+static DensityBlocks density_blocks(const mgpu_engine *e) {
+    const auto &d = e->density;
+    DensityBlocks b;
+    b.per_group = (size_t)d.n_channels * d.n[0] * d.n[1] * d.n[2];
+    b.hist = (unsigned long long *)d.d_acc.p;
+    b.samples = b.hist + (size_t)d.n_groups * b.per_group;
+    return b;
+}
+
+static int density_ready(const mgpu_engine *e, const char *who) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    if (e->density.n_channels == 0) return set_error(MGPU_ERR_STATE, std::string(who) + ": no density map is configured (mgpu_density_configure)");
+    return MGPU_OK;
+}
+
+static int check_group_list(const mgpu_engine *e, int n, const int *groups, const char *who) {
+    if (n < 0 || (n > 0 && !groups)) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": bad group list");
+    std::vector<char> seen((size_t)e->density.n_groups, 0);
+    for (int i = 0; i < n; ++i) {
+        const int g = groups[i];
+        if (g < 0 || g >= e->density.n_groups) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": group out of range");
+        if (seen[g]) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": group " + std::to_string(g) + " listed twice");
+        seen[g] = 1;
+    }
     return MGPU_OK;
 }
 
@@ -578,6 +612,152 @@ int mgpu_rdf_reset(mgpu_engine *e, int n, const int *replicas) {
         HIP_TRY(hipMemset(acc.hist + r * acc.per_hist, 0, acc.per_hist * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(acc.eligible + r * np, 0, np * sizeof(unsigned long long)));
         HIP_TRY(hipMemset(acc.samples + r, 0, sizeof(unsigned long long)));
+    }
+    return MGPU_OK;
+}
+
+int mgpu_density_configure(mgpu_engine *e, const int *n, int n_channels, const int *types, int n_groups, const int *group_of) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc;
+    auto &d = e->density;
+    if (n_channels == 0) {
+        if ((rc = use_device(e))) return rc;
+        if ((rc = sync_all_lanes(e))) return rc;
+        d.d_acc.release();
+        d.d_group.release();
+        d.n_channels = 0; d.n_groups = 0;
+        return MGPU_OK;
+    }
+    if (!n) return set_error(MGPU_ERR_INVALID_ARG, "density_configure: null grid");
+    unsigned long long voxels = 1;
+    for (int k = 0; k < 3; ++k) {
+        if (n[k] < 1 || n[k] > kDensityMaxAxis)
+            return set_error(MGPU_ERR_INVALID_ARG, "density_configure: grid axis " + std::to_string(k) + " has " + std::to_string(n[k]) +
+                             " voxels, outside [1, " + std::to_string(kDensityMaxAxis) + "]");
+        voxels *= (unsigned long long)n[k];
+    }
+    if (voxels > (unsigned long long)kDensityMaxVoxels)
+        return set_error(MGPU_ERR_INVALID_ARG, "density_configure: a grid of " + std::to_string(voxels) + " voxels exceeds the limit of " +
+                         std::to_string(kDensityMaxVoxels));
+    if (n_channels < 1 || n_channels > kDensityMaxChannels)
+        return set_error(MGPU_ERR_INVALID_ARG, "density_configure: n_channels " + std::to_string(n_channels) + " is outside [1, " +
+                         std::to_string(kDensityMaxChannels) + "]");
+    if (!types) return set_error(MGPU_ERR_INVALID_ARG, "density_configure: null type list");
+    const int nt = e->tp.n_types;
+    unsigned long long table = ~0ull;
+    for (int c = 0; c < n_channels; ++c) {
+        const int t = types[c];
+        if (t < 0 || t >= nt || t >= kMaxTypes)
+            return set_error(MGPU_ERR_INVALID_ARG, "density_configure: channel " + std::to_string(c) + ": atom type out of range [0, " +
+                             std::to_string(nt - 1) + "]");
+        if (((table >> (4 * t)) & kDensityNone) != (unsigned)kDensityNone)
+            return set_error(MGPU_ERR_INVALID_ARG, "density_configure: channel " + std::to_string(c) + " (atom type " + std::to_string(t) +
+                             ") is a duplicate");
+        table = (table & ~((unsigned long long)kDensityNone << (4 * t))) | ((unsigned long long)c << (4 * t));
+    }
+    const int R = e->n_replicas;
+    if (n_groups < 1 || n_groups > R)
+        return set_error(MGPU_ERR_INVALID_ARG, "density_configure: n_groups " + std::to_string(n_groups) + " is outside [1, " +
+                         std::to_string(R) + "]");
+    if (!group_of) return set_error(MGPU_ERR_INVALID_ARG, "density_configure: null group_of");
+    for (int r = 0; r < R; ++r)
+        if (group_of[r] < -1 || group_of[r] >= n_groups)
+            return set_error(MGPU_ERR_INVALID_ARG, "density_configure: replica " + std::to_string(r) + ": group " + std::to_string(group_of[r]) +
+                             " is outside [0, " + std::to_string(n_groups - 1) + "] and not -1");
+    // (2^24 voxels x 8 channels x 2^31 groups x 8 bytes stays below 2^64)
+    const unsigned long long bytes = ((unsigned long long)n_groups * n_channels * voxels + n_groups) * sizeof(unsigned long long);
+    if (bytes > MGPU_DENSITY_MAX_BYTES)
+        return set_error(MGPU_ERR_INVALID_ARG, "density_configure: the accumulators would take " + std::to_string(bytes) +
+                         " bytes, the limit is " + std::to_string(MGPU_DENSITY_MAX_BYTES));
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    d.d_acc.release();
+    d.n_channels = 0; d.n_groups = 0;
+    HIP_TRY(hipMalloc(&d.d_acc.p, (size_t)bytes));             // exactly: a map may be large
+    d.d_acc.bytes = (size_t)bytes;
+    if ((rc = d.d_group.reserve((size_t)R * sizeof(int)))) return rc;
+    HIP_TRY(hipMemset(d.d_acc.p, 0, (size_t)bytes));
+    HIP_TRY(hipMemcpy(d.d_group.p, group_of, (size_t)R * sizeof(int), hipMemcpyHostToDevice));
+    for (int k = 0; k < 3; ++k) d.n[k] = n[k];
+    for (int c = 0; c < n_channels; ++c) d.types[c] = types[c];
+    d.table = table;
+    d.n_channels = n_channels; d.n_groups = n_groups;
+    return MGPU_OK;
+}
+
+int mgpu_density_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int chunk) {
+    int rc = check_replica_list(e, n, replicas, "density_accumulate_replicas");
+    if (rc) return rc;
+    if ((rc = density_ready(e, "density_accumulate_replicas"))) return rc;
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const auto &d = e->density;
+    const DensityBlocks acc = density_blocks(e);
+    if ((rc = e->d_items2.reserve((size_t)n * sizeof(int)))) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_items2.p, replicas, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
+    const int most = chunk > 0 ? std::min(chunk, kDensityPassMax) : kDensityPassMax;
+    const int n_blk = (e->tp.n_cap_atoms + kDensityBlock - 1) / kDensityBlock;
+    const DensityArgs da{{d.n[0], d.n[1], d.n[2]}, d.n_channels, d.table};
+    for (int first = 0; first < n; first += most) {
+        const int c = std::min(most, n - first);
+        const int *d_reps = (const int *)e->d_items2.p + first;
+        with_bools([&](auto tri) {
+            hipLaunchKernelGGL((density_map_kernel<decltype(tri)::value>), dim3((unsigned)n_blk, (unsigned)c), dim3(kDensityBlock), 0, e->stream,
+                               e->tp, e->bx, da, (const double *)e->d_pos, (const int *)e->d_nmol, (const int *)e->d_atom_res,
+                               (const int *)e->d_atom_mol, d_reps, (const int *)d.d_group.p, acc.hist, acc.samples);
+        }, e->bx.triclinic != 0);
+        HIP_TRY(hipGetLastError());
+    }
+    return sync_stream(e);
+}
+
+int mgpu_density_read(mgpu_engine *e, int n, const int *groups, unsigned long long *hist, unsigned long long *samples) {
+    int rc = density_ready(e, "density_read");
+    if (rc) return rc;
+    if ((rc = check_group_list(e, n, groups, "density_read"))) return rc;
+    if (n > 0 && (!hist || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "density_read: null output");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const DensityBlocks acc = density_blocks(e);
+    for (int i = 0; i < n; ++i) {
+        const size_t g = (size_t)groups[i];
+        HIP_TRY(hipMemcpy(hist + (size_t)i * acc.per_group, acc.hist + g * acc.per_group, acc.per_group * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(samples + i, acc.samples + g, sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    }
+    return MGPU_OK;
+}
+
+int mgpu_density_load(mgpu_engine *e, int n, const int *groups, const unsigned long long *hist, const unsigned long long *samples) {
+    int rc = density_ready(e, "density_load");
+    if (rc) return rc;
+    if ((rc = check_group_list(e, n, groups, "density_load"))) return rc;
+    if (n > 0 && (!hist || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "density_load: null input");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const DensityBlocks acc = density_blocks(e);
+    for (int i = 0; i < n; ++i) {
+        const size_t g = (size_t)groups[i];
+        HIP_TRY(hipMemcpy(acc.hist + g * acc.per_group, hist + (size_t)i * acc.per_group, acc.per_group * sizeof(unsigned long long), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(acc.samples + g, samples + i, sizeof(unsigned long long), hipMemcpyHostToDevice));
+    }
+    return MGPU_OK;
+}
+
+int mgpu_density_reset(mgpu_engine *e, int n, const int *groups) {
+    int rc = density_ready(e, "density_reset");
+    if (rc) return rc;
+    if ((rc = check_group_list(e, n, groups, "density_reset"))) return rc;
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const DensityBlocks acc = density_blocks(e);
+    for (int i = 0; i < n; ++i) {
+        const size_t g = (size_t)groups[i];
+        HIP_TRY(hipMemset(acc.hist + g * acc.per_group, 0, acc.per_group * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(acc.samples + g, 0, sizeof(unsigned long long)));
     }
     return MGPU_OK;
 }

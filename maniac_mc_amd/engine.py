@@ -571,6 +571,64 @@ class Engine:
         r = self._replica_list(replicas)
         check(self.L.mgpu_rdf_reset(self.h, C.c_int(r.shape[0]), _i(r)))
 
+    # ---- density maps --------------------------------------------------------------------
+    def density_configure(self, grid, types, group_of=None, n_groups=None):
+        """mgpu_density_configure: maps of grid = (n0, n1, n2) voxels along the three cell vectors for the channels `types`
+        (0-based atom types, at most 8), zeroed.  group_of (R,): the map every replica adds into, -1 for a replica that is
+        never counted (None: all replicas into map 0); n_groups: None = the largest entry + 1.  types = [] frees them."""
+        types = np.ascontiguousarray([int(t) for t in types], dtype=np.int32)
+        grid = np.ascontiguousarray([int(v) for v in grid], dtype=np.int32)
+        if grid.shape != (3,):
+            raise ValueError(f"density_configure: the grid takes three voxel counts, not {grid.tolist()}")
+        if group_of is None:
+            group_of = np.zeros(self.n_replicas, dtype=np.int32)
+        group_of = np.ascontiguousarray(group_of, dtype=np.int32)
+        if group_of.shape != (self.n_replicas,):
+            raise ValueError(f"density_configure: group_of takes one entry per replica ({self.n_replicas}), not {group_of.shape}")
+        if n_groups is None:
+            n_groups = max(1, int(group_of.max()) + 1)
+        check(self.L.mgpu_density_configure(self.h, _i(grid), C.c_int(types.shape[0]), _i(types) if types.size else None,
+                                            C.c_int(int(n_groups)), _i(group_of)))
+        self.density_shape = (int(n_groups), types.shape[0], int(grid[2]), int(grid[1]), int(grid[0])) if types.size else None
+
+    def _density_groups(self, groups):
+        shape = getattr(self, "density_shape", None)
+        if shape is None:
+            raise _lib.MgpuError(5, "no density map is configured (Engine.density_configure)")
+        g = np.arange(shape[0], dtype=np.int32) if groups is None else np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+        return g, shape[1:]
+
+    def density_accumulate(self, replicas=None, chunk=None):
+        """mgpu_density_accumulate_replicas: one sample of every listed replica (None: all) from the resident coordinates."""
+        r = self._replica_list(replicas)
+        check(self.L.mgpu_density_accumulate_replicas(self.h, C.c_int(r.shape[0]), _i(r), C.c_int(0 if chunk is None else int(chunk))))
+
+    def density_read(self, groups=None):
+        """mgpu_density_read: (hist (n, n_channels, n2, n1, n0), samples (n,)) of the listed groups (None: all), uint64."""
+        g, per = self._density_groups(groups)
+        n = g.shape[0]
+        hist = np.zeros((n,) + per, dtype=np.uint64)
+        samples = np.zeros(n, dtype=np.uint64)
+        u = C.POINTER(C.c_ulonglong)
+        check(self.L.mgpu_density_read(self.h, C.c_int(n), _i(g), hist.ctypes.data_as(u), samples.ctypes.data_as(u)))
+        return hist, samples
+
+    def density_load(self, hist, samples, groups=None):
+        """mgpu_density_load: overwrite the listed groups' accumulators with arrays shaped as density_read returns them."""
+        g, per = self._density_groups(groups)
+        n = g.shape[0]
+        hist = np.ascontiguousarray(hist, dtype=np.uint64)
+        samples = np.ascontiguousarray(samples, dtype=np.uint64)
+        if hist.shape != (n,) + per or samples.shape != (n,):
+            raise ValueError(f"density_load: arrays of shapes {hist.shape}, {samples.shape} for {n} groups of maps {per}")
+        u = C.POINTER(C.c_ulonglong)
+        check(self.L.mgpu_density_load(self.h, C.c_int(n), _i(g), hist.ctypes.data_as(u), samples.ctypes.data_as(u)))
+
+    def density_reset(self, groups=None):
+        """mgpu_density_reset: zero the listed groups' accumulators (None: all)."""
+        g, _ = self._density_groups(groups)
+        check(self.L.mgpu_density_reset(self.h, C.c_int(g.shape[0]), _i(g)))
+
     def structure_factor(self, replica=0):
         a = np.zeros((self.nk, 2))
         check(self.L.mgpu_get_structure_factor(self.h, C.c_int(replica), _d(a)))

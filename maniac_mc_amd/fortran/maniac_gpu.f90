@@ -194,6 +194,46 @@ module maniac_gpu
             integer(c_int), intent(in) :: replicas(*)
             integer(c_int) :: rc
         end function
+        ! density maps of many replicas: integer counts per voxel of the resident coordinates (0-based atom types)
+        function mgpu_density_configure(e, n, n_channels, types, n_groups, group_of) &
+                bind(C, name="mgpu_density_configure") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n_channels, n_groups
+            integer(c_int), intent(in) :: n(*), types(*), group_of(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_density_accumulate_replicas(e, n, replicas, chunk) &
+                bind(C, name="mgpu_density_accumulate_replicas") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n, chunk
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_density_read(e, n, groups, hist, samples) bind(C, name="mgpu_density_read") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: groups(*)
+            integer(c_long_long), intent(out) :: hist(*), samples(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_density_load(e, n, groups, hist, samples) bind(C, name="mgpu_density_load") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: groups(*)
+            integer(c_long_long), intent(in) :: hist(*), samples(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_density_reset(e, n, groups) bind(C, name="mgpu_density_reset") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: groups(*)
+            integer(c_int) :: rc
+        end function
         ! energies by residue-type pair of many replicas (0-based residue types): out(5, n_sel, n) in K
         function mgpu_energy_pairs_replicas(e, n, replicas, chunk, n_sel, res_a, res_b, out) &
                 bind(C, name="mgpu_energy_pairs_replicas") result(rc)
@@ -842,6 +882,52 @@ contains
         integer, intent(out), optional :: stat
         call GpuCheck(mgpu_rdf_reset(engine, int(n, c_int), int(replicas, c_int)), 'GpuRdfReset', stat)
     end subroutine GpuRdfReset
+
+    !---------------------------------------------------------------------------
+    ! Density maps.  Atom types are 1-based here, as in the data file; replicas and groups are
+    ! 0-based, as everywhere in this module (group_of(r) = -1: replica r is never counted).  The
+    ! counts are integer(c_long_long): hist(n0, n1, n2, n_channels, n), samples(n).
+    !---------------------------------------------------------------------------
+    ! group_of(n_replicas): one entry per replica of the engine
+    subroutine GpuDensityConfigure(engine, grid, n_channels, types, n_groups, n_replicas, group_of, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: grid(3), n_channels, types(n_channels), n_groups, n_replicas, group_of(n_replicas)
+        integer, intent(out), optional :: stat
+        integer(c_int) :: ty(max(1, n_channels)), rc
+        ty(1:n_channels) = int(types - 1, c_int)
+        rc = mgpu_density_configure(engine, int(grid, c_int), int(n_channels, c_int), ty, int(n_groups, c_int), int(group_of, c_int))
+        call GpuCheck(rc, 'GpuDensityConfigure', stat)
+    end subroutine GpuDensityConfigure
+
+    subroutine GpuDensityAccumulate(engine, n, replicas, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, replicas(n)
+        integer, intent(out), optional :: stat
+        call GpuCheck(mgpu_density_accumulate_replicas(engine, int(n, c_int), int(replicas, c_int), 0_c_int), 'GpuDensityAccumulate', stat)
+    end subroutine GpuDensityAccumulate
+
+    subroutine GpuDensityRead(engine, n, groups, hist, samples, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, groups(n)
+        integer(c_long_long), intent(out) :: hist(*), samples(*)
+        integer, intent(out), optional :: stat
+        call GpuCheck(mgpu_density_read(engine, int(n, c_int), int(groups, c_int), hist, samples), 'GpuDensityRead', stat)
+    end subroutine GpuDensityRead
+
+    subroutine GpuDensityLoad(engine, n, groups, hist, samples, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, groups(n)
+        integer(c_long_long), intent(in) :: hist(*), samples(*)
+        integer, intent(out), optional :: stat
+        call GpuCheck(mgpu_density_load(engine, int(n, c_int), int(groups, c_int), hist, samples), 'GpuDensityLoad', stat)
+    end subroutine GpuDensityLoad
+
+    subroutine GpuDensityReset(engine, n, groups, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, groups(n)
+        integer, intent(out), optional :: stat
+        call GpuCheck(mgpu_density_reset(engine, int(n, c_int), int(groups, c_int)), 'GpuDensityReset', stat)
+    end subroutine GpuDensityReset
 
     !---------------------------------------------------------------------------
     ! Energies by residue-type pair: out(5, n_sel, n) in K = non_coulomb, coulomb, recip_coulomb,

@@ -301,6 +301,12 @@ class FortranFarm:
         self.eng.rdf_accumulate(replicas, chunk)
         self._select()
 
+    def density_sample(self, replicas=None, chunk=None):
+        """One sample of every listed chain (None: all) into the engine's density maps (Engine.density_configure first), from
+        the coordinates the engine holds -- which are current between two run() calls in every farm mode."""
+        self.eng.density_accumulate(replicas, chunk)
+        self._select()
+
     def energy_pairs_sample(self, pairs, replicas=None, chunk=None):
         """The energy by residue-type pair of every listed chain (None: all), (n, n_sel, 5) in K (Engine.energy_pairs_replicas),
         from the coordinates the engine holds -- which are current between two run() calls in every farm mode."""

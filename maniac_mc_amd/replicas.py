@@ -23,6 +23,7 @@ import numpy as np
 
 from . import _lib, checkpoint, fortran_host, io_maniac
 from . import energy_pairs as epairs_mod
+from . import density as density_mod
 from . import rdf as rdf_mod
 from .fortran_host import FortranFarm
 from .run import header_text, set_chain_state
@@ -74,7 +75,7 @@ def _stats(x):
 def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=None, fugacities=None, frames=(0,),
                  mode="auto", device=0, nb_block=None, nb_step=None, mol_capacity=None, n_lanes=2, n_threads=8,
                  chunk=None, wide_triclinic=False, restart_from=None, audit=False, checkpoint_every=0, resume=False,
-                 recalibrate_moves=None, rdf=None, energy_pairs=None):
+                 recalibrate_moves=None, rdf=None, energy_pairs=None, density=None):
     """Run `replicas` independent chains of the input; returns a dict with the final energies (R, 5) in K (non-Coulomb,
     Coulomb, reciprocal, self, intramolecular), counts (R, n_active), chain counters (R, 8), the farm's counters, the
     mode that ran and the block timings.
@@ -123,6 +124,14 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     guest-guest).  After the last block <outdir>/energy_pairs.dat holds, per fugacity group and pair, mean and standard error
     over the replicas (maniac_mc_amd.energy_pairs).  The sampling keeps no state: a checkpoint only records the option, and a
     resumed run must ask for the same.  None (default): nothing of this, and every file is what it always was.
+    ``density``: dict(grid=(n0, n1, n2), types=[...] (0-based atom types; default: the atom types of the active residue types, at
+    most 8), every=1, per_replica=False) -> after every `every`-th block one sample of every replica goes into the engine's
+    density maps (Engine.density_accumulate; its time in seconds["density"]), one map per fugacity group and type, or per
+    replica and type with per_replica; after the last block <outdir>/density_counts.npz (hist, samples, the spec, every
+    replica's map and group), <outdir>/density_profiles.dat (per map, type and cell axis the slab densities) and one Gaussian
+    cube file <outdir>/density_gGG_typeTT.cube per map and type (sites per cubic Angstrom over the cell, with the atoms of the
+    inactive residue types) are written (maniac_mc_amd.density).  A checkpoint then carries the accumulators, and a resumed
+    run must ask for the same density.  None (default): nothing of this, and every file is what it always was.
     """
     import time
     if mode not in MODES:
@@ -176,6 +185,10 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         if rdf_spec["r_max"] > limit:
             raise ValueError(f"rdf: r_max {rdf_spec['r_max']!r} exceeds half the smallest perpendicular width of the cell, {limit!r}")
 
+    den_spec = None
+    if density is not None:
+        den_spec = density_mod.check_spec(density, topo)
+
     ep_spec = None
     if energy_pairs is not None:
         unknown = set(energy_pairs) - {"every", "pairs"}
@@ -194,6 +207,10 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         fug_grid = np.array([[_with_fugacity(inp, fugacities[g]).fugacity_per_A3()[t] for t in active] for g in group])
     else:
         fug_grid = np.tile(np.array([inp.fugacity_per_A3()[t] for t in active])[None, :], (R, 1)) if gcmc else None
+    if den_spec is not None:
+        den_group = np.arange(R) if den_spec["per_replica"] else np.asarray(group)
+        den_n_groups = R if den_spec["per_replica"] else (len(fugacities) if fugacities is not None else 1)
+        density_mod.check_size(den_spec["grid"], len(den_spec["types"]), den_n_groups)
     gcmc_arg = dict(p_translation=inp.translation_proba, p_rotation=inp.rotation_proba, fugacity=fug_grid) if gcmc else None
     reservoir = io_maniac.reservoir_offsets(reservoir_path, inp) if reservoir_path else None
     recalibrate = bool(inp.recalibrate_moves) if recalibrate_moves is None else bool(recalibrate_moves)
@@ -205,6 +222,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
             ident["rdf"] = rdf_mod.identity_array(rdf_spec)
         if ep_spec is not None:
             ident["energy_pairs"] = epairs_mod.identity_array(ep_spec)
+        if den_spec is not None:
+            ident["density"] = density_mod.identity_array(den_spec)
     if resume:
         ck = checkpoint.load(outdir)
         checkpoint.check(ck, ident, nb_block)
@@ -261,6 +280,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         if rdf_spec is not None:
             farm.eng.rdf_configure(rdf_spec["n_bins"], rdf_spec["r_max"], rdf_spec["pairs"], rdf_spec["include_intra"])
             times["rdf"] = 0.0
+        if den_spec is not None:
+            farm.eng.density_configure(den_spec["grid"], den_spec["types"], den_group, den_n_groups)
+            times["density"] = 0.0
         ep_paths = [os.path.join(root, f"replica_{r:04d}", epairs_mod.FILE_NAME) for r in range(R)]
         if ep_spec is not None:
             times["energy_pairs"] = 0.0
@@ -314,6 +336,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
             extra = None
             if rdf_spec is not None:
                 extra = dict(zip(("rdf_hist", "rdf_eligible", "rdf_samples"), farm.eng.rdf_read()))
+            if den_spec is not None:
+                extra = dict(extra or {}, **dict(zip(("density_hist", "density_samples"), farm.eng.density_read())))
             checkpoint.save(outdir, ident, next_block, nb_block, ran, state["engine"], state["driver"],
                             checkpoint.output_sizes(outdir, R), extra=extra)
             times["checkpoint"] = times.get("checkpoint", 0.0) + time.perf_counter() - t0
@@ -327,6 +351,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
             if rdf_spec is not None:
                 x = ck["extra"]
                 farm.eng.rdf_load(x["rdf_hist"], x["rdf_eligible"], x["rdf_samples"])
+            if den_spec is not None:
+                x = ck["extra"]
+                farm.eng.density_load(x["density_hist"], x["density_samples"])
             first = int(ck["next_block"])
         else:
             write(0, False)
@@ -340,6 +367,10 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
                 t0 = time.perf_counter()
                 farm.rdf_sample()
                 times["rdf"] += time.perf_counter() - t0
+            if den_spec is not None and block % den_spec["every"] == 0:
+                t0 = time.perf_counter()
+                farm.density_sample()
+                times["density"] += time.perf_counter() - t0
             if ep_spec is not None and block % ep_spec["every"] == 0:
                 t0 = time.perf_counter()
                 values = farm.energy_pairs_sample(ep_spec["pairs"])
@@ -356,6 +387,19 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
                                  rdf_spec["r_max"], rdf_spec["n_bins"], rdf_spec["every"], rdf_spec["include_intra"])
             rdf_mod.write_dat(os.path.join(root, "rdf.dat"), hist, eligible, group, rdf_spec["pairs"],
                               rdf_mod.volume(system.box_matrix), rdf_spec["r_max"])
+        if den_spec is not None:
+            hist, samples = farm.eng.density_read()
+            density_mod.write_counts(os.path.join(root, "density_counts.npz"), hist, samples, den_group, group, den_spec["types"],
+                                     den_spec["grid"], den_spec["every"], den_spec["per_replica"])
+            density_mod.write_profiles(os.path.join(root, "density_profiles.dat"), hist, samples, den_spec["types"], system.box_matrix)
+            rho = density_mod.number_density(hist, samples, system.box_matrix)
+            atoms = [(density_mod.atomic_number(dat["masses"][int(topo.atom_types[t, a]) - 1]), *xyz)
+                     for t in range(n_res) if topo.is_active[t] != 1
+                     for mol in system.all_sites(t) for a, xyz in enumerate(mol.tolist())]
+            for g in range(hist.shape[0]):
+                for c, ty in enumerate(den_spec["types"]):
+                    density_mod.write_cube(os.path.join(root, density_mod.cube_name(g, ty)), rho[g, c], system.box_matrix,
+                                           system.bounds_lo, atoms, title=f"map {g} atom type {ty + 1} samples {int(samples[g])}")
         if ep_spec is not None:
             f_atm = fugacities if fugacities is not None else [inp.residues[active[0]].fugacity_atm if active else 0.0]
             epairs_mod.write_pooled_file(os.path.join(root, epairs_mod.FILE_NAME), ep_paths, group, f_atm)

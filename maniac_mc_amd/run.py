@@ -330,6 +330,14 @@ def main(argv=None):
                          "<out>/replica_NNNN/energy_pairs.dat and <out>/energy_pairs.dat")
     ap.add_argument("--energy-pairs-select", dest="energy_pairs_select", default=None, metavar="NAME:NAME,...",
                     help="with --energy-pairs: the pairs, by the input's residue names (default: every pair with an active type)")
+    ap.add_argument("--density", default=None, metavar="N0,N1,N2[,EVERY]",
+                    help="with --replicas: density maps of N0 x N1 x N2 voxels along the cell vectors, one sample of every replica "
+                         "after every EVERY-th block (default 1), pooled per fugacity group; writes <out>/density_counts.npz, "
+                         "<out>/density_profiles.dat and <out>/density_gGG_typeTT.cube")
+    ap.add_argument("--density-types", dest="density_types", default=None, metavar="T,T,...",
+                    help="with --density: the atom types, ids as in the data file (default: the active types' atom types; at most 8)")
+    ap.add_argument("--density-per-replica", dest="density_per_replica", action="store_true",
+                    help="with --density: one map per replica instead of one per fugacity group")
     a = ap.parse_args(argv)
     try:
         chain_run = parse_chain_run(a.chain_run) if a.chain_run is not None else None
@@ -354,6 +362,8 @@ def main(argv=None):
             ap.error("--rdf, --rdf-pairs and --rdf-intra need --replicas: the single chain writes no distribution functions")
         if a.energy_pairs is not None or a.energy_pairs_select is not None:
             ap.error("--energy-pairs and --energy-pairs-select need --replicas: the single chain writes no energy decomposition")
+        if a.density is not None or a.density_types is not None or a.density_per_replica:
+            ap.error("--density, --density-types and --density-per-replica need --replicas: the single chain writes no density maps")
     else:
         from . import replicas as farm_run
         if a.as_written:
@@ -394,6 +404,17 @@ def main(argv=None):
                     energy_pairs["pairs"] = epairs_mod.parse_select(a.energy_pairs_select, names)
             except ValueError as err:
                 ap.error(str(err))
+        density = None
+        if a.density is None and (a.density_types is not None or a.density_per_replica):
+            ap.error("--density-types and --density-per-replica need --density N0,N1,N2[,EVERY]")
+        if a.density is not None:
+            from . import density as density_mod
+            try:
+                density = density_mod.parse_spec(a.density)
+                density["types"] = density_mod.parse_types(a.density_types) if a.density_types is not None else None
+                density["per_replica"] = bool(a.density_per_replica)
+            except ValueError as err:
+                ap.error(str(err))
     for path, what in ((a.maniac, "Input"), (a.data, "Data"), (a.inc, "Parameter"), (a.reservoir, "Reservoir")):
         if path is not None and not os.path.isfile(path):
             print(f"{what} file not found: {path}", file=sys.stderr)
@@ -404,7 +425,7 @@ def main(argv=None):
                                         fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device,
                                         wide_triclinic=a.wide_triclinic, restart_from=a.restart_from, audit=a.audit,
                                         checkpoint_every=a.checkpoint_every, resume=a.resume, rdf=rdf,
-                                        energy_pairs=energy_pairs)
+                                        energy_pairs=energy_pairs, density=density)
         except ValueError as err:
             print(f"error: {err}", file=sys.stderr)
             return 2
