@@ -20,6 +20,7 @@ DIR_NAME = "checkpoint"
 FILE_NAME = "farm.ckpt"
 TMP_NAME = FILE_NAME + ".tmp"
 REWRITTEN = ("topology.data",)        # output files written anew every time (all others grow by appending)
+ANALYSES = ("rdf", "energy_pairs", "density")     # the identity entries of the farm analyses, in the order check names them
 
 
 def path_of(outdir):
@@ -126,18 +127,11 @@ _NAMES = dict(abi_version="ABI version", nb_step="nb_step", seed="seed", mode="m
 def check(ck, ident, nb_block):
     """ValueError naming the first thing in which the run asked for differs from the run that wrote the checkpoint.  A larger
     nb_block than recorded extends the run; one below the blocks already done is refused."""
-    if "id_rdf" in ck and "rdf" not in ident:
-        # (an entry only a run with --rdf has: the checkpointed run had it switched on and this one has not)
-        raise ValueError(f"resume: {_NAMES['rdf']} differs from the checkpoint's (checkpoint "
-                         f"{np.asarray(ck['id_rdf']).tolist()!r}, this run without it)")
-    if "id_energy_pairs" in ck and "energy_pairs" not in ident:
-        # (likewise: only a run with --energy-pairs writes the entry)
-        raise ValueError(f"resume: {_NAMES['energy_pairs']} differs from the checkpoint's (checkpoint "
-                         f"{np.asarray(ck['id_energy_pairs']).tolist()!r}, this run without it)")
-    if "id_density" in ck and "density" not in ident:
-        # (likewise: only a run with --density writes the entry)
-        raise ValueError(f"resume: {_NAMES['density']} differs from the checkpoint's (checkpoint "
-                         f"{np.asarray(ck['id_density']).tolist()!r}, this run without it)")
+    for k in ANALYSES:
+        # (an entry only a run with the analysis has: the checkpointed run had it switched on and this one has not)
+        if "id_" + k in ck and k not in ident:
+            raise ValueError(f"resume: {_NAMES[k]} differs from the checkpoint's (checkpoint "
+                             f"{np.asarray(ck['id_' + k]).tolist()!r}, this run without it)")
     for k, want in ident.items():
         got = ck.get("id_" + k)
         same = got is not None and np.asarray(got).shape == np.asarray(want).shape and np.array_equal(np.asarray(got), np.asarray(want))

@@ -422,21 +422,23 @@ struct mgpu_engine {
         std::deque<std::pair<int, int>> log;         // (first, consumed) of the last launches seen since open
     } run;
     // radial distribution functions (mgpu_rdf_*, mgpu_replicas.hip): the selection, and the accumulators of every replica --
-    // d_acc = hist [R][n_pairs][n_bins] | eligible [R][n_pairs] | samples [R], unsigned long long; d_tab = the RdfTable.
-    // Nothing but the mgpu_rdf_* calls touches them.
+    // d_acc = hist [R][n_pairs][n_bins] | eligible [R][n_pairs] | samples [R], unsigned long long, as `acc` describes it
+    // (mgpu_internal.h); d_tab = the RdfTable.  Nothing but the mgpu_rdf_* calls touches them.
     struct Rdf {
         int n_bins = 0, n_pairs = 0, include_intra = 0;       // n_pairs = 0: not configured
         double r_max = 0.0, r_max2 = 0.0, inv_dr = 0.0;
         int type_a[8]{}, type_b[8]{};
+        Accum acc;
         DevBuf d_acc, d_tab;
     } rdf;
     // density maps (mgpu_density_*, mgpu_replicas.hip): the grid, the channels' atom types, every replica's group, and the
-    // accumulators -- d_acc = hist [n_groups][n_channels][n2][n1][n0] | samples [n_groups], unsigned long long; d_group =
-    // group_of [R].  Nothing but the mgpu_density_* calls touches them.
+    // accumulators -- d_acc = hist [n_groups][n_channels][n2][n1][n0] | samples [n_groups], unsigned long long, as `acc`
+    // describes it; d_group = group_of [R].  Nothing but the mgpu_density_* calls touches them.
     struct Density {
         int n[3]{}, n_channels = 0, n_groups = 0;             // n_channels = 0: not configured
         int types[8]{};
         unsigned long long table = ~0ull;                     // atom type -> channel, a nibble each (0xF: none)
+        Accum acc;
         DevBuf d_acc, d_group;
     } density;
     // profiling

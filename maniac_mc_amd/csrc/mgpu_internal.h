@@ -244,6 +244,64 @@ inline StateSegs state_type_segments(size_t at, int n, int nf, int n1, int rsv_c
 // 16-byte accesses for a run-strided item: block offset, engine offset, run length and run stride all even
 inline bool state_item_vec(long long src, long long dst, long long len, long long stride) { return ((src | dst | len | stride) & 1) == 0; }
 
+// ---- The passes of a call over many replicas (mgpu_system_energy_replicas, mgpu_energy_pairs_replicas; mgpu_replicas.hip):
+// the listed replicas in the caller's order, per pass as many as `chunk`, a byte budget of scratch and a budget of pair work
+// units allow, never fewer than one.
+constexpr size_t kReplicasPassBytes = (size_t)256 << 20;       // scratch a pass may take: what bounds the engine's own choice of `chunk`
+constexpr int kReplicasPassMax = 32768;                        // replicas per pass (the grids' y extent)
+constexpr long long kReplicasPassItems = (long long)1 << 28;   // pair work units (items x splits) per pass
+struct Pass { int first, c; long long n_pair, n_in; };
+// counts(i, n_pair, n_in): the pair and intra items of list entry i; bytes_of(n_pair, n_in): what such a replica adds to a
+// pass.  False (and no passes): one pass's sweep -- a single replica's, past the item budget -- would not fit 2^31 work units
+// (less the kWindowPairWaves = kPairWaves a sweep's grid rounds up by); the caller words the refusal.
+template <class Counts, class BytesOf>
+inline bool plan_passes(int n, Counts counts, BytesOf bytes_of, int chunk, int nsplit, std::vector<Pass> &passes) {
+    const int most = chunk > 0 ? std::min(chunk, kReplicasPassMax) : kReplicasPassMax;
+    passes.clear();
+    for (int i = 0; i < n;) {
+        Pass p{i, 0, 0, 0};
+        size_t bytes = 0;
+        while (i < n && p.c < most) {
+            long long np, ni;
+            counts(i, np, ni);
+            const size_t b = bytes_of(np, ni);
+            if (p.c > 0 && (bytes + b > kReplicasPassBytes || (p.n_pair + np) * nsplit > kReplicasPassItems)) break;
+            bytes += b; p.n_pair += np; p.n_in += ni; p.c += 1; ++i;
+        }
+        if (p.n_pair * nsplit >= ((long long)1 << 31) - kWindowPairWaves) { passes.clear(); return false; }
+        passes.push_back(p);
+    }
+    return true;
+}
+
+// ---- The accumulators of a farm analysis (mgpu_engine::Rdf, ::Density): one device block of unsigned long long words cut
+// into at most three segments; segment s holds per[s] words for every entry (a replica, a group of replicas), entry after
+// entry, from word at[s] of the block on.  The read / load / reset calls of every analysis go through this description.
+struct Accum {
+    int n_seg = 0;
+    size_t entries = 0, at[3] = {0, 0, 0}, per[3] = {0, 0, 0}, words = 0;
+    size_t word(int s, size_t entry) const { return at[s] + entry * per[s]; }
+    size_t bytes() const { return words * sizeof(unsigned long long); }
+};
+inline Accum accum_layout(size_t entries, size_t per0, size_t per1, size_t per2 = 0) {
+    Accum a;
+    a.entries = entries;
+    for (size_t per : {per0, per1, per2}) {
+        if (per == 0) break;
+        a.at[a.n_seg] = a.words; a.per[a.n_seg] = per;
+        a.words += entries * per; ++a.n_seg;
+    }
+    return a;
+}
+
+// ---- Packed tables of sixteen 4-bit slots in one 64-bit word (RdfTable.row: atom type -> pair index; Density::table: atom
+// type -> channel): kNibbleNone marks an empty slot, ~0ull an empty table.
+constexpr unsigned kNibbleNone = 0xF;
+inline unsigned nibble_get(unsigned long long word, int slot) { return (unsigned)(word >> (4 * slot)) & kNibbleNone; }
+inline unsigned long long nibble_set(unsigned long long word, int slot, unsigned v) {
+    return (word & ~((unsigned long long)kNibbleNone << (4 * slot))) | ((unsigned long long)v << (4 * slot));
+}
+
 }  // namespace mgpu
 
 #endif

@@ -8,6 +8,10 @@
 // the same budget, per pass one sweep over (molecule, partner type) items, the partial structure factors of the selected types
 // and one ordered reduction per (replica, pair).  And the density maps (mgpu_density_*): integer counts per voxel of selected
 // atom types, pooled per group of replicas, one density_map_kernel launch per pass.
+// What the analyses share has one home each: the passes of the two energy calls are plan_passes (mgpu_internal.h), every list
+// of replicas or groups goes through check_index_list, the accumulators of rdf and density are an Accum (mgpu_internal.h) read,
+// loaded and cleared by accum_read / accum_load / accum_reset, their packed type tables are built with nibble_get / nibble_set,
+// and the phase tables of a pass are launched by launch_phase_tables_replicas.
 #include "mgpu_engine.h"
 #include "mgpu_kernels_replicas.h"
 #include "mgpu_kernels_rdf.h"
@@ -16,19 +20,14 @@
 
 namespace mgpu {
 
-// scratch a pass may take (items, partials, phase tables, S): what bounds the engine's own choice of `chunk`
-constexpr size_t kReplicasPassBytes = (size_t)256 << 20;
-constexpr int kReplicasPassMax = 32768;                    // replicas per pass (the grids' y extent)
-constexpr long long kReplicasPassItems = (long long)1 << 28;   // pair work units (items x splits) per pass
-
-static int check_replica_list(const mgpu_engine *e, int n, const int *replicas, const char *who) {
-    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
-    if (n < 0 || (n > 0 && !replicas)) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": bad replica list");
-    std::vector<char> seen((size_t)e->n_replicas, 0);
+// a list of n distinct indices below `limit`: replicas, or the groups of the density maps (`noun`)
+static int check_index_list(int n, const int *ids, int limit, const char *noun, const char *who) {
+    if (n < 0 || (n > 0 && !ids)) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": bad " + noun + " list");
+    std::vector<char> seen((size_t)limit, 0);
     for (int i = 0; i < n; ++i) {
-        const int r = replicas[i];
-        if (r < 0 || r >= e->n_replicas) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": replica out of range");
-        if (seen[r]) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": replica " + std::to_string(r) + " listed twice");
+        const int r = ids[i];
+        if (r < 0 || r >= limit) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": " + noun + " out of range");
+        if (seen[r]) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": " + noun + " " + std::to_string(r) + " listed twice");
         seen[r] = 1;
     }
     return MGPU_OK;
@@ -36,18 +35,21 @@ static int check_replica_list(const mgpu_engine *e, int n, const int *replicas, 
 
 static size_t phase_tab_entries(const mgpu_engine *e) { return (size_t)recip_ktot(e) * e->tp.n_cap_atoms; }
 
+// the phase tables of the replicas d_reps[0 .. c) into d_tab
+static void launch_phase_tables_replicas(mgpu_engine *e, const int *d_reps, int c, double2 *d_tab) {
+    hipLaunchKernelGGL(phase_table_replicas_kernel, dim3((e->tp.n_cap_atoms + 255) / 256, c), dim3(256), 0, e->stream, e->tp, e->bx,
+                       e->d_pos, e->d_nmol, e->d_atom_res, e->d_atom_mol, d_reps, phase_tab_entries(e), d_tab);
+}
+
 // the phase tables of the replicas d_reps[0 .. c) into d_tab, then their S(k): into block i of S_all (to_replica = false) or
 // into block d_reps[i] (true: S_all = the replicas' A(k))
 static int launch_sfactor_replicas(mgpu_engine *e, const int *d_reps, int c, double2 *d_tab, bool to_replica, double2 *S_all) {
-    const int ncap = e->tp.n_cap_atoms;
-    const size_t stride = phase_tab_entries(e);
     hipEvent_t a = nullptr, b = nullptr;
     int rc = prof_begin(e, e->lanes[0], MGPU_KERNEL_SFACTOR, &a, &b);
     if (rc) return rc;
-    hipLaunchKernelGGL(phase_table_replicas_kernel, dim3((ncap + 255) / 256, c), dim3(256), 0, e->stream, e->tp, e->bx, e->d_pos,
-                       e->d_nmol, e->d_atom_res, e->d_atom_mol, d_reps, stride, d_tab);
+    launch_phase_tables_replicas(e, d_reps, c, d_tab);
     hipExtLaunchKernelGGL(sfactor_replicas_kernel, dim3(e->nk, c), dim3(kBlock), 0, e->stream, a, b, 0, e->tp, e->bx, e->d_nmol,
-                          e->d_atom_res, e->d_atom_mol, e->d_atom_q, e->d_kpack, e->d_kslot, d_reps, stride,
+                          e->d_atom_res, e->d_atom_mol, e->d_atom_q, e->d_kpack, e->d_kslot, d_reps, phase_tab_entries(e),
                           (const double2 *)d_tab, to_replica ? 1 : 0, S_all);
     rc = prof_end(e, e->lanes[0], MGPU_KERNEL_SFACTOR, a, b);
     if (rc) return rc;
@@ -55,10 +57,44 @@ static int launch_sfactor_replicas(mgpu_engine *e, const int *d_reps, int c, dou
     return MGPU_OK;
 }
 
-struct Pass { int first, c; long long n_pair, n_in; };
+// ---- the accumulators of rdf and density: segment s of the block, and the three calls on a checked list of entries.  `host[s]`
+// holds the listed entries' words of segment s, entry after entry.
+static unsigned long long *accum_seg(const Accum &a, const DevBuf &d_acc, int s) { return (unsigned long long *)d_acc.p + a.at[s]; }
+
+// whole = true: one copy of the whole block and a scatter on the host (a farm checkpoint reads every replica: a few small
+// copies per entry would be slower); false: one copy per entry and segment (a block may be large, and few entries wanted)
+static int accum_read(const Accum &a, const DevBuf &d_acc, int n, const int *ids, unsigned long long *const host[3], bool whole) {
+    std::vector<unsigned long long> all;
+    if (whole) {
+        all.resize(a.words);
+        HIP_TRY(hipMemcpy(all.data(), d_acc.p, a.bytes(), hipMemcpyDeviceToHost));
+    }
+    for (int i = 0; i < n; ++i)
+        for (int s = 0; s < a.n_seg; ++s) {
+            const size_t at = a.word(s, (size_t)ids[i]), bytes = a.per[s] * sizeof(unsigned long long);
+            if (whole) std::memcpy(host[s] + (size_t)i * a.per[s], all.data() + at, bytes);
+            else HIP_TRY(hipMemcpy(host[s] + (size_t)i * a.per[s], (const unsigned long long *)d_acc.p + at, bytes, hipMemcpyDeviceToHost));
+        }
+    return MGPU_OK;
+}
+
+static int accum_load(const Accum &a, const DevBuf &d_acc, int n, const int *ids, const unsigned long long *const host[3]) {
+    for (int i = 0; i < n; ++i)
+        for (int s = 0; s < a.n_seg; ++s)
+            HIP_TRY(hipMemcpy((unsigned long long *)d_acc.p + a.word(s, (size_t)ids[i]), host[s] + (size_t)i * a.per[s],
+                              a.per[s] * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    return MGPU_OK;
+}
+
+static int accum_reset(const Accum &a, const DevBuf &d_acc, int n, const int *ids) {
+    for (int i = 0; i < n; ++i)
+        for (int s = 0; s < a.n_seg; ++s)
+            HIP_TRY(hipMemset((unsigned long long *)d_acc.p + a.word(s, (size_t)ids[i]), 0, a.per[s] * sizeof(unsigned long long)));
+    return MGPU_OK;
+}
 
 // ---- radial distribution functions
-constexpr int kRdfPassMax = 32768;                         // replicas per pass (the grid's y extent)
+static_assert(kRdfNone == (int)kNibbleNone && kDensityNone == (int)kNibbleNone, "the kernels read the tables nibble_set packs");
 
 // half the smallest perpendicular width of the cell: the largest r_max a histogram may have.  Orthorhombic: min L / 2;
 // triclinic: width i = V / |a_j x a_k| from box%matrix (its columns are the cell vectors).  Plain rounded operations in a
@@ -93,54 +129,26 @@ static std::string rdf_number(double v) {
     return buf;
 }
 
-// the three accumulator arrays inside d_acc
-struct RdfBlocks { unsigned long long *hist, *eligible, *samples; size_t per_hist, bytes; };
-static RdfBlocks rdf_blocks(const mgpu_engine *e) {
-    const size_t R = (size_t)e->n_replicas, per = (size_t)e->rdf.n_pairs * e->rdf.n_bins;
-    RdfBlocks b;
-    b.hist = (unsigned long long *)e->rdf.d_acc.p;
-    b.eligible = b.hist + R * per;
-    b.samples = b.eligible + R * e->rdf.n_pairs;
-    b.per_hist = per;
-    b.bytes = (R * per + R * e->rdf.n_pairs + R) * sizeof(unsigned long long);
-    return b;
-}
-
-static int rdf_ready(const mgpu_engine *e, const char *who) {
+// the replica list of an mgpu_rdf_* call, then "configured": in this order
+static int rdf_ready(const mgpu_engine *e, int n, const int *replicas, const char *who) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    const int rc = check_index_list(n, replicas, e->n_replicas, "replica", who);
+    if (rc) return rc;
     if (e->rdf.n_pairs == 0) return set_error(MGPU_ERR_STATE, std::string(who) + ": no histogram is configured (mgpu_rdf_configure)");
     return MGPU_OK;
 }
 
 // ---- density maps
-constexpr int kDensityPassMax = 32768;                     // replicas per pass (the grid's y extent)
-
-// the two accumulator arrays inside d_acc
-struct DensityBlocks { unsigned long long *hist, *samples; size_t per_group; };
-static DensityBlocks density_blocks(const mgpu_engine *e) {
-    const auto &d = e->density;
-    DensityBlocks b;
-    b.per_group = (size_t)d.n_channels * d.n[0] * d.n[1] * d.n[2];
-    b.hist = (unsigned long long *)d.d_acc.p;
-    b.samples = b.hist + (size_t)d.n_groups * b.per_group;
-    return b;
-}
-
 static int density_ready(const mgpu_engine *e, const char *who) {
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
     if (e->density.n_channels == 0) return set_error(MGPU_ERR_STATE, std::string(who) + ": no density map is configured (mgpu_density_configure)");
     return MGPU_OK;
 }
 
-static int check_group_list(const mgpu_engine *e, int n, const int *groups, const char *who) {
-    if (n < 0 || (n > 0 && !groups)) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": bad group list");
-    std::vector<char> seen((size_t)e->density.n_groups, 0);
-    for (int i = 0; i < n; ++i) {
-        const int g = groups[i];
-        if (g < 0 || g >= e->density.n_groups) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": group out of range");
-        if (seen[g]) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": group " + std::to_string(g) + " listed twice");
-        seen[g] = 1;
-    }
-    return MGPU_OK;
+// "configured", then the group list of an mgpu_density_read / _load / _reset call: in this order
+static int density_groups_ready(const mgpu_engine *e, int n, const int *groups, const char *who) {
+    const int rc = density_ready(e, who);
+    return rc ? rc : check_index_list(n, groups, e->density.n_groups, "group", who);
 }
 
 }  // namespace mgpu
@@ -148,7 +156,8 @@ static int check_group_list(const mgpu_engine *e, int n, const int *groups, cons
 extern "C" {
 
 int mgpu_system_energy_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, double *out, double *a_deviation) {
-    int rc = check_replica_list(e, n, replicas, "system_energy_replicas");
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc = check_index_list(n, replicas, e->n_replicas, "replica", "system_energy_replicas");
     if (rc) return rc;
     if (n > 0 && !out) return set_error(MGPU_ERR_INVALID_ARG, "system_energy_replicas: null out");
     if (n == 0) return MGPU_OK;
@@ -163,10 +172,10 @@ int mgpu_system_energy_replicas(mgpu_engine *e, int n, const int *replicas, int 
         if (e->is_active[t] == 1) active_mask |= 1u << t;
         self.v[t] = self_energy_host(e, t);
     }
-    auto counts = [&](int r, long long &n_pair, long long &n_in) {
+    auto counts = [&](int i, long long &n_pair, long long &n_in) {
         n_pair = 0; n_in = 0;
         for (int t = 0; t < tp.n_res; ++t) {
-            const int nm = e->h_nmol[r * tp.n_res + t];
+            const int nm = e->h_nmol[replicas[i] * tp.n_res + t];
             n_pair += nm;
             if (e->is_active[t] == 1) n_in += nm;
         }
@@ -177,23 +186,11 @@ int mgpu_system_energy_replicas(mgpu_engine *e, int n, const int *replicas, int 
                (size_t)n_pair * nsplit * sizeof(double2) + (size_t)(2 * n_pair + n_in + 1) * sizeof(double) + sizeof(RecipItem) +
                sizeof(EnergyRep) + sizeof(int);
     };
-    // the passes: replicas in the caller's order, as many as `chunk` and the budget allow, never fewer than one
-    const int most = chunk > 0 ? std::min(chunk, kReplicasPassMax) : kReplicasPassMax;
     std::vector<Pass> passes;
+    if (!plan_passes(n, counts, bytes_of, chunk, nsplit, passes))
+        return set_error(MGPU_ERR_CAPACITY, "system_energy_replicas: one replica's pair sweep exceeds 2^31 work units");
     size_t max_tab = 0, max_items = 0, max_rec = 0, max_res = 0;
-    for (int i = 0; i < n;) {
-        Pass p{i, 0, 0, 0};
-        size_t bytes = 0;
-        while (i < n && p.c < most) {
-            long long np, ni;
-            counts(replicas[i], np, ni);
-            const size_t b = bytes_of(np, ni);
-            if (p.c > 0 && (bytes + b > kReplicasPassBytes || (p.n_pair + np) * nsplit > kReplicasPassItems)) break;
-            bytes += b; p.n_pair += np; p.n_in += ni; p.c += 1; ++i;
-        }
-        if (p.n_pair * nsplit >= ((long long)1 << 31) - kPairWaves)
-            return set_error(MGPU_ERR_CAPACITY, "system_energy_replicas: one replica's pair sweep exceeds 2^31 work units");
-        passes.push_back(p);
+    for (const Pass &p : passes) {
         max_tab = std::max(max_tab, (size_t)p.c * (tab_n + e->n_slots) * sizeof(double2));
         max_items = std::max(max_items, (size_t)(p.n_pair + p.n_in) * sizeof(PairItem));
         max_rec = std::max(max_rec, (size_t)p.c * (sizeof(RecipItem) + sizeof(EnergyRep) + sizeof(int)));
@@ -272,7 +269,8 @@ int mgpu_system_energy_replicas(mgpu_engine *e, int n, const int *replicas, int 
 }
 
 int mgpu_init_structure_factor_replicas(mgpu_engine *e, int n, const int *replicas, int mode) {
-    int rc = check_replica_list(e, n, replicas, "init_structure_factor_replicas");
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc = check_index_list(n, replicas, e->n_replicas, "replica", "init_structure_factor_replicas");
     if (rc) return rc;
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
@@ -304,7 +302,8 @@ int mgpu_init_structure_factor_replicas(mgpu_engine *e, int n, const int *replic
 int mgpu_energy_pairs_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, int n_sel, const int *res_a, const int *res_b,
                                double *out) {
     const char *who = "energy_pairs_replicas";
-    int rc = check_replica_list(e, n, replicas, who);
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc = check_index_list(n, replicas, e->n_replicas, "replica", who);
     if (rc) return rc;
     const Topo &tp = e->tp;
     const int n_res = tp.n_res;
@@ -348,7 +347,8 @@ int mgpu_energy_pairs_replicas(mgpu_engine *e, int n, const int *replicas, int c
         item_t[p] = a_side ? sel_a[p] : sel_b[p];
         part_t[p] = a_side ? sel_b[p] : sel_a[p];
     }
-    auto counts = [&](int r, long long &n_it, long long &n_in) {
+    auto counts = [&](int i, long long &n_it, long long &n_in) {
+        const int r = replicas[i];
         n_it = 0; n_in = 0;
         for (int p = 0; p < n_sel; ++p) {
             n_it += e->h_nmol[r * n_res + item_t[p]];
@@ -361,23 +361,11 @@ int mgpu_energy_pairs_replicas(mgpu_engine *e, int n, const int *replicas, int c
                (size_t)n_it * nsplit * sizeof(double2) + (size_t)(2 * n_it + n_in + n_sel) * sizeof(double) +
                (size_t)n_sel * sizeof(EpRec) + sizeof(int);
     };
-    // the passes: replicas in the caller's order, as many as `chunk` and the budget allow, never fewer than one
-    const int most = chunk > 0 ? std::min(chunk, kReplicasPassMax) : kReplicasPassMax;
     std::vector<Pass> passes;
+    if (!plan_passes(n, counts, bytes_of, chunk, nsplit, passes))
+        return set_error(MGPU_ERR_CAPACITY, std::string(who) + ": one replica's sweep exceeds 2^31 work units");
     size_t max_tab = 0, max_items = 0, max_rec = 0, max_res = 0, max_part = 0;
-    for (int i = 0; i < n;) {
-        Pass p{i, 0, 0, 0};
-        size_t bytes = 0;
-        while (i < n && p.c < most) {
-            long long ni, nn;
-            counts(replicas[i], ni, nn);
-            const size_t b = bytes_of(ni, nn);
-            if (p.c > 0 && (bytes + b > kReplicasPassBytes || (p.n_pair + ni) * nsplit > kReplicasPassItems)) break;
-            bytes += b; p.n_pair += ni; p.n_in += nn; p.c += 1; ++i;
-        }
-        if (p.n_pair * nsplit >= ((long long)1 << 31) - kPairWaves)
-            return set_error(MGPU_ERR_CAPACITY, std::string(who) + ": one replica's sweep exceeds 2^31 work units");
-        passes.push_back(p);
+    for (const Pass &p : passes) {
         max_tab = std::max(max_tab, (size_t)p.c * s_n * sizeof(double2));
         max_items = std::max(max_items, (size_t)p.n_pair * sizeof(EpItem) + (size_t)p.n_in * sizeof(PairItem));
         max_rec = std::max(max_rec, (size_t)p.c * ((size_t)n_sel * sizeof(EpRec) + sizeof(int)));
@@ -451,8 +439,7 @@ int mgpu_energy_pairs_replicas(mgpu_engine *e, int n, const int *replicas, int c
             return rc;
         double2 *d_tab = (double2 *)e->lanes[0].d_scratch.p, *d_S = d_tab + (size_t)c * tab_n;
         if (types.n > 0) {
-            hipLaunchKernelGGL(phase_table_replicas_kernel, dim3((tp.n_cap_atoms + 255) / 256, c), dim3(256), 0, e->stream, tp, e->bx,
-                               e->d_pos, e->d_nmol, e->d_atom_res, e->d_atom_mol, d_idx, tab_n, d_tab);
+            launch_phase_tables_replicas(e, d_idx, c, d_tab);
             hipLaunchKernelGGL(sfactor_types_replicas_kernel, dim3(nk, c), dim3(kBlock), 0, e->stream, tp, e->bx, (const int *)e->d_nmol,
                                (const int *)e->d_atom_mol, (const double *)e->d_atom_q, (const int *)e->d_kpack, d_idx, tab_n,
                                (const double2 *)d_tab, types, d_S);
@@ -497,11 +484,11 @@ int mgpu_rdf_configure(mgpu_engine *e, int n_bins, double r_max, int n_pairs, co
         if (a < 0 || a >= nt || b < 0 || b >= nt || a >= kMaxTypes || b >= kMaxTypes)
             return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: pair " + std::to_string(p) + ": atom type out of range [0, " +
                              std::to_string(nt - 1) + "]");
-        if (((tab.row[a] >> (4 * b)) & kRdfNone) != (unsigned)kRdfNone)
+        if (nibble_get(tab.row[a], b) != kNibbleNone)
             return set_error(MGPU_ERR_INVALID_ARG, "rdf_configure: pair " + std::to_string(p) + " (" + std::to_string(a) + ", " +
                              std::to_string(b) + ") is a duplicate");
-        tab.row[a] = (tab.row[a] & ~((unsigned long long)kRdfNone << (4 * b))) | ((unsigned long long)p << (4 * b));
-        tab.row[b] = (tab.row[b] & ~((unsigned long long)kRdfNone << (4 * a))) | ((unsigned long long)p << (4 * a));
+        tab.row[a] = nibble_set(tab.row[a], b, (unsigned)p);
+        tab.row[b] = nibble_set(tab.row[b], a, (unsigned)p);
         tab.partner[a] |= 1u << b;
         tab.partner[b] |= 1u << a;
     }
@@ -512,12 +499,12 @@ int mgpu_rdf_configure(mgpu_engine *e, int n_bins, double r_max, int n_pairs, co
     if ((rc = sync_all_lanes(e))) return rc;
     e->rdf.d_acc.release();
     e->rdf.n_pairs = 0;
-    const size_t R = (size_t)e->n_replicas;
-    const size_t bytes = (R * n_pairs * n_bins + R * n_pairs + R) * sizeof(unsigned long long);
-    if ((rc = e->rdf.d_acc.reserve(bytes))) return rc;
+    const Accum acc = accum_layout((size_t)e->n_replicas, (size_t)n_pairs * n_bins, (size_t)n_pairs, 1);   // hist | eligible | samples
+    if ((rc = e->rdf.d_acc.reserve(acc.bytes()))) return rc;
     if ((rc = e->rdf.d_tab.reserve(sizeof(RdfTable)))) return rc;
-    HIP_TRY(hipMemset(e->rdf.d_acc.p, 0, bytes));
+    HIP_TRY(hipMemset(e->rdf.d_acc.p, 0, acc.bytes()));
     HIP_TRY(hipMemcpy(e->rdf.d_tab.p, &tab, sizeof tab, hipMemcpyHostToDevice));
+    e->rdf.acc = acc;
     e->rdf.n_bins = n_bins; e->rdf.n_pairs = n_pairs; e->rdf.include_intra = include_intra;
     e->rdf.r_max = r_max; e->rdf.r_max2 = r_max * r_max; e->rdf.inv_dr = (double)n_bins / r_max;
     for (int p = 0; p < n_pairs; ++p) { e->rdf.type_a[p] = type_a[p]; e->rdf.type_b[p] = type_b[p]; }
@@ -525,18 +512,17 @@ int mgpu_rdf_configure(mgpu_engine *e, int n_bins, double r_max, int n_pairs, co
 }
 
 int mgpu_rdf_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int chunk) {
-    int rc = check_replica_list(e, n, replicas, "rdf_accumulate_replicas");
+    int rc = rdf_ready(e, n, replicas, "rdf_accumulate_replicas");
     if (rc) return rc;
-    if ((rc = rdf_ready(e, "rdf_accumulate_replicas"))) return rc;
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    const RdfBlocks acc = rdf_blocks(e);
+    const Accum &acc = e->rdf.acc;
     if ((rc = e->d_items2.reserve((size_t)n * sizeof(int)))) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_items2.p, replicas, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    const int most = chunk > 0 ? std::min(chunk, kRdfPassMax) : kRdfPassMax;
+    const int most = chunk > 0 ? std::min(chunk, kReplicasPassMax) : kReplicasPassMax;
     const int n_iblk = (e->tp.n_cap_atoms + kRdfBlock - 1) / kRdfBlock;
-    const size_t lds = acc.per_hist * sizeof(unsigned);
+    const size_t lds = acc.per[0] * sizeof(unsigned);
     for (int first = 0; first < n; first += most) {
         const int c = std::min(most, n - first);
         // j chunks per i block: few replicas -> many chunks, to give every CU some workgroups; many replicas -> one
@@ -548,7 +534,8 @@ int mgpu_rdf_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int
         with_bools([&](auto tri) {
             hipLaunchKernelGGL((rdf_hist_kernel<decltype(tri)::value>), grid, dim3(kRdfBlock), lds, e->stream, e->tp, e->bx, ra,
                                (const double *)e->d_pos, (const int *)e->d_nmol, (const int *)e->d_atom_res,
-                               (const int *)e->d_atom_mol, d_reps, (const RdfTable *)e->rdf.d_tab.p, acc.hist, acc.eligible, acc.samples);
+                               (const int *)e->d_atom_mol, d_reps, (const RdfTable *)e->rdf.d_tab.p, accum_seg(acc, e->rdf.d_acc, 0),
+                               accum_seg(acc, e->rdf.d_acc, 1), accum_seg(acc, e->rdf.d_acc, 2));
         }, e->bx.triclinic != 0);
         HIP_TRY(hipGetLastError());
     }
@@ -557,63 +544,35 @@ int mgpu_rdf_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int
 
 int mgpu_rdf_read(mgpu_engine *e, int n, const int *replicas, unsigned long long *hist, unsigned long long *eligible,
                   unsigned long long *samples) {
-    int rc = check_replica_list(e, n, replicas, "rdf_read");
+    int rc = rdf_ready(e, n, replicas, "rdf_read");
     if (rc) return rc;
-    if ((rc = rdf_ready(e, "rdf_read"))) return rc;
     if (n > 0 && (!hist || !eligible || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "rdf_read: null output");
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    const RdfBlocks acc = rdf_blocks(e);
-    std::vector<unsigned long long> all(acc.bytes / sizeof(unsigned long long));
-    HIP_TRY(hipMemcpy(all.data(), e->rdf.d_acc.p, acc.bytes, hipMemcpyDeviceToHost));
-    const size_t R = (size_t)e->n_replicas, np = (size_t)e->rdf.n_pairs;
-    const unsigned long long *h = all.data(), *el = h + R * acc.per_hist, *sm = el + R * np;
-    for (int i = 0; i < n; ++i) {
-        const size_t r = (size_t)replicas[i];
-        std::memcpy(hist + (size_t)i * acc.per_hist, h + r * acc.per_hist, acc.per_hist * sizeof(unsigned long long));
-        std::memcpy(eligible + (size_t)i * np, el + r * np, np * sizeof(unsigned long long));
-        samples[i] = sm[r];
-    }
-    return MGPU_OK;
+    unsigned long long *const host[3] = {hist, eligible, samples};
+    return accum_read(e->rdf.acc, e->rdf.d_acc, n, replicas, host, true);
 }
 
 int mgpu_rdf_load(mgpu_engine *e, int n, const int *replicas, const unsigned long long *hist, const unsigned long long *eligible,
                   const unsigned long long *samples) {
-    int rc = check_replica_list(e, n, replicas, "rdf_load");
+    int rc = rdf_ready(e, n, replicas, "rdf_load");
     if (rc) return rc;
-    if ((rc = rdf_ready(e, "rdf_load"))) return rc;
     if (n > 0 && (!hist || !eligible || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "rdf_load: null input");
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    const RdfBlocks acc = rdf_blocks(e);
-    const size_t np = (size_t)e->rdf.n_pairs;
-    for (int i = 0; i < n; ++i) {
-        const size_t r = (size_t)replicas[i];
-        HIP_TRY(hipMemcpy(acc.hist + r * acc.per_hist, hist + (size_t)i * acc.per_hist, acc.per_hist * sizeof(unsigned long long), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(acc.eligible + r * np, eligible + (size_t)i * np, np * sizeof(unsigned long long), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(acc.samples + r, samples + i, sizeof(unsigned long long), hipMemcpyHostToDevice));
-    }
-    return MGPU_OK;
+    const unsigned long long *const host[3] = {hist, eligible, samples};
+    return accum_load(e->rdf.acc, e->rdf.d_acc, n, replicas, host);
 }
 
 int mgpu_rdf_reset(mgpu_engine *e, int n, const int *replicas) {
-    int rc = check_replica_list(e, n, replicas, "rdf_reset");
+    int rc = rdf_ready(e, n, replicas, "rdf_reset");
     if (rc) return rc;
-    if ((rc = rdf_ready(e, "rdf_reset"))) return rc;
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    const RdfBlocks acc = rdf_blocks(e);
-    const size_t np = (size_t)e->rdf.n_pairs;
-    for (int i = 0; i < n; ++i) {
-        const size_t r = (size_t)replicas[i];
-        HIP_TRY(hipMemset(acc.hist + r * acc.per_hist, 0, acc.per_hist * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(acc.eligible + r * np, 0, np * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(acc.samples + r, 0, sizeof(unsigned long long)));
-    }
-    return MGPU_OK;
+    return accum_reset(e->rdf.acc, e->rdf.d_acc, n, replicas);
 }
 
 int mgpu_density_configure(mgpu_engine *e, const int *n, int n_channels, const int *types, int n_groups, const int *group_of) {
@@ -650,10 +609,10 @@ int mgpu_density_configure(mgpu_engine *e, const int *n, int n_channels, const i
         if (t < 0 || t >= nt || t >= kMaxTypes)
             return set_error(MGPU_ERR_INVALID_ARG, "density_configure: channel " + std::to_string(c) + ": atom type out of range [0, " +
                              std::to_string(nt - 1) + "]");
-        if (((table >> (4 * t)) & kDensityNone) != (unsigned)kDensityNone)
+        if (nibble_get(table, t) != kNibbleNone)
             return set_error(MGPU_ERR_INVALID_ARG, "density_configure: channel " + std::to_string(c) + " (atom type " + std::to_string(t) +
                              ") is a duplicate");
-        table = (table & ~((unsigned long long)kDensityNone << (4 * t))) | ((unsigned long long)c << (4 * t));
+        table = nibble_set(table, t, (unsigned)c);
     }
     const int R = e->n_replicas;
     if (n_groups < 1 || n_groups > R)
@@ -665,7 +624,8 @@ int mgpu_density_configure(mgpu_engine *e, const int *n, int n_channels, const i
             return set_error(MGPU_ERR_INVALID_ARG, "density_configure: replica " + std::to_string(r) + ": group " + std::to_string(group_of[r]) +
                              " is outside [0, " + std::to_string(n_groups - 1) + "] and not -1");
     // (2^24 voxels x 8 channels x 2^31 groups x 8 bytes stays below 2^64)
-    const unsigned long long bytes = ((unsigned long long)n_groups * n_channels * voxels + n_groups) * sizeof(unsigned long long);
+    const Accum acc = accum_layout((size_t)n_groups, (size_t)n_channels * voxels, 1);       // hist | samples
+    const unsigned long long bytes = acc.bytes();
     if (bytes > MGPU_DENSITY_MAX_BYTES)
         return set_error(MGPU_ERR_INVALID_ARG, "density_configure: the accumulators would take " + std::to_string(bytes) +
                          " bytes, the limit is " + std::to_string(MGPU_DENSITY_MAX_BYTES));
@@ -681,22 +641,23 @@ int mgpu_density_configure(mgpu_engine *e, const int *n, int n_channels, const i
     for (int k = 0; k < 3; ++k) d.n[k] = n[k];
     for (int c = 0; c < n_channels; ++c) d.types[c] = types[c];
     d.table = table;
+    d.acc = acc;
     d.n_channels = n_channels; d.n_groups = n_groups;
     return MGPU_OK;
 }
 
 int mgpu_density_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int chunk) {
-    int rc = check_replica_list(e, n, replicas, "density_accumulate_replicas");
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc = check_index_list(n, replicas, e->n_replicas, "replica", "density_accumulate_replicas");
     if (rc) return rc;
     if ((rc = density_ready(e, "density_accumulate_replicas"))) return rc;
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
     const auto &d = e->density;
-    const DensityBlocks acc = density_blocks(e);
     if ((rc = e->d_items2.reserve((size_t)n * sizeof(int)))) return rc;
     HIP_TRY(hipMemcpyAsync(e->d_items2.p, replicas, (size_t)n * sizeof(int), hipMemcpyHostToDevice, e->stream));
-    const int most = chunk > 0 ? std::min(chunk, kDensityPassMax) : kDensityPassMax;
+    const int most = chunk > 0 ? std::min(chunk, kReplicasPassMax) : kReplicasPassMax;
     const int n_blk = (e->tp.n_cap_atoms + kDensityBlock - 1) / kDensityBlock;
     const DensityArgs da{{d.n[0], d.n[1], d.n[2]}, d.n_channels, d.table};
     for (int first = 0; first < n; first += most) {
@@ -705,7 +666,8 @@ int mgpu_density_accumulate_replicas(mgpu_engine *e, int n, const int *replicas,
         with_bools([&](auto tri) {
             hipLaunchKernelGGL((density_map_kernel<decltype(tri)::value>), dim3((unsigned)n_blk, (unsigned)c), dim3(kDensityBlock), 0, e->stream,
                                e->tp, e->bx, da, (const double *)e->d_pos, (const int *)e->d_nmol, (const int *)e->d_atom_res,
-                               (const int *)e->d_atom_mol, d_reps, (const int *)d.d_group.p, acc.hist, acc.samples);
+                               (const int *)e->d_atom_mol, d_reps, (const int *)d.d_group.p, accum_seg(d.acc, d.d_acc, 0),
+                               accum_seg(d.acc, d.d_acc, 1));
         }, e->bx.triclinic != 0);
         HIP_TRY(hipGetLastError());
     }
@@ -713,53 +675,34 @@ int mgpu_density_accumulate_replicas(mgpu_engine *e, int n, const int *replicas,
 }
 
 int mgpu_density_read(mgpu_engine *e, int n, const int *groups, unsigned long long *hist, unsigned long long *samples) {
-    int rc = density_ready(e, "density_read");
+    int rc = density_groups_ready(e, n, groups, "density_read");
     if (rc) return rc;
-    if ((rc = check_group_list(e, n, groups, "density_read"))) return rc;
     if (n > 0 && (!hist || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "density_read: null output");
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    const DensityBlocks acc = density_blocks(e);
-    for (int i = 0; i < n; ++i) {
-        const size_t g = (size_t)groups[i];
-        HIP_TRY(hipMemcpy(hist + (size_t)i * acc.per_group, acc.hist + g * acc.per_group, acc.per_group * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(samples + i, acc.samples + g, sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    }
-    return MGPU_OK;
+    unsigned long long *const host[3] = {hist, samples, nullptr};
+    return accum_read(e->density.acc, e->density.d_acc, n, groups, host, false);       // (a block may be 2 GiB: not as a whole)
 }
 
 int mgpu_density_load(mgpu_engine *e, int n, const int *groups, const unsigned long long *hist, const unsigned long long *samples) {
-    int rc = density_ready(e, "density_load");
+    int rc = density_groups_ready(e, n, groups, "density_load");
     if (rc) return rc;
-    if ((rc = check_group_list(e, n, groups, "density_load"))) return rc;
     if (n > 0 && (!hist || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "density_load: null input");
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    const DensityBlocks acc = density_blocks(e);
-    for (int i = 0; i < n; ++i) {
-        const size_t g = (size_t)groups[i];
-        HIP_TRY(hipMemcpy(acc.hist + g * acc.per_group, hist + (size_t)i * acc.per_group, acc.per_group * sizeof(unsigned long long), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(acc.samples + g, samples + i, sizeof(unsigned long long), hipMemcpyHostToDevice));
-    }
-    return MGPU_OK;
+    const unsigned long long *const host[3] = {hist, samples, nullptr};
+    return accum_load(e->density.acc, e->density.d_acc, n, groups, host);
 }
 
 int mgpu_density_reset(mgpu_engine *e, int n, const int *groups) {
-    int rc = density_ready(e, "density_reset");
+    int rc = density_groups_ready(e, n, groups, "density_reset");
     if (rc) return rc;
-    if ((rc = check_group_list(e, n, groups, "density_reset"))) return rc;
     if (n == 0) return MGPU_OK;
     if ((rc = use_device(e))) return rc;
     if ((rc = sync_all_lanes(e))) return rc;
-    const DensityBlocks acc = density_blocks(e);
-    for (int i = 0; i < n; ++i) {
-        const size_t g = (size_t)groups[i];
-        HIP_TRY(hipMemset(acc.hist + g * acc.per_group, 0, acc.per_group * sizeof(unsigned long long)));
-        HIP_TRY(hipMemset(acc.samples + g, 0, sizeof(unsigned long long)));
-    }
-    return MGPU_OK;
+    return accum_reset(e->density.acc, e->density.d_acc, n, groups);
 }
 
 }  // extern "C"

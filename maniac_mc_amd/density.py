@@ -8,6 +8,8 @@ box%matrix).
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 MAX_CHANNELS = 8
@@ -112,6 +114,22 @@ def check_spec(spec, topo):
     if out["every"] < 1:
         raise ValueError("density: every must be at least 1")
     return out
+
+
+def from_args(ap, a):
+    """--density, --density-types, --density-per-replica of the parsed command line `a` -> run_replicas' ``density`` dict,
+    None without --density; ap.error for a sub-option without --density or an argument that does not parse."""
+    if a.density is None and (a.density_types is not None or a.density_per_replica):
+        ap.error("--density-types and --density-per-replica need --density N0,N1,N2[,EVERY]")
+    if a.density is None:
+        return None
+    try:
+        spec = parse_spec(a.density)
+        spec["types"] = parse_types(a.density_types) if a.density_types is not None else None
+        spec["per_replica"] = bool(a.density_per_replica)
+    except ValueError as err:
+        ap.error(str(err))
+    return spec
 
 
 def identity_array(spec):
@@ -251,3 +269,50 @@ def read_cube(path):
         raise ValueError(f"{path}: {vals.size} values for a grid of {n}")
     return dict(comments=comments, origin=origin, vectors=np.array(vec), n=np.array(n), atoms=atoms,
                 rho=vals.reshape(n[0], n[1], n[2]).transpose(2, 1, 0))
+
+
+class Sampler:
+    """run_replicas' ``density`` option as one of its farm analyses ("adding a farm analysis")"""
+    name = "density"
+
+    def __init__(self, option, ctx):
+        self.ctx = ctx
+        self.spec = check_spec(option, ctx.topo)
+        self.every = self.spec["every"]
+
+    def check_size(self):
+        """Once ctx holds the groups: the map every replica adds into, and the accumulators' size against MAX_BYTES"""
+        ctx, per_replica = self.ctx, self.spec["per_replica"]
+        self.group_of = np.arange(ctx.R) if per_replica else np.asarray(ctx.group)
+        self.n_groups = ctx.R if per_replica else (len(ctx.fugacities) if ctx.fugacities is not None else 1)
+        check_size(self.spec["grid"], len(self.spec["types"]), self.n_groups)
+
+    def identity_array(self):
+        return identity_array(self.spec)
+
+    def configure(self, farm, root, resumed):
+        farm.eng.density_configure(self.spec["grid"], self.spec["types"], self.group_of, self.n_groups)
+
+    def sample(self, farm, block):
+        farm.density_sample()
+
+    def state(self, farm):
+        return dict(zip(("density_hist", "density_samples"), farm.eng.density_read()))
+
+    def load(self, farm, extra):
+        farm.eng.density_load(extra["density_hist"], extra["density_samples"])
+
+    def finish(self, farm, root, inp, dat):
+        s, topo, system = self.spec, self.ctx.topo, self.ctx.system
+        hist, samples = farm.eng.density_read()
+        write_counts(os.path.join(root, "density_counts.npz"), hist, samples, self.group_of, self.ctx.group, s["types"], s["grid"],
+                     s["every"], s["per_replica"])
+        write_profiles(os.path.join(root, "density_profiles.dat"), hist, samples, s["types"], system.box_matrix)
+        rho = number_density(hist, samples, system.box_matrix)
+        atoms = [(atomic_number(dat["masses"][int(topo.atom_types[t, a]) - 1]), *xyz)
+                 for t in range(topo.n_res) if topo.is_active[t] != 1
+                 for mol in system.all_sites(t) for a, xyz in enumerate(mol.tolist())]
+        for g in range(hist.shape[0]):
+            for c, ty in enumerate(s["types"]):
+                write_cube(os.path.join(root, cube_name(g, ty)), rho[g, c], system.box_matrix, system.bounds_lo, atoms,
+                           title=f"map {g} atom type {ty + 1} samples {int(samples[g])}")

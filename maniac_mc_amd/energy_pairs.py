@@ -12,6 +12,8 @@ components non_coulomb, coulomb, recip_coulomb, ewald_self, intra_coulomb in K. 
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 from .system import KB_KCALMOL
@@ -89,6 +91,38 @@ def default_pairs(topo):
 
 def pair_names(pairs, names):
     return [f"{names[a]}:{names[b]}" for a, b in pairs]
+
+
+def check_spec(spec, topo):
+    """run_replicas' ``energy_pairs`` dict -> dict(every, pairs), checked; ValueError naming what is wrong."""
+    unknown = set(spec) - {"every", "pairs"}
+    if unknown:
+        raise ValueError(f"energy_pairs: takes every and pairs ({sorted(unknown)} unknown)")
+    pairs = spec.get("pairs")
+    out = dict(every=int(spec.get("every", 1)), pairs=check_pairs(default_pairs(topo) if pairs is None else pairs, topo.n_res))
+    if out["every"] < 1:
+        raise ValueError("energy_pairs: every must be at least 1")
+    return out
+
+
+def from_args(ap, a):
+    """--energy-pairs, --energy-pairs-select of the parsed command line `a` -> run_replicas' ``energy_pairs`` dict, None
+    without --energy-pairs; ap.error for the sub-option without it or an argument that does not parse.  The names of
+    --energy-pairs-select are the input file's (a missing input file is reported by the caller)."""
+    if a.energy_pairs is None and a.energy_pairs_select is not None:
+        ap.error("--energy-pairs-select needs --energy-pairs [EVERY]")
+    if a.energy_pairs is None:
+        return None
+    try:
+        spec = parse_spec(a.energy_pairs)
+        spec["pairs"] = None
+        if a.energy_pairs_select is not None and os.path.isfile(a.maniac):
+            from . import io_maniac
+            names = [r.name for r in io_maniac.read_maniac_input(a.maniac).residues]
+            spec["pairs"] = parse_select(a.energy_pairs_select, names)
+    except ValueError as err:
+        ap.error(str(err))
+    return spec
 
 
 def identity_array(spec):
@@ -194,3 +228,43 @@ def read_pooled_file(path):
             nums = np.asarray([float(x) for x in r[5:]], dtype=np.float64).reshape(len(COLUMNS), 2)
             out.append((int(r[0]), float(r[1]), int(r[2]), int(r[3]), r[4], nums[:, 0].copy(), nums[:, 1].copy()))
     return out
+
+
+class Sampler:
+    """run_replicas' ``energy_pairs`` option as one of its farm analyses ("adding a farm analysis").  It keeps no
+    state on the device: every sample goes to the replicas' files at once."""
+    name = "energy_pairs"
+
+    def __init__(self, option, ctx):
+        self.ctx = ctx
+        self.spec = check_spec(option, ctx.topo)
+        self.every = self.spec["every"]
+
+    def check_size(self):
+        """(nothing of it depends on the groups)"""
+
+    def identity_array(self):
+        return identity_array(self.spec)
+
+    def configure(self, farm, root, resumed):
+        self.paths = [os.path.join(root, f"replica_{r:04d}", FILE_NAME) for r in range(self.ctx.R)]
+        if not resumed:
+            labels = pair_names(self.spec["pairs"], self.ctx.residue_names)
+            for p in self.paths:
+                start_replica_file(p, labels)
+
+    def sample(self, farm, block):
+        values = farm.energy_pairs_sample(self.spec["pairs"])
+        for r, p in enumerate(self.paths):
+            append_replica_file(p, block, values[r])
+
+    def state(self, farm):
+        return {}
+
+    def load(self, farm, extra):
+        pass
+
+    def finish(self, farm, root, inp, dat):
+        active = [t for t in range(self.ctx.topo.n_res) if self.ctx.topo.is_active[t] == 1]
+        f_atm = self.ctx.fugacities if self.ctx.fugacities is not None else [inp.residues[active[0]].fugacity_atm if active else 0.0]
+        write_pooled_file(os.path.join(root, FILE_NAME), self.paths, self.ctx.group, f_atm)

@@ -540,36 +540,35 @@ class Engine:
         r = self._replica_list(replicas)
         check(self.L.mgpu_rdf_accumulate_replicas(self.h, C.c_int(r.shape[0]), _i(r), C.c_int(0 if chunk is None else int(chunk))))
 
+    def _accum_call(self, name, ids, shapes=(), arrays=None, what=""):
+        """mgpu_<name>, one of the rdf / density read, load and reset calls, on the entries `ids`.  Its uint64 buffers, one per
+        entry of `shapes` (the per-entry shape of an accumulator segment), are zeroed and returned (arrays None: a read;
+        no shapes: a reset) or are `arrays`, which must have those shapes (a load; ValueError naming `what` otherwise)."""
+        n = ids.shape[0]
+        if arrays is None:
+            bufs = [np.zeros((n,) + tuple(s), dtype=np.uint64) for s in shapes]
+        else:
+            bufs = [np.ascontiguousarray(a, dtype=np.uint64) for a in arrays]
+            if [b.shape for b in bufs] != [(n,) + tuple(s) for s in shapes]:
+                raise ValueError(f"{name}: arrays of shapes {', '.join(str(b.shape) for b in bufs)} for {n} {what}")
+        check(getattr(self.L, "mgpu_" + name)(self.h, C.c_int(n), _i(ids), *[b.ctypes.data_as(C.POINTER(C.c_ulonglong)) for b in bufs]))
+        return tuple(bufs)
+
     def rdf_read(self, replicas=None):
         """mgpu_rdf_read: (hist (n, n_pairs, n_bins), eligible (n, n_pairs), samples (n,)) of the listed replicas, uint64."""
         r = self._replica_list(replicas)
         np_, nb = self._rdf_shape()
-        n = r.shape[0]
-        hist = np.zeros((n, np_, nb), dtype=np.uint64)
-        elig = np.zeros((n, np_), dtype=np.uint64)
-        samples = np.zeros(n, dtype=np.uint64)
-        u = C.POINTER(C.c_ulonglong)
-        check(self.L.mgpu_rdf_read(self.h, C.c_int(n), _i(r), hist.ctypes.data_as(u), elig.ctypes.data_as(u), samples.ctypes.data_as(u)))
-        return hist, elig, samples
+        return self._accum_call("rdf_read", r, ((np_, nb), (np_,), ()))
 
     def rdf_load(self, hist, eligible, samples, replicas=None):
         """mgpu_rdf_load: overwrite the listed replicas' accumulators with arrays shaped as rdf_read returns them."""
         r = self._replica_list(replicas)
         np_, nb = self._rdf_shape()
-        n = r.shape[0]
-        hist = np.ascontiguousarray(hist, dtype=np.uint64)
-        elig = np.ascontiguousarray(eligible, dtype=np.uint64)
-        samples = np.ascontiguousarray(samples, dtype=np.uint64)
-        if hist.shape != (n, np_, nb) or elig.shape != (n, np_) or samples.shape != (n,):
-            raise ValueError(f"rdf_load: arrays of shapes {hist.shape}, {elig.shape}, {samples.shape} for {n} replicas of "
-                             f"{np_} pairs and {nb} bins")
-        u = C.POINTER(C.c_ulonglong)
-        check(self.L.mgpu_rdf_load(self.h, C.c_int(n), _i(r), hist.ctypes.data_as(u), elig.ctypes.data_as(u), samples.ctypes.data_as(u)))
+        self._accum_call("rdf_load", r, ((np_, nb), (np_,), ()), (hist, eligible, samples), f"replicas of {np_} pairs and {nb} bins")
 
     def rdf_reset(self, replicas=None):
         """mgpu_rdf_reset: zero the listed replicas' accumulators (None: all)."""
-        r = self._replica_list(replicas)
-        check(self.L.mgpu_rdf_reset(self.h, C.c_int(r.shape[0]), _i(r)))
+        self._accum_call("rdf_reset", self._replica_list(replicas))
 
     # ---- density maps --------------------------------------------------------------------
     def density_configure(self, grid, types, group_of=None, n_groups=None):
@@ -606,28 +605,16 @@ class Engine:
     def density_read(self, groups=None):
         """mgpu_density_read: (hist (n, n_channels, n2, n1, n0), samples (n,)) of the listed groups (None: all), uint64."""
         g, per = self._density_groups(groups)
-        n = g.shape[0]
-        hist = np.zeros((n,) + per, dtype=np.uint64)
-        samples = np.zeros(n, dtype=np.uint64)
-        u = C.POINTER(C.c_ulonglong)
-        check(self.L.mgpu_density_read(self.h, C.c_int(n), _i(g), hist.ctypes.data_as(u), samples.ctypes.data_as(u)))
-        return hist, samples
+        return self._accum_call("density_read", g, (per, ()))
 
     def density_load(self, hist, samples, groups=None):
         """mgpu_density_load: overwrite the listed groups' accumulators with arrays shaped as density_read returns them."""
         g, per = self._density_groups(groups)
-        n = g.shape[0]
-        hist = np.ascontiguousarray(hist, dtype=np.uint64)
-        samples = np.ascontiguousarray(samples, dtype=np.uint64)
-        if hist.shape != (n,) + per or samples.shape != (n,):
-            raise ValueError(f"density_load: arrays of shapes {hist.shape}, {samples.shape} for {n} groups of maps {per}")
-        u = C.POINTER(C.c_ulonglong)
-        check(self.L.mgpu_density_load(self.h, C.c_int(n), _i(g), hist.ctypes.data_as(u), samples.ctypes.data_as(u)))
+        self._accum_call("density_load", g, (per, ()), (hist, samples), f"groups of maps {per}")
 
     def density_reset(self, groups=None):
         """mgpu_density_reset: zero the listed groups' accumulators (None: all)."""
-        g, _ = self._density_groups(groups)
-        check(self.L.mgpu_density_reset(self.h, C.c_int(g.shape[0]), _i(g)))
+        self._accum_call("density_reset", self._density_groups(groups)[0])
 
     def structure_factor(self, replica=0):
         a = np.zeros((self.nk, 2))

@@ -9,6 +9,7 @@ a grand-canonical run with fluctuating N needs.
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 
@@ -74,6 +75,43 @@ def default_pairs(topo):
     types = sorted({int(topo.atom_types[t, a]) - 1 for t in range(topo.n_res) if topo.is_active[t] == 1
                     for a in range(int(topo.atoms_in_res[t]))})
     return [(a, b) for i, a in enumerate(types) for b in types[i:]]
+
+
+def check_spec(spec, topo, box_matrix):
+    """run_replicas' ``rdf`` dict -> dict(r_max, n_bins, pairs, every, include_intra), checked; ValueError naming what is wrong."""
+    unknown = set(spec) - {"r_max", "n_bins", "pairs", "every", "include_intra"}
+    if unknown or "r_max" not in spec or "n_bins" not in spec:
+        raise ValueError(f"rdf: needs r_max and n_bins, and takes pairs, every and include_intra besides ({sorted(unknown)} unknown)")
+    pairs = spec.get("pairs")
+    pairs = check_pairs(default_pairs(topo) if pairs is None else pairs, topo.n_atom_types)
+    out = dict(r_max=float(spec["r_max"]), n_bins=int(spec["n_bins"]), pairs=pairs, every=int(spec.get("every", 1)),
+               include_intra=bool(spec.get("include_intra", False)))
+    if not out["r_max"] > 0.0:
+        raise ValueError("rdf: r_max must be greater than 0")
+    if not 1 <= out["n_bins"] <= MAX_BINS:
+        raise ValueError(f"rdf: n_bins must lie in [1, {MAX_BINS}]")
+    if out["every"] < 1:
+        raise ValueError("rdf: every must be at least 1")
+    limit = half_width(box_matrix)
+    if out["r_max"] > limit:
+        raise ValueError(f"rdf: r_max {out['r_max']!r} exceeds half the smallest perpendicular width of the cell, {limit!r}")
+    return out
+
+
+def from_args(ap, a):
+    """--rdf, --rdf-pairs, --rdf-intra of the parsed command line `a` -> run_replicas' ``rdf`` dict, None without --rdf;
+    ap.error for a sub-option without --rdf or an argument that does not parse."""
+    if a.rdf is None and (a.rdf_pairs is not None or a.rdf_intra):
+        ap.error("--rdf-pairs and --rdf-intra need --rdf R_MAX,N_BINS[,EVERY]")
+    if a.rdf is None:
+        return None
+    try:
+        spec = parse_spec(a.rdf)
+        spec["pairs"] = parse_pairs(a.rdf_pairs) if a.rdf_pairs is not None else None
+        spec["include_intra"] = bool(a.rdf_intra)
+    except ValueError as err:
+        ap.error(str(err))
+    return spec
 
 
 def half_width(box_matrix):
@@ -232,3 +270,38 @@ def identity_array(spec):
     for a, b in spec["pairs"]:
         flat += [float(a), float(b)]
     return np.asarray(flat, dtype=np.float64)
+
+
+class Sampler:
+    """run_replicas' ``rdf`` option as one of its farm analyses ("adding a farm analysis")"""
+    name = "rdf"
+
+    def __init__(self, option, ctx):
+        self.ctx = ctx
+        self.spec = check_spec(option, ctx.topo, ctx.system.box_matrix)
+        self.every = self.spec["every"]
+
+    def check_size(self):
+        """(nothing of it depends on the groups)"""
+
+    def identity_array(self):
+        return identity_array(self.spec)
+
+    def configure(self, farm, root, resumed):
+        farm.eng.rdf_configure(self.spec["n_bins"], self.spec["r_max"], self.spec["pairs"], self.spec["include_intra"])
+
+    def sample(self, farm, block):
+        farm.rdf_sample()
+
+    def state(self, farm):
+        return dict(zip(("rdf_hist", "rdf_eligible", "rdf_samples"), farm.eng.rdf_read()))
+
+    def load(self, farm, extra):
+        farm.eng.rdf_load(extra["rdf_hist"], extra["rdf_eligible"], extra["rdf_samples"])
+
+    def finish(self, farm, root, inp, dat):
+        s, box = self.spec, self.ctx.system.box_matrix
+        hist, eligible, samples = farm.eng.rdf_read()
+        write_counts(os.path.join(root, "rdf_counts.npz"), hist, eligible, samples, self.ctx.group, s["pairs"], s["r_max"],
+                     s["n_bins"], s["every"], s["include_intra"])
+        write_dat(os.path.join(root, "rdf.dat"), hist, eligible, self.ctx.group, s["pairs"], volume(box), s["r_max"])

@@ -18,6 +18,7 @@ from __future__ import annotations
 import ctypes as C
 import dataclasses
 import os
+import types
 
 import numpy as np
 
@@ -166,40 +167,11 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     nb_step = inp.nb_step if nb_step is None else int(nb_step)
     if seed is None:
         seed = inp.seed if inp.has_seed and inp.seed > 0 else 1
-    rdf_spec = None
-    if rdf is not None:
-        unknown = set(rdf) - {"r_max", "n_bins", "pairs", "every", "include_intra"}
-        if unknown or "r_max" not in rdf or "n_bins" not in rdf:
-            raise ValueError(f"rdf: needs r_max and n_bins, and takes pairs, every and include_intra besides ({sorted(unknown)} unknown)")
-        pairs = rdf.get("pairs")
-        pairs = rdf_mod.check_pairs(rdf_mod.default_pairs(topo) if pairs is None else pairs, topo.n_atom_types)
-        rdf_spec = dict(r_max=float(rdf["r_max"]), n_bins=int(rdf["n_bins"]), pairs=pairs, every=int(rdf.get("every", 1)),
-                        include_intra=bool(rdf.get("include_intra", False)))
-        if not rdf_spec["r_max"] > 0.0:
-            raise ValueError("rdf: r_max must be greater than 0")
-        if not 1 <= rdf_spec["n_bins"] <= rdf_mod.MAX_BINS:
-            raise ValueError(f"rdf: n_bins must lie in [1, {rdf_mod.MAX_BINS}]")
-        if rdf_spec["every"] < 1:
-            raise ValueError("rdf: every must be at least 1")
-        limit = rdf_mod.half_width(system.box_matrix)
-        if rdf_spec["r_max"] > limit:
-            raise ValueError(f"rdf: r_max {rdf_spec['r_max']!r} exceeds half the smallest perpendicular width of the cell, {limit!r}")
-
-    den_spec = None
-    if density is not None:
-        den_spec = density_mod.check_spec(density, topo)
-
-    ep_spec = None
-    if energy_pairs is not None:
-        unknown = set(energy_pairs) - {"every", "pairs"}
-        if unknown:
-            raise ValueError(f"energy_pairs: takes every and pairs ({sorted(unknown)} unknown)")
-        pairs = energy_pairs.get("pairs")
-        ep_spec = dict(every=int(energy_pairs.get("every", 1)),
-                       pairs=epairs_mod.check_pairs(epairs_mod.default_pairs(topo) if pairs is None else pairs, n_res))
-        if ep_spec["every"] < 1:
-            raise ValueError("energy_pairs: every must be at least 1")
-
+    # the analyses asked for, in the order every later loop takes them; the groups reach ctx once they are known
+    ctx = types.SimpleNamespace(topo=topo, system=system, R=R, residue_names=[res.name for res in inp.residues],
+                                group=None, fugacities=None)
+    analyses = [mod.Sampler(option, ctx) for mod, option in ((rdf_mod, rdf), (density_mod, density), (epairs_mod, energy_pairs))
+                if option is not None]
     group = np.zeros(R, dtype=np.int64)
     if fugacities is not None:
         fugacities = [float(f) for f in fugacities]
@@ -207,10 +179,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         fug_grid = np.array([[_with_fugacity(inp, fugacities[g]).fugacity_per_A3()[t] for t in active] for g in group])
     else:
         fug_grid = np.tile(np.array([inp.fugacity_per_A3()[t] for t in active])[None, :], (R, 1)) if gcmc else None
-    if den_spec is not None:
-        den_group = np.arange(R) if den_spec["per_replica"] else np.asarray(group)
-        den_n_groups = R if den_spec["per_replica"] else (len(fugacities) if fugacities is not None else 1)
-        density_mod.check_size(den_spec["grid"], len(den_spec["types"]), den_n_groups)
+    ctx.group, ctx.fugacities = group, fugacities
+    for s in analyses:
+        s.check_size()
     gcmc_arg = dict(p_translation=inp.translation_proba, p_rotation=inp.rotation_proba, fugacity=fug_grid) if gcmc else None
     reservoir = io_maniac.reservoir_offsets(reservoir_path, inp) if reservoir_path else None
     recalibrate = bool(inp.recalibrate_moves) if recalibrate_moves is None else bool(recalibrate_moves)
@@ -218,12 +189,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     if checkpoint_every or resume:
         ident = checkpoint.identity(_lib.ABI_VERSION, nb_step, seed, mode, R, fugacities, frames, maniac, data, inc, reservoir_path)
         ident["recalibrate"] = int(recalibrate)
-        if rdf_spec is not None:
-            ident["rdf"] = rdf_mod.identity_array(rdf_spec)
-        if ep_spec is not None:
-            ident["energy_pairs"] = epairs_mod.identity_array(ep_spec)
-        if den_spec is not None:
-            ident["density"] = density_mod.identity_array(den_spec)
+        for s in sorted(analyses, key=lambda s: checkpoint.ANALYSES.index(s.name)):      # (the order checkpoint.check names them in)
+            ident[s.name] = s.identity_array()
     if resume:
         ck = checkpoint.load(outdir)
         checkpoint.check(ck, ident, nb_block)
@@ -277,19 +244,9 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         names = [inp.residues[t].name for t in active]
         stats_path = os.path.join(root, "replicas.dat")
         times = dict(run=0.0, write=0.0, snapshot=0.0)
-        if rdf_spec is not None:
-            farm.eng.rdf_configure(rdf_spec["n_bins"], rdf_spec["r_max"], rdf_spec["pairs"], rdf_spec["include_intra"])
-            times["rdf"] = 0.0
-        if den_spec is not None:
-            farm.eng.density_configure(den_spec["grid"], den_spec["types"], den_group, den_n_groups)
-            times["density"] = 0.0
-        ep_paths = [os.path.join(root, f"replica_{r:04d}", epairs_mod.FILE_NAME) for r in range(R)]
-        if ep_spec is not None:
-            times["energy_pairs"] = 0.0
-            if ck is None:
-                labels = epairs_mod.pair_names(ep_spec["pairs"], [res.name for res in inp.residues])
-                for p in ep_paths:
-                    epairs_mod.start_replica_file(p, labels)
+        for s in analyses:
+            s.configure(farm, root, ck is not None)
+            times[s.name] = 0.0
 
         def write(block, final):
             t0 = time.perf_counter()
@@ -333,13 +290,11 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
         def save_checkpoint(next_block):
             t0 = time.perf_counter()
             state = farm.checkpoint_state()
-            extra = None
-            if rdf_spec is not None:
-                extra = dict(zip(("rdf_hist", "rdf_eligible", "rdf_samples"), farm.eng.rdf_read()))
-            if den_spec is not None:
-                extra = dict(extra or {}, **dict(zip(("density_hist", "density_samples"), farm.eng.density_read())))
+            extra = {}
+            for s in analyses:
+                extra.update(s.state(farm))
             checkpoint.save(outdir, ident, next_block, nb_block, ran, state["engine"], state["driver"],
-                            checkpoint.output_sizes(outdir, R), extra=extra)
+                            checkpoint.output_sizes(outdir, R), extra=extra or None)
             times["checkpoint"] = times.get("checkpoint", 0.0) + time.perf_counter() - t0
 
         first = 1
@@ -348,12 +303,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
             checkpoint.truncate_outputs(outdir, ck["sizes"])
             checkpoint.restate_block_count(outdir, ck["sizes"], int(ck["nb_block"]), nb_block)
             farm.restore_state(dict(engine=ck["engine"], driver=ck["driver"]))
-            if rdf_spec is not None:
-                x = ck["extra"]
-                farm.eng.rdf_load(x["rdf_hist"], x["rdf_eligible"], x["rdf_samples"])
-            if den_spec is not None:
-                x = ck["extra"]
-                farm.eng.density_load(x["density_hist"], x["density_samples"])
+            for s in analyses:
+                s.load(farm, ck["extra"])
             first = int(ck["next_block"])
         else:
             write(0, False)
@@ -363,46 +314,17 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
             if recalibrate:
                 farm.recalibrate()
             times["run"] += time.perf_counter() - t0
-            if rdf_spec is not None and block % rdf_spec["every"] == 0:
-                t0 = time.perf_counter()
-                farm.rdf_sample()
-                times["rdf"] += time.perf_counter() - t0
-            if den_spec is not None and block % den_spec["every"] == 0:
-                t0 = time.perf_counter()
-                farm.density_sample()
-                times["density"] += time.perf_counter() - t0
-            if ep_spec is not None and block % ep_spec["every"] == 0:
-                t0 = time.perf_counter()
-                values = farm.energy_pairs_sample(ep_spec["pairs"])
-                for r in range(R):
-                    epairs_mod.append_replica_file(ep_paths[r], block, values[r])
-                times["energy_pairs"] += time.perf_counter() - t0
+            for s in analyses:
+                if block % s.every == 0:
+                    t0 = time.perf_counter()
+                    s.sample(farm, block)
+                    times[s.name] += time.perf_counter() - t0
             write(block, False)
             if checkpoint_every and (block % int(checkpoint_every) == 0 or block == nb_block):
                 save_checkpoint(block + 1)
         write(nb_block, True)
-        if rdf_spec is not None:
-            hist, eligible, samples = farm.eng.rdf_read()
-            rdf_mod.write_counts(os.path.join(root, "rdf_counts.npz"), hist, eligible, samples, group, rdf_spec["pairs"],
-                                 rdf_spec["r_max"], rdf_spec["n_bins"], rdf_spec["every"], rdf_spec["include_intra"])
-            rdf_mod.write_dat(os.path.join(root, "rdf.dat"), hist, eligible, group, rdf_spec["pairs"],
-                              rdf_mod.volume(system.box_matrix), rdf_spec["r_max"])
-        if den_spec is not None:
-            hist, samples = farm.eng.density_read()
-            density_mod.write_counts(os.path.join(root, "density_counts.npz"), hist, samples, den_group, group, den_spec["types"],
-                                     den_spec["grid"], den_spec["every"], den_spec["per_replica"])
-            density_mod.write_profiles(os.path.join(root, "density_profiles.dat"), hist, samples, den_spec["types"], system.box_matrix)
-            rho = density_mod.number_density(hist, samples, system.box_matrix)
-            atoms = [(density_mod.atomic_number(dat["masses"][int(topo.atom_types[t, a]) - 1]), *xyz)
-                     for t in range(n_res) if topo.is_active[t] != 1
-                     for mol in system.all_sites(t) for a, xyz in enumerate(mol.tolist())]
-            for g in range(hist.shape[0]):
-                for c, ty in enumerate(den_spec["types"]):
-                    density_mod.write_cube(os.path.join(root, density_mod.cube_name(g, ty)), rho[g, c], system.box_matrix,
-                                           system.bounds_lo, atoms, title=f"map {g} atom type {ty + 1} samples {int(samples[g])}")
-        if ep_spec is not None:
-            f_atm = fugacities if fugacities is not None else [inp.residues[active[0]].fugacity_atm if active else 0.0]
-            epairs_mod.write_pooled_file(os.path.join(root, epairs_mod.FILE_NAME), ep_paths, group, f_atm)
+        for s in analyses:
+            s.finish(farm, root, inp, dat)
         _lib.check(0)
         energies = np.array([farm.energy(r) for r in range(R)])
         res = dict(energy=energies, counts=farm.counts(), chain_counters=farm.chain_counters(), counters=farm.counters(),

@@ -379,42 +379,10 @@ def main(argv=None):
             fugacities = farm_run.parse_fugacities(a.fugacities) if a.fugacities is not None else None
         except ValueError as err:
             ap.error(str(err))
-        rdf = None
-        if a.rdf is None and (a.rdf_pairs is not None or a.rdf_intra):
-            ap.error("--rdf-pairs and --rdf-intra need --rdf R_MAX,N_BINS[,EVERY]")
-        if a.rdf is not None:
-            from . import rdf as rdf_mod
-            try:
-                rdf = rdf_mod.parse_spec(a.rdf)
-                rdf["pairs"] = rdf_mod.parse_pairs(a.rdf_pairs) if a.rdf_pairs is not None else None
-                rdf["include_intra"] = bool(a.rdf_intra)
-            except ValueError as err:
-                ap.error(str(err))
-        energy_pairs = None
-        if a.energy_pairs is None and a.energy_pairs_select is not None:
-            ap.error("--energy-pairs-select needs --energy-pairs [EVERY]")
-        if a.energy_pairs is not None:
-            from . import energy_pairs as epairs_mod
-            try:
-                energy_pairs = epairs_mod.parse_spec(a.energy_pairs)
-                energy_pairs["pairs"] = None
-                if a.energy_pairs_select is not None and os.path.isfile(a.maniac):
-                    from . import io_maniac
-                    names = [r.name for r in io_maniac.read_maniac_input(a.maniac).residues]
-                    energy_pairs["pairs"] = epairs_mod.parse_select(a.energy_pairs_select, names)
-            except ValueError as err:
-                ap.error(str(err))
-        density = None
-        if a.density is None and (a.density_types is not None or a.density_per_replica):
-            ap.error("--density-types and --density-per-replica need --density N0,N1,N2[,EVERY]")
-        if a.density is not None:
-            from . import density as density_mod
-            try:
-                density = density_mod.parse_spec(a.density)
-                density["types"] = density_mod.parse_types(a.density_types) if a.density_types is not None else None
-                density["per_replica"] = bool(a.density_per_replica)
-            except ValueError as err:
-                ap.error(str(err))
+        from . import density as density_mod, energy_pairs as epairs_mod, rdf as rdf_mod
+        rdf = rdf_mod.from_args(ap, a)
+        energy_pairs = epairs_mod.from_args(ap, a)
+        density = density_mod.from_args(ap, a)
     for path, what in ((a.maniac, "Input"), (a.data, "Data"), (a.inc, "Parameter"), (a.reservoir, "Reservoir")):
         if path is not None and not os.path.isfile(path):
             print(f"{what} file not found: {path}", file=sys.stderr)
