@@ -28,6 +28,18 @@
 ! and mgpu_structure_factor_add) -- no kernel knows about it.  Intended physics stays the default.
 ! Energies are evaluated against the engine's resident state; nothing is saved or restored on
 ! rejection (the reference's Save/RestoreSingleMolFourier have no counterpart).
+!
+! Every mode takes a step through the same three stages, each written once:
+!   DRAW      draw_step: the reference's order of random numbers and the conditions under which a draw is skipped, into a
+!             step_draws record of raw uniforms.  The chain runs push such records as they are; build_trial forms the trial
+!             geometry from one for the paths that build on the host.
+!   EVALUATE  one routine per way of asking the engine, each giving the rows o / w (w2) and a verdict: evaluate_seams,
+!             evaluate_batch (a window of steps, or one), evaluate_launch (the one-launch window), and the collect of a
+!             chain run (run_block).
+!   RESOLVE   energy_states (old / new from the rows), acceptance_prefactor + accepts (the rule), count_trial,
+!             book_accepted, reservoir_take / reservoir_give, commit_as_written, commit_step; resolve_step strings them
+!             together for a step built on the host, run_block books a collected record with the same pieces.
+! The mode variables (fused, spec_k, chain_cap, run_on, run_gc) choose the evaluator in mchain_run and take_steps only.
 !===============================================================================
 module mc_chain
 
@@ -93,7 +105,7 @@ module mc_chain
     integer, save :: run_k = 0, run_depth = 3
     logical, save :: run_on = .false.
     ! Grand-canonical chain runs (mchain_set_chain_run_gcmc; mgpu_chain_run_set_gc, mgpu_chain_run_push_gc): a block with exchange
-    ! moves runs as a chain run of by-count records (run_block_gc).  run_gc_want: the host asked; run_gc: it applies to this run;
+    ! moves runs as a chain run of by-count records (run_block, by_count).  run_gc_want: the host asked; run_gc: it applies to this run;
     ! run_fallback: steps of the last mchain_run taken through the windows because the ahead-of-outcome rule failed.
     ! Orthorhombic boxes, and triclinic ones whose engine has triclinic runs on (mgpu_chain_run_set_triclinic); never with a
     ! reservoir or as_written.
@@ -106,13 +118,26 @@ module mc_chain
     ! ... in ComputeSystemEnergy before the loop, and in the output files (UpdateFiles, PrintStatus)
     real(real64), save :: init_seconds = 0.0_real64, file_seconds = 0.0_real64
 
+    ! how an accepted step that the host decided reaches the engine (commit_step): set by the evaluator that was used
+    integer, parameter :: COMMIT_SEAM = 1, COMMIT_ROWS = 2, COMMIT_SITES = 3
+
+    ! One step as drawn (draw_step): its type, kind (MGPU_* or STEP_*) and move type, and the raw uniforms.  A chain run
+    ! pushes these as they are; build_trial forms a proposal's geometry from them.
+    type :: step_draws
+        integer :: t = 0, m = 0, kind = STEP_NOOP, mtype = 0   ! m: the slot `sel` picks from the count at the draw (creation: count + 1)
+        real(real64) :: sel = 0.0_real64                ! the molecule draw itself
+        real(real64) :: pos(3) = 0.0_real64             ! displacement, or an insertion's position
+        real(real64) :: angle = 0.0_real64, axis = 0.0_real64
+        real(real64) :: pick = 0.0_real64               ! the reservoir molecule an insertion copies
+        real(real64) :: u = 0.0_real64                  ! acceptance
+    end type step_draws
     type :: proposal
-        integer :: t = 0, m = 0, kind = STEP_NOOP, mtype = 0
+        type(step_draws) :: d
         integer :: cand = 0, cand2 = 0                  ! rows of the batch (cand2: the second row of an as-written deletion)
         integer :: pick = 0                             ! reservoir molecule an insertion copies
-        real(real64) :: com(3) = 0.0_real64, u = 0.0_real64
+        real(real64) :: com(3) = 0.0_real64
         real(real64), allocatable :: off(:, :)          ! (3, n1)
-        integer, allocatable :: rng(:)                  ! generator state after the step's draws
+        integer, allocatable :: rng(:)                  ! generator state after the step's draws (windows only)
     end type proposal
     ! the window's candidate list as handed to the engine (kept for the resident-row commit)
     integer(c_int), allocatable, save :: w_rep(:), w_t(:), w_m(:), w_kind(:), w_acc(:), w_link(:)
@@ -329,73 +354,63 @@ contains
         end if
     end function axis_rotation
 
-    ! ApplyRandomRotation: the angle is drawn before the axis
-    subroutine random_rotation(t, m, full)
-        integer, intent(in) :: t, m
-        logical, intent(in) :: full
-        real(real64) :: theta, rot(3, 3)
-        integer :: axis, n1
-        n1 = S%res(t)%n1
-        if (n1 == 1) return
-        if (full) then
-            theta = rand_uniform() * TWOPI
-        else
-            theta = (rand_uniform() - half) * S%rotation_step
-        end if
-        axis = int(rand_uniform() * three) + 1
-        rot = axis_rotation(axis, theta)
-        S%res(t)%off(:, 1:n1, m) = matmul(rot, S%res(t)%off(:, 1:n1, m))
-    end subroutine random_rotation
-
     !---------------------------------------------------------------------------
-    ! Energies of one molecule: e = non_coulomb, coulomb, recip, self, intra, total
+    ! Evaluators.  Each hands back the engine's rows of a step, e = non_coulomb, coulomb, recip, self, intra: o of the
+    ! molecule where it is, w of the trial (w2: the second row of an as-written deletion).
+    ! The seams: the reference-named calls one by one, in the order ComputeOldEnergy and ComputeNewEnergy make them; the
+    ! old state is the mirror's slot m, the new one the proposal's geometry.
     !---------------------------------------------------------------------------
-    subroutine molecule_energy(t, m, e, creation, deletion, is_new)
-        integer, intent(in) :: t, m
-        real(real64), intent(out) :: e(6)
-        logical, intent(in) :: creation, deletion, is_new
-        integer :: n1, stat, exclude
+    subroutine evaluate_seams(p, o, w, w2)
+        type(proposal), intent(in) :: p
+        real(real64), intent(out) :: o(5), w(5), w2(5)
+        integer :: t, m, n1, last, stat
+        t = p%d%t
+        m = p%d%m
         n1 = S%res(t)%n1
-        e = zero
-        if (creation .and. .not. is_new) then
-            e(IE_RECIP) = S%energy(IE_RECIP)                              ! ComputeOldEnergy, creation branch
-        else if (deletion .and. is_new) then
-            ! ComputeNewEnergy, deletion branch: only the reciprocal energy of the system without the
-            ! molecule (the engine still holds it in slot m)
-            call ComputeRecipEnergySingleMol(S%engine, t, m, S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, &
-                                             e(IE_RECIP), is_deletion=.true., stat=stat)
+        o = zero
+        w = zero
+        w2 = zero
+        select case (p%d%kind)
+        case (MGPU_MOVE)
+            call ComputeRecipEnergySingleMol(S%engine, t, m, S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, o(IE_RECIP), stat=stat)
             call note(stat)
-        else
-            if (creation) then
-                call ComputeRecipEnergySingleMol(S%engine, t, m, S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, &
-                                                 e(IE_RECIP), is_creation=.true., stat=stat)
-            else if (deletion) then
-                e(IE_RECIP) = S%energy(IE_RECIP)                          ! ComputeOldEnergy, deletion branch
-                stat = 0
-            else
-                call ComputeRecipEnergySingleMol(S%engine, t, m, S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, &
-                                                 e(IE_RECIP), stat=stat)
-            end if
+            call ComputePairInteractionEnergy_singlemol(S%engine, t, m, S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, &
+                                                        o(IE_NONC), o(IE_COUL), stat=stat)
             call note(stat)
-            exclude = m
-            if (creation) exclude = 0                                   ! the engine does not hold the molecule yet
-            call ComputePairInteractionEnergy_singlemol(S%engine, t, exclude, S%res(t)%com(:, m), &
-                                                        S%res(t)%off(:, 1:n1, m), n1, e(IE_NONC), e(IE_COUL), stat=stat)
+            call ComputeRecipEnergySingleMol(S%engine, t, m, p%com, p%off, n1, w(IE_RECIP), stat=stat)
             call note(stat)
-            if (creation .or. deletion) then
-                call ComputeEwaldSelfInteractionSingleMol(S%engine, t, e(IE_SELF), stat=stat)
-                call note(stat)
-                call ComputeIntraResidueRealCoulombEnergySingleMol(S%engine, t, m, S%res(t)%com(:, m), &
-                                                                   S%res(t)%off(:, 1:n1, m), n1, e(IE_INTRA), stat=stat)
+            call ComputePairInteractionEnergy_singlemol(S%engine, t, m, p%com, p%off, n1, w(IE_NONC), w(IE_COUL), stat=stat)
+            call note(stat)
+        case (MGPU_CREATION)
+            call ComputeRecipEnergySingleMol(S%engine, t, m, p%com, p%off, n1, w(IE_RECIP), is_creation=.true., stat=stat)
+            call note(stat)
+            ! (exclude nothing: the engine does not hold the molecule yet)
+            call ComputePairInteractionEnergy_singlemol(S%engine, t, 0, p%com, p%off, n1, w(IE_NONC), w(IE_COUL), stat=stat)
+            call note(stat)
+            call ComputeEwaldSelfInteractionSingleMol(S%engine, t, w(IE_SELF), stat=stat)
+            call note(stat)
+            call ComputeIntraResidueRealCoulombEnergySingleMol(S%engine, t, m, p%com, p%off, n1, w(IE_INTRA), stat=stat)
+            call note(stat)
+        case (MGPU_DELETION)
+            call ComputePairInteractionEnergy_singlemol(S%engine, t, m, p%com, p%off, n1, o(IE_NONC), o(IE_COUL), stat=stat)
+            call note(stat)
+            call ComputeEwaldSelfInteractionSingleMol(S%engine, t, o(IE_SELF), stat=stat)
+            call note(stat)
+            call ComputeIntraResidueRealCoulombEnergySingleMol(S%engine, t, m, p%com, p%off, n1, o(IE_INTRA), stat=stat)
+            call note(stat)
+            ! the system without the molecule (the engine still holds it in slot m)
+            call ComputeRecipEnergySingleMol(S%engine, t, m, p%com, p%off, n1, w(IE_RECIP), is_deletion=.true., stat=stat)
+            call note(stat)
+            if (as_written) then
+                ! ComputeNewEnergy as written (monte_carlo_utils.f90:301-309): after RemoveMolecule slot m holds the
+                ! former last molecule, and the reciprocal update runs with is_creation = .true. on that slot
+                last = S%res(t)%count
+                call ComputeRecipEnergySingleMol(S%engine, t, last, S%res(t)%com(:, last), S%res(t)%off(:, 1:n1, last), n1, &
+                                                 w2(IE_RECIP), is_creation=.true., stat=stat)
                 call note(stat)
             end if
-        end if
-        if (creation .or. deletion) then
-            e(IE_TOTAL) = e(IE_NONC) + e(IE_COUL) + e(IE_RECIP) + e(IE_SELF) + e(IE_INTRA)
-        else
-            e(IE_TOTAL) = e(IE_NONC) + e(IE_COUL) + e(IE_RECIP)
-        end if
-    end subroutine molecule_energy
+        end select
+    end subroutine evaluate_seams
 
     ! seams /= 0: call the reference-named seams one by one (the literal integration of INTEGRATION.md section 3)
     subroutine mchain_set_mode(seams) bind(C, name="mchain_set_mode")
@@ -508,644 +523,471 @@ contains
     end subroutine mchain_set_as_written
 
     !---------------------------------------------------------------------------
-    ! Both energy states of a move from ONE engine call (fused mode): the candidate's sites are the
-    ! molecule's current com + offsets in the host state; `old` / `new` are filled exactly as
-    ! ComputeOldEnergy / ComputeNewEnergy fill them for that move type.
+    ! DRAW.  One step's random numbers in the order MonteCarloLoop's body and the move drivers draw them: type, molecule,
+    ! move, insertion or deletion; then the displacement | the angle, then the axis (ApplyRandomRotation) | the position
+    ! with its reservoir pick or its angle and axis; the acceptance draw last.  A step with nothing to do draws nothing
+    ! further and stays STEP_NOOP: Translation, Rotation and DeleteMolecule return at once for an empty type, Rotation
+    ! for a one-site type.  A creation into a full type is STEP_ABORT (CheckMoleculeIndex aborts the reference there).
+    ! The placement of an accepted deletion in the reservoir is drawn after the outcome, by reservoir_give.
     !---------------------------------------------------------------------------
-    subroutine fused_energies(t, m, kind, old, new)
-        integer, intent(in) :: t, m, kind
-        real(real64), intent(out) :: old(6), new(6)
-        integer :: n1
-        integer(c_int) :: rep(1), tt(1), mm(1), kk(1), rc
-        real(real64) :: o(5), w(5)
-        real(real64), allocatable :: sites(:, :)
+    subroutine draw_step(d)
+        type(step_draws), intent(out) :: d
+        real(real64) :: draw
+        integer :: n, n1
+        d%t = pick_residue_type()
+        n = S%res(d%t)%count
+        n1 = S%res(d%t)%n1
+        if (n /= 0) then                                                 ! PickRandomMoleculeIndex
+            d%sel = rand_uniform()
+            d%m = min(int(d%sel * n) + 1, n)
+        end if
+        draw = rand_uniform()
+        if (draw <= S%p_translation) then
+            if (d%m /= 0) then
+                d%mtype = TYPE_TRANSLATION
+                d%kind = MGPU_MOVE
+                call random_number(d%pos)
+            end if
+        else if (draw <= S%p_rotation + S%p_translation) then
+            if (n1 /= 1 .and. d%m /= 0) then
+                d%mtype = TYPE_ROTATION
+                d%kind = MGPU_MOVE
+                d%angle = rand_uniform()
+                d%axis = rand_uniform()
+            end if
+        else if (rand_uniform() <= PROB_CREATE_DELETE) then
+            d%m = n + 1
+            d%mtype = TYPE_CREATION
+            d%kind = STEP_ABORT
+            if (d%m <= NB_MAX_MOLECULE .and. d%m <= S%res(d%t)%cap) then
+                d%kind = MGPU_CREATION
+                call random_number(d%pos)
+                if (S%has_reservoir) then
+                    call random_number(d%pick)
+                else if (n1 /= 1) then
+                    d%angle = rand_uniform()
+                    d%axis = rand_uniform()
+                end if
+            end if
+        else if (n /= 0) then
+            d%mtype = TYPE_DELETION
+            d%kind = MGPU_DELETION
+        end if
+        if (d%kind >= 0) d%u = rand_uniform()
+    end subroutine draw_step
+
+    ! The trial geometry of a drawn step, for the paths that build on the host (Translation / RandomTranslation,
+    ! ApplyRandomRotation, InsertAndOrientMolecule); the chain's state is not touched.  A deletion's "trial" is the
+    ! molecule where it is.
+    subroutine build_trial(p)
+        type(proposal), intent(inout) :: p
+        integer :: t, m, n1, axis
+        real(real64) :: trial(3), theta, rot(3, 3)
+        logical :: turn
+        t = p%d%t
+        m = p%d%m
         n1 = S%res(t)%n1
-        allocate(sites(3, n1))
-        call MoleculeSites(S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, sites)
-        rep = 0; tt = t - 1; mm = m - 1; kk = int(kind, c_int)
-        if (kind == MGPU_CREATION) mm = -1
-        rc = mgpu_gcmc_trial_submit(S%engine, 0_c_int, 1_c_int, rep, tt, mm, kk, sites, int(n1, c_int))
+        trial = p%d%pos
+        turn = .false.
+        if (p%d%mtype == TYPE_CREATION) then
+            p%com = S%box%lo + matmul(S%box%matrix, trial)
+            if (S%has_reservoir) then
+                p%pick = int(p%d%pick * S%rsv(t)%count) + 1
+                p%off = S%rsv(t)%off(:, 1:n1, p%pick)
+            else
+                p%off = S%res(t)%off(:, 1:n1, 1)
+                theta = p%d%angle * TWOPI
+                turn = n1 /= 1
+            end if
+        else
+            p%com = S%res(t)%com(:, m)
+            p%off = S%res(t)%off(:, 1:n1, m)
+            if (p%d%mtype == TYPE_TRANSLATION) then
+                trial = (trial - half) * S%translation_step
+                p%com = S%res(t)%com(:, m) + trial
+                call apply_pbc(p%com, S%box)
+            else if (p%d%mtype == TYPE_ROTATION) then
+                theta = (p%d%angle - half) * S%rotation_step
+                turn = .true.
+            end if
+        end if
+        if (turn) then
+            axis = int(p%d%axis * three) + 1
+            rot = axis_rotation(axis, theta)
+            p%off = matmul(rot, p%off)
+        end if
+    end subroutine build_trial
+
+    !---------------------------------------------------------------------------
+    ! EVALUATE (evaluate_seams above; the batched call and the one-launch window here; a chain run's collect in run_block).
+    ! add_rows appends a proposal's row(s) to the candidate list w_* and their sites; `stride` = sites per row.
+    !---------------------------------------------------------------------------
+    subroutine add_rows(p, n_cand, sites, stride)
+        type(proposal), intent(inout) :: p
+        integer, intent(inout) :: n_cand
+        integer, intent(in) :: stride
+        real(real64), intent(inout) :: sites(3, stride, *)
+        integer :: t, n1, last
+        if (.not. allocated(w_rep)) then
+            allocate(w_rep(128), w_t(128), w_m(128), w_kind(128), w_acc(128), w_link(128), w_u(128), w_pref(128))
+        end if
+        t = p%d%t
+        n1 = S%res(t)%n1
+        w_stride = stride
+        n_cand = n_cand + 1
+        p%cand = n_cand
+        w_rep(n_cand) = 0
+        w_t(n_cand) = t - 1
+        w_m(n_cand) = p%d%m - 1
+        if (p%d%kind == MGPU_CREATION) w_m(n_cand) = -1
+        w_kind(n_cand) = p%d%kind
+        w_link(n_cand) = -1
+        w_u(n_cand) = p%d%u
+        w_pref(n_cand) = acceptance_prefactor(t, p%d%mtype)
+        call MoleculeSites(p%com, p%off, n1, sites(:, 1:n1, n_cand))
+        if (p%d%kind == MGPU_DELETION .and. as_written) then
+            ! F3: the reciprocal update runs with is_creation on the molecule RemoveMolecule moves into slot m
+            last = S%res(t)%count
+            n_cand = n_cand + 1
+            p%cand2 = n_cand
+            w_link(n_cand - 1) = n_cand - 1                                 ! 0-based row of the companion
+            w_rep(n_cand) = 0
+            w_t(n_cand) = t - 1
+            w_m(n_cand) = -1
+            w_kind(n_cand) = MGPU_CREATION
+            w_link(n_cand) = -2                                             ! energy only
+            w_u(n_cand) = zero
+            w_pref(n_cand) = zero
+            call MoleculeSites(S%res(t)%com(:, last), S%res(t)%off(:, 1:n1, last), n1, sites(:, 1:n1, n_cand))
+        end if
+    end subroutine add_rows
+
+    ! the batched call: every row's energies, the rule left to the host (the rows stay resident for COMMIT_ROWS)
+    subroutine evaluate_batch(n_cand, sites, o, w)
+        integer, intent(in) :: n_cand
+        real(real64), intent(in) :: sites(3, w_stride, *)
+        real(real64), intent(out) :: o(5, *), w(5, *)
+        integer(c_int) :: rc
+        rc = mgpu_gcmc_trial_submit(S%engine, 0_c_int, int(n_cand, c_int), w_rep, w_t, w_m, w_kind, sites, int(w_stride, c_int))
         if (rc == MGPU_OK) rc = mgpu_gcmc_trial_wait(S%engine, 0_c_int, o, w)
         call note(int(rc))
+    end subroutine evaluate_batch
+
+    ! one launch per window: the engine also applies the rule to the rows in order and commits the first accepted one
+    ! (`first`); a row too close to call (`und`) is left to the host.  Both 0-based, -1 = none.
+    subroutine evaluate_launch(n_cand, sites, o, w, first, und)
+        integer, intent(in) :: n_cand
+        real(real64), intent(in) :: sites(3, w_stride, *)
+        real(real64), intent(out) :: o(5, *), w(5, *)
+        integer(c_int), intent(out) :: first, und
+        integer(c_int) :: rc
+        rc = mgpu_chain_window(S%engine, 0_c_int, int(n_cand, c_int), w_t, w_m, w_kind, w_link, sites, int(w_stride, c_int), &
+                               w_u, w_pref, S%temperature, S%energy(IE_RECIP), o, w, first, und)
+        call note(int(rc))
+    end subroutine evaluate_launch
+
+    !---------------------------------------------------------------------------
+    ! RESOLVE.  The part of Translation / Rotation / CreateMolecule / DeleteMolecule that follows the energy evaluation,
+    ! in pieces every path shares.
+    !---------------------------------------------------------------------------
+    ! ComputeOldEnergy / ComputeNewEnergy: old and new of a move type from the engine's rows
+    subroutine energy_states(mtype, o, w, w2, old, new)
+        integer, intent(in) :: mtype
+        real(real64), intent(in) :: o(5), w(5), w2(5)
+        real(real64), intent(out) :: old(6), new(6)
         old = zero
         new = zero
-        select case (kind)
-        case (MGPU_CREATION)
+        select case (mtype)
+        case (TYPE_CREATION)
             old(IE_RECIP) = S%energy(IE_RECIP)
             new(1:5) = w
-        case (MGPU_DELETION)
+        case (TYPE_DELETION)
             old(1:5) = o
             old(IE_RECIP) = S%energy(IE_RECIP)
             new(IE_RECIP) = w(IE_RECIP)
+            if (as_written) new(IE_RECIP) = w2(IE_RECIP)                  ! creation-kind energy of the swapped-in molecule (F3)
         case default
             old(1:3) = o(1:3)
             new(1:3) = w(1:3)
         end select
-        if (kind == MGPU_MOVE) then
-            old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP)
-            new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP)
-        else
+        if (mtype == TYPE_CREATION .or. mtype == TYPE_DELETION) then
             old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP) + old(IE_SELF) + old(IE_INTRA)
             new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP) + new(IE_SELF) + new(IE_INTRA)
+        else
+            old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP)
+            new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP)
         end if
-    end subroutine fused_energies
+    end subroutine energy_states
 
-    ! apply the move the lane has just evaluated (fused mode): the rows are still on the device
-    subroutine fused_commit(t, m, kind)
-        integer, intent(in) :: t, m, kind
-        integer(c_int) :: rep(1), tt(1), mm(1), kk(1), acc(1), rc
-        rep = 0; tt = t - 1; mm = m - 1; kk = int(kind, c_int); acc = 1
-        if (kind == MGPU_CREATION) mm = -1
-        rc = mgpu_commit_submit(S%engine, 0_c_int, 1_c_int, rep, tt, mm, kk, c_null_ptr, int(S%res(t)%n1, c_int), acc)
-        call note(int(rc))
-    end subroutine fused_commit
-
-    function acceptance_probability(old, new, t, move_type) result(p)
-        real(real64), intent(in) :: old(6), new(6)
-        integer, intent(in) :: t, move_type
-        real(real64) :: p, n, v, phi, temp, delta_e
-        n = real(S%res(t)%count)
-        v = S%box%volume
-        phi = S%res(t)%fugacity
-        temp = S%temperature
-        delta_e = new(IE_TOTAL) - old(IE_TOTAL)
-        select case (move_type)
-        case (TYPE_CREATION)
-            p = min(one, (phi * v / n) * exp(-delta_e / temp))
-        case (TYPE_DELETION)
-            p = min(one, ((n + one) / (phi * v)) * exp(-delta_e / temp))
-        case default
-            p = min(one, exp(-delta_e / temp))
-        end select
-    end function acceptance_probability
-
-    ! The factor in front of exp(-delta_e / T) in mc_acceptance_probability, formed exactly as acceptance_probability forms
-    ! it; n_after = the type's molecule count as the move drivers have it when they call the rule (after the insertion /
-    ! after the removal)
-    function acceptance_prefactor(t, move_type, n_after) result(f)
-        integer, intent(in) :: t, move_type, n_after
+    ! The factor in front of exp(-delta_e / T) in mc_acceptance_probability (monte_carlo_utils.f90:184-226); n = the type's
+    ! count as the move drivers have it when they call the rule: after the insertion, after the removal
+    function acceptance_prefactor(t, mtype) result(f)
+        integer, intent(in) :: t, mtype
         real(real64) :: f, n, v, phi
-        n = real(n_after)
         v = S%box%volume
         phi = S%res(t)%fugacity
-        select case (move_type)
+        select case (mtype)
         case (TYPE_CREATION)
+            n = real(S%res(t)%count + 1)
             f = (phi * v / n)
         case (TYPE_DELETION)
+            n = real(S%res(t)%count - 1)
             f = ((n + one) / (phi * v))
         case default
             f = one
         end select
     end function acceptance_prefactor
 
-    ! AcceptMove: running energies, then the engine applies the move
-    subroutine accept_move(t, m, old, new, which)
-        integer, intent(in) :: t, m, which
+    ! mc_acceptance_probability against the step's acceptance draw u
+    function accepts(t, mtype, old, new, u) result(yes)
+        integer, intent(in) :: t, mtype
+        real(real64), intent(in) :: old(6), new(6), u
+        logical :: yes
+        real(real64) :: delta_e
+        delta_e = new(IE_TOTAL) - old(IE_TOTAL)
+        yes = u <= min(one, acceptance_prefactor(t, mtype) * exp(-delta_e / S%temperature))
+    end function accepts
+
+    subroutine count_trial(mtype)
+        integer, intent(in) :: mtype
+        integer, parameter :: TRIAL_OF(4) = [C_TRIAL_C, C_TRIAL_D, C_TRIAL_T, C_TRIAL_R]
+        S%counter(TRIAL_OF(mtype)) = S%counter(TRIAL_OF(mtype)) + 1
+    end subroutine count_trial
+
+    ! AcceptMove and the Accept of CreateMolecule / DeleteMolecule: running energies, accepted counter, count, num_atoms.
+    ! A move touches only the three components it has: adding the zeros of the other two would turn the -0.0 an uncharged
+    ! system's self energy can be into +0.0, and energy.dat prints the sign.
+    subroutine book_accepted(t, mtype, old, new)
+        integer, intent(in) :: t, mtype
         real(real64), intent(in) :: old(6), new(6)
-        integer :: stat, n1
-        S%energy(IE_RECIP) = S%energy(IE_RECIP) + new(IE_RECIP) - old(IE_RECIP)
+        integer, parameter :: ACCEPTED_OF(4) = [C_C, C_D, C_T, C_R]
+        integer :: dn
+        if (mtype == TYPE_CREATION .or. mtype == TYPE_DELETION) then
+            dn = merge(1, -1, mtype == TYPE_CREATION)
+            S%energy(IE_RECIP) = new(IE_RECIP)
+            S%energy(IE_SELF) = S%energy(IE_SELF) + new(IE_SELF) - old(IE_SELF)
+            S%energy(IE_INTRA) = S%energy(IE_INTRA) + new(IE_INTRA) - old(IE_INTRA)
+            S%res(t)%count = S%res(t)%count + dn
+            S%box%num_atoms = S%box%num_atoms + dn * S%res(t)%n1
+        else
+            S%energy(IE_RECIP) = S%energy(IE_RECIP) + new(IE_RECIP) - old(IE_RECIP)
+        end if
         S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
         S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
         S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
-        S%counter(which) = S%counter(which) + 1
-        n1 = S%res(t)%n1
-        if (fused) then
-            call fused_commit(t, m, MGPU_MOVE)
-        else
-            call GpuAcceptMove(S%engine, t, m, MGPU_MOVE, S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, stat=stat)
-            call note(stat)
-        end if
-    end subroutine accept_move
+        S%counter(ACCEPTED_OF(mtype)) = S%counter(ACCEPTED_OF(mtype)) + 1
+    end subroutine book_accepted
 
-    subroutine translation(t, m)
-        integer, intent(in) :: t, m
-        real(real64) :: com_old(3), old(6), new(6), trial(3), p
-        if (m == 0) return
-        S%counter(C_TRIAL_T) = S%counter(C_TRIAL_T) + 1
-        com_old = S%res(t)%com(:, m)
-        if (.not. fused) call molecule_energy(t, m, old, .false., .false., .false.)
+    ! the inserted molecule leaves the reservoir: its slot takes the reservoir's last molecule
+    subroutine reservoir_take(t, pick)
+        integer, intent(in) :: t, pick
+        integer :: n1, last
+        n1 = S%res(t)%n1
+        last = S%rsv(t)%count
+        S%rsv(t)%com(:, pick) = S%rsv(t)%com(:, last)
+        S%rsv(t)%off(:, 1:n1, pick) = S%rsv(t)%off(:, 1:n1, last)
+        S%rsv(t)%count = S%rsv(t)%count - 1
+        S%rbox%num_atoms = S%rbox%num_atoms - n1
+    end subroutine reservoir_take
+
+    ! the reservoir receives the geometry the primary box's last slot held, at a place drawn now (after the outcome)
+    subroutine reservoir_give(t, off_last)
+        integer, intent(in) :: t
+        real(real64), intent(in) :: off_last(:, :)
+        real(real64) :: trial(3)
+        integer :: n1
+        n1 = S%res(t)%n1
         call random_number(trial)
-        trial = (trial - half) * S%translation_step
-        S%res(t)%com(:, m) = S%res(t)%com(:, m) + trial
-        call apply_pbc(S%res(t)%com(:, m), S%box)
-        if (fused) then
-            call fused_energies(t, m, MGPU_MOVE, old, new)
-        else
-            call molecule_energy(t, m, new, .false., .false., .true.)
-        end if
-        p = acceptance_probability(old, new, t, TYPE_TRANSLATION)
-        if (rand_uniform() <= p) then
-            call accept_move(t, m, old, new, C_T)
-        else
-            S%res(t)%com(:, m) = com_old
-        end if
-    end subroutine translation
-
-    subroutine rotation(t, m)
-        integer, intent(in) :: t, m
-        real(real64) :: old(6), new(6), p
-        real(real64), allocatable :: off_old(:, :)
-        if (S%res(t)%n1 == 1 .or. m == 0) return
-        S%counter(C_TRIAL_R) = S%counter(C_TRIAL_R) + 1
-        off_old = S%res(t)%off(:, :, m)
-        if (.not. fused) call molecule_energy(t, m, old, .false., .false., .false.)
-        call random_rotation(t, m, .false.)
-        if (fused) then
-            call fused_energies(t, m, MGPU_MOVE, old, new)
-        else
-            call molecule_energy(t, m, new, .false., .false., .true.)
-        end if
-        p = acceptance_probability(old, new, t, TYPE_ROTATION)
-        if (rand_uniform() <= p) then
-            call accept_move(t, m, old, new, C_R)
-        else
-            S%res(t)%off(:, :, m) = off_old
-        end if
-    end subroutine rotation
-
-    subroutine create_molecule(t, m)
-        integer, intent(in) :: t, m
-        real(real64) :: old(6), new(6), p, trial(3), u
-        integer :: n1, pick, last, stat
-        n1 = S%res(t)%n1
-        if (m > NB_MAX_MOLECULE .or. m > S%res(t)%cap) then            ! CheckMoleculeIndex aborts the reference here
-            call note(4)
-            return
-        end if
-        S%counter(C_TRIAL_C) = S%counter(C_TRIAL_C) + 1
-        if (.not. fused) call molecule_energy(t, m, old, .true., .false., .false.)
-        S%res(t)%count = S%res(t)%count + 1
-        S%box%num_atoms = S%box%num_atoms + n1
-        ! InsertAndOrientMolecule
-        call random_number(trial)
-        S%res(t)%com(:, m) = S%box%lo + matmul(S%box%matrix, trial)
-        pick = 0
-        if (S%has_reservoir) then
-            call random_number(u)
-            pick = int(u * S%rsv(t)%count) + 1
-            S%res(t)%off(:, 1:n1, m) = S%rsv(t)%off(:, 1:n1, pick)
-        else
-            S%res(t)%off(:, 1:n1, m) = S%res(t)%off(:, 1:n1, 1)
-            call random_rotation(t, m, .true.)
-        end if
-        if (fused) then
-            call fused_energies(t, m, MGPU_CREATION, old, new)
-        else
-            call molecule_energy(t, m, new, .true., .false., .true.)
-        end if
-        p = acceptance_probability(old, new, t, TYPE_CREATION)
-        if (rand_uniform() <= p) then
-            S%energy(IE_RECIP) = new(IE_RECIP)
-            S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
-            S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
-            S%energy(IE_SELF) = S%energy(IE_SELF) + new(IE_SELF) - old(IE_SELF)
-            S%energy(IE_INTRA) = S%energy(IE_INTRA) + new(IE_INTRA) - old(IE_INTRA)
-            S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
-            S%counter(C_C) = S%counter(C_C) + 1
-            if (fused) then
-                call fused_commit(t, m, MGPU_CREATION)
+        trial = trial - half
+        associate (r => S%rsv(t))
+            if (r%count + 1 <= r%cap) then
+                r%com(:, r%count + 1) = trial(1) * S%rbox%matrix(:, 1) + trial(2) * S%rbox%matrix(:, 2) + &
+                                        trial(3) * S%rbox%matrix(:, 3)
+                r%off(:, 1:n1, r%count + 1) = off_last(:, 1:n1)
+                r%count = r%count + 1
+                S%rbox%num_atoms = S%rbox%num_atoms + n1
             else
-                call GpuAcceptMove(S%engine, t, m, MGPU_CREATION, S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, stat=stat)
-                call note(stat)
+                call note(4)
             end if
-            if (S%has_reservoir) then
-                ! the copied molecule leaves the reservoir: its slot takes the reservoir's last molecule
-                last = S%rsv(t)%count
-                S%rsv(t)%com(:, pick) = S%rsv(t)%com(:, last)
-                S%rsv(t)%off(:, 1:n1, pick) = S%rsv(t)%off(:, 1:n1, last)
-                S%rsv(t)%count = S%rsv(t)%count - 1
-                S%rbox%num_atoms = S%rbox%num_atoms - n1
-            end if
-        else
-            S%box%num_atoms = S%box%num_atoms - n1
-            S%res(t)%count = S%res(t)%count - 1
-        end if
-    end subroutine create_molecule
+        end associate
+    end subroutine reservoir_give
 
-    subroutine delete_molecule(t, m)
-        integer, intent(in) :: t, m
-        real(real64) :: old(6), new(6), p, trial(3), com_old(3)
-        real(real64), allocatable :: off_old(:, :), off_last(:, :), sites_last(:, :)
-        integer :: n1, last, stat
-        if (S%res(t)%count == 0) return
+    ! An accepted deletion as written (F3), after the mirror's slot m has taken the former last molecule: coordinates and
+    ! count as RemoveMolecule leaves them; A(k) gains the swapped-in molecule's terms and keeps them
+    subroutine commit_as_written(t, m, last)
+        integer, intent(in) :: t, m, last
+        real(real64), allocatable :: sites_last(:, :)
+        integer :: n1, stat
         n1 = S%res(t)%n1
-        S%counter(C_TRIAL_D) = S%counter(C_TRIAL_D) + 1
-        if (.not. fused) call molecule_energy(t, m, old, .false., .true., .false.)
-        com_old = S%res(t)%com(:, m)
-        off_old = S%res(t)%off(:, :, m)
-        last = S%res(t)%count
-        ! the engine evaluates the removal of the molecule that sits in slot m, so the new energy is
-        ! taken before the host mirror is compacted (RemoveMolecule in the reference comes first)
-        if (fused) then
-            call fused_energies(t, m, MGPU_DELETION, old, new)
-        else
-            call molecule_energy(t, m, new, .false., .true., .true.)
-        end if
-        if (as_written) then
-            ! ComputeNewEnergy as written (monte_carlo_utils.f90:301-309): after RemoveMolecule slot m holds the
-            ! former last molecule, and the reciprocal update runs with is_creation = .true. on that slot
-            new = zero
-            call ComputeRecipEnergySingleMol(S%engine, t, last, S%res(t)%com(:, last), S%res(t)%off(:, 1:n1, last), n1, &
-                                             new(IE_RECIP), is_creation=.true., stat=stat)
-            call note(stat)
-            new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP) + new(IE_SELF) + new(IE_INTRA)
-        end if
-        off_last = S%res(t)%off(:, :, last)
-        S%res(t)%com(:, m) = S%res(t)%com(:, last)
-        S%res(t)%off(:, :, m) = S%res(t)%off(:, :, last)
-        S%res(t)%count = S%res(t)%count - 1
-        S%box%num_atoms = S%box%num_atoms - n1
-        p = acceptance_probability(old, new, t, TYPE_DELETION)
-        if (rand_uniform() <= p) then
-            S%energy(IE_RECIP) = new(IE_RECIP)
-            S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
-            S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
-            S%energy(IE_SELF) = S%energy(IE_SELF) + new(IE_SELF) - old(IE_SELF)
-            S%energy(IE_INTRA) = S%energy(IE_INTRA) + new(IE_INTRA) - old(IE_INTRA)
-            S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
-            S%counter(C_D) = S%counter(C_D) + 1
-            if (as_written) then
-                ! coordinates and count as RemoveMolecule leaves them; A(k) keeps the swapped-in molecule's terms
-                allocate(sites_last(3, n1))
-                call MoleculeSites(S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, sites_last)   ! slot m now = former last
-                stat = mgpu_replica_replace_molecule(S%engine, 0_c_int, int(t - 1, c_int), int(m - 1, c_int), int(last - 1, c_int))
-                call note(stat)
-                stat = mgpu_replica_set_num_molecules(S%engine, 0_c_int, int(t - 1, c_int), int(last - 1, c_int))
-                call note(stat)
-                stat = mgpu_structure_factor_add(S%engine, 0_c_int, int(t - 1, c_int), sites_last)
-                call note(stat)
-                deallocate(sites_last)
-            else if (fused) then
-                call fused_commit(t, m, MGPU_DELETION)
-            else
-                call GpuAcceptMove(S%engine, t, m, MGPU_DELETION, com_old, off_old(:, 1:n1), n1, stat=stat)
-                call note(stat)
-            end if
-            if (S%has_reservoir) then
-                ! the reservoir receives the geometry stored in the primary box's last slot, at a random place
-                call random_number(trial)
-                trial = trial - half
-                associate (r => S%rsv(t))
-                    if (r%count + 1 <= r%cap) then
-                        r%com(:, r%count + 1) = trial(1) * S%rbox%matrix(:, 1) + trial(2) * S%rbox%matrix(:, 2) + &
-                                                trial(3) * S%rbox%matrix(:, 3)
-                        r%off(:, 1:n1, r%count + 1) = off_last(:, 1:n1)
-                        r%count = r%count + 1
-                        S%rbox%num_atoms = S%rbox%num_atoms + n1
-                    else
-                        call note(4)
-                    end if
-                end associate
-            end if
-        else
-            S%res(t)%count = S%res(t)%count + 1
-            S%box%num_atoms = S%box%num_atoms + n1
-            S%res(t)%com(:, m) = com_old
-            S%res(t)%off(:, :, m) = off_old
-        end if
-    end subroutine delete_molecule
+        allocate(sites_last(3, n1))
+        call MoleculeSites(S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, sites_last)
+        stat = mgpu_replica_replace_molecule(S%engine, 0_c_int, int(t - 1, c_int), int(m - 1, c_int), int(last - 1, c_int))
+        call note(stat)
+        stat = mgpu_replica_set_num_molecules(S%engine, 0_c_int, int(t - 1, c_int), int(last - 1, c_int))
+        call note(stat)
+        stat = mgpu_structure_factor_add(S%engine, 0_c_int, int(t - 1, c_int), sites_last)
+        call note(stat)
+    end subroutine commit_as_written
 
-
-    !---------------------------------------------------------------------------
-    ! Speculative window.  propose_step draws one step's random numbers exactly as the loop body of MonteCarloLoop and
-    ! the move drivers draw them (type, molecule, move, [insertion / deletion], displacement | angle then axis | position
-    ! then pick / angle then axis, acceptance) and builds the trial geometry WITHOUT touching the chain's state.
-    !---------------------------------------------------------------------------
-    subroutine propose_step(p)
-        type(proposal), intent(out) :: p
-        integer :: t, m, n1, axis, nseed
-        real(real64) :: draw, trial(3), theta, rot(3, 3), u
-        t = pick_residue_type()
-        m = pick_molecule_index(S%res(t)%count)
-        draw = rand_uniform()
-        n1 = S%res(t)%n1
-        p%t = t
-        p%m = m
-        p%kind = STEP_NOOP
-        if (draw <= S%p_translation) then
-            if (m /= 0) then                                             ! Translation returns at once for an empty type
-                p%mtype = TYPE_TRANSLATION
-                p%kind = MGPU_MOVE
-                call random_number(trial)
-                trial = (trial - half) * S%translation_step
-                p%com = S%res(t)%com(:, m) + trial
-                call apply_pbc(p%com, S%box)
-                p%off = S%res(t)%off(:, 1:n1, m)
-                p%u = rand_uniform()
-            end if
-        else if (draw <= S%p_rotation + S%p_translation) then
-            if (n1 /= 1 .and. m /= 0) then
-                p%mtype = TYPE_ROTATION
-                p%kind = MGPU_MOVE
-                p%com = S%res(t)%com(:, m)
-                theta = (rand_uniform() - half) * S%rotation_step        ! ApplyRandomRotation: angle, then axis
-                axis = int(rand_uniform() * three) + 1
-                rot = axis_rotation(axis, theta)
-                p%off = matmul(rot, S%res(t)%off(:, 1:n1, m))
-                p%u = rand_uniform()
-            end if
-        else
-            if (rand_uniform() <= PROB_CREATE_DELETE) then
-                m = S%res(t)%count + 1
-                p%m = m
-                p%mtype = TYPE_CREATION
-                if (m > NB_MAX_MOLECULE .or. m > S%res(t)%cap) then     ! CheckMoleculeIndex aborts the reference here
-                    p%kind = STEP_ABORT
-                else
-                    p%kind = MGPU_CREATION
-                    call random_number(trial)
-                    p%com = S%box%lo + matmul(S%box%matrix, trial)
-                    if (S%has_reservoir) then
-                        call random_number(u)
-                        p%pick = int(u * S%rsv(t)%count) + 1
-                        p%off = S%rsv(t)%off(:, 1:n1, p%pick)
-                    else
-                        p%off = S%res(t)%off(:, 1:n1, 1)
-                        if (n1 /= 1) then
-                            theta = rand_uniform() * TWOPI
-                            axis = int(rand_uniform() * three) + 1
-                            rot = axis_rotation(axis, theta)
-                            p%off = matmul(rot, p%off)
-                        end if
-                    end if
-                    p%u = rand_uniform()
-                end if
-            else
-                if (S%res(t)%count /= 0) then                            ! DeleteMolecule returns for an empty type
-                    p%mtype = TYPE_DELETION
-                    p%kind = MGPU_DELETION
-                    p%com = S%res(t)%com(:, m)
-                    p%off = S%res(t)%off(:, 1:n1, m)
-                    p%u = rand_uniform()
-                end if
-            end if
-        end if
-        call random_seed(size=nseed)
-        allocate(p%rng(nseed))
-        call random_seed(get=p%rng)
-    end subroutine propose_step
-
-    ! Walk one evaluated step: o / w = the engine's old / new rows of its candidate (w2: the second row of an as-written
-    ! deletion).  Mirrors the part of Translation / Rotation / CreateMolecule / DeleteMolecule that follows the energy
-    ! evaluation; `restore` = the generator must be put back to this step's state before anything else is drawn.
-    ! verdict: BY_HOST -- the rule is applied here and an accepted step is committed through the engine (from the lane's
-    ! resident rows, or with explicit sites after a one-launch window); DEVICE_REJECTED / DEVICE_ACCEPTED -- the engine has
-    ! applied the rule (and the commit) already: only the chain's own bookkeeping follows.
-    subroutine resolve_step(p, o, w, w2, n_cand, restore, accepted, verdict)
+    ! An accepted step the host decided reaches the engine the way its evaluator left open: the seam (GpuAcceptMove), the
+    ! batch's rows still resident on the lane, or -- after a one-launch window, whose rows are not the lane's -- its sites
+    subroutine commit_step(p, how, n_cand)
         type(proposal), intent(in) :: p
-        real(real64), intent(in) :: o(5), w(5), w2(5)
-        integer, intent(in) :: n_cand, verdict
-        logical, intent(in) :: restore
-        logical, intent(out) :: accepted
-        real(real64) :: old(6), new(6), prob, trial(3)
-        real(real64), allocatable :: off_last(:, :), sites_last(:, :)
-        integer :: t, m, n1, last, stat
-        t = p%t
-        m = p%m
-        n1 = S%res(t)%n1
-        old = zero
-        new = zero
-        accepted = .false.
-        select case (p%mtype)
-        case (TYPE_TRANSLATION, TYPE_ROTATION)
-            if (p%mtype == TYPE_TRANSLATION) then
-                S%counter(C_TRIAL_T) = S%counter(C_TRIAL_T) + 1
-            else
-                S%counter(C_TRIAL_R) = S%counter(C_TRIAL_R) + 1
-            end if
-            old(1:3) = o(1:3)
-            new(1:3) = w(1:3)
-            old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP)
-            new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP)
-            if (decide(old, new, t, p%mtype, p%u, verdict)) then
-                accepted = .true.
-                if (restore) call random_seed(put=p%rng)
-                if (p%mtype == TYPE_TRANSLATION) then
-                    S%res(t)%com(:, m) = p%com
-                else
-                    S%res(t)%off(:, 1:n1, m) = p%off
-                end if
-                S%energy(IE_RECIP) = S%energy(IE_RECIP) + new(IE_RECIP) - old(IE_RECIP)
-                S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
-                S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
-                S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
-                if (p%mtype == TYPE_TRANSLATION) then
-                    S%counter(C_T) = S%counter(C_T) + 1
-                else
-                    S%counter(C_R) = S%counter(C_R) + 1
-                end if
-                if (verdict == BY_HOST) call window_commit(p, n_cand)
-            end if
-        case (TYPE_CREATION)
-            S%counter(C_TRIAL_C) = S%counter(C_TRIAL_C) + 1
-            old(IE_RECIP) = S%energy(IE_RECIP)
-            new(1:5) = w
-            old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP) + old(IE_SELF) + old(IE_INTRA)
-            new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP) + new(IE_SELF) + new(IE_INTRA)
-            S%res(t)%count = S%res(t)%count + 1
-            S%box%num_atoms = S%box%num_atoms + n1
-            if (decide(old, new, t, TYPE_CREATION, p%u, verdict)) then
-                accepted = .true.
-                if (restore) call random_seed(put=p%rng)
-                S%res(t)%com(:, m) = p%com
-                S%res(t)%off(:, 1:n1, m) = p%off
-                S%energy(IE_RECIP) = new(IE_RECIP)
-                S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
-                S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
-                S%energy(IE_SELF) = S%energy(IE_SELF) + new(IE_SELF) - old(IE_SELF)
-                S%energy(IE_INTRA) = S%energy(IE_INTRA) + new(IE_INTRA) - old(IE_INTRA)
-                S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
-                S%counter(C_C) = S%counter(C_C) + 1
-                if (verdict == BY_HOST) call window_commit(p, n_cand)
-                if (S%has_reservoir) then
-                    last = S%rsv(t)%count
-                    S%rsv(t)%com(:, p%pick) = S%rsv(t)%com(:, last)
-                    S%rsv(t)%off(:, 1:n1, p%pick) = S%rsv(t)%off(:, 1:n1, last)
-                    S%rsv(t)%count = S%rsv(t)%count - 1
-                    S%rbox%num_atoms = S%rbox%num_atoms - n1
-                end if
-            else
-                S%box%num_atoms = S%box%num_atoms - n1
-                S%res(t)%count = S%res(t)%count - 1
-            end if
-        case (TYPE_DELETION)
-            S%counter(C_TRIAL_D) = S%counter(C_TRIAL_D) + 1
-            old(1:5) = o
-            old(IE_RECIP) = S%energy(IE_RECIP)
-            new(IE_RECIP) = w(IE_RECIP)
-            if (as_written) new(IE_RECIP) = w2(IE_RECIP)                  ! creation-kind energy of the swapped-in molecule (F3)
-            old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP) + old(IE_SELF) + old(IE_INTRA)
-            new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP) + new(IE_SELF) + new(IE_INTRA)
-            last = S%res(t)%count
-            S%res(t)%count = S%res(t)%count - 1
-            S%box%num_atoms = S%box%num_atoms - n1
-            if (decide(old, new, t, TYPE_DELETION, p%u, verdict)) then
-                accepted = .true.
-                if (restore) call random_seed(put=p%rng)
-                off_last = S%res(t)%off(:, :, last)
-                S%res(t)%com(:, m) = S%res(t)%com(:, last)                ! RemoveMolecule: slot m <- the last slot
-                S%res(t)%off(:, :, m) = S%res(t)%off(:, :, last)
-                S%energy(IE_RECIP) = new(IE_RECIP)
-                S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
-                S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
-                S%energy(IE_SELF) = S%energy(IE_SELF) + new(IE_SELF) - old(IE_SELF)
-                S%energy(IE_INTRA) = S%energy(IE_INTRA) + new(IE_INTRA) - old(IE_INTRA)
-                S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
-                S%counter(C_D) = S%counter(C_D) + 1
-                if (verdict /= BY_HOST) then
-                    continue                                                   ! the engine has applied the removal
-                else if (as_written) then
-                    allocate(sites_last(3, n1))
-                    call MoleculeSites(S%res(t)%com(:, m), S%res(t)%off(:, 1:n1, m), n1, sites_last)
-                    stat = mgpu_replica_replace_molecule(S%engine, 0_c_int, int(t - 1, c_int), int(m - 1, c_int), int(last - 1, c_int))
-                    call note(stat)
-                    stat = mgpu_replica_set_num_molecules(S%engine, 0_c_int, int(t - 1, c_int), int(last - 1, c_int))
-                    call note(stat)
-                    stat = mgpu_structure_factor_add(S%engine, 0_c_int, int(t - 1, c_int), sites_last)
-                    call note(stat)
-                    deallocate(sites_last)
-                else
-                    call window_commit(p, n_cand)
-                end if
-                if (S%has_reservoir) then
-                    call random_number(trial)
-                    trial = trial - half
-                    associate (r => S%rsv(t))
-                        if (r%count + 1 <= r%cap) then
-                            r%com(:, r%count + 1) = trial(1) * S%rbox%matrix(:, 1) + trial(2) * S%rbox%matrix(:, 2) + &
-                                                    trial(3) * S%rbox%matrix(:, 3)
-                            r%off(:, 1:n1, r%count + 1) = off_last(:, 1:n1)
-                            r%count = r%count + 1
-                            S%rbox%num_atoms = S%rbox%num_atoms + n1
-                        else
-                            call note(4)
-                        end if
-                    end associate
-                end if
-            else
-                S%res(t)%count = S%res(t)%count + 1
-                S%box%num_atoms = S%box%num_atoms + n1
-            end if
-        end select
-    end subroutine resolve_step
-
-    ! the step's outcome: the engine's where it has decided, else the rule applied here
-    function decide(old, new, t, move_type, u, verdict) result(yes)
-        real(real64), intent(in) :: old(6), new(6), u
-        integer, intent(in) :: t, move_type, verdict
-        logical :: yes
-        if (verdict == BY_HOST) then
-            yes = u <= acceptance_probability(old, new, t, move_type)
-        else
-            yes = verdict == DEVICE_ACCEPTED
-        end if
-    end function decide
-
-    ! apply candidate p%cand of the window's batch from the rows still resident on the lane -- or, after a one-launch
-    ! window (whose rows are not the lane's), from the proposal itself
-    subroutine window_commit(p, n_cand)
-        type(proposal), intent(in) :: p
-        integer, intent(in) :: n_cand
+        integer, intent(in) :: how, n_cand
         integer(c_int) :: rc, rep(1), tt(1), mm(1), kk(1), acc(1)
         real(real64), allocatable, target :: sites(:, :)
-        integer :: n1
-        if (chain_cap > 0) then
-            n1 = S%res(p%t)%n1
+        integer :: n1, stat
+        n1 = S%res(p%d%t)%n1
+        select case (how)
+        case (COMMIT_SEAM)
+            call GpuAcceptMove(S%engine, p%d%t, p%d%m, p%d%kind, p%com, p%off, n1, stat=stat)
+            call note(stat)
+        case (COMMIT_SITES)
             allocate(sites(3, n1))
             call MoleculeSites(p%com, p%off, n1, sites)
-            rep = 0; tt = p%t - 1; mm = p%m - 1; kk = int(p%kind, c_int); acc = 1
-            if (p%kind == MGPU_CREATION) mm = -1
+            rep = 0; tt = p%d%t - 1; mm = p%d%m - 1; kk = int(p%d%kind, c_int); acc = 1
+            if (p%d%kind == MGPU_CREATION) mm = -1
             rc = mgpu_commit_submit(S%engine, 0_c_int, 1_c_int, rep, tt, mm, kk, c_loc(sites), int(n1, c_int), acc)
             call note(int(rc))
-            return
-        end if
-        w_acc(1:n_cand) = 0
-        w_acc(p%cand) = 1
-        rc = mgpu_commit_submit(S%engine, 0_c_int, int(n_cand, c_int), w_rep, w_t, w_m, w_kind, c_null_ptr, &
-                                int(w_stride, c_int), w_acc)
-        call note(int(rc))
-    end subroutine window_commit
+        case (COMMIT_ROWS)
+            w_acc(1:n_cand) = 0
+            w_acc(p%cand) = 1
+            rc = mgpu_commit_submit(S%engine, 0_c_int, int(n_cand, c_int), w_rep, w_t, w_m, w_kind, c_null_ptr, &
+                                    int(w_stride, c_int), w_acc)
+            call note(int(rc))
+        end select
+    end subroutine commit_step
 
-    ! Propose up to kwin steps, evaluate them in one engine call, walk them; returns the number of steps consumed.
-    ! With the engine's one-launch path (chain_cap > 0) the engine also applies the acceptance rule to the steps in order
-    ! and commits the first accepted one; the walk then only books what the engine decided.
-    function run_window(kwin) result(done)
-        integer, intent(in) :: kwin
+    ! One evaluated step of a path that builds on the host.  verdict: BY_HOST -- the rule is applied here and an accepted
+    ! step is committed through the engine (`how`); DEVICE_REJECTED / DEVICE_ACCEPTED -- the engine has applied the rule
+    ! and the commit already.  `restore`: a window may have drawn past this step, so the generator goes back to the state
+    ! saved after this step's draws before anything else is drawn.
+    subroutine resolve_step(p, o, w, w2, verdict, how, n_cand, restore, accepted)
+        type(proposal), intent(in) :: p
+        real(real64), intent(in) :: o(5), w(5), w2(5)
+        integer, intent(in) :: verdict, how, n_cand
+        logical, intent(in) :: restore
+        logical, intent(out) :: accepted
+        real(real64) :: old(6), new(6)
+        real(real64), allocatable :: off_last(:, :)
+        integer :: t, m, n1, last, mtype
+        t = p%d%t
+        m = p%d%m
+        mtype = p%d%mtype
+        n1 = S%res(t)%n1
+        call count_trial(mtype)
+        call energy_states(mtype, o, w, w2, old, new)
+        if (verdict == BY_HOST) then
+            accepted = accepts(t, mtype, old, new, p%d%u)
+        else
+            accepted = verdict == DEVICE_ACCEPTED
+        end if
+        if (.not. accepted) return
+        if (restore) call random_seed(put=p%rng)
+        last = S%res(t)%count
+        if (mtype == TYPE_DELETION) then
+            off_last = S%res(t)%off(:, :, last)
+            S%res(t)%com(:, m) = S%res(t)%com(:, last)                    ! RemoveMolecule: slot m <- the last slot
+            S%res(t)%off(:, :, m) = S%res(t)%off(:, :, last)
+        else
+            S%res(t)%com(:, m) = p%com
+            S%res(t)%off(:, 1:n1, m) = p%off
+        end if
+        call book_accepted(t, mtype, old, new)
+        if (verdict == BY_HOST) then
+            if (mtype == TYPE_DELETION .and. as_written) then
+                call commit_as_written(t, m, last)
+            else
+                call commit_step(p, how, n_cand)
+            end if
+        end if
+        if (S%has_reservoir .and. mtype == TYPE_CREATION) call reservoir_take(t, p%pick)
+        if (S%has_reservoir .and. mtype == TYPE_DELETION) call reservoir_give(t, off_last)
+    end subroutine resolve_step
+
+    ! One step of MonteCarloLoop's body: draw, evaluate that step alone -- through the seams, or as a batch of one -- resolve
+    subroutine plain_step(batched)
+        logical, intent(in) :: batched
+        type(proposal) :: p
+        real(real64) :: o(5, 2), w(5, 2)
+        real(real64), allocatable :: sites(:, :, :)
+        integer :: n1, n_cand
+        logical :: accepted
+        call draw_step(p%d)
+        if (p%d%kind == STEP_ABORT) call note(4)
+        if (p%d%kind < 0) return
+        call build_trial(p)
+        n1 = S%res(p%d%t)%n1
+        if (p%d%kind == MGPU_CREATION) then
+            ! InsertAndOrientMolecule builds the trial in slot count + 1 and a rejection leaves it there: the next insertion
+            ! into a type that is still empty copies slot 1 as this one left it
+            S%res(p%d%t)%com(:, p%d%m) = p%com
+            S%res(p%d%t)%off(:, 1:n1, p%d%m) = p%off
+        end if
+        o = zero
+        w = zero
+        if (batched) then
+            allocate(sites(3, n1, 2))
+            n_cand = 0
+            call add_rows(p, n_cand, sites, n1)
+            call evaluate_batch(n_cand, sites, o, w)
+            call resolve_step(p, o(:, 1), w(:, 1), w(:, 2), BY_HOST, COMMIT_ROWS, n_cand, .false., accepted)
+        else
+            call evaluate_seams(p, o(:, 1), w(:, 1), w(:, 2))
+            call resolve_step(p, o(:, 1), w(:, 1), w(:, 2), BY_HOST, COMMIT_SEAM, 0, .false., accepted)
+        end if
+    end subroutine plain_step
+
+    !---------------------------------------------------------------------------
+    ! Speculative window: up to kwin steps are drawn and built ASSUMING every one of them is rejected, evaluated in one
+    ! engine call -- the batched call, or the engine's one-launch window of launch_cap > 0 rows, which also decides -- and walked in order;
+    ! returns the number of steps consumed.  The generator's state after a step's draws is kept only here, where the walk
+    ! may have to go back to it.
+    !---------------------------------------------------------------------------
+    function run_window(kwin, launch_cap) result(done)
+        integer, intent(in) :: kwin, launch_cap
         integer :: done
         type(proposal), allocatable :: P(:)
         real(real64), allocatable :: sites(:, :, :), o(:, :), w(:, :)
         real(real64) :: none5(5)
-        integer :: j, n_prop, n_cand, t, n1, c, last, mx, verdict
-        integer(c_int) :: rc, first, und
+        integer :: j, n_prop, n_cand, t, c, mx, verdict, how, nseed
+        integer(c_int) :: first, und
         logical :: accepted, one_launch
-        one_launch = chain_cap > 0
+        one_launch = launch_cap > 0
         mx = 1
         do t = 1, S%n_res
             mx = max(mx, S%res(t)%n1)
         end do
         allocate(P(kwin))
-        if (.not. allocated(w_rep)) then
-            allocate(w_rep(128), w_t(128), w_m(128), w_kind(128), w_acc(128), w_link(128), w_u(128), w_pref(128))
-        end if
         allocate(sites(3, mx, 2 * kwin), o(5, 2 * kwin), w(5, 2 * kwin))
         sites = zero
-        w_stride = mx
+        call random_seed(size=nseed)
         n_prop = 0
         n_cand = 0
         do j = 1, kwin
             ! a step may need two rows (as-written deletion): never draw a step the engine's window cannot hold
-            if (one_launch .and. n_cand + 2 > chain_cap) exit
-            call propose_step(P(j))
-            n_prop = j
-            if (P(j)%kind == STEP_ABORT) exit
-            if (P(j)%kind == STEP_NOOP) cycle
-            t = P(j)%t
-            n1 = S%res(t)%n1
-            n_cand = n_cand + 1
-            P(j)%cand = n_cand
-            w_rep(n_cand) = 0
-            w_t(n_cand) = t - 1
-            w_m(n_cand) = P(j)%m - 1
-            if (P(j)%kind == MGPU_CREATION) w_m(n_cand) = -1
-            w_kind(n_cand) = P(j)%kind
-            w_link(n_cand) = -1
-            w_u(n_cand) = P(j)%u
-            select case (P(j)%mtype)
-            case (TYPE_CREATION)
-                w_pref(n_cand) = acceptance_prefactor(t, TYPE_CREATION, S%res(t)%count + 1)
-            case (TYPE_DELETION)
-                w_pref(n_cand) = acceptance_prefactor(t, TYPE_DELETION, S%res(t)%count - 1)
-            case default
-                w_pref(n_cand) = one
-            end select
-            call MoleculeSites(P(j)%com, P(j)%off, n1, sites(:, 1:n1, n_cand))
-            if (P(j)%kind == MGPU_DELETION .and. as_written) then
-                ! F3: the reciprocal update runs with is_creation on the molecule RemoveMolecule moves into slot m
-                last = S%res(t)%count
-                n_cand = n_cand + 1
-                P(j)%cand2 = n_cand
-                w_link(n_cand - 1) = n_cand - 1                             ! 0-based row of the companion
-                w_rep(n_cand) = 0
-                w_t(n_cand) = t - 1
-                w_m(n_cand) = -1
-                w_kind(n_cand) = MGPU_CREATION
-                w_link(n_cand) = -2                                         ! energy only
-                w_u(n_cand) = zero
-                w_pref(n_cand) = zero
-                call MoleculeSites(S%res(t)%com(:, last), S%res(t)%off(:, 1:n1, last), n1, sites(:, 1:n1, n_cand))
+            if (one_launch .and. n_cand + 2 > launch_cap) exit
+            call draw_step(P(j)%d)
+            if (kwin > 1) then
+                allocate(P(j)%rng(nseed))
+                call random_seed(get=P(j)%rng)
             end if
+            n_prop = j
+            if (P(j)%d%kind == STEP_ABORT) exit
+            if (P(j)%d%kind == STEP_NOOP) cycle
+            call build_trial(P(j))
+            call add_rows(P(j), n_cand, sites, mx)
         end do
         first = -1
         und = -1
+        how = COMMIT_ROWS
+        if (one_launch) how = COMMIT_SITES
         if (n_cand > 0) then
             if (one_launch) then
-                rc = mgpu_chain_window(S%engine, 0_c_int, int(n_cand, c_int), w_t, w_m, w_kind, w_link, sites, int(mx, c_int), &
-                                       w_u, w_pref, S%temperature, S%energy(IE_RECIP), o, w, first, und)
+                call evaluate_launch(n_cand, sites, o, w, first, und)
             else
-                rc = mgpu_gcmc_trial_submit(S%engine, 0_c_int, int(n_cand, c_int), w_rep, w_t, w_m, w_kind, sites, int(mx, c_int))
-                if (rc == MGPU_OK) rc = mgpu_gcmc_trial_wait(S%engine, 0_c_int, o, w)
+                call evaluate_batch(n_cand, sites, o, w)
             end if
-            call note(int(rc))
         end if
         none5 = zero
         done = n_prop
@@ -1154,12 +996,12 @@ contains
                 done = j - 1
                 exit
             end if
-            if (P(j)%kind == STEP_ABORT) then
+            if (P(j)%d%kind == STEP_ABORT) then
                 call note(4)
                 done = j
                 exit
             end if
-            if (P(j)%kind == STEP_NOOP) cycle
+            if (P(j)%d%kind == STEP_NOOP) cycle
             c = P(j)%cand
             verdict = BY_HOST
             if (one_launch) then
@@ -1168,9 +1010,9 @@ contains
                 if (c - 1 == und) verdict = BY_HOST                         ! too close to call on the device: decided here
             end if
             if (P(j)%cand2 > 0) then
-                call resolve_step(P(j), o(:, c), w(:, c), w(:, P(j)%cand2), n_cand, j < n_prop, accepted, verdict)
+                call resolve_step(P(j), o(:, c), w(:, c), w(:, P(j)%cand2), verdict, how, n_cand, j < n_prop, accepted)
             else
-                call resolve_step(P(j), o(:, c), w(:, c), none5, n_cand, j < n_prop, accepted, verdict)
+                call resolve_step(P(j), o(:, c), w(:, c), none5, verdict, how, n_cand, j < n_prop, accepted)
             end if
             if (accepted) then
                 done = j
@@ -1187,139 +1029,45 @@ contains
     end function run_window
 
     !---------------------------------------------------------------------------
-    ! One block of nb_step NVT steps as a chain run.  The draws are propose_step's statements in its order (type, molecule, move;
-    ! displacement | angle then axis; acceptance -- a translation or rotation with nothing to move draws nothing more), kept as
-    ! records; the engine builds the geometry (its construction is the one held to the reference; this loop's matmul contracts
-    ! where the reference's doubles do not), so the mirror S%res is NOT kept in step here: refresh_frames reloads it at the end.
-    ! Each collected step is booked as resolve_step books DEVICE_ACCEPTED / DEVICE_REJECTED; a step the engine left undecided is
-    ! decided here (decide, BY_HOST) and forced.
+    ! One block of nb_step steps as a chain run: the steps are drawn ahead and pushed as records of their draws -- the
+    ! engine builds the geometry (its construction is the one held to the reference; this file's matmul contracts where the
+    ! reference's doubles do not), applies the rule and commits, in launches queued back to back -- so the mirror S%res is
+    ! NOT kept in step here: refresh_frames reloads it when the run closes.  This loop keeps run_depth launches in flight
+    ! and collects the verdicts in order; a step the engine left undecided is decided here and forced.
+    ! by_count: a grand-canonical block.  Its records carry the molecule draw itself (the launch that takes the record
+    ! picks the slot from the count it finds), an NVT block's the slot.  How many numbers a step draws depends on the
+    ! molecule count at its edges (draw_step), so such a record is drawn AHEAD OF THE OUTCOMES before it only while no
+    ! count can reach an edge (ahead_ok).  Where the rule fails with records outstanding they are collected first; where
+    ! it fails with none, the run is closed, the mirror refreshed, steps go through the path the loop takes without runs
+    ! until it holds again (at least one; counted in run_fallback), the frames are uploaded and the run reopened.
+    ! An NVT block's counts never change: its rule always holds, and an empty active type pushes no-op records.
+    ! A verdict other than accepted / rejected for a by-count record that was not drawn as a no-op means the engine's count
+    ! is not this loop's: an engine-state error.
     !---------------------------------------------------------------------------
-    subroutine run_block(nb_step)
+    subroutine run_block(nb_step, by_count)
         integer, intent(in) :: nb_step
+        logical, intent(in) :: by_count
+        integer, parameter :: RUN_MOVE(4) = [3, 4, 1, 2]                    ! the record's move code of a TYPE_*
         integer(c_int), allocatable :: rt(:), rm(:), rmove(:), verdict(:)
-        real(c_double), allocatable :: ru(:, :), rau(:), o(:, :), w(:, :)
-        integer, allocatable :: mtype(:)
-        integer :: j, t, m, n1, pushed, collected, queued, n, i, chunk
-        integer(c_int) :: rc, n_got, stalled_at
-        integer(c_long_long) :: seen0, seen, st_steps, st_void, st_und
-        real(real64) :: draw, trial(3), old(6), new(6)
-        logical :: yes
-        allocate(rt(nb_step), rm(nb_step), rmove(nb_step), mtype(nb_step), ru(5, nb_step), rau(nb_step))
-        chunk = 256
-        allocate(o(5, chunk), w(5, chunk), verdict(chunk))
-        rmove = 0; ru = zero; rau = zero; mtype = 0
-        do j = 1, nb_step
-            t = pick_residue_type()
-            m = pick_molecule_index(S%res(t)%count)
-            draw = rand_uniform()
-            n1 = S%res(t)%n1
-            rt(j) = t - 1
-            rm(j) = max(m - 1, 0)
-            if (draw <= S%p_translation) then
-                if (m /= 0) then
-                    call random_number(trial)
-                    ru(1:3, j) = trial
-                    rau(j) = rand_uniform()
-                    rmove(j) = 1
-                    mtype(j) = TYPE_TRANSLATION
-                end if
-            else
-                if (n1 /= 1 .and. m /= 0) then
-                    ru(4, j) = rand_uniform()                                ! ApplyRandomRotation: angle, then axis
-                    ru(5, j) = rand_uniform()
-                    rau(j) = rand_uniform()
-                    rmove(j) = 2
-                    mtype(j) = TYPE_ROTATION
-                end if
-            end if
-        end do
-        rc = mgpu_chain_run_get_stats(S%engine, seen0, st_steps, st_void, st_und)
-        call note(int(rc))
-        rc = mgpu_chain_run_open(S%engine, 0_c_int, int(run_k, c_int), S%translation_step, S%rotation_step, S%temperature)
-        call note(int(rc))
-        if (status /= 0) return
-        pushed = 0; collected = 0; queued = 0
-        do while (collected < nb_step .and. status == 0)
-            ! records as far ahead as the ring takes them, then launches up to the depth, then the next results in order
-            n = min(nb_step - pushed, int(run_ring) - (pushed - collected))
-            if (n > 0) then
-                rc = mgpu_chain_run_push(S%engine, int(n, c_int), rt(pushed + 1:), rm(pushed + 1:), rmove(pushed + 1:), &
-                                         ru(:, pushed + 1:), rau(pushed + 1:))
-                call note(int(rc))
-                pushed = pushed + n
-            end if
-            rc = mgpu_chain_run_get_stats(S%engine, seen, st_steps, st_void, st_und)
-            call note(int(rc))
-            n = run_depth - (queued - int(seen - seen0))
-            if (n > 0) then
-                rc = mgpu_chain_run_launch(S%engine, int(n, c_int))
-                call note(int(rc))
-                queued = queued + n
-            end if
-            if (status /= 0) exit
-            rc = mgpu_chain_run_collect(S%engine, int(min(chunk, nb_step - collected), c_int), 1_c_int, o, w, verdict, n_got, stalled_at)
-            call note(int(rc))
-            if (status /= 0) exit
-            do i = 1, int(n_got)
-                j = collected + 1
-                if (verdict(i) == 2) then
-                    ! too close to call on the device: this loop's own exp decides, and the engine obeys
-                    old = zero; new = zero
-                    old(1:3) = o(1:3, i); new(1:3) = w(1:3, i)
-                    old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP)
-                    new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP)
-                    yes = decide(old, new, int(rt(j)) + 1, mtype(j), rau(j), BY_HOST)
-                    rc = mgpu_chain_run_force(S%engine, stalled_at, merge(1_c_int, 0_c_int, yes))
-                    call note(int(rc))
-                    queued = queued + 1
-                    exit                                                     ! (collected again, with its final verdict)
-                end if
-                if (mtype(j) /= 0) call book_step(mtype(j), o(:, i), w(:, i), verdict(i) == DEVICE_ACCEPTED)
-                collected = j
-            end do
-        end do
-        rc = mgpu_chain_run_close(S%engine)
-        call note(int(rc))
-        call refresh_frames()
-    end subroutine run_block
-
-    !---------------------------------------------------------------------------
-    ! One block of nb_step steps of a GRAND-CANONICAL input as a chain run of by-count records.  The draws are propose_step's
-    ! statements in its order -- type, molecule (kept as the number itself: the launch that takes the record picks the slot from the
-    ! count it finds), move, insertion / deletion; then the displacement | the angle then the axis | the position, with its angle and
-    ! axis when n1 /= 1; the acceptance draw last -- kept as records.
-    ! How many numbers a step draws depends on the molecule count at its edges (pick_molecule_index draws nothing for an empty type,
-    ! the moves and the deletion return early for one, CheckMoleculeIndex aborts a creation into a full one), so a record is drawn
-    ! AHEAD OF THE OUTCOMES before it only while no count can reach an edge: with count_t from the verdicts collected so far and
-    ! I_t / D_t the insertion / deletion records pushed and not yet collected, count_t - D_t >= 1 (>= 2 for a type of more than one
-    ! site: ahead_ok) and
-    ! count_t + I_t <= min(cap_t, NB_MAX_MOLECULE) - 1 for EVERY active type.  Where the rule fails with records outstanding they are
-    ! collected first; where it fails with none, the run is closed, the mirror refreshed, steps go through the window path until it
-    ! holds again (at least one; counted in run_fallback), the frames are uploaded and the run reopened.
-    ! Collected steps are booked as resolve_step books DEVICE_ACCEPTED / DEVICE_REJECTED; an undecided one is decided here (the
-    ! prefactor from this loop's own count) and forced.  A verdict 5 for a record that was not drawn as a no-op means the engine's
-    ! count is not this loop's: an engine-state error.
-    !---------------------------------------------------------------------------
-    subroutine run_block_gc(nb_step)
-        integer, intent(in) :: nb_step
-        integer(c_int), allocatable :: rt(:), rmove(:), verdict(:)
         real(c_double), allocatable :: ru(:, :), rau(:), rsel(:), rphi(:), o(:, :), w(:, :)
         integer, allocatable :: mtype(:), n_ins(:), n_del(:)
+        type(step_draws) :: d
+        real(real64) :: old(6), new(6), none5(5)
         integer :: j, t, pushed, collected, queued, n, i, chunk, done, n0
         integer(c_int) :: rc, n_got, stalled_at
         integer(c_long_long) :: seen0, seen, st_steps, st_void, st_und
-        logical :: yes, is_open
-        allocate(rt(nb_step), rmove(nb_step), mtype(nb_step), ru(5, nb_step), rau(nb_step), rsel(nb_step), rphi(nb_step))
+        logical :: is_open
+        allocate(rt(nb_step), rm(nb_step), rmove(nb_step), mtype(nb_step), ru(5, nb_step), rau(nb_step), rsel(nb_step), rphi(nb_step))
         allocate(n_ins(S%n_res), n_del(S%n_res))
         chunk = 256
         allocate(o(5, chunk), w(5, chunk), verdict(chunk))
-        rt = 0; rmove = 0; ru = zero; rau = zero; rsel = zero; rphi = one; mtype = 0
         n_ins = 0; n_del = 0
+        none5 = zero
         pushed = 0; collected = 0; queued = 0; seen0 = 0
         is_open = .false.
         do while (collected < nb_step .and. status == 0)
             if (pushed == collected .and. .not. ahead_ok()) then
-                ! nothing outstanding and a count at an edge: the windows take over until the rule holds again
+                ! nothing outstanding and a count at an edge
                 if (is_open) then
                     rc = mgpu_chain_run_close(S%engine)
                     call note(int(rc))
@@ -1328,7 +1076,7 @@ contains
                 end if
                 call drop_frames()
                 do while (collected < nb_step .and. status == 0)
-                    done = fallback_steps(nb_step - collected)
+                    done = take_steps(nb_step - collected)
                     collected = collected + done
                     run_fallback = run_fallback + done
                     if (ahead_ok()) exit
@@ -1350,12 +1098,18 @@ contains
             n0 = pushed
             do while (pushed < nb_step .and. pushed - collected < int(run_ring))
                 if (.not. ahead_ok()) exit
-                call draw_record(pushed + 1)
+                call draw_step(d)
                 pushed = pushed + 1
+                call keep_record(pushed)
             end do
             if (pushed > n0) then
-                rc = mgpu_chain_run_push_gc(S%engine, int(pushed - n0, c_int), rt(n0 + 1:), rmove(n0 + 1:), ru(:, n0 + 1:), rau(n0 + 1:), &
-                                            rsel(n0 + 1:), rphi(n0 + 1:))
+                if (by_count) then
+                    rc = mgpu_chain_run_push_gc(S%engine, int(pushed - n0, c_int), rt(n0 + 1:), rmove(n0 + 1:), ru(:, n0 + 1:), &
+                                                rau(n0 + 1:), rsel(n0 + 1:), rphi(n0 + 1:))
+                else
+                    rc = mgpu_chain_run_push(S%engine, int(pushed - n0, c_int), rt(n0 + 1:), rm(n0 + 1:), rmove(n0 + 1:), &
+                                             ru(:, n0 + 1:), rau(n0 + 1:))
+                end if
                 call note(int(rc))
             end if
             rc = mgpu_chain_run_get_stats(S%engine, seen, st_steps, st_void, st_und)
@@ -1367,7 +1121,9 @@ contains
                 queued = queued + n
             end if
             if (status /= 0) exit
-            rc = mgpu_chain_run_collect(S%engine, int(min(chunk, pushed - collected), c_int), 1_c_int, o, w, verdict, n_got, stalled_at)
+            ! (the engine hands over no more than it was pushed; the two kinds of run have always asked for these two limits)
+            n = merge(pushed, nb_step, by_count) - collected
+            rc = mgpu_chain_run_collect(S%engine, int(min(chunk, n), c_int), 1_c_int, o, w, verdict, n_got, stalled_at)
             call note(int(rc))
             if (status /= 0) exit
             do i = 1, int(n_got)
@@ -1375,18 +1131,22 @@ contains
                 t = int(rt(j)) + 1
                 if (verdict(i) == 2) then
                     ! too close to call on the device: this loop's own exp decides, and the engine obeys
-                    yes = decide_gc(mtype(j), t, o(:, i), w(:, i), rau(j))
-                    rc = mgpu_chain_run_force(S%engine, stalled_at, merge(1_c_int, 0_c_int, yes))
+                    call energy_states(mtype(j), o(:, i), w(:, i), none5, old, new)
+                    rc = mgpu_chain_run_force(S%engine, stalled_at, merge(1_c_int, 0_c_int, accepts(t, mtype(j), old, new, rau(j))))
                     call note(int(rc))
                     queued = queued + 1
                     exit                                                     ! (collected again, with its final verdict)
                 end if
                 if (mtype(j) /= 0) then
-                    if (verdict(i) /= DEVICE_ACCEPTED .and. verdict(i) /= DEVICE_REJECTED) then
-                        call note(4)                                         ! (verdict 5: the engine's count is not this loop's)
+                    if (by_count .and. verdict(i) /= DEVICE_ACCEPTED .and. verdict(i) /= DEVICE_REJECTED) then
+                        call note(4)
                         exit
                     end if
-                    call book_gc(mtype(j), t, o(:, i), w(:, i), verdict(i) == DEVICE_ACCEPTED)
+                    call count_trial(mtype(j))
+                    if (verdict(i) == DEVICE_ACCEPTED) then
+                        call energy_states(mtype(j), o(:, i), w(:, i), none5, old, new)
+                        call book_accepted(t, mtype(j), old, new)
+                    end if
                     if (mtype(j) == TYPE_CREATION) n_ins(t) = n_ins(t) - 1
                     if (mtype(j) == TYPE_DELETION) n_del(t) = n_del(t) - 1
                 end if
@@ -1399,207 +1159,63 @@ contains
             call refresh_frames()                                            ! (the engine's counts must be this loop's: note(4) otherwise)
         end if
     contains
-        ! may one more record be drawn before the outstanding ones are decided?
+        ! may one more record be drawn before the outstanding ones are decided?  With count_t from the verdicts collected so
+        ! far and I_t / D_t the insertion / deletion records pushed and not yet collected: count_t - D_t >= 1 and
+        ! count_t + I_t <= min(cap_t, NB_MAX_MOLECULE) - 1 for EVERY active type
         function ahead_ok() result(ok)
             logical :: ok
             integer :: tt
             ok = .true.
+            if (.not. by_count) return
             do tt = 1, S%n_res
                 if (S%res(tt)%active /= 1) cycle
                 if (S%res(tt)%count - n_del(tt) < 1) ok = .false.
-                ! a type of more than one site keeps its LAST molecule for the window path: an insertion copies the geometry the
-                ! mirror holds in slot 1 (propose_step), which for an emptied type is the deleted molecule's as it was last moved --
-                ! the window path's mirror has it, refresh_frames cannot ask the engine for the frame of an empty type
+                ! a type of more than one site keeps its LAST molecule for the host's path: an insertion copies the geometry the
+                ! mirror holds in slot 1 (build_trial), which for an emptied type is the deleted molecule's as it was last moved --
+                ! the host's mirror has it, refresh_frames cannot ask the engine for the frame of an empty type
                 if (S%res(tt)%n1 /= 1 .and. S%res(tt)%count - n_del(tt) < 2) ok = .false.
                 if (S%res(tt)%count + n_ins(tt) > min(S%res(tt)%cap, NB_MAX_MOLECULE) - 1) ok = .false.
             end do
         end function ahead_ok
 
-        ! step jj's numbers, propose_step's statements in its order (every count is away from its edges: ahead_ok)
-        subroutine draw_record(jj)
+        ! record jj = the step just drawn, as it is
+        subroutine keep_record(jj)
             integer, intent(in) :: jj
-            integer :: tt, nn1
-            real(real64) :: draw, trial(3)
-            tt = pick_residue_type()
-            rsel(jj) = rand_uniform()                                    ! PickRandomMoleculeIndex (the type is not empty)
-            draw = rand_uniform()
-            nn1 = S%res(tt)%n1
-            rt(jj) = tt - 1
-            if (draw <= S%p_translation) then
-                call random_number(trial)
-                ru(1:3, jj) = trial
-                rau(jj) = rand_uniform()
-                rmove(jj) = 1
-                mtype(jj) = TYPE_TRANSLATION
-            else if (draw <= S%p_rotation + S%p_translation) then
-                if (nn1 /= 1) then
-                    ru(4, jj) = rand_uniform()                           ! ApplyRandomRotation: angle, then axis
-                    ru(5, jj) = rand_uniform()
-                    rau(jj) = rand_uniform()
-                    rmove(jj) = 2
-                    mtype(jj) = TYPE_ROTATION
-                end if
-            else
-                rphi(jj) = S%res(tt)%fugacity * S%box%volume
-                if (rand_uniform() <= PROB_CREATE_DELETE) then
-                    call random_number(trial)
-                    ru(1:3, jj) = trial
-                    if (nn1 /= 1) then
-                        ru(4, jj) = rand_uniform()
-                        ru(5, jj) = rand_uniform()
-                    end if
-                    rau(jj) = rand_uniform()
-                    rmove(jj) = 3
-                    mtype(jj) = TYPE_CREATION
-                    n_ins(tt) = n_ins(tt) + 1
-                else
-                    rau(jj) = rand_uniform()
-                    rmove(jj) = 4
-                    mtype(jj) = TYPE_DELETION
-                    n_del(tt) = n_del(tt) + 1
-                end if
-            end if
-        end subroutine draw_record
-    end subroutine run_block_gc
+            rt(jj) = d%t - 1
+            rm(jj) = max(d%m - 1, 0)
+            rsel(jj) = d%sel
+            ru(1, jj) = d%pos(1)                                         ! (element by element: the compiler hands the
+            ru(2, jj) = d%pos(2)                                         ! section's assignment to the runtime, per record)
+            ru(3, jj) = d%pos(3)
+            ru(4, jj) = d%angle
+            ru(5, jj) = d%axis
+            rau(jj) = d%u
+            rphi(jj) = one
+            rmove(jj) = 0
+            mtype(jj) = 0
+            if (d%kind < 0) return
+            mtype(jj) = d%mtype
+            rmove(jj) = RUN_MOVE(d%mtype)
+            if (d%mtype == TYPE_CREATION .or. d%mtype == TYPE_DELETION) rphi(jj) = S%res(d%t)%fugacity * S%box%volume
+            if (d%mtype == TYPE_CREATION) n_ins(d%t) = n_ins(d%t) + 1
+            if (d%mtype == TYPE_DELETION) n_del(d%t) = n_del(d%t) + 1
+        end subroutine keep_record
+    end subroutine run_block
 
-    ! steps of the block through the path the loop takes without chain runs: a window of up to `left` steps, or one plain step;
-    ! returns the number of steps taken
-    function fallback_steps(left) result(done)
+    ! Steps of a block on the host: the evaluator the mode variables choose -- a window of up to `left` steps, or one plain
+    ! step; returns the number of steps taken
+    function take_steps(left) result(done)
         integer, intent(in) :: left
         integer :: done
         if (fused .and. (spec_k > 1 .or. chain_cap > 0)) then
-            done = run_window(min(spec_k, left))
+            ! a window never crosses the end of a block (AdjustMoveStepSizes and the files come there)
+            done = run_window(min(spec_k, left), chain_cap)
         else
-            call plain_step()
+            call plain_step(fused)
             done = 1
         end if
-    end function fallback_steps
+    end function take_steps
 
-    ! one step of MonteCarloLoop's body through the move drivers
-    subroutine plain_step()
-        integer :: t, m
-        real(real64) :: draw
-        t = pick_residue_type()
-        m = pick_molecule_index(S%res(t)%count)
-        draw = rand_uniform()
-        if (draw <= S%p_translation) then
-            call translation(t, m)
-        else if (draw <= S%p_rotation + S%p_translation) then
-            call rotation(t, m)
-        else
-            if (rand_uniform() <= PROB_CREATE_DELETE) then
-                m = S%res(t)%count + 1
-                call create_molecule(t, m)
-            else
-                call delete_molecule(t, m)
-            end if
-        end if
-    end subroutine plain_step
-
-    ! old / new as resolve_step forms them for the engine's rows of a step of a grand-canonical run
-    subroutine gc_states(move_type, o, w, old, new)
-        integer, intent(in) :: move_type
-        real(real64), intent(in) :: o(5), w(5)
-        real(real64), intent(out) :: old(6), new(6)
-        old = zero
-        new = zero
-        select case (move_type)
-        case (TYPE_CREATION)
-            old(IE_RECIP) = S%energy(IE_RECIP)
-            new(1:5) = w
-        case (TYPE_DELETION)
-            old(1:5) = o
-            old(IE_RECIP) = S%energy(IE_RECIP)
-            new(IE_RECIP) = w(IE_RECIP)
-        case default
-            old(1:3) = o(1:3)
-            new(1:3) = w(1:3)
-        end select
-        old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP) + old(IE_SELF) + old(IE_INTRA)
-        new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP) + new(IE_SELF) + new(IE_INTRA)
-    end subroutine gc_states
-
-    ! the rule for a step the engine left undecided, as resolve_step applies it (the count as the move drivers have it there)
-    function decide_gc(move_type, t, o, w, u) result(yes)
-        integer, intent(in) :: move_type, t
-        real(real64), intent(in) :: o(5), w(5), u
-        logical :: yes
-        real(real64) :: old(6), new(6)
-        integer :: dn
-        call gc_states(move_type, o, w, old, new)
-        dn = 0
-        if (move_type == TYPE_CREATION) dn = 1
-        if (move_type == TYPE_DELETION) dn = -1
-        S%res(t)%count = S%res(t)%count + dn
-        yes = decide(old, new, t, move_type, u, BY_HOST)
-        S%res(t)%count = S%res(t)%count - dn
-    end function decide_gc
-
-    ! counters, running energies and the count of one decided step of a grand-canonical run, as resolve_step books
-    ! DEVICE_ACCEPTED / DEVICE_REJECTED (the engine has applied the step; the mirror's frames follow at refresh_frames)
-    subroutine book_gc(move_type, t, o, w, accepted)
-        integer, intent(in) :: move_type, t
-        real(real64), intent(in) :: o(5), w(5)
-        logical, intent(in) :: accepted
-        real(real64) :: old(6), new(6)
-        integer :: n1
-        if (move_type == TYPE_TRANSLATION .or. move_type == TYPE_ROTATION) then
-            call book_step(move_type, o, w, accepted)
-            return
-        end if
-        n1 = S%res(t)%n1
-        call gc_states(move_type, o, w, old, new)
-        if (move_type == TYPE_CREATION) then
-            S%counter(C_TRIAL_C) = S%counter(C_TRIAL_C) + 1
-        else
-            S%counter(C_TRIAL_D) = S%counter(C_TRIAL_D) + 1
-        end if
-        if (.not. accepted) return
-        S%energy(IE_RECIP) = new(IE_RECIP)
-        S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
-        S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
-        S%energy(IE_SELF) = S%energy(IE_SELF) + new(IE_SELF) - old(IE_SELF)
-        S%energy(IE_INTRA) = S%energy(IE_INTRA) + new(IE_INTRA) - old(IE_INTRA)
-        S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
-        if (move_type == TYPE_CREATION) then
-            S%counter(C_C) = S%counter(C_C) + 1
-            S%res(t)%count = S%res(t)%count + 1
-            S%box%num_atoms = S%box%num_atoms + n1
-        else
-            S%counter(C_D) = S%counter(C_D) + 1
-            S%res(t)%count = S%res(t)%count - 1
-            S%box%num_atoms = S%box%num_atoms - n1
-        end if
-    end subroutine book_gc
-
-    ! counters and running energies of one decided translation / rotation, as resolve_step books them
-    subroutine book_step(move_type, o, w, accepted)
-        integer, intent(in) :: move_type
-        real(real64), intent(in) :: o(5), w(5)
-        logical, intent(in) :: accepted
-        real(real64) :: old(6), new(6)
-        old = zero
-        new = zero
-        if (move_type == TYPE_TRANSLATION) then
-            S%counter(C_TRIAL_T) = S%counter(C_TRIAL_T) + 1
-        else
-            S%counter(C_TRIAL_R) = S%counter(C_TRIAL_R) + 1
-        end if
-        if (.not. accepted) return
-        old(1:3) = o(1:3)
-        new(1:3) = w(1:3)
-        old(IE_TOTAL) = old(IE_NONC) + old(IE_COUL) + old(IE_RECIP)
-        new(IE_TOTAL) = new(IE_NONC) + new(IE_COUL) + new(IE_RECIP)
-        S%energy(IE_RECIP) = S%energy(IE_RECIP) + new(IE_RECIP) - old(IE_RECIP)
-        S%energy(IE_NONC) = S%energy(IE_NONC) + new(IE_NONC) - old(IE_NONC)
-        S%energy(IE_COUL) = S%energy(IE_COUL) + new(IE_COUL) - old(IE_COUL)
-        S%energy(IE_TOTAL) = S%energy(IE_TOTAL) + new(IE_TOTAL) - old(IE_TOTAL)
-        if (move_type == TYPE_TRANSLATION) then
-            S%counter(C_T) = S%counter(C_T) + 1
-        else
-            S%counter(C_R) = S%counter(C_R) + 1
-        end if
-    end subroutine book_step
 
     ! the mirror's frames of the active types from the engine, which built and committed the block's moves
     subroutine refresh_frames()
@@ -1699,17 +1315,6 @@ contains
         end do
     end function pick_residue_type
 
-    function pick_molecule_index(n) result(m)
-        integer, intent(in) :: n
-        integer :: m
-        if (n == 0) then
-            m = 0
-        else
-            m = int(rand_uniform() * n) + 1
-            if (m > n) m = n
-        end if
-    end function pick_molecule_index
-
     !---------------------------------------------------------------------------
     ! program MANIAC from ComputeSystemEnergy on (main.f90:26-33): initial energy, MonteCarloLoop,
     ! FinalReport, with every output file.  outdir ends with '/'.  seed > 0 seeds the generator by the
@@ -1760,7 +1365,7 @@ contains
         ! elsewhere the windows above
         ! A block WITH insertions / deletions: only where the host has asked for it (mchain_set_chain_run_gcmc), the run is not
         ! --as-written and the engine takes the switch (no reservoir; a triclinic box only with triclinic runs on, which the
-        ! capacity above has already said): run_block_gc, for either kind of box -- the engine builds the insertion's centre
+        ! capacity above has already said): run_block by count, for either kind of box -- the engine builds the insertion's centre
         ! (lo + box%matrix u) and wraps the translations, refresh_frames reads them back, and the fallback's windows are the
         ! ones such a box takes without runs: host-built rows through the loop's own ApplyPBC, after drop_frames.
         run_on = .false.
@@ -1795,23 +1400,11 @@ contains
             step = 1
             call system_clock(c0, crate)
             if (run_on) then
-                if (run_gc) then
-                    call run_block_gc(int(nb_step))
-                else
-                    call run_block(int(nb_step))
-                end if
+                call run_block(int(nb_step), run_gc)
                 step = nb_step + 1
             end if
-            do while (step <= nb_step)
-                if (fused .and. (spec_k > 1 .or. chain_cap > 0)) then
-                    ! a window never crosses the end of a block (AdjustMoveStepSizes and the files come there)
-                    step = step + run_window(min(spec_k, nb_step - step + 1))
-                    if (status /= 0) exit
-                    cycle
-                end if
-                call plain_step()
-                if (status /= 0) exit
-                step = step + 1
+            do while (step <= nb_step .and. status == 0)
+                step = step + take_steps(nb_step - step + 1)
             end do
             call system_clock(c1)
             loop_seconds = loop_seconds + real(c1 - c0, real64) / real(crate, real64)

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _totals(kind, o, w, e_recip, w_link=None):
-    """old%total / new%total as the move drivers form them (mc_chain.f90 resolve_step)."""
+    """old%total / new%total as the move drivers form them (mc_chain.f90 energy_states)."""
     if kind == MGPU_MOVE:
         return (o[0] + o[1]) + o[2], (w[0] + w[1]) + w[2]
     if kind == MGPU_CREATION:

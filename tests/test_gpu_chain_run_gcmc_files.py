@@ -1,5 +1,5 @@
 """The single-chain driver's grand-canonical chain runs (run_simulation(chain_run=(k, depth), chain_run_gcmc=True), mc_chain.f90
-run_block_gc): a block with insertions and deletions is drawn ahead as BY-COUNT records -- while no molecule count can reach 0
+run_block by count): a block with insertions and deletions is drawn ahead as BY-COUNT records -- while no molecule count can reach 0
 or the capacity -- and run as launches queued back to back.  It must still write the reference's files character for character
 (the comparison tests/test_gpu_run.py makes) or, for the charged inputs whose fixtures are the as-written runs, the files of
 the default-window run of the same input; as-written runs and inputs with a reservoir keep their windows."""

@@ -1,5 +1,5 @@
 """The single-chain driver's grand-canonical chain runs on TRICLINIC inputs (run_simulation(chain_run=(k, depth),
-chain_run_triclinic=True, chain_run_gcmc=True), mc_chain.f90 run_block_gc): with BOTH switches a block with insertions and
+chain_run_triclinic=True, chain_run_gcmc=True), mc_chain.f90 run_block by count): with BOTH switches a block with insertions and
 deletions in a tilted cell is drawn ahead as by-count records and run as launches queued back to back, which build the
 inserted centres (lo + box%matrix u) and wrap the translations on the device.  It must write the reference's files character
 for character (tests/golden/runs_triclinic_gcmc, made by tests/golden/make_triclinic_gcmc_fixtures.py: the dumbbell_gcmc
