@@ -311,6 +311,42 @@ int mgpu_density_reset(mgpu_engine *e, int n, const int *groups);
  * change by a bit with the order of the replicas, chunk, the other pairs selected or their order, or a repeated call. */
 int mgpu_energy_pairs_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, int n_sel, const int *res_a, const int *res_b, double *out);
 
+/* Per-molecule removal energies of many replicas, from the resident coordinates: for every molecule m of a selected residue type
+ * t, u[c](t, m) = E[c](X) - E[c](X without m) in K, c = mgpu_system_energy's first five components:
+ *   non_coulomb, coulomb   the Lennard-Jones and real-space Coulomb terms of m's sites against the sites of every OTHER molecule,
+ *                          of every type, inactive ones too (ComputePairInteractionEnergy_singlemol's pairs), in the static
+ *                          total's arithmetic and with its skips;
+ *   recip_coulomb          ComputeReciprocalEnergy's prefactor times sum_k ff(k) W(k) (2 Re(conj(S) A_m) - |A_m|^2), S(k) the
+ *                          replica's structure factor formed IN THE CALL from the coordinates, A_m(k) the molecule's own sum
+ *                          (A(k) is neither read nor written);
+ *   ewald_self, intra      ComputeEwaldSelfInteractionSingleMol of t, ComputeIntraResidueRealCoulombEnergySingleMol of (t, m).
+ * total = ((((non_coulomb + coulomb) + recip_coulomb) + ewald_self) + intra_coulomb), every add rounded.
+ *
+ * The selection is n_sel in [1, 8] distinct ACTIVE residue types (0-based); anything else is MGPU_ERR_INVALID_ARG with a text
+ * that names the type.  The replica list and chunk are those of mgpu_system_energy_replicas.
+ *
+ *   mgpu_molecule_energies_replicas   stateless and synchronous.  out[n][rows][5], rows = the sum of the selected types'
+ *                molecule capacities: molecule m of types[s] lies at row (capacities of types[0 .. s)) + m; rows from a type's
+ *                count on are exactly 0.0.  counts[n][n_sel] = the molecule counts.
+ *   configure    n_bins in [1, 4096] bins over [e_min, e_max) (both finite, e_min < e_max) for the selected types; allocates
+ *                and zeroes hist[R][n_sel][n_bins + 2] and samples[R], unsigned long long; n_sel = 0 frees them.
+ *   accumulate   one sample of each listed replica: every molecule's total, formed exactly as above, adds 1 to slot 0 where
+ *                total < e_min, to slot 1 + min(n_bins - 1, (int)floor((total - e_min) * inv_w)) where total < e_max, and to
+ *                slot n_bins + 1 otherwise (a total that is not a number included); inv_w = n_bins / (e_max - e_min) formed once
+ *                in double, the difference and the product rounded separately.  Nothing is dropped: a replica's slots add up to
+ *                the molecules counted.  samples[replica] grows by 1.  Nothing is copied to the host.
+ *   read / load / reset   the listed replicas' hist[n][n_sel][n_bins + 2] and samples[n], as the mgpu_rdf_* calls.
+ * accumulate, read, load and reset return MGPU_ERR_STATE while nothing is configured.  Every value is a function of the
+ * replica's configuration and of (t, m) alone: not one bit moves with the order of the replicas, chunk, what shares a launch,
+ * the other types selected or their order, or a repeated call.  A type without a charged site gives exactly 0 in coulomb,
+ * recip_coulomb, ewald_self and intra_coulomb. */
+int mgpu_molecule_energies_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, int n_sel, const int *types, double *out, int *counts);
+int mgpu_molecule_energy_configure(mgpu_engine *e, int n_bins, double e_min, double e_max, int n_sel, const int *types);
+int mgpu_molecule_energy_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int chunk);
+int mgpu_molecule_energy_read(mgpu_engine *e, int n, const int *replicas, unsigned long long *hist, unsigned long long *samples);
+int mgpu_molecule_energy_load(mgpu_engine *e, int n, const int *replicas, const unsigned long long *hist, const unsigned long long *samples);
+int mgpu_molecule_energy_reset(mgpu_engine *e, int n, const int *replicas);
+
 /* a[n_kvectors][2] = (re, im) of ewald%recip_amplitude */
 int mgpu_get_structure_factor(mgpu_engine *e, int replica, double *a);
 int mgpu_set_structure_factor(mgpu_engine *e, int replica, const double *a);

@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libmaniac_hip.so")
 CSRC = os.path.join(_HERE, "csrc")
 SOURCES = ["mgpu_engine.hip", "mgpu_launch.hip", "mgpu_lanes.hip", "mgpu_windows.hip", "mgpu_replicas.hip", "mgpu_host_setup.cpp",
            "mgpu_comm.cpp"]
-HEADERS = ["mgpu_kernels.h", "mgpu_kernels_replicas.h", "mgpu_kernels_rdf.h", "mgpu_kernels_density.h", "mgpu_kernels_epairs.h", "mgpu_kernels_common.h", "mgpu_kernels_pair.h", "mgpu_kernels_recip.h", "mgpu_kernels_windows.h",
+HEADERS = ["mgpu_kernels.h", "mgpu_kernels_replicas.h", "mgpu_kernels_rdf.h", "mgpu_kernels_density.h", "mgpu_kernels_epairs.h", "mgpu_kernels_molen.h", "mgpu_kernels_common.h", "mgpu_kernels_pair.h", "mgpu_kernels_recip.h", "mgpu_kernels_windows.h",
            "mgpu_internal.h", "mgpu_engine.h"]
 
 MGPU_OK = 0
@@ -47,7 +47,21 @@ EXPORTS = [
     "mgpu_rdf_configure", "mgpu_rdf_accumulate_replicas", "mgpu_rdf_read", "mgpu_rdf_load", "mgpu_rdf_reset",
     "mgpu_energy_pairs_replicas",
     "mgpu_density_configure", "mgpu_density_accumulate_replicas", "mgpu_density_read", "mgpu_density_load", "mgpu_density_reset",
+    "mgpu_molecule_energies_replicas", "mgpu_molecule_energy_configure", "mgpu_molecule_energy_accumulate_replicas",
+    "mgpu_molecule_energy_read", "mgpu_molecule_energy_load", "mgpu_molecule_energy_reset",
 ]
+
+
+_E, _I, _IP, _DP, _UP = C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)
+# the argument lists of the molecule-energy calls (include/maniac_gpu.h), set on the loaded library
+SIGNATURES = {
+    "mgpu_molecule_energies_replicas": [_E, _I, _IP, _I, _I, _IP, _DP, _IP],
+    "mgpu_molecule_energy_configure": [_E, _I, C.c_double, C.c_double, _I, _IP],
+    "mgpu_molecule_energy_accumulate_replicas": [_E, _I, _IP, _I],
+    "mgpu_molecule_energy_read": [_E, _I, _IP, _UP, _UP],
+    "mgpu_molecule_energy_load": [_E, _I, _IP, _UP, _UP],
+    "mgpu_molecule_energy_reset": [_E, _I, _IP],
+}
 
 
 class MgpuError(RuntimeError):
@@ -124,6 +138,8 @@ def lib():
             if name in ("mgpu_last_error", "mgpu_host_prefetch"):
                 continue
             getattr(L, name).restype = C.c_int          # a missing export raises here, not at first use
+        for name, args in SIGNATURES.items():
+            getattr(L, name).argtypes = args
         _lib = L
     return _lib
 

@@ -20,7 +20,7 @@ DIR_NAME = "checkpoint"
 FILE_NAME = "farm.ckpt"
 TMP_NAME = FILE_NAME + ".tmp"
 REWRITTEN = ("topology.data",)        # output files written anew every time (all others grow by appending)
-ANALYSES = ("rdf", "energy_pairs", "density")     # the identity entries of the farm analyses, in the order check names them
+ANALYSES = ("rdf", "energy_pairs", "density", "molecule_energy")     # the identity entries of the farm analyses, in the order check names them
 
 
 def path_of(outdir):
@@ -121,7 +121,8 @@ _NAMES = dict(abi_version="ABI version", nb_step="nb_step", seed="seed", mode="m
               digest_inc="the parameter file's digest", digest_reservoir="the reservoir (file's digest)",
               recalibrate="recalibrate_moves", rdf="rdf (--rdf, --rdf-pairs, --rdf-intra)",
               energy_pairs="energy_pairs (--energy-pairs, --energy-pairs-select)",
-              density="density (--density, --density-types, --density-per-replica)")
+              density="density (--density, --density-types, --density-per-replica)",
+              molecule_energy="molecule_energy (--molecule-energy, --molecule-energy-types)")
 
 
 def check(ck, ident, nb_block):

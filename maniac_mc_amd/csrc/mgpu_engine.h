@@ -441,6 +441,16 @@ struct mgpu_engine {
         Accum acc;
         DevBuf d_acc, d_group;
     } density;
+    // per-molecule removal energies (mgpu_molecule_energy_*, mgpu_replicas.hip): the bins, the selected residue types, and the
+    // accumulators of every replica -- d_acc = hist [R][n_sel][n_bins + 2] | samples [R], unsigned long long, as `acc`
+    // describes it.  Nothing but the mgpu_molecule_energy_* calls touches them.
+    struct MolEnergy {
+        int n_bins = 0, n_sel = 0;                            // n_sel = 0: not configured
+        double e_min = 0.0, e_max = 0.0, inv_w = 0.0;
+        int types[8]{};
+        Accum acc;
+        DevBuf d_acc;
+    } molen;
     // profiling
     bool profiling = false;
 };

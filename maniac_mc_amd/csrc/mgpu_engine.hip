@@ -830,6 +830,7 @@ int mgpu_engine_destroy(mgpu_engine *e) {
     e->rdf.d_tab.release();
     e->density.d_acc.release();
     e->density.d_group.release();
+    e->molen.d_acc.release();
     for (void *p : {(void *)e->chain.h_out, (void *)e->chain.h_tag, (void *)e->chain.h_rows})
         if (p) (void)hipHostFree(p);
     for (void *p : {(void *)e->chain.d_res, (void *)e->chain.d_part, (void *)e->chain.d_ticket, (void *)e->chain.d_topo, (void *)e->chain.d_alt,

@@ -7,7 +7,10 @@
 // coordinates, one rdf_hist_kernel launch per pass.  And the energies by residue-type pair (mgpu_energy_pairs_replicas): passes of
 // the same budget, per pass one sweep over (molecule, partner type) items, the partial structure factors of the selected types
 // and one ordered reduction per (replica, pair).  And the density maps (mgpu_density_*): integer counts per voxel of selected
-// atom types, pooled per group of replicas, one density_map_kernel launch per pass.
+// atom types, pooled per group of replicas, one density_map_kernel launch per pass.  And the per-molecule removal energies
+// (mgpu_molecule_energies_replicas, mgpu_molecule_energy_*): passes of the energy calls' budget, per pass one sweep over
+// (molecule, partner type) items, the pass's S(k), one workgroup per molecule for its reciprocal part and one thread per molecule
+// for its row or its histogram slot.
 // What the analyses share has one home each: the passes of the two energy calls are plan_passes (mgpu_internal.h), every list
 // of replicas or groups goes through check_index_list, the accumulators of rdf and density are an Accum (mgpu_internal.h) read,
 // loaded and cleared by accum_read / accum_load / accum_reset, their packed type tables are built with nibble_get / nibble_set,
@@ -17,6 +20,7 @@
 #include "mgpu_kernels_rdf.h"
 #include "mgpu_kernels_density.h"
 #include "mgpu_kernels_epairs.h"
+#include "mgpu_kernels_molen.h"
 
 namespace mgpu {
 
@@ -151,9 +155,248 @@ static int density_groups_ready(const mgpu_engine *e, int n, const int *groups, 
     return rc ? rc : check_index_list(n, groups, e->density.n_groups, "group", who);
 }
 
+// ---- per-molecule removal energies
+// the selection of an mgpu_molecule_energies_replicas / mgpu_molecule_energy_configure call: 1 to kMaxRes distinct ACTIVE types
+static int molen_check_types(const mgpu_engine *e, int n_sel, const int *types, const char *who) {
+    if (n_sel < 1 || n_sel > kMaxRes)
+        return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": n_sel " + std::to_string(n_sel) + " types is outside [1, " +
+                         std::to_string(kMaxRes) + "]");
+    if (!types) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": null type list");
+    bool taken[kMaxRes] = {};
+    for (int s = 0; s < n_sel; ++s) {
+        const int t = types[s];
+        const std::string name = ": type " + std::to_string(s) + " (residue type " + std::to_string(t) + ")";
+        if (t < 0 || t >= e->tp.n_res)
+            return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + name + " is out of range [0, " + std::to_string(e->tp.n_res - 1) + "]");
+        if (e->is_active[t] != 1) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + name + " is not an active type");
+        if (taken[t]) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + name + " is a duplicate");
+        taken[t] = true;
+    }
+    return MGPU_OK;
+}
+
+// The passes of both molecule-energy calls over a checked replica list and selection: the same kernels in the same order.
+// out != null (the stateless call): every pass's rows [c][rows][5] come back behind it, and counts [n][n_sel] is filled from
+// the host's molecule counts.  bins != null (the accumulate call): every molecule's total goes into the engine's histograms,
+// nothing comes back.
+static int molen_passes(mgpu_engine *e, int n, const int *replicas, int chunk, int n_sel, const int *types, double *out, int *counts,
+                        const MolenBins *bins, const char *who) {
+    int rc;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const Topo &tp = e->tp;
+    const int n_res = tp.n_res, nsplit = e->pair_nsplit;
+    const size_t tab_n = phase_tab_entries(e);
+    const int ktot = recip_ktot(e);
+    size_t rows = 0;
+    int row_first[kMaxRes], tile_of[kMaxRes], charged_of[kMaxRes];
+    double self_of[kMaxRes];
+    bool any_charged = false;
+    int max_tile = 0;
+    for (int s = 0; s < n_sel; ++s) {
+        const int t = types[s];
+        row_first[s] = (int)rows;
+        rows += (size_t)e->mol_capacity[t];
+        bool charged = false;
+        for (int a = 0; a < tp.n1[t]; ++a) charged = charged || std::fabs(e->charges[(size_t)t * tp.max_atom + a]) >= kErrorTol;
+        charged_of[s] = charged ? 1 : 0;
+        // the sites whose table entries fit the reciprocal kernel's LDS tile: fixed by the type and the k table alone
+        tile_of[s] = std::min(tp.n1[t], (int)(kMolenTileBytes / ((size_t)ktot * kLdsPhase)));
+        self_of[s] = self_energy_host(e, t);
+        if (charged) { any_charged = true; max_tile = std::max(max_tile, tile_of[s]); }
+    }
+    const size_t recip_lds = (size_t)ktot * max_tile * kLdsPhase;
+    const size_t row_bytes = out ? rows * 5 * sizeof(double) : 0;
+    auto counts_of = [&](int i, long long &n_it, long long &n_mol) {
+        n_mol = 0;
+        for (int s = 0; s < n_sel; ++s) n_mol += e->h_nmol[replicas[i] * n_res + types[s]];
+        n_it = n_mol * n_res;
+    };
+    const size_t s_n = any_charged ? tab_n + e->n_slots : 0;           // complex entries of a replica's tables and S(k)
+    // what a replica adds to a pass: its tables and S(k), its items, their split partials and results, its records and rows
+    auto bytes_of = [&](long long n_it, long long n_mol) {
+        return s_n * sizeof(double2) + (size_t)n_it * sizeof(EpItem) + (size_t)n_mol * (sizeof(PairItem) + sizeof(MolRec)) +
+               (size_t)n_it * nsplit * sizeof(double2) + (size_t)(2 * n_it + 2 * n_mol) * sizeof(double) + sizeof(int) + row_bytes;
+    };
+    std::vector<Pass> passes;
+    if (!plan_passes(n, counts_of, bytes_of, chunk, nsplit, passes))
+        return set_error(MGPU_ERR_CAPACITY, std::string(who) + ": one replica's sweep exceeds 2^31 work units");
+    size_t max_tab = 0, max_items = 0, max_rec = 0, max_res = 0, max_part = 0;
+    for (const Pass &p : passes) {
+        max_tab = std::max(max_tab, (size_t)p.c * s_n * sizeof(double2));
+        max_items = std::max(max_items, (size_t)p.n_pair * sizeof(EpItem) + (size_t)p.n_in * sizeof(PairItem));
+        max_rec = std::max(max_rec, (size_t)p.n_in * sizeof(MolRec) + (size_t)p.c * sizeof(int));
+        max_res = std::max(max_res, (size_t)p.c * row_bytes + (size_t)(2 * p.n_pair + 2 * p.n_in) * sizeof(double));
+        max_part = std::max(max_part, (size_t)p.n_pair * nsplit * sizeof(double2));
+    }
+    // every block is reserved once, before the first pass: nothing is freed under a pass still in flight
+    if ((rc = e->d_out.reserve(std::max<size_t>(max_res, 8)))) return rc;
+    if ((rc = e->d_items.reserve(std::max<size_t>(max_items, 8)))) return rc;
+    if ((rc = e->d_items2.reserve(std::max<size_t>(max_rec, 8)))) return rc;
+    if ((rc = e->d_partials.reserve(std::max<size_t>(max_part, 16)))) return rc;
+    if ((rc = e->lanes[0].d_scratch.reserve(std::max<size_t>(max_tab, 16)))) return rc;
+    const MolenBins no_bins{};
+    // the host images of the passes' uploads live until the stream has been waited for
+    std::deque<std::vector<char>> h_items, h_recs;
+    for (const Pass &p : passes) {
+        const int c = p.c, n_it = (int)p.n_pair, n_mol = (int)p.n_in;
+        h_items.emplace_back((size_t)n_it * sizeof(EpItem) + (size_t)n_mol * sizeof(PairItem));
+        EpItem *items = (EpItem *)h_items.back().data();
+        PairItem *in_items = (PairItem *)(h_items.back().data() + (size_t)n_it * sizeof(EpItem));
+        h_recs.emplace_back((size_t)n_mol * sizeof(MolRec) + (size_t)c * sizeof(int));
+        MolRec *recs = (MolRec *)h_recs.back().data();
+        int *idx = (int *)(h_recs.back().data() + (size_t)n_mol * sizeof(MolRec));
+        int at = 0;
+        for (int i = 0; i < c; ++i) {
+            const int r = replicas[p.first + i];
+            idx[i] = r;
+            for (int s = 0; s < n_sel; ++s) {
+                const int t = types[s], nm = e->h_nmol[r * n_res + t];
+                if (counts) counts[(size_t)(p.first + i) * n_sel + s] = nm;
+                for (int m = 0; m < nm; ++m, ++at) {
+                    recs[at] = MolRec{i, r, t, m, s, row_first[s] + m, charged_of[s], tile_of[s], self_of[s]};
+                    for (int t2 = 0; t2 < n_res; ++t2) items[(size_t)at * n_res + t2] = EpItem{r, t, m, t2};
+                    in_items[at] = PairItem{r, t, m, -1, 0};
+                }
+            }
+        }
+        HIP_TRY(hipMemcpyAsync(e->d_items2.p, h_recs.back().data(), h_recs.back().size(), hipMemcpyHostToDevice, e->stream));
+        const MolRec *d_recs = (const MolRec *)e->d_items2.p;
+        const int *d_idx = (const int *)((const char *)e->d_items2.p + (size_t)n_mol * sizeof(MolRec));
+        double *d_rows = (double *)e->d_out.p, *d_lj = (double *)((char *)e->d_out.p + (size_t)c * row_bytes);
+        double *d_c = d_lj + n_it, *d_in = d_c + n_it, *d_u = d_in + n_mol;
+        if (out) HIP_TRY(hipMemsetAsync(d_rows, 0, (size_t)c * row_bytes, e->stream));       // rows from the count on: exactly 0.0
+        if (n_mol > 0) {
+            HIP_TRY(hipMemcpyAsync(e->d_items.p, h_items.back().data(), h_items.back().size(), hipMemcpyHostToDevice, e->stream));
+            const int n_work = n_it * nsplit;
+            const int grid = std::max(1, std::min((n_work + kPairWaves - 1) / kPairWaves, e->n_cu * e->pair_blocks_per_cu));
+            with_bools([&](auto tri) {
+                hipLaunchKernelGGL((molen_sweep_kernel<decltype(tri)::value>), dim3(grid), dim3(kPairBlock), e->coul_bytes, e->stream, tp,
+                                   e->bx, (const double *)e->d_pos, (const int *)e->d_nmol, (const double *)e->d_res_q,
+                                   (const int *)e->d_res_atype, (const double2 *)e->d_pair_tab, (const char *)e->d_coul_tab,
+                                   (const EpItem *)e->d_items.p, nsplit, n_work, (double2 *)e->d_partials.p);
+            }, e->bx.triclinic != 0);
+            hipLaunchKernelGGL(pair_finalize_kernel, dim3((n_it + 255) / 256), dim3(256), 0, e->stream, (const double2 *)e->d_partials.p,
+                               n_it, nsplit, d_lj, d_c);
+            if ((rc = launch_intra(e, e->lanes[0], (const PairItem *)((const char *)e->d_items.p + (size_t)n_it * sizeof(EpItem)), n_mol,
+                                   nullptr, 1, d_in)))
+                return rc;
+            double2 *d_tab = (double2 *)e->lanes[0].d_scratch.p, *d_S = d_tab + (size_t)c * tab_n;
+            if (any_charged && (rc = launch_sfactor_replicas(e, d_idx, c, d_tab, false, d_S))) return rc;
+            hipLaunchKernelGGL(molen_recip_kernel, dim3(n_mol), dim3(kBlock), recip_lds, e->stream, tp, e->bx, (const double *)e->d_kw,
+                               (const int *)e->d_kpack, (const int *)e->d_kslot, (const double *)e->d_atom_q, d_recs, tab_n,
+                               (const double2 *)d_tab, (const double2 *)d_S, d_u);
+        }
+        if (n_mol > 0 || bins)
+            hipLaunchKernelGGL(molen_reduce_kernel, dim3((n_mol + (bins ? c : 0) + 63) / 64), dim3(64), 0, e->stream, n_res, d_recs, n_mol,
+                               d_idx, c, (const double *)d_lj, (const double *)d_c, (const double *)d_in, (const double *)d_u, rows,
+                               out ? d_rows : nullptr, bins ? *bins : no_bins, bins ? accum_seg(e->molen.acc, e->molen.d_acc, 0) : nullptr,
+                               bins ? accum_seg(e->molen.acc, e->molen.d_acc, 1) : nullptr);
+        HIP_TRY(hipGetLastError());
+        if (out) HIP_TRY(hipMemcpyAsync(out + (size_t)p.first * rows * 5, d_rows, (size_t)c * row_bytes, hipMemcpyDeviceToHost, e->stream));
+    }
+    return sync_stream(e);
+}
+
+// the replica list of an mgpu_molecule_energy_* call, then "configured": in this order
+static int molen_ready(const mgpu_engine *e, int n, const int *replicas, const char *who) {
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    const int rc = check_index_list(n, replicas, e->n_replicas, "replica", who);
+    if (rc) return rc;
+    if (e->molen.n_sel == 0)
+        return set_error(MGPU_ERR_STATE, std::string(who) + ": no histogram is configured (mgpu_molecule_energy_configure)");
+    return MGPU_OK;
+}
+
 }  // namespace mgpu
 
 extern "C" {
+
+int mgpu_molecule_energies_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, int n_sel, const int *types, double *out,
+                                    int *counts) {
+    const char *who = "molecule_energies_replicas";
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc = check_index_list(n, replicas, e->n_replicas, "replica", who);
+    if (rc) return rc;
+    if ((rc = molen_check_types(e, n_sel, types, who))) return rc;
+    if (n > 0 && (!out || !counts)) return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": null out or counts");
+    if (n == 0) return MGPU_OK;
+    return molen_passes(e, n, replicas, chunk, n_sel, types, out, counts, nullptr, who);
+}
+
+int mgpu_molecule_energy_configure(mgpu_engine *e, int n_bins, double e_min, double e_max, int n_sel, const int *types) {
+    const char *who = "molecule_energy_configure";
+    if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");
+    int rc;
+    auto &me = e->molen;
+    if (n_sel == 0) {
+        if ((rc = use_device(e))) return rc;
+        if ((rc = sync_all_lanes(e))) return rc;
+        me.d_acc.release();
+        me.n_sel = 0; me.n_bins = 0;
+        return MGPU_OK;
+    }
+    if (n_bins < 1 || n_bins > kMolenMaxBins)
+        return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": n_bins " + std::to_string(n_bins) + " is outside [1, " +
+                         std::to_string(kMolenMaxBins) + "]");
+    if (!std::isfinite(e_min) || !std::isfinite(e_max) || !(e_min < e_max))
+        return set_error(MGPU_ERR_INVALID_ARG, std::string(who) + ": e_min and e_max must be finite, e_min below e_max");
+    if ((rc = molen_check_types(e, n_sel, types, who))) return rc;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    me.d_acc.release();
+    me.n_sel = 0;
+    const Accum acc = accum_layout((size_t)e->n_replicas, (size_t)n_sel * (n_bins + 2), 1);      // hist | samples
+    if ((rc = me.d_acc.reserve(acc.bytes()))) return rc;
+    HIP_TRY(hipMemset(me.d_acc.p, 0, acc.bytes()));
+    me.acc = acc;
+    me.n_bins = n_bins; me.n_sel = n_sel;
+    me.e_min = e_min; me.e_max = e_max; me.inv_w = (double)n_bins / (e_max - e_min);
+    for (int s = 0; s < n_sel; ++s) me.types[s] = types[s];
+    return MGPU_OK;
+}
+
+int mgpu_molecule_energy_accumulate_replicas(mgpu_engine *e, int n, const int *replicas, int chunk) {
+    const char *who = "molecule_energy_accumulate_replicas";
+    int rc = molen_ready(e, n, replicas, who);
+    if (rc) return rc;
+    if (n == 0) return MGPU_OK;
+    const auto &me = e->molen;
+    const MolenBins bins{me.n_bins, me.n_sel, me.e_min, me.e_max, me.inv_w};
+    return molen_passes(e, n, replicas, chunk, me.n_sel, me.types, nullptr, nullptr, &bins, who);
+}
+
+int mgpu_molecule_energy_read(mgpu_engine *e, int n, const int *replicas, unsigned long long *hist, unsigned long long *samples) {
+    int rc = molen_ready(e, n, replicas, "molecule_energy_read");
+    if (rc) return rc;
+    if (n > 0 && (!hist || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "molecule_energy_read: null output");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    unsigned long long *const host[3] = {hist, samples, nullptr};
+    return accum_read(e->molen.acc, e->molen.d_acc, n, replicas, host, true);
+}
+
+int mgpu_molecule_energy_load(mgpu_engine *e, int n, const int *replicas, const unsigned long long *hist,
+                              const unsigned long long *samples) {
+    int rc = molen_ready(e, n, replicas, "molecule_energy_load");
+    if (rc) return rc;
+    if (n > 0 && (!hist || !samples)) return set_error(MGPU_ERR_INVALID_ARG, "molecule_energy_load: null input");
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    const unsigned long long *const host[3] = {hist, samples, nullptr};
+    return accum_load(e->molen.acc, e->molen.d_acc, n, replicas, host);
+}
+
+int mgpu_molecule_energy_reset(mgpu_engine *e, int n, const int *replicas) {
+    int rc = molen_ready(e, n, replicas, "molecule_energy_reset");
+    if (rc) return rc;
+    if (n == 0) return MGPU_OK;
+    if ((rc = use_device(e))) return rc;
+    if ((rc = sync_all_lanes(e))) return rc;
+    return accum_reset(e->molen.acc, e->molen.d_acc, n, replicas);
+}
 
 int mgpu_system_energy_replicas(mgpu_engine *e, int n, const int *replicas, int chunk, double *out, double *a_deviation) {
     if (!e) return set_error(MGPU_ERR_INVALID_ARG, "null engine");

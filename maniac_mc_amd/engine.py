@@ -616,6 +616,54 @@ class Engine:
         """mgpu_density_reset: zero the listed groups' accumulators (None: all)."""
         self._accum_call("density_reset", self._density_groups(groups)[0])
 
+    # ---- per-molecule removal energies ---------------------------------------------------
+    def molecule_energies_replicas(self, types, replicas=None, chunk=None):
+        """mgpu_molecule_energies_replicas: (energies (n, rows, 5) float64 in K, counts (n, n_sel) int32) of the listed replicas
+        (None: all) for the ACTIVE 0-based residue `types`: row (capacities of types[:s]).sum() + m holds E(X) - E(X without m)
+        of molecule m of types[s] (non_coulomb, coulomb, recip_coulomb, ewald_self, intra_coulomb); rows from a count on are 0."""
+        types = _ints([int(t) for t in types]) if len(types) else np.zeros(0, dtype=np.int32)
+        r = self._replica_list(replicas)
+        n = r.shape[0]
+        rows = int(sum(int(self.mol_capacity[t]) for t in types if 0 <= t < self.topo.n_res))
+        out = np.zeros((n, rows, 5))
+        counts = np.zeros((n, types.shape[0]), dtype=np.int32)
+        check(self.L.mgpu_molecule_energies_replicas(self.h, C.c_int(n), _i(r), C.c_int(0 if chunk is None else int(chunk)),
+                                                     C.c_int(types.shape[0]), _i(types) if types.size else None, _d(out), _i(counts)))
+        return out, counts
+
+    def molecule_energy_configure(self, n_bins, e_min, e_max, types):
+        """mgpu_molecule_energy_configure: histograms of n_bins bins over [e_min, e_max) K (and one slot below, one above) of the
+        molecules' total removal energy for the ACTIVE 0-based residue `types`, zeroed, for every replica.  types = [] frees them."""
+        types = _ints([int(t) for t in types]) if len(types) else np.zeros(0, dtype=np.int32)
+        check(self.L.mgpu_molecule_energy_configure(self.h, C.c_int(int(n_bins)), C.c_double(float(e_min)), C.c_double(float(e_max)),
+                                                    C.c_int(types.shape[0]), _i(types) if types.size else None))
+        self.molecule_energy_shape = (types.shape[0], int(n_bins) + 2) if types.size else None
+
+    def _molecule_energy_shape(self):
+        shape = getattr(self, "molecule_energy_shape", None)
+        if shape is None:
+            raise _lib.MgpuError(5, "no histogram is configured (Engine.molecule_energy_configure)")
+        return shape
+
+    def molecule_energy_accumulate(self, replicas=None, chunk=None):
+        """mgpu_molecule_energy_accumulate_replicas: one sample of every listed replica (None: all) from the resident coordinates."""
+        r = self._replica_list(replicas)
+        check(self.L.mgpu_molecule_energy_accumulate_replicas(self.h, C.c_int(r.shape[0]), _i(r), C.c_int(0 if chunk is None else int(chunk))))
+
+    def molecule_energy_read(self, replicas=None):
+        """mgpu_molecule_energy_read: (hist (n, n_sel, n_bins + 2), samples (n,)) of the listed replicas, uint64."""
+        return self._accum_call("molecule_energy_read", self._replica_list(replicas), (self._molecule_energy_shape(), ()))
+
+    def molecule_energy_load(self, hist, samples, replicas=None):
+        """mgpu_molecule_energy_load: overwrite the listed replicas' accumulators with arrays shaped as molecule_energy_read returns them."""
+        ns, slots = self._molecule_energy_shape()
+        self._accum_call("molecule_energy_load", self._replica_list(replicas), ((ns, slots), ()), (hist, samples),
+                         f"replicas of {ns} types and {slots} slots")
+
+    def molecule_energy_reset(self, replicas=None):
+        """mgpu_molecule_energy_reset: zero the listed replicas' accumulators (None: all)."""
+        self._accum_call("molecule_energy_reset", self._replica_list(replicas))
+
     def structure_factor(self, replica=0):
         a = np.zeros((self.nk, 2))
         check(self.L.mgpu_get_structure_factor(self.h, C.c_int(replica), _d(a)))

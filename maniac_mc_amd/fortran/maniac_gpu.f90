@@ -244,6 +244,57 @@ module maniac_gpu
             real(c_double), intent(out) :: out(*)
             integer(c_int) :: rc
         end function
+        ! per-molecule removal energies of many replicas (0-based residue types): out(5, rows, n) in K, counts(n_sel, n)
+        function mgpu_molecule_energies_replicas(e, n, replicas, chunk, n_sel, types, out, counts) &
+                bind(C, name="mgpu_molecule_energies_replicas") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: n, chunk, n_sel
+            integer(c_int), intent(in) :: replicas(*), types(*)
+            real(c_double), intent(out) :: out(*)
+            integer(c_int), intent(out) :: counts(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_molecule_energy_configure(e, n_bins, e_min, e_max, n_sel, types) &
+                bind(C, name="mgpu_molecule_energy_configure") result(rc)
+            import :: c_ptr, c_int, c_double
+            type(c_ptr), value :: e
+            integer(c_int), value :: n_bins, n_sel
+            real(c_double), value :: e_min, e_max
+            integer(c_int), intent(in) :: types(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_molecule_energy_accumulate_replicas(e, n, replicas, chunk) &
+                bind(C, name="mgpu_molecule_energy_accumulate_replicas") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n, chunk
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_molecule_energy_read(e, n, replicas, hist, samples) bind(C, name="mgpu_molecule_energy_read") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_long_long), intent(out) :: hist(*), samples(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_molecule_energy_load(e, n, replicas, hist, samples) bind(C, name="mgpu_molecule_energy_load") result(rc)
+            import :: c_ptr, c_int, c_long_long
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_long_long), intent(in) :: hist(*), samples(*)
+            integer(c_int) :: rc
+        end function
+        function mgpu_molecule_energy_reset(e, n, replicas) bind(C, name="mgpu_molecule_energy_reset") result(rc)
+            import :: c_ptr, c_int
+            type(c_ptr), value :: e
+            integer(c_int), value :: n
+            integer(c_int), intent(in) :: replicas(*)
+            integer(c_int) :: rc
+        end function
         function mgpu_pair_energy_candidates(e, n, replica, t, m, use_resident, sites, site_stride, e_nc, e_c) &
                 bind(C, name="mgpu_pair_energy_candidates") result(rc)
             import :: c_ptr, c_int, c_double
@@ -945,5 +996,24 @@ contains
         rc = mgpu_energy_pairs_replicas(engine, int(n, c_int), int(replicas, c_int), 0_c_int, int(n_sel, c_int), a, b, out)
         call GpuCheck(rc, 'GpuEnergyPairs', stat)
     end subroutine GpuEnergyPairs
+
+    !---------------------------------------------------------------------------
+    ! Per-molecule removal energies: out(5, rows, n) in K = non_coulomb, coulomb, recip_coulomb,
+    ! ewald_self, intra_coulomb of E(X) - E(X without m) for every molecule m of the ACTIVE residue
+    ! types types(1:n_sel), rows = the sum of their molecule capacities (type s's molecule m at row
+    ! sum of the capacities before s + m, rows from the count on 0); counts(n_sel, n).  Residue types
+    ! are 1-based here, as in the input file; replicas are 0-based, as everywhere in this module.
+    !---------------------------------------------------------------------------
+    subroutine GpuMoleculeEnergies(engine, n, replicas, n_sel, types, out, counts, stat)
+        type(c_ptr), intent(in) :: engine
+        integer, intent(in) :: n, replicas(n), n_sel, types(n_sel)
+        real(real64), intent(out) :: out(*)
+        integer(c_int), intent(out) :: counts(*)
+        integer, intent(out), optional :: stat
+        integer(c_int) :: ty(max(1, n_sel)), rc
+        ty(1:n_sel) = int(types - 1, c_int)
+        rc = mgpu_molecule_energies_replicas(engine, int(n, c_int), int(replicas, c_int), 0_c_int, int(n_sel, c_int), ty, out, counts)
+        call GpuCheck(rc, 'GpuMoleculeEnergies', stat)
+    end subroutine GpuMoleculeEnergies
 
 end module maniac_gpu

@@ -301,6 +301,13 @@ class FortranFarm:
         self.eng.rdf_accumulate(replicas, chunk)
         self._select()
 
+    def molecule_energy_sample(self, replicas=None, chunk=None):
+        """One sample of every listed chain (None: all) into the engine's molecule-energy histograms
+        (Engine.molecule_energy_configure first), from the coordinates the engine holds -- which are current between two run()
+        calls in every farm mode."""
+        self.eng.molecule_energy_accumulate(replicas, chunk)
+        self._select()
+
     def density_sample(self, replicas=None, chunk=None):
         """One sample of every listed chain (None: all) into the engine's density maps (Engine.density_configure first), from
         the coordinates the engine holds -- which are current between two run() calls in every farm mode."""

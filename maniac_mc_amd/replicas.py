@@ -25,6 +25,7 @@ import numpy as np
 from . import _lib, checkpoint, fortran_host, io_maniac
 from . import energy_pairs as epairs_mod
 from . import density as density_mod
+from . import molecule_energy as molen_mod
 from . import rdf as rdf_mod
 from .fortran_host import FortranFarm
 from .run import header_text, set_chain_state
@@ -76,7 +77,7 @@ def _stats(x):
 def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=None, fugacities=None, frames=(0,),
                  mode="auto", device=0, nb_block=None, nb_step=None, mol_capacity=None, n_lanes=2, n_threads=8,
                  chunk=None, wide_triclinic=False, restart_from=None, audit=False, checkpoint_every=0, resume=False,
-                 recalibrate_moves=None, rdf=None, energy_pairs=None, density=None):
+                 recalibrate_moves=None, rdf=None, energy_pairs=None, density=None, molecule_energy=None):
     """Run `replicas` independent chains of the input; returns a dict with the final energies (R, 5) in K (non-Coulomb,
     Coulomb, reciprocal, self, intramolecular), counts (R, n_active), chain counters (R, 8), the farm's counters, the
     mode that ran and the block timings.
@@ -133,6 +134,15 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     cube file <outdir>/density_gGG_typeTT.cube per map and type (sites per cubic Angstrom over the cell, with the atoms of the
     inactive residue types) are written (maniac_mc_amd.density).  A checkpoint then carries the accumulators, and a resumed
     run must ask for the same density.  None (default): nothing of this, and every file is what it always was.
+    ``molecule_energy``: dict(e_min=..., e_max=..., n_bins=..., types=None, every=1) -> after every `every`-th block every
+    molecule of the 0-based ACTIVE residue ``types`` (default: every active type) of every replica adds its removal energy
+    E(X) - E(X without m) to the engine's histograms of n_bins bins over [e_min, e_max) kcal/mol and one slot below, one above
+    (FortranFarm.molecule_energy_sample; its time in seconds["molecule_energy"]); after the last block
+    <outdir>/molecule_energy_counts.npz (hist, samples per replica, the spec, every replica's group) and
+    <outdir>/molecule_energy.dat (per fugacity group and type: the bin centre, the probability density pooled over the group's
+    replicas, its standard error over the replicas, the pooled raw count) are written (maniac_mc_amd.molecule_energy).  A
+    checkpoint then carries the accumulators, and a resumed run must ask for the same molecule_energy.  None (default): nothing
+    of this, and every file is what it always was.
     """
     import time
     if mode not in MODES:
@@ -170,7 +180,8 @@ def run_replicas(maniac, data, inc, outdir, replicas, seed=None, reservoir_path=
     # the analyses asked for, in the order every later loop takes them; the groups reach ctx once they are known
     ctx = types.SimpleNamespace(topo=topo, system=system, R=R, residue_names=[res.name for res in inp.residues],
                                 group=None, fugacities=None)
-    analyses = [mod.Sampler(option, ctx) for mod, option in ((rdf_mod, rdf), (density_mod, density), (epairs_mod, energy_pairs))
+    analyses = [mod.Sampler(option, ctx) for mod, option in ((rdf_mod, rdf), (density_mod, density), (epairs_mod, energy_pairs),
+                                                             (molen_mod, molecule_energy))
                 if option is not None]
     group = np.zeros(R, dtype=np.int64)
     if fugacities is not None:

@@ -338,6 +338,18 @@ def main(argv=None):
                     help="with --density: the atom types, ids as in the data file (default: the active types' atom types; at most 8)")
     ap.add_argument("--density-per-replica", dest="density_per_replica", action="store_true",
                     help="with --density: one map per replica instead of one per fugacity group")
+    ap.add_argument("--molecule-energy", dest="molecule_energy", default=None, metavar="EMIN,EMAX,BINS[,EVERY]",
+                    help="with --replicas: the distribution of the molecules' removal energies E(X) - E(X without m) in BINS bins "
+                         "over [EMIN, EMAX) kcal/mol, one sample of every replica after every EVERY-th block (default 1); writes "
+                         "<out>/molecule_energy.dat and <out>/molecule_energy_counts.npz")
+    ap.add_argument("--molecule-energy-types", dest="molecule_energy_types", default=None, metavar="NAME,NAME",
+                    help="with --molecule-energy: the residue types, by the input's names (default: every active type)")
+    argv = list(sys.argv[1:] if argv is None else argv)
+    for i in range(len(argv) - 1):
+        # EMIN is usually negative: "--molecule-energy -12,2,64" would be read as a switch named -12,2,64
+        if argv[i] == "--molecule-energy" and argv[i + 1][:1] == "-" and argv[i + 1][1:2] in tuple("0123456789."):
+            argv[i:i + 2] = [argv[i] + "=" + argv[i + 1]]
+            break
     a = ap.parse_args(argv)
     try:
         chain_run = parse_chain_run(a.chain_run) if a.chain_run is not None else None
@@ -364,6 +376,8 @@ def main(argv=None):
             ap.error("--energy-pairs and --energy-pairs-select need --replicas: the single chain writes no energy decomposition")
         if a.density is not None or a.density_types is not None or a.density_per_replica:
             ap.error("--density, --density-types and --density-per-replica need --replicas: the single chain writes no density maps")
+        if a.molecule_energy is not None or a.molecule_energy_types is not None:
+            ap.error("--molecule-energy and --molecule-energy-types need --replicas: the single chain writes no molecule energies")
     else:
         from . import replicas as farm_run
         if a.as_written:
@@ -379,10 +393,11 @@ def main(argv=None):
             fugacities = farm_run.parse_fugacities(a.fugacities) if a.fugacities is not None else None
         except ValueError as err:
             ap.error(str(err))
-        from . import density as density_mod, energy_pairs as epairs_mod, rdf as rdf_mod
+        from . import density as density_mod, energy_pairs as epairs_mod, molecule_energy as molen_mod, rdf as rdf_mod
         rdf = rdf_mod.from_args(ap, a)
         energy_pairs = epairs_mod.from_args(ap, a)
         density = density_mod.from_args(ap, a)
+        molecule_energy = molen_mod.from_args(ap, a)
     for path, what in ((a.maniac, "Input"), (a.data, "Data"), (a.inc, "Parameter"), (a.reservoir, "Reservoir")):
         if path is not None and not os.path.isfile(path):
             print(f"{what} file not found: {path}", file=sys.stderr)
@@ -393,7 +408,7 @@ def main(argv=None):
                                         fugacities=fugacities, frames=frames, mode=a.farm_mode, device=a.device,
                                         wide_triclinic=a.wide_triclinic, restart_from=a.restart_from, audit=a.audit,
                                         checkpoint_every=a.checkpoint_every, resume=a.resume, rdf=rdf,
-                                        energy_pairs=energy_pairs, density=density)
+                                        energy_pairs=energy_pairs, density=density, molecule_energy=molecule_energy)
         except ValueError as err:
             print(f"error: {err}", file=sys.stderr)
             return 2
